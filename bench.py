@@ -18,7 +18,10 @@ The headline (`metric` / `value` / `roofline` / `cpu_baseline` / `parity` at the
                              backward on the generic path; reports correctness against the closed form, ~1 s),
   N > 1 : "strong_f64_32768" configs[2] itself: 32768 fp64 problems sharded over the N GPUs (strong scaling), each rank's
           share solved in sub-batches of 4096, one all_gather of the solved poses,
-each with its own value / ms_per_step / roofline / parity / cpu_baseline (`--legs none` skips them).
+each with its own value / ms_per_step / roofline / parity / cpu_baseline (`--legs none` skips them), summarised (leg_summary).
+
+`--dump-outputs DIR` writes what the headline's last timed call returned (solved poses, final cost per problem) as .npy files:
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Multi GPU (one rank per GPU; `python bench.py --gpus N` re-executes itself under torch.distributed.run when it was not
 launched by it): the batch dimension shards -- every rank owns B independent problems (weak scaling) -- and one RCCL
@@ -319,14 +322,58 @@ def algorithmic_bytes(P, E, es):
 
 def compact(x, digits=9):
     """Floats to ``digits`` significant digits, recursively: the line carries five configurations and must stay readable (and
-    inside whatever tail of stdout a harness keeps)."""
+    inside whatever tail of stdout a harness keeps).  NaN / inf become null: the line is strict JSON."""
     if isinstance(x, float):
-        return float(f"{x:.{digits}g}") if x == x and abs(x) != float("inf") else x
+        return float(f"{x:.{digits}g}") if x == x and abs(x) != float("inf") else None
     if isinstance(x, dict):
         return {k: compact(v, digits) for k, v in x.items()}
     if isinstance(x, (list, tuple)):
         return [compact(v, digits) for v in x]
     return x
+
+
+LEG_TABLES = ("phases_ms_per_call", "hbm_bound_kernels")   # per-kernel tables: the headline carries its own
+
+
+def leg_summary(x, prose=48):
+    """A leg as it rides under "configs": its numbers and short labels, without the per-kernel tables, the prose longer than
+    ``prose`` characters and the null fields, floats to 6 digits.  Eight full legs made a 21 kB line; summarised the whole line
+    stays near 12 kB.  A leg's full record is its own configuration run alone (bench.py --dtype f64 / --implicit / ...,
+    tools/bench_ba.py, tools/bench_sparse.py)."""
+    def keep(k, v):
+        return k not in LEG_TABLES and v is not None and not (isinstance(v, str) and len(v) > prose and k != "error")
+
+    def brief(y):
+        if isinstance(y, dict):
+            return {k: brief(v) for k, v in y.items() if keep(k, v)}
+        if isinstance(y, (list, tuple)):
+            return [brief(v) for v in y]
+        return y
+    return compact(brief(x), 6)
+
+
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, sol, info, P):
+    """--dump-outputs: what the timed LM call returned to its caller -- the solved poses ``poses.npy`` (B, P, 3, 4) and the
+    per-problem cost at the last iteration ``last_err.npy`` (B,), in the run dtype.  When the batch exceeds DUMP_BYTES a fixed
+    sample of problems is written (torch.randperm(B) under seed 0, sorted): the same arguments always write the same problems.
+    Runs after the clock has stopped.  Returns what was written, for the result line."""
+    import numpy as np
+    poses = torch.stack([sol[f"VERTEX_SE3__{k}"].detach() for k in range(P)], 1)
+    last_err = info.last_err.detach()
+    B = poses.shape[0]
+    per_problem = (poses[0].numel() + 1) * poses.element_size()
+    n = min(B, DUMP_BYTES // per_problem)
+    if n < B:
+        idx = torch.randperm(B, generator=torch.Generator().manual_seed(0))[:n].sort().values
+        poses, last_err = poses[idx.to(poses.device)], last_err[idx.to(last_err.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"poses": poses, "last_err": last_err}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
+    return {"dir": out_dir, "problems": n, "of": B, "arrays": {name: list(t.shape) for name, t in arrays.items()}}
 
 
 def free_device_memory():
@@ -409,8 +456,9 @@ def pg_run(cfg, ctx):
         timer.enabled = on_gpu
         t0 = time.perf_counter()
         sol, info = layer.forward(inputs, optimizer_kwargs=dict(track_err_history=True, **okw))
+        last = (sol, info)
         for more in sub_inputs[1:]:  # strong scaling: the rank's remaining sub-batches through the same workspaces
-            layer.forward(more, optimizer_kwargs=okw)
+            last = layer.forward(more, optimizer_kwargs=okw)
         if cfg.implicit:  # backward: retract VJP + ONE linear solve with the cached factor + cost VJP
             loss = torch.stack(list(sol.values())).sum()   # (one reduction over all poses; 256 separate .sum() calls were
                                                             #  1.6 ms of 6 us kernels in the timed backward)
@@ -436,6 +484,8 @@ def pg_run(cfg, ctx):
         barrier()
         dt = time.perf_counter() - t0
         timer.enabled = False
+    dumped = dump_outputs(cfg.dump_outputs, *last, P) if cfg.dump_outputs and rank == 0 else None
+    del last
     rank_ms = [local_dt * 1e3]
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=device)
@@ -473,6 +523,8 @@ def pg_run(cfg, ctx):
             "iters_done": iters_done,
             "mean_error": [float(err_hist[:, 0].mean()), float(err_hist[:, iters_done].mean())],
         }
+        if dumped is not None:
+            result["dumped_outputs"] = dumped
         if on_gpu:
             sparse = cfg.solver == "sparse"
             fac = (phases.get("chol_factor_hblocks") or phases.get("chol_factor_sparse" if sparse else "chol_factor")
@@ -1113,6 +1165,10 @@ def main():
     ap.add_argument("--legs", default="auto",
                     help="the other BASELINE configs under 'configs' in the same line: 'auto' (default: all of them when the "
                          "headline configuration is run unmodified), 'none', or a comma list of fp64,ba,implicit,strong")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the headline's last timed LM call returned -- DIR/poses.npy "
+                         "(batch, poses, 3, 4) and DIR/last_err.npy (batch,), run dtype, at most 64 MB (a fixed seeded sample "
+                         "of the problems beyond that) -- to compare two builds output for output (rank 0's batch at N > 1)")
     # TEST SEAM (tests/test_bench_cli.py): run the launcher / sharding / reporting logic without a GPU.  The numbers of such
     # a run are not measurements: the line says "data": "TEST-STANDIN" and carries no roofline.
     ap.add_argument("--test-kernels", default="", help=argparse.SUPPRESS)   # "module:Class" of a stand-in kernels class
@@ -1151,7 +1207,8 @@ def main():
     head = SimpleNamespace(poses=args.poses, edges=args.edges, batch=args.batch, total_batch=args.total_batch, steps=args.steps,
                            warmup=args.warmup, dtype=args.dtype, damping=args.damping, adaptive=args.adaptive,
                            solver=args.solver, implicit=args.implicit, cpu_sample=args.cpu_sample, cpu_chunk=args.cpu_chunk,
-                           cpu_iters=args.cpu_iters, parity_sample=args.parity_sample, sparse_leg=not args.no_sparse_leg)
+                           cpu_iters=args.cpu_iters, parity_sample=args.parity_sample, sparse_leg=not args.no_sparse_leg,
+                           dump_outputs=args.dump_outputs)
     result = pg_run(head, ctx)
 
     # ---- the other BASELINE configs, as legs of the same line ----
@@ -1178,10 +1235,10 @@ def main():
             free_device_memory()
         if r is not None:
             r["leg_wall_s"] = round(time.perf_counter() - t0, 1)
-            configs[name] = r
+            configs[name] = leg_summary(r)
 
     def variant(**kw):
-        d = dict(vars(head))
+        d = dict(vars(head), dump_outputs="")   # (only the headline dumps its outputs)
         d.update(kw)
         return SimpleNamespace(**d)
 
@@ -1196,11 +1253,12 @@ def main():
                                                      cpu_sample=min(args.cpu_sample, 4), parity_sample=min(args.parity_sample, 4)),
                                              ctx))
     if not os.environ.get("THX_REFERENCE_ROOT") and world == 1 and not standin and legs and ("dropin" in legs or args.legs == "auto"):
-        configs["dropin_real_theseus_loop"] = {
-            "skipped": "reference absent (no THX_REFERENCE_ROOT on this box): the REAL theseus loop over theseus_amd.plugin cannot run "
-                       "here", "recorded": {"fraction_of_mirror_loop": [0.909, 0.949], "tests_on_cuda": "43 passed",
-                                            "source": "profiles/r6/z_bench_dropin_leg.json, profiles/r6/z_pytest_plugin_cuda.txt "
-                                                      "(tools/dropin_gpu.sh stages a copy of the reference for one gpurun call)"}}
+        # (the REAL theseus loop over theseus_amd.plugin cannot run without a copy of the reference; recorded:
+        #  profiles/r6/z_bench_dropin_leg.json, profiles/r6/z_pytest_plugin_cuda.txt)
+        configs["dropin_real_theseus_loop"] = leg_summary({
+            "skipped": "reference absent (no THX_REFERENCE_ROOT)",
+            "recorded": {"fraction_of_mirror_loop": [0.909, 0.949], "tests_on_cuda": "43 passed",
+                         "source": "profiles/r6/z_bench_dropin_leg.json"}})
     if os.environ.get("THX_REFERENCE_ROOT") and world == 1 and not standin and ("dropin" in legs or args.legs == "auto"):
         # the DROP-IN on hardware: the REAL theseus loop (its Objective / LevenbergMarquardt / TheseusLayer) with theseus_amd.plugin
         # behind it on the headline workload, next to theseus_amd's own loop on the same inputs (tools/dropin_bench.py; only where

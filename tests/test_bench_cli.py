@@ -107,3 +107,21 @@ def test_gpus_8_uneven_shards():
     assert r["n_gpus"] == 8 and r["scaling"] == "strong" and r["config"]["global_batch"] == 37
     assert r["value"] == pytest.approx(37 * 2 / (r["ms_per_step"] * 2 * 1e-3), rel=1e-6)
     assert r["iters_done"] == 2 and r["all_gather_ms"] is not None
+
+
+def test_dump_outputs_writes_what_the_timed_call_returned(tmp_path):
+    """--dump-outputs DIR: the headline's solved poses and final per-problem cost, in the run dtype; the same arguments give the
+    same inputs, so two runs write the same arrays; --steps sets the timed LM iterations."""
+    import numpy as np
+    runs = []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        seam = [("3" if prev == "--steps" else a) for prev, a in zip([None] + SEAM, SEAM)]
+        r = _bench("--batch", "3", "--dump-outputs", str(d), seam=seam)
+        assert r["steps"] == 3 and r["iters_done"] == 3 and r["ms_per_step"] > 0
+        assert r["dumped_outputs"]["problems"] == 3 and sorted(os.listdir(d)) == ["last_err.npy", "poses.npy"]
+        runs.append({n: np.load(d / f"{n}.npy") for n in ("poses", "last_err")})
+    a, b = runs
+    assert a["poses"].shape == (3, 6, 3, 4) and a["poses"].dtype == np.float64 and a["last_err"].shape == (3,)
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    assert float(a["last_err"].mean()) == pytest.approx(r["mean_error"][1], rel=1e-7)
