@@ -296,9 +296,10 @@ int thx_se3_retract(const void* poses, const void* delta, int64_t ldd, double st
  *          the tile in registers (eight tiles per CU in their pivot chains instead of three).  The split pays from this many
  *          problems per launch on (the level schedule: problems x block columns of the level); 0 = always split, INT32_MAX =
  *          never; < 0: the default (2048, or the environment's THX_CHOL_SPLIT_DIAG_MIN read once at load time).
- *        column_pairs: fp32 factorisations on dense factor frames, two block columns at a time -- diag(j), tile (j+1, j),
- *          diag(j+1), then ONE workgroup per row tile i >= j+2 produces L_ij and L_i,j+1, streaming row panel L_i,0:j from HBM
- *          once for both; 1 on, 0 off, < 0: the default (on, or THX_CHOL_COLPAIR).
+ *        column_pairs: fp32 factorisations on dense factor frames of at least column_pairs_min_batch problems (and not on the
+ *          right-looking schedule), two block columns at a time -- diag(j), tile (j+1, j), diag(j+1), then ONE workgroup per row tile
+ *          i >= j+2 produces L_ij and L_i,j+1, streaming row panel L_i,0:j from HBM once for both; 1 on, 0 off, < 0: the default
+ *          (on, or THX_CHOL_COLPAIR).  Bit-identical to the column-by-column schedule.
  *        right_looking_max_batch: factorisations (fp32 and fp64) on dense factor frames (no tile pattern, ld >= ntiles * THX_TILE) of at most
  *          this many problems take the RIGHT-LOOKING schedule -- per block column the tile factorisation, the substitutions and
  *          one workgroup per tile of the trailing matrix, each a single 128^3 product -- instead of the left-looking one whose
@@ -318,7 +319,15 @@ int thx_se3_retract(const void* poses, const void* delta, int64_t ldd, double st
  *        f64_half_max_ktiles: fp64, column-by-column schedule on a dense factor frame: the off-diagonal tiles of the first this many
  *          block columns are produced as two HALF tiles (64 rows each) by four-wave workgroups that need 37 KB of LDS and 128
  *          VGPRs -- four per CU instead of two; takes precedence over f64_wide_max_ktiles for those columns.  Bit-identical.
- *          0 = never; < 0: the default (8, or THX_F64_HALF_MAX_KTILES). */
+ *          0 = never; < 0: the default (8, or THX_F64_HALF_MAX_KTILES).
+ *        column_pairs_min_batch: the column-pair schedule (column_pairs) is taken from this many problems per call on; 0 = at any
+ *          batch; < 0: the default (128, or THX_CHOL_COLPAIR_MIN_BATCH).
+ *        right_looking_mode: the launch arrangement of the right-looking schedule -- 0: three dependent launches per block column
+ *          (tile factorisation, substitutions, trailing update); 1: two -- the diagonal tile and the substitution tiles of column j
+ *          take column j - 1's update themselves (one-tile K-loop), the rest of that update rides in the substitutions' launch, and
+ *          block column 1 is read straight from H; 2: the diagonal tile takes its own update, the rest of the update runs on the
+ *          library's second stream beside it.  The three sum in different orders (to rounding, not bit for bit).  < 0: the default
+ *          (THX_CHOL_RL_LOOKAHEAD, else 1 for fp32 and 2 for fp64); > 2: 1. */
 typedef struct {
   int32_t split_diag_min_batch;
   int32_t column_pairs;
@@ -326,7 +335,28 @@ typedef struct {
   int32_t hb_scatter_max_pieces;
   int32_t f64_wide_max_ktiles;
   int32_t f64_half_max_ktiles;
+  int32_t column_pairs_min_batch;
+  int32_t right_looking_mode;
 } thx_chol_schedule;
+
+/* ---- thx_chol_plan: HOST-ONLY query (no device is touched, no GPU needed) -- the schedule a DENSE-frame factorisation
+ *      (thx_chol_factor, thx_chol_factor_forward with has_rhs != 0, thx_chol_factor_hblocks with layout != NULL and no tile pattern)
+ *      with these arguments takes: the same decision function the factorisation runs.  has_damping: a damping vector is given;
+ *      ldv: row stride of rhs / y (with has_rhs; y assumed 16-byte aligned, as every torch allocation is); layout: only its host
+ *      fields are read (bd, max_tile_pieces, whether diag_blk is set).  For tests and tools that must know which kernels a call
+ *      reaches. */
+typedef struct {
+  int32_t right_looking;       /* 1: the right-looking schedule */
+  int32_t right_looking_mode;  /* its launch arrangement (thx_chol_schedule.right_looking_mode), -1 when left-looking */
+  int32_t split_diag;          /* 1: the diagonal phase as SYRK kernel + one-wave-per-tile kernel, 0: the fused chol_diag kernel */
+  int32_t nparts;              /* streams the batch is dealt over (1: the caller's alone) */
+  int32_t column_pairs;        /* 1: the column-pair schedule (chol_offdiag2_f32_kernel) */
+  int32_t f64_half_cols;       /* fp64: block columns whose off-diagonal tiles come from chol_offdiag_f64h_kernel */
+  int32_t f64_wide_cols;       /* fp64: ... from chol_offdiag_f64w8_kernel */
+  int32_t forward_fused;       /* has_rhs: 1 the forward substitution rides in the factorisation's kernels, 0 a kernel of its own */
+} thx_chol_plan_info;
+int thx_chol_plan(int32_t n, int64_t ld, int32_t B, int dtype, int has_damping, int has_rhs, int64_t ldv,
+                  const thx_hblock_layout* layout, const thx_chol_schedule* schedule, thx_chol_plan_info* out);
 
 /* ---- tile-sparse Cholesky for LARGE pose graphs -- the functional analogue of BaspachoSparseSolver
  *      (theseus/optimizer/linear/baspacho_sparse_solver.py:23-148; symbolic analysis once, numeric factorisation per iteration).

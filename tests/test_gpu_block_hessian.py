@@ -63,36 +63,56 @@ def test_block_assembly_is_bit_identical_to_the_dense_frame(K, name):
 GATHER = {"mfma": -1, "lds": 0}
 
 
-@pytest.mark.parametrize("gather", list(GATHER))
-@pytest.mark.parametrize("split", [False, True])
-@pytest.mark.parametrize("name,ellipsoidal", [("pg_full_f32_lm", False), ("pg_full_f64_lm", True), ("pg_f64_lm", False)])
-def test_factor_from_blocks_is_bit_identical(K, name, ellipsoidal, split, gather):
-    """thx_chol_factor_hblocks against thx_chol_factor_forward on the dense frame of the same H: (0 - L L^T) + H and H - L L^T
-    round identically, so L, the panels, y and info agree bit for bit -- fused and split diagonal phase, 12-tile and 1-tile n,
-    pieces added by the matrix cores (hb_scatter) and gathered through LDS."""
-    s, hb, dhb, H, gv, Hc, g2, n, ld = _assembled(K, name)
+def _sched_kernels(**fields):
+    """A kernels object with a schedule of its own (thx_chol_schedule fields; the others: the library defaults)."""
+    from theseus_amd.kernels import HipKernels
+    Ks = HipKernels()
+    for k, v in fields.items():
+        setattr(Ks.chol_schedule, k, v)
+    return Ks
+
+
+def _assert_plans(Ks, n, ld, B, dtype, dhb, gv, **expect):
+    """thx_chol_plan: the dense frame and the block list of this H take the path the test names."""
+    for layout in (None, dhb.c):
+        p = Ks.chol_plan(n, ld, B, dtype, damping=True, rhs=True, ldv=gv.stride(0), layout=layout)
+        for k, v in expect.items():
+            assert p[k] == v, (k, layout is not None, p)
+
+
+def _lapack_backward_error(H, L, lam, ellipsoidal, n, eps_damp=1e-8):
+    """L against LAPACK in fp64 (host): the backward error bound of tests/test_gpu_kernels.py:_chol_vs_lapack on every problem."""
+    Hl = torch.tril(H[:, :n, :n]).double().cpu()
+    M = Hl + torch.tril(Hl, -1).transpose(1, 2)
+    dg = torch.diagonal(M, dim1=1, dim2=2)
+    lam = lam.double().cpu().view(-1, 1)
+    M = M + torch.diag_embed(lam * dg + eps_damp if ellipsoidal else lam.expand_as(dg))
+    assert int(torch.linalg.cholesky_ex(M).info.abs().sum()) == 0
+    Lg = torch.tril(L[:, :n, :n]).double().cpu()
+    eps = 1.2e-7 if H.dtype == torch.float32 else 2.3e-16
+    resid = float((Lg @ Lg.transpose(1, 2) - M).abs().max() / M.abs().max())
+    assert resid < 60 * eps * max(1, n / 64), resid
+
+
+def _factor_from_blocks_vs_dense(Ks, name, ellipsoidal, expect):
+    s, hb, dhb, H, gv, Hc, g2, n, ld = _assembled(Ks, name)
     B = H.shape[0]
     nt = (n + 127) // 128
     if nt > 1:   # the default really is the matrix-core path here
         assert 1 <= dhb.c.max_tile_pieces <= 64
+    _assert_plans(Ks, n, ld, B, H.dtype, dhb, gv, **expect)
     lam = torch.full((B,), 1e-3, dtype=H.dtype, device="cuda")
-    prev = K.chol_split_diag_min_batch(0 if split else 2 ** 31 - 1)
-    prev_g = K.chol_hb_scatter_max_pieces(GATHER[gather])
-    try:
-        out = []
-        for compact in (False, True):
-            L = torch.zeros_like(H)
-            panels = torch.zeros(B, nt, 128, 128, dtype=H.dtype, device="cuda")
-            info = torch.empty(B, dtype=torch.int32, device="cuda")
-            y = torch.empty_like(gv)
-            if compact:
-                K.chol_factor_hblocks(dhb, Hc, n, lam, ellipsoidal, 1e-8, L, panels, info, rhs=gv, y=y)
-            else:
-                K.chol_factor(H, n, lam, ellipsoidal, 1e-8, L, panels, info, rhs=gv, y=y)
-            out.append((torch.tril(L[:, :n, :n]), panels, y, info))
-    finally:
-        K.chol_split_diag_min_batch(prev)
-        K.chol_hb_scatter_max_pieces(prev_g)
+    out = []
+    for compact in (False, True):
+        L = torch.zeros_like(H)
+        panels = torch.zeros(B, nt, 128, 128, dtype=H.dtype, device="cuda")
+        info = torch.empty(B, dtype=torch.int32, device="cuda")
+        y = torch.empty_like(gv)
+        if compact:
+            Ks.chol_factor_hblocks(dhb, Hc, n, lam, ellipsoidal, 1e-8, L, panels, info, rhs=gv, y=y)
+        else:
+            Ks.chol_factor(H, n, lam, ellipsoidal, 1e-8, L, panels, info, rhs=gv, y=y)
+        out.append((torch.tril(L[:, :n, :n]), panels, y, info))
     (La, Pa, ya, ia), (Lb, Pb, yb, ib) = out
     assert int(ia.abs().sum()) == 0 and int(ib.abs().sum()) == 0
     assert torch.equal(La, Lb) and torch.equal(ya, yb)
@@ -103,37 +123,55 @@ def test_factor_from_blocks_is_bit_identical(K, name, ellipsoidal, split, gather
 
 @pytest.mark.parametrize("gather", list(GATHER))
 @pytest.mark.parametrize("split", [False, True])
+@pytest.mark.parametrize("name,ellipsoidal", [("pg_full_f32_lm", False), ("pg_full_f64_lm", True), ("pg_f64_lm", False)])
+def test_factor_from_blocks_is_bit_identical(name, ellipsoidal, split, gather):
+    """thx_chol_factor_hblocks against thx_chol_factor_forward on the dense frame of the same H: (0 - L L^T) + H and H - L L^T
+    round identically, so L, the panels, y and info agree bit for bit -- the LEFT-LOOKING schedule (right-looking off: at these
+    batches it would be the default, see test_factor_from_blocks_right_looking_is_bit_identical), fused and split diagonal phase,
+    12-tile and 1-tile n, pieces added by the matrix cores (hb_scatter) and gathered through LDS."""
+    Ks = _sched_kernels(split_diag_min_batch=0 if split else 2 ** 31 - 1, hb_scatter_max_pieces=GATHER[gather],
+                        right_looking_max_batch=0)
+    _factor_from_blocks_vs_dense(Ks, name, ellipsoidal, dict(right_looking=0, split_diag=int(split), column_pairs=0))
+
+
+@pytest.mark.parametrize("gather", list(GATHER))
+@pytest.mark.parametrize("name,ellipsoidal", [("pg_full_f32_lm", False), ("pg_full_f64_lm", True)])
+def test_factor_from_blocks_right_looking_is_bit_identical(name, ellipsoidal, gather):
+    """The same on the RIGHT-LOOKING schedule (12 block columns, 2 / 4 problems; its default mode per dtype): block list and dense
+    frame bit for bit (the other modes: tests/test_gpu_chol_schedules.py)."""
+    Ks = _sched_kernels(hb_scatter_max_pieces=GATHER[gather], right_looking_max_batch=64)
+    _factor_from_blocks_vs_dense(Ks, name, ellipsoidal, dict(right_looking=1, split_diag=0))
+
+
+@pytest.mark.parametrize("gather", list(GATHER))
+@pytest.mark.parametrize("split", [False, True])
 def test_factor_from_blocks_in_column_pairs_is_bit_identical(K, split, gather):
     """thx_chol_factor_hblocks, fp32, 12 tile columns: the column-pair schedule (both H tiles of a workgroup taken from the
-    block list) against the column-by-column one -- L, panels, y bit for bit."""
+    block list) against the column-by-column one -- L, panels, y bit for bit.  4 problems: below the pair schedule's default floor
+    (thx_chol_schedule.column_pairs_min_batch, 128) and inside the right-looking schedule's batches -- both set here, the paths
+    confirmed by thx_chol_plan; the factor against LAPACK."""
     s, hb, dhb, H, gv, Hc, g2, n, ld = _assembled(K, "pg_full_f32_lm")
     B = H.shape[0]
     nt = (n + 127) // 128
     lam = torch.full((B,), 1e-3, dtype=H.dtype, device="cuda")
-    prev_split = K.chol_split_diag_min_batch(0 if split else 2 ** 31 - 1)
-    prev_g = K.chol_hb_scatter_max_pieces(GATHER[gather])
     out = []
-    try:
-        for pairs in (True, False):
-            prev = K.chol_column_pairs(pairs)
-            try:
-                L = torch.zeros_like(H)
-                panels = torch.zeros(B, nt, 128, 128, dtype=H.dtype, device="cuda")
-                info = torch.empty(B, dtype=torch.int32, device="cuda")
-                y = torch.empty_like(gv)
-                K.chol_factor_hblocks(dhb, Hc, n, lam, False, 1e-8, L, panels, info, rhs=gv, y=y)
-                out.append((torch.tril(L[:, :n, :n]), panels, y, info))
-            finally:
-                K.chol_column_pairs(prev)
-    finally:
-        K.chol_split_diag_min_batch(prev_split)
-        K.chol_hb_scatter_max_pieces(prev_g)
+    for pairs in (True, False):
+        Ks = _sched_kernels(split_diag_min_batch=0 if split else 2 ** 31 - 1, hb_scatter_max_pieces=GATHER[gather],
+                            right_looking_max_batch=0, column_pairs_min_batch=0, column_pairs=int(pairs))
+        _assert_plans(Ks, n, ld, B, H.dtype, dhb, gv, column_pairs=int(pairs), right_looking=0, split_diag=int(split))
+        L = torch.zeros_like(H)
+        panels = torch.zeros(B, nt, 128, 128, dtype=H.dtype, device="cuda")
+        info = torch.empty(B, dtype=torch.int32, device="cuda")
+        y = torch.empty_like(gv)
+        Ks.chol_factor_hblocks(dhb, Hc, n, lam, False, 1e-8, L, panels, info, rhs=gv, y=y)
+        out.append((torch.tril(L[:, :n, :n]), panels, y, info))
     (La, Pa, ya, ia), (Lb, Pb, yb, ib) = out
     assert int(ia.abs().sum()) == 0 and int(ib.abs().sum()) == 0
     assert torch.equal(La, Lb) and torch.equal(ya, yb)
     for u in range(4):
         for v in range(u + 1):
             assert torch.equal(Pa[:, :, 32 * u:32 * u + 32, 32 * v:32 * v + 32], Pb[:, :, 32 * u:32 * u + 32, 32 * v:32 * v + 32])
+    _lapack_backward_error(H, La, lam, False, n)
 
 
 @pytest.mark.parametrize("solver", ["dense", "sparse"])
@@ -168,28 +206,29 @@ def test_fp64_eight_wave_and_half_tile_offdiag_kernels_are_bit_identical(K, comp
     """thx_chol_schedule.f64_wide_max_ktiles / f64_half_max_ktiles: the off-diagonal tiles of the first block columns from eight-wave
     workgroups (16 rows of the tile per wave) or as two half tiles from four-wave workgroups (four per CU) -- the same MFMAs in the
     same order as the four-wave kernel: L, y bit for bit, for the block-compact H (matrix-core scatter) and the dense frame, every
-    setting from "no column" to "all of them", and the defaults."""
+    setting from "no column" to "all of them", and the defaults.  On the column-by-column schedule (right-looking off: at 2
+    problems it would be the default and take neither kernel); thx_chol_plan confirms the block columns of each kernel per
+    setting; the factor against LAPACK."""
     s, hb, dhb, H, gv, Hc, g2, n, ld = _assembled(K, "pg_full_f64_lm")
     B = H.shape[0]
     nt = (n + 127) // 128
     lam = torch.full((B,), 1e-3, dtype=H.dtype, device="cuda")
     out = []
     for wide, half in ((0, 0), (1, 0), (3, 0), (nt, 0), (0, 1), (0, 5), (0, nt), (nt, 4), (-1, -1)):
-        prev = K.chol_f64_wide_max_ktiles(wide)
-        prev_h = K.chol_f64_half_max_ktiles(half)
-        try:
-            L = torch.zeros_like(H)
-            panels = torch.zeros(B, nt, 128, 128, dtype=H.dtype, device="cuda")
-            info = torch.empty(B, dtype=torch.int32, device="cuda")
-            y = torch.empty_like(gv)
-            if compact:
-                K.chol_factor_hblocks(dhb, Hc, n, lam, True, 1e-8, L, panels, info, rhs=gv, y=y)
-            else:
-                K.chol_factor(H, n, lam, True, 1e-8, L, panels, info, rhs=gv, y=y)
-            out.append((torch.tril(L[:, :n, :n]), y, info))
-        finally:
-            K.chol_f64_wide_max_ktiles(prev)
-            K.chol_f64_half_max_ktiles(prev_h)
+        Ks = _sched_kernels(f64_wide_max_ktiles=wide, f64_half_max_ktiles=half, right_looking_max_batch=0)
+        h = min(8 if half < 0 else half, nt - 1)
+        w = min(nt if wide < 0 else wide, nt - 1) - h
+        _assert_plans(Ks, n, ld, B, H.dtype, dhb, gv, right_looking=0, f64_half_cols=h, f64_wide_cols=max(w, 0))
+        L = torch.zeros_like(H)
+        panels = torch.zeros(B, nt, 128, 128, dtype=H.dtype, device="cuda")
+        info = torch.empty(B, dtype=torch.int32, device="cuda")
+        y = torch.empty_like(gv)
+        if compact:
+            Ks.chol_factor_hblocks(dhb, Hc, n, lam, True, 1e-8, L, panels, info, rhs=gv, y=y)
+        else:
+            Ks.chol_factor(H, n, lam, True, 1e-8, L, panels, info, rhs=gv, y=y)
+        out.append((torch.tril(L[:, :n, :n]), y, info))
     for La, ya, ia in out:
         assert int(ia.abs().sum()) == 0
         assert torch.equal(La, out[0][0]) and torch.equal(ya, out[0][1])
+    _lapack_backward_error(H, out[0][0], lam, True, n)

@@ -237,12 +237,12 @@ def test_assemble_error_jacobians_vs_reference_golden(K, name):
         np.testing.assert_allclose(b, g["b0"], rtol=0, atol=np.abs(g["b0"]).max() * 1e-11 + 1e-30)
 
 
-def _random_spd(B, n, dtype, seed, cond=1e3):
-    gen = torch.Generator().manual_seed(seed)
-    A = torch.randn(B, n, n + 8, dtype=torch.float64, generator=gen)
+def _random_spd(B, n, dtype, seed, cond=1e3, device="cpu"):
+    gen = torch.Generator(device=device).manual_seed(seed)
+    A = torch.randn(B, n, n + 8, dtype=torch.float64, generator=gen, device=device)
     M = A @ A.transpose(1, 2) / (n + 8)
-    M = M + (1.0 / cond) * torch.eye(n, dtype=torch.float64)
-    return M.to(dtype)
+    M = M + (1.0 / cond) * torch.eye(n, dtype=torch.float64, device=device)
+    return M.to(dtype).cpu()
 
 
 @pytest.fixture
@@ -359,16 +359,18 @@ def test_chol_right_looking_reports_non_positive_definite(K):
 
 
 @pytest.mark.parametrize("split", [False, True])
-@pytest.mark.parametrize("n,B", [(258, 5), (390, 12), (700, 9), (1100, 16), (1536, 8)])
+@pytest.mark.parametrize("n,B", [(258, 5), (390, 12), (700, 9), (1100, 16), (1536, 8), (700, 130), (1536, 130)])
 def test_chol_column_pairs_are_bit_identical(K, n, B, split):
     """fp32, dense frame: two block columns per off-diagonal launch (chol_offdiag2_f32_kernel: row panel L_i streamed once for
     tiles (i, j) and (i, j + 1), column j's share of the second tile from the first tile's registers) run the same MFMAs in the
     same order as the column-by-column schedule: L, the panels, the fused forward substitution and the solution agree bit for
-    bit -- 3 ... 12 tile columns, last tile partial (258, 390, 700, 1100) or full, batch not a multiple of 8."""
+    bit -- 3 ... 12 tile columns, last tile partial (258, 390, 700, 1100) or full, batch not a multiple of 8.  The pair schedule
+    is taken from thx_chol_schedule.column_pairs_min_batch problems on (default 128) and never with the right-looking schedule:
+    both are set here, and thx_chol_plan confirms each arm's path; a sample against LAPACK in fp64."""
     from tests.gpu_helpers import factor_and_solve
-    from theseus_amd.kernels import round_up
+    from theseus_amd.kernels import HipKernels, round_up
     dtype = torch.float32
-    M = _random_spd(B, n, dtype, seed=n + B)
+    M = _random_spd(B, n, dtype, seed=n + B, device="cuda" if B > 64 else "cpu")   # (the large batches: generated on the device)
     rhs = torch.randn(B, n, dtype=torch.float64, generator=torch.Generator().manual_seed(2)).to(dtype).cuda()
     ld = round_up(n, 32)
     H = torch.zeros(B, ld, ld, dtype=dtype)
@@ -376,20 +378,36 @@ def test_chol_column_pairs_are_bit_identical(K, n, B, split):
     H = H.cuda()
     lam = torch.full((B,), 0.05, dtype=dtype, device="cuda")
     out = {}
-    prev_split = K.chol_split_diag_min_batch(0 if split else 2 ** 31 - 1)
-    try:
-        for pairs in (True, False):
-            prev = K.chol_column_pairs(pairs)
-            try:
-                out[pairs] = factor_and_solve(K, H, n, rhs, damping=lam, ellipsoidal=True, eps=1e-8, fused=True)
-            finally:
-                K.chol_column_pairs(prev)
-    finally:
-        K.chol_split_diag_min_batch(prev_split)
+    for pairs in (True, False):
+        Kp = HipKernels()                    # (a schedule of its own: the module's K keeps the defaults)
+        Kp.chol_split_diag_min_batch(0 if split else 2 ** 31 - 1)
+        Kp.chol_right_looking_max_batch(0)
+        Kp.chol_column_pairs_min_batch(0)
+        Kp.chol_column_pairs(pairs)
+        plan = Kp.chol_plan(n, ld, B, dtype, damping=True, rhs=True, ldv=n)
+        assert plan["column_pairs"] == int(pairs) and plan["right_looking"] == 0 and plan["split_diag"] == int(split), plan
+        out[pairs] = factor_and_solve(Kp, H, n, rhs, damping=lam, ellipsoidal=True, eps=1e-8, fused=True)
     (La, xa, ia), (Lb, xb, ib) = out[True], out[False]
     assert int(ia.abs().sum()) == 0 and int(ib.abs().sum()) == 0
     assert torch.equal(torch.tril(La[:, :n, :n]), torch.tril(Lb[:, :n, :n]))
     assert torch.equal(xa, xb)
+    # the pair arm against LAPACK (fp64, host) on a sample, with the bounds of _chol_vs_lapack
+    sample = sorted({0, B // 2, B - 1})
+    Md = M[sample].double()
+    Md = Md + torch.diag_embed(0.05 * torch.diagonal(Md, dim1=1, dim2=2) + 1e-8)
+    _lapack_bounds(La[sample, :n, :n], xa[sample], Md, rhs[sample], dtype, n)
+
+
+def _lapack_bounds(L, x, M64, rhs, dtype, n):
+    """The bounds of _chol_vs_lapack: backward error of the factor, forward error of the solution (M64: the damped fp64 matrix)."""
+    Lref = torch.linalg.cholesky(M64)
+    xref = torch.cholesky_solve(rhs.double().cpu().unsqueeze(2), Lref).squeeze(2)
+    Lg = torch.tril(L).cpu().double()
+    eps = 1.2e-7 if dtype == torch.float32 else 2.3e-16
+    resid = (Lg @ Lg.transpose(1, 2) - M64).abs().max() / M64.abs().max()
+    assert resid < 60 * eps * max(1, n / 64), resid
+    xerr = (x.cpu().double() - xref).abs().max() / xref.abs().max()
+    assert xerr < (5e-3 if dtype == torch.float32 else 1e-10), xerr
 
 
 def test_chol_split_diagonal_phase_reports_non_positive_definite(K, split_diag):

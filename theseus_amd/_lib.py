@@ -21,7 +21,7 @@ THX_BA_ERR_CHUNKS = 256
 LOSS_NONE, LOSS_WELSCH, LOSS_HUBER, LOSS_HINGE = 0, 1, 2, 3  # THX_LOSS_* (theseus/core/robust_loss.py:33-62)
 LOSS_FLATTEN = 4  # THX_LOSS_FLATTEN: RobustCostFunction(flatten_dims=True), or-ed into a loss code
 LOSS_GEMAN_MCCLURE = 8  # THX_LOSS_GEMAN_MCCLURE (robust_loss.py:92-113; the radius entry carries log(mu * radius))
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 
 class LieEps(Structure):
@@ -65,7 +65,12 @@ class TilePattern(Structure):  # thx_tile_pattern: tile-level symbolic factorisa
 class CholSchedule(Structure):  # thx_chol_schedule: per-call schedule of the factorisations (negative = the library default)
     _fields_ = [("split_diag_min_batch", c_int32), ("column_pairs", c_int32), ("right_looking_max_batch", c_int32),
                 ("hb_scatter_max_pieces", c_int32), ("f64_wide_max_ktiles", c_int32),
-                ("f64_half_max_ktiles", c_int32)]
+                ("f64_half_max_ktiles", c_int32), ("column_pairs_min_batch", c_int32), ("right_looking_mode", c_int32)]
+
+
+class CholPlanInfo(Structure):  # thx_chol_plan_info: the schedule a dense-frame factorisation takes (thx_chol_plan, host only)
+    _fields_ = [(k, c_int32) for k in ("right_looking", "right_looking_mode", "split_diag", "nparts", "column_pairs",
+                                       "f64_half_cols", "f64_wide_cols", "forward_fused")]
 
 
 class LevelSchedule(Structure):  # thx_level_schedule: elimination-tree levels of a tile pattern (2 host + 2 device int32 tables)
@@ -196,6 +201,8 @@ _SIGNATURES = {
     "thx_chol_factor_hblocks": [POINTER(HBlockLayout), c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int, c_double, c_void_p,
                                 c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, POINTER(TilePattern), c_int, c_void_p,
                                 POINTER(CholSchedule)],
+    "thx_chol_plan": [c_int32, c_int64, c_int32, c_int, c_int, c_int, c_int64, POINTER(HBlockLayout), POINTER(CholSchedule),
+                      POINTER(CholPlanInfo)],
     "thx_chol_factor_levels": [POINTER(HBlockLayout), c_void_p, c_int64, c_int32, c_void_p, c_int, c_double, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_int64, POINTER(TilePattern), POINTER(LevelSchedule), c_int, c_void_p,
                                POINTER(CholSchedule)],

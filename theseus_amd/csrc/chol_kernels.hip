@@ -3890,6 +3890,119 @@ static DeviceLaunchState& launch_state() {
   return st[(dev >= 0 && dev < MAX_DEVICES) ? dev : 0];
 }
 
+// Environment defaults of the launch plan below (read once at load time, like the schedule defaults above).
+// how an off-diagonal tile takes its pieces of H: a few per tile (pose graphs) -> added by the matrix cores (hb_scatter); many (a
+// bundle adjustment's reduced camera system: up to 21 x 21 blocks per tile) or unknown -> gathered through LDS in rounds
+static const int g_hb_scatter_max_default = [] {
+  const char* e = getenv("THX_HB_SCATTER_MAX_PIECES");   // (0: always the gather rounds)
+  return e ? atoi(e) : 64;
+}();
+// fp64: the first f64_wide_max block columns (K-loops shorter than that many tiles) take the 8-wave off-diagonal kernel
+// (chol_offdiag_f64w8_kernel).  Default: ALL of them -- measured +1.0 ... 1.3 % at batch 256 / 1024 / 4096 (n = 1536), growing with
+// the number of columns that use it (profiles/r6/ae_): four waves per SIMD serve the K-loop better than two; the early columns,
+// for which the kernel was written, gain nothing.
+static const int g_f64_wide_default = [] {
+  const char* e = getenv("THX_F64_WIDE_MAX_KTILES");   // (0: never)
+  return e ? atoi(e) : (1 << 30);
+}();
+// ... and the first f64_half_max of them (K-loops shorter than that many tiles) the HALF-TILE kernel (chol_offdiag_f64h_kernel, four
+// workgroups per CU): measured optimum 6 ... 8 at n = 1536 / batch 4096 (profiles/r6/af_: 90.0 -> 88.5 ms; all twelve columns 89.0)
+static const int g_f64_half_default = [] {
+  const char* e = getenv("THX_F64_HALF_MAX_KTILES");   // (0: never)
+  return e ? atoi(e) : 8;
+}();
+static const int g_split_min = [] {
+  const char* e = getenv("THX_CHOL_SPLIT_MIN");  // batch size from which the multi-stream schedule is used (0: never)
+  return e ? atoi(e) : 1024;
+}();
+// number of parts (streams): 2; THX_CHOL_PARTS=3 staggers three thirds (measured)
+static const int g_nparts_cfg = [] {
+  const char* e = getenv("THX_CHOL_PARTS");
+  const int v = e ? atoi(e) : 2;
+  return v < 2 ? 2 : (v > 3 ? 3 : v);
+}();
+static const bool g_lookahead_cfg = [] {
+  const char* e = getenv("THX_CHOL_LOOKAHEAD");
+  return e ? atoi(e) != 0 : true;
+}();
+// (dense frames: see the look-ahead in factor_impl -- experiment, default 0 = off)
+static const int g_dense_la_max = [] {
+  const char* e = getenv("THX_CHOL_LOOKAHEAD_DENSE_MAX_BATCH");
+  return e ? atoi(e) : 0;
+}();
+static const int g_rl_mode_default = [] {
+  const char* e = getenv("THX_CHOL_RL_LOOKAHEAD");
+  return e ? atoi(e) : -1;   // (-1: by dtype, plan_factor)
+}();
+// (pairs from 128 problems per call on: the pair schedule's chain per two columns is diag, head tile, diag, pair tiles -- one
+//  more dependent launch than two plain columns -- and below ~128 problems the launches are too small to pay for it: n = 1536,
+//  batch 8 / 16 / 32 / 64: 1.62 / 1.64 / 1.67 / 1.85 ms with pairs, 1.42 / 1.44 / 1.50 / 1.73 ms without; 128: 2.25 / 2.23; 256:
+//  3.25 / 3.30 -- profiles/r6/j_ab_small_batch.txt.  Bit-identical either way.)
+static const int g_pair_min_batch_default = [] {
+  const char* e = getenv("THX_CHOL_COLPAIR_MIN_BATCH");
+  return e ? atoi(e) : 128;
+}();
+
+// THE LAUNCH PLAN of a factorisation: every schedule decision factor_impl takes from its arguments, the per-call schedule and the
+// environment defaults -- in one place, so that thx_chol_plan reports exactly what a call with those arguments runs.
+struct FactorPlan {
+  int ntiles;
+  int split_diag_min;    // (the level schedule decides per level with it)
+  bool fused_diag;       // the diagonal phase as one kernel (else SYRK + potrf)
+  int rl_max_batch;
+  bool split;            // the batch dealt over nparts streams
+  int nparts;
+  bool lookahead;        // one part, REST of a column on the second stream (tile-sparse with col_head_host, or the dense experiment)
+  bool rl;               // the right-looking schedule of small dense batches
+  int rl_mode;           // its launch arrangement (0 | 1 | 2)
+  bool rl_fwd_fused;     // ... with the forward substitution riding on it (else FACTOR_NEEDS_FORWARD)
+  bool colpair;          // the column-pair schedule (left-looking, fp32)
+  int hbm;               // the off-diagonal kernels' HB template argument: 0 dense H, HB_MODE_SCATTER, HB_MODE_ROUNDS
+  int f64_wide_max, f64_half_max;
+};
+
+static FactorPlan plan_factor(bool f64, int n, int64_t ld, int B, bool has_damping, bool has_rhs, int64_t ldv, bool y_aligned16,
+                              const thx_tile_pattern* tp, const HBlk* hbp, const thx_level_schedule* ls, const thx_chol_schedule* sched) {
+  FactorPlan p{};
+  const bool use_hb = hbp != nullptr;
+  const bool packed = ld == 0;
+  p.ntiles = (n + TILE - 1) / TILE;
+  const int hb_scatter_max = (sched && sched->hb_scatter_max_pieces >= 0) ? sched->hb_scatter_max_pieces : g_hb_scatter_max_default;
+  const bool hb_sc = use_hb && hbp->bd <= 6 && hbp->max_tile_pieces > 0 && hbp->max_tile_pieces <= hb_scatter_max;
+  p.hbm = !use_hb ? 0 : (hb_sc ? HB_MODE_SCATTER : HB_MODE_ROUNDS);
+  p.f64_wide_max = (sched && sched->f64_wide_max_ktiles >= 0) ? sched->f64_wide_max_ktiles : g_f64_wide_default;
+  p.f64_half_max = (sched && sched->f64_half_max_ktiles >= 0) ? sched->f64_half_max_ktiles : g_f64_half_default;
+  // diagonal phase: chol_syrk_kernel + chol_potrf_kernel from split_diag_min problems per call on (measured, n = 1536: fp32
+  // 45.1 vs 46.0 ms at batch 4096, fp64 101.6 vs 105.2 ms; equal at batch 1024; 3.74 vs 3.51 ms at batch 256 -- the second
+  // launch per column costs more than the chain there), else the fused chol_diag_kernel
+  p.split_diag_min = (sched && sched->split_diag_min_batch >= 0) ? sched->split_diag_min_batch : g_split_diag_min_default;
+  const int column_pairs = (sched && sched->column_pairs >= 0) ? sched->column_pairs : g_column_pairs_default;
+  const int pair_min_batch = (sched && sched->column_pairs_min_batch >= 0) ? sched->column_pairs_min_batch : g_pair_min_batch_default;
+  // (default hand-over to the left-looking schedule, measured at 12 block columns with two launches per column, profiles/r6/ar_:
+  //  fp32 right-looking wins through 64 problems -- batch 40 1.49 -> 1.16 ms, 64 1.66 -> 1.58 --, fp64 through 40; the update
+  //  launches grow with the SQUARE of the block columns, so the limit shrinks with them, down to round 6's first 32)
+  const int rl_auto = !f64 ? min(64, max(32, 768 / max(p.ntiles, 1))) : min(40, max(32, 480 / max(p.ntiles, 1)));
+  p.rl_max_batch = (sched && sched->right_looking_max_batch >= 0) ? sched->right_looking_max_batch
+                   : (g_right_looking_max_default >= 0 ? g_right_looking_max_default : rl_auto);
+  p.fused_diag = B < p.split_diag_min;
+  p.split = g_split_min > 0 && B >= g_split_min && p.ntiles > 1;
+  p.nparts = p.split ? g_nparts_cfg : 1;
+  if (ls) return p;   // (the level schedule: its own launch loop, per level)
+  const bool dense_la = !tp && !packed && B > p.rl_max_batch && B <= g_dense_la_max;
+  p.lookahead = g_lookahead_cfg && !p.split && p.ntiles > 2 && ((tp && tp->col_head_host != nullptr) || dense_la);
+  if (p.lookahead) return p;
+  p.rl = !tp && !packed && !p.split && p.fused_diag && p.ntiles >= 3 && B <= p.rl_max_batch && ld >= (int64_t)p.ntiles * TILE &&
+         (!use_hb || !has_damping || hbp->diag_blk);
+  if (p.rl) {
+    const int m = (sched && sched->right_looking_mode >= 0) ? sched->right_looking_mode : g_rl_mode_default;
+    p.rl_mode = m < 0 ? (f64 ? 2 : 1) : (m > 2 ? 1 : m);
+    p.rl_fwd_fused = has_rhs && (ldv % 4) == 0 && y_aligned16;
+    return p;
+  }
+  p.colpair = column_pairs != 0 && !f64 && !tp && !packed && B >= pair_min_batch;
+  return p;
+}
+
 template <typename T>
 static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damping, int ellipsoidal, double eps,
                        void* L, void* panel, int32_t* info, const void* rhs, void* y, int64_t ldv, hipStream_t st,
@@ -3897,31 +4010,10 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
                        const thx_chol_schedule* sched = nullptr) {
   const bool use_hb = hbp != nullptr;
   const HBlk hb = use_hb ? *hbp : HBlk{nullptr, 0, 0, nullptr, nullptr, nullptr};
-  // how an off-diagonal tile takes its pieces of H: a few per tile (pose graphs) -> added by the matrix cores (hb_scatter); many (a
-  // bundle adjustment's reduced camera system: up to 21 x 21 blocks per tile) or unknown -> gathered through LDS in rounds
-  static const int hb_scatter_max_default = [] {
-    const char* e = getenv("THX_HB_SCATTER_MAX_PIECES");   // (0: always the gather rounds)
-    return e ? atoi(e) : 64;
-  }();
-  const int hb_scatter_max = (sched && sched->hb_scatter_max_pieces >= 0) ? sched->hb_scatter_max_pieces : hb_scatter_max_default;
-  const bool hb_sc = use_hb && hb.bd <= 6 && hb.max_tile_pieces > 0 && hb.max_tile_pieces <= hb_scatter_max;
-  // fp64: the first f64_wide_max block columns (K-loops shorter than that many tiles) take the 8-wave off-diagonal kernel
-  // (chol_offdiag_f64w8_kernel).  Default: ALL of them -- measured +1.0 ... 1.3 % at batch 256 / 1024 / 4096 (n = 1536), growing with
-  // the number of columns that use it (profiles/r6/ae_): four waves per SIMD serve the K-loop better than two; the early columns,
-  // for which the kernel was written, gain nothing.
-  static const int f64_wide_default = [] {
-    const char* e = getenv("THX_F64_WIDE_MAX_KTILES");   // (0: never)
-    return e ? atoi(e) : (1 << 30);
-  }();
-  const int f64_wide_max = (sched && sched->f64_wide_max_ktiles >= 0) ? sched->f64_wide_max_ktiles : f64_wide_default;
-  // ... and the first f64_half_max of them (K-loops shorter than that many tiles) the HALF-TILE kernel (chol_offdiag_f64h_kernel, four
-  // workgroups per CU): measured optimum 6 ... 8 at n = 1536 / batch 4096 (profiles/r6/af_: 90.0 -> 88.5 ms; all twelve columns 89.0)
-  static const int f64_half_default = [] {
-    const char* e = getenv("THX_F64_HALF_MAX_KTILES");   // (0: never)
-    return e ? atoi(e) : 8;
-  }();
-  const int f64_half_max = (sched && sched->f64_half_max_ktiles >= 0) ? sched->f64_half_max_ktiles : f64_half_default;
-  const int ntiles = (n + TILE - 1) / TILE;
+  const FactorPlan P = plan_factor(sizeof(T) == 8, n, ld, B, damping != nullptr, rhs != nullptr, ldv,
+                                   (reinterpret_cast<uintptr_t>(y) % 16) == 0, tp, hbp, ls, sched);
+  const int f64_wide_max = P.f64_wide_max, f64_half_max = P.f64_half_max;
+  const int ntiles = P.ntiles;
   TilePat pat{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr};
   // ld == 0: L is the TILE-PACKED factor (B, nslots, TILE, TILE) of the pattern
   const bool packed = ld == 0;
@@ -3937,18 +4029,8 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
   const int64_t lstride = packed ? (int64_t)tp->nslots * TILE * TILE : (int64_t)ld * ld;   // elements of L per problem
   if (packed && lstride * (int64_t)sizeof(T) > 0x7fffffffLL)
     return fail("thx_chol_factor: tile-packed factor larger than 2 GB per problem");
-  // diagonal phase: chol_syrk_kernel + chol_potrf_kernel from split_diag_min problems per call on (measured, n = 1536: fp32
-  // 45.1 vs 46.0 ms at batch 4096, fp64 101.6 vs 105.2 ms; equal at batch 1024; 3.74 vs 3.51 ms at batch 256 -- the second
-  // launch per column costs more than the chain there), else the fused chol_diag_kernel
-  const int split_diag_min = (sched && sched->split_diag_min_batch >= 0) ? sched->split_diag_min_batch : g_split_diag_min_default;
-  const int column_pairs = (sched && sched->column_pairs >= 0) ? sched->column_pairs : g_column_pairs_default;
-  // (default hand-over to the left-looking schedule, measured at 12 block columns with two launches per column, profiles/r6/ar_:
-  //  fp32 right-looking wins through 64 problems -- batch 40 1.49 -> 1.16 ms, 64 1.66 -> 1.58 --, fp64 through 40; the update
-  //  launches grow with the SQUARE of the block columns, so the limit shrinks with them, down to round 6's first 32)
-  const int rl_auto = sizeof(T) == 4 ? min(64, max(32, 768 / max(ntiles, 1))) : min(40, max(32, 480 / max(ntiles, 1)));
-  const int rl_max_batch = (sched && sched->right_looking_max_batch >= 0) ? sched->right_looking_max_batch
-                           : (g_right_looking_max_default >= 0 ? g_right_looking_max_default : rl_auto);
-  const bool fused_diag = B < split_diag_min;
+  const int split_diag_min = P.split_diag_min;
+  const bool fused_diag = P.fused_diag;
   const size_t dsm = fused_diag ? DiagSmem<T>::bytes(rhs ? ntiles * TILE : 0) : SyrkSmem<T>::bytes(rhs ? ntiles * TILE : 0);
   if (dsm > LDS_LIMIT) return fail("thx_chol_factor: n too large for the fused forward substitution (LDS)");
   if (ls && (!packed || !use_hb)) return fail("thx_chol_factor_levels: tile-packed factor + block-compact H");
@@ -4033,18 +4115,8 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
     hipStream_t s;
     int b0, nb;
   };
-  static const int split_min = [] {
-    const char* e = getenv("THX_CHOL_SPLIT_MIN");  // batch size from which the multi-stream schedule is used (0: never)
-    return e ? atoi(e) : 1024;
-  }();
-  // number of parts (streams): 2; THX_CHOL_PARTS=3 staggers three thirds (measured)
-  static const int nparts_cfg = [] {
-    const char* e = getenv("THX_CHOL_PARTS");
-    const int v = e ? atoi(e) : 2;
-    return v < 2 ? 2 : (v > 3 ? 3 : v);
-  }();
-  const bool split = split_min > 0 && B >= split_min && ntiles > 1;
-  const int nparts = split ? nparts_cfg : 1;
+  const bool split = P.split;
+  const int nparts = P.nparts;
   Half halves[3] = {{st, 0, B}, {st, 0, 0}, {st, 0, 0}};
   if (split) {
     if (!ds.ev_fork) hipEventCreateWithFlags(&ds.ev_fork, hipEventDisableTiming);
@@ -4070,7 +4142,7 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
     if (use_hb) x.blocks = static_cast<const T*>(hb.blocks) + (int64_t)h.b0 * hb.bstride;
     return x;
   };
-  const int hbm = !use_hb ? 0 : (hb_sc ? HB_MODE_SCATTER : HB_MODE_ROUNDS);   // the off-diagonal kernels' HB template argument
+  const int hbm = P.hbm;   // the off-diagonal kernels' HB template argument
   auto launch_off = [&](const Half& h, int j, int i_first, int nrt) {
     const int Bpad = (h.nb + 7) / 8 * 8;
     const int64_t mo = (int64_t)h.b0 * lstride, po = (int64_t)h.b0 * ntiles * TILE * TILE;
@@ -4253,10 +4325,6 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
   //   diag(j+1) after HEAD(j) [stream order] -- its other inputs, rows j + 1 of columns < j, were waited for by HEAD(j).
   // Tile-sparse: only if the host put tile (j + 1, j) FIRST in column j's entry list (col_head_host); otherwise the column runs
   // as before (diag(j + 1) waits for all of column j).  Same kernels, same arithmetic: bit-identical results.
-  static const bool lookahead_cfg = [] {
-    const char* e = getenv("THX_CHOL_LOOKAHEAD");
-    return e ? atoi(e) != 0 : true;
-  }();
   // Measured (profiles/r4/c_ab_lookahead_small_batch_factor.txt, same box, two rounds): the banded reduced camera system of the
   // bundle-adjustment config (3072 columns, batch 256, 158 of 300 tiles) 6.82 -> 6.60 ms; DENSE frames do not gain (n = 1536:
   // batch 256 3.5 ms either way, batch 512 6.2 -> 6.4 ms; n = 3072 batch 256 21.6 -> 21.8 ms: REST(j) of a dense column is most
@@ -4265,12 +4333,7 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
   // 0 = off): the launches of a block column do not fill the chip there either (batch 64: diag(j) is 64 workgroups, REST(j)
   // 64 (10 - j)).  MEASURED, NOT A WIN (profiles/r6/ai_: batch 64 1.66 -> 1.88 ms, 128 2.18 -> 2.22, 256 3.16 -> 3.27): the whole
   // off-diagonal launch is one round of workgroups, HEAD(j) alone takes as long -- the chain is the serial K-loops.
-  static const int dense_la_max = [] {
-    const char* e = getenv("THX_CHOL_LOOKAHEAD_DENSE_MAX_BATCH");
-    return e ? atoi(e) : 0;
-  }();
-  const bool dense_la = !tp && !packed && B > rl_max_batch && B <= dense_la_max;
-  const bool lookahead = lookahead_cfg && !split && ntiles > 2 && ((tp && tp->col_head_host != nullptr) || dense_la);
+  const bool lookahead = P.lookahead;
   static const bool lpt_cfg = [] {
     const char* e = getenv("THX_CHOL_LPT");
     return e ? atoi(e) != 0 : true;
@@ -4331,8 +4394,7 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
   // one in the last bits (tests: against LAPACK and against the left-looking solution).  The forward substitution runs as its
   // own kernel afterwards.
   {
-    if (!tp && !packed && !split && fused_diag && ntiles >= 3 && B <= rl_max_batch && ld >= (int64_t)ntiles * TILE &&
-        (!use_hb || !damping || hb.diag_blk)) {
+    if (P.rl) {
       if (dsm > ds.attr_diag[ti][0]) {   // (the later columns run the dense-frame instance on the L frame whatever H is)
         hipFuncSetAttribute(reinterpret_cast<const void*>(chol_diag_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dsm);
         ds.attr_diag[ti][0] = dsm;
@@ -4341,7 +4403,7 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
       const int Bpad = (B + 7) / 8 * 8;
       // forward substitution riding on the schedule (vectors with 16-byte rows; else its own kernel afterwards, FACTOR_NEEDS_FORWARD): y starts
       // as a copy of g; chol_diag(j) turns block j into y_j in place, the substitution tiles of column j update the blocks below
-      const bool fwd_fused = rhs && (ldv % 4) == 0 && (reinterpret_cast<uintptr_t>(y) % 16) == 0;
+      const bool fwd_fused = P.rl_fwd_fused;
       if (fwd_fused) {
         hipMemcpy2DAsync(y, (size_t)ldv * sizeof(T), rhs, (size_t)ldv * sizeof(T), (size_t)n * sizeof(T), (size_t)B, hipMemcpyDeviceToDevice, st);
         rhs = y;
@@ -4380,11 +4442,7 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
         pu.rl = 2 + jc;
         off(first && use_hb, first ? (const T*)H : Lc, jc, 0, m * (m + 1) / 2, pu);
       };
-      static const int rl_la_cfg = [] {
-        const char* e = getenv("THX_CHOL_RL_LOOKAHEAD");
-        return e ? atoi(e) : -1;
-      }();
-      const int la = rl_la_cfg < 0 ? (sizeof(T) == 8 ? 2 : 1) : (rl_la_cfg > 2 ? 1 : rl_la_cfg);
+      const int la = P.rl_mode;
       // block column 0: the kernels as they are (no earlier columns), reading H
       launch_diag_n(h, 0, 1, true, dsm);   // (with a right-hand side: y_0 = W_00 g_0 -- kept when the forward substitution is fused)
       off(use_hb, (const T*)H, 0, 1, ntiles - 1, p0);
@@ -4458,15 +4516,11 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
         if (la == 0) {
           off(false, Lc, j, j + 1, ntiles - 1 - j, p1);
           upd(j, false);
-        } else if (la == 1) {
-          if (j == 1) {   // (column 1's tiles carry column 0's update already; its own update is folded into column 2's launches)
-            off(false, Lc, 1, 2, ntiles - 2, p1);
-          } else {
-            const int nsub = ntiles - 1 - j;
-            TilePat pc = pd;
-            pc.rl_nsub = nsub;
-            off(false, Lc, j, j + 1, nsub + nsub * (nsub + 1) / 2, pc);
-          }
+        } else if (la == 1) {   // (from column 2 on: column 1 ran straight from H above)
+          const int nsub = ntiles - 1 - j;
+          TilePat pc = pd;
+          pc.rl_nsub = nsub;
+          off(false, Lc, j, j + 1, nsub + nsub * (nsub + 1) / 2, pc);
         } else {
           if (upd_pending) {   // the substitutions read the tiles update(j - 1) wrote
             hipStreamWaitEvent(st, ds.ev_rest, 0);
@@ -4490,15 +4544,7 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
       return (rhs && !fwd_fused) ? FACTOR_NEEDS_FORWARD : 0;   // (the caller runs the forward substitution as its own kernel)
     }
   }
-  // (pairs from 128 problems per call on: the pair schedule's chain per two columns is diag, head tile, diag, pair tiles -- one
-  //  more dependent launch than two plain columns -- and below ~128 problems the launches are too small to pay for it: n = 1536,
-  //  batch 8 / 16 / 32 / 64: 1.62 / 1.64 / 1.67 / 1.85 ms with pairs, 1.42 / 1.44 / 1.50 / 1.73 ms without; 128: 2.25 / 2.23; 256:
-  //  3.25 / 3.30 -- profiles/r6/j_ab_small_batch.txt.  Bit-identical either way.)
-  static const int pair_min_batch = [] {
-    const char* e = getenv("THX_CHOL_COLPAIR_MIN_BATCH");
-    return e ? atoi(e) : 128;
-  }();
-  const bool colpair = column_pairs != 0 && sizeof(T) == 4 && !tp && !packed && B >= pair_min_batch;
+  const bool colpair = P.colpair;   // (from column_pairs_min_batch problems per call on, see plan_factor)
   // STAGGERED PIPELINE (THX_CHOL_LAG_COLS=<columns>, THX_CHOL_PIPE=<parts per stream>; experiment, default off): the batch in
   // 2 x PIPE parts, even parts one after the other on the caller's stream, odd parts on the auxiliary stream which starts LAG
   // block columns behind -- so that one stream's early columns (short K-loops: substitution / store bound, 0.4 - 0.7 of peak per
@@ -4775,6 +4821,33 @@ int thx_chol_factor_hblocks(const thx_hblock_layout* layout, const void* Hc, int
                                          as_stream(stream), pattern, &hb, nullptr, schedule),
                return factor_then_forward<double>(nullptr, ld, n, B, damping, ellipsoidal, damping_eps, L, Winv, info, rhs, y, ldv,
                                           as_stream(stream), pattern, &hb, nullptr, schedule));
+  return 0;
+}
+
+int thx_chol_plan(int32_t n, int64_t ld, int32_t B, int dtype, int has_damping, int has_rhs, int64_t ldv,
+                  const thx_hblock_layout* layout, const thx_chol_schedule* schedule, thx_chol_plan_info* out) {
+  if (!out) return fail("thx_chol_plan: null pointer");
+  if (n <= 0 || B <= 0 || ld < n || (ld % 32) != 0) return fail("thx_chol_plan: need n>0, B>0, ld>=n, ld%32==0 (dense factor frame)");
+  if (has_rhs && ldv < n) return fail("thx_chol_plan: ldv < n");
+  if (dtype != THX_F32 && dtype != THX_F64) return fail("bad dtype");
+  if (layout && layout->ntiles != (n + TILE - 1) / TILE) return fail("thx_chol_plan: the block layout is not this matrix's");
+  const HBlk hb{nullptr, 0, layout ? layout->bd : 0, nullptr, nullptr, nullptr, layout ? layout->diag_blk : nullptr,
+                layout ? layout->max_tile_pieces : 0};
+  const FactorPlan p = plan_factor(dtype == THX_F64, n, ld, B, has_damping != 0, has_rhs != 0, ldv, true, nullptr,
+                                   layout ? &hb : nullptr, nullptr, schedule);
+  out->right_looking = p.rl;
+  out->right_looking_mode = p.rl ? p.rl_mode : -1;
+  out->split_diag = !p.fused_diag;
+  out->nparts = p.nparts;
+  out->column_pairs = p.colpair;
+  // (fp64 off-diagonal launches of the column-by-column schedule: block columns 0 .. ntiles - 2; the half-tile kernel first, then the
+  //  eight-wave one -- launch_off; neither takes the LDS gather rounds of a block list)
+  const int cols = p.ntiles - 1;
+  const bool f64_lanes = dtype == THX_F64 && !p.rl && p.hbm != HB_MODE_ROUNDS;
+  const int half = f64_lanes ? std::max(0, std::min(p.f64_half_max, cols)) : 0;
+  out->f64_half_cols = half;
+  out->f64_wide_cols = f64_lanes ? std::max(0, std::min(p.f64_wide_max, cols) - half) : 0;
+  out->forward_fused = has_rhs && (!p.rl || p.rl_fwd_fused);
   return 0;
 }
 

@@ -146,6 +146,20 @@ def round_up(x, m):
     return (x + m - 1) // m * m
 
 
+def chol_plan(n, ld, B, dtype, damping=True, rhs=True, ldv=None, layout=None, schedule=None) -> dict:
+    """thx_chol_plan (include/theseus_hip.h): which schedule a dense-frame factorisation of these arguments takes -- right-looking and
+    its mode, split diagonal phase, streams, column pairs, fp64 half-tile / eight-wave block columns, fused forward substitution.
+    Host only: no device is touched.  ``layout``: a thx_hblock_layout (block-compact H); ``schedule``: a thx_chol_schedule (None:
+    the defaults)."""
+    import ctypes
+    lib = _lib.load()
+    out = _lib.CholPlanInfo()
+    _lib.check(lib.thx_chol_plan(int(n), int(ld), int(B), _lib.dtype_code(dtype), int(bool(damping)), int(bool(rhs)),
+                                 int(n if ldv is None else ldv), None if layout is None else ctypes.byref(layout),
+                                 None if schedule is None else ctypes.byref(schedule), ctypes.byref(out)), "thx_chol_plan")
+    return {k: int(getattr(out, k)) for k, _ in _lib.CholPlanInfo._fields_}
+
+
 GROUP_RECORD = {"SE3": (12, 6), "SO3": (9, 3), "SE2": (4, 3), "SO2": (2, 1)}   # (scalars per record, dof)
 
 
@@ -233,7 +247,7 @@ class HipKernels:
         self.lib = _lib.load()
         # per-call schedule of the factorisations (include/theseus_hip.h: thx_chol_schedule), handed to every thx_chol_factor* call
         # of THIS kernels object: -1 = the library default.  The library itself keeps no schedule state.
-        self.chol_schedule = _lib.CholSchedule(-1, -1, -1, -1, -1, -1)
+        self.chol_schedule = _lib.CholSchedule(-1, -1, -1, -1, -1, -1, -1, -1)
 
     def _sched(self):
         import ctypes
@@ -754,6 +768,14 @@ class HipKernels:
         self.chol_schedule.column_pairs = int(on)
         return prev
 
+    def chol_column_pairs_min_batch(self, min_batch: int) -> int:
+        """Schedule of THIS kernels object's fp32 dense-frame factorisations (thx_chol_schedule.column_pairs_min_batch): the
+        column-pair schedule is taken from ``min_batch`` problems per call on (0 at any batch, -1 the library default: 128).
+        Returns the previous setting."""
+        prev = int(self.chol_schedule.column_pairs_min_batch)
+        self.chol_schedule.column_pairs_min_batch = int(min_batch)
+        return prev
+
     def chol_right_looking_max_batch(self, max_batch: int) -> int:
         """Schedule of THIS kernels object's fp32 dense-frame factorisations (thx_chol_schedule.right_looking_max_batch): batches of
         at most ``max_batch`` problems take the right-looking schedule (0 never, -1 the library default: by dtype and size -- fp32 64 /
@@ -761,6 +783,19 @@ class HipKernels:
         prev = int(self.chol_schedule.right_looking_max_batch)
         self.chol_schedule.right_looking_max_batch = int(max_batch)
         return prev
+
+    def chol_right_looking_mode(self, mode: int) -> int:
+        """Schedule of THIS kernels object's right-looking factorisations (thx_chol_schedule.right_looking_mode): 0 three launches
+        per block column, 1 two (block column 1 straight from H), 2 the trailing update on the second stream (-1 the library
+        default: 1 for fp32, 2 for fp64).  Returns the previous setting."""
+        prev = int(self.chol_schedule.right_looking_mode)
+        self.chol_schedule.right_looking_mode = int(mode)
+        return prev
+
+    def chol_plan(self, n, ld, B, dtype, damping=True, rhs=True, ldv=None, layout=None):
+        """thx_chol_plan: the schedule a dense-frame factorisation with these arguments and THIS object's schedule takes (host
+        only; ``layout``: a device block layout for thx_chol_factor_hblocks).  Returns a dict of thx_chol_plan_info's fields."""
+        return chol_plan(n, ld, B, dtype, damping=damping, rhs=rhs, ldv=ldv, layout=layout, schedule=self.chol_schedule)
 
     def chol_hb_scatter_max_pieces(self, max_pieces: int) -> int:
         """Schedule of THIS kernels object's factorisations from a block-compact H (thx_chol_schedule.hb_scatter_max_pieces): layouts
