@@ -156,6 +156,15 @@ int thx_pgso2_jacobians(const thx_pg_structure* s, const thx_pg_data* d, void* J
 int thx_so2_retract(const void* poses, const void* delta, int64_t ldd, double step, const uint8_t* ignore_mask, void* out,
                     int32_t P, int32_t B, int dtype, void* stream);
 int thx_so2_op(int op, const void* a, const void* b, void* out, void* jac, int64_t N, int dtype, void* stream);
+/* implicit backward on SO2 graphs (thx_se3_retract_vjp / thx_pg_vjp below, with 2-element records [cos, sin], 1-vectors; no eps
+ * argument): plain derivatives of the so2.py closed forms -- the reference has no custom backward for SO2: compose (:225-231),
+ * inverse (:233-235), log = atan2 (:206-223), exp (:167-186, update_from_angle :96-100); Jlog / Jexp / adjoint are constant ones
+ * (:116-117, :180-185, :210-219).  grad_meas / grad_prior_target (E|K,B,2), grad_w_between / grad_w_prior (E|K,B). */
+int thx_so2_retract_vjp(const void* poses, const void* delta, int64_t ldd, double step, const void* grad_out,
+                        void* grad_delta, int64_t ldg, int32_t P, int32_t B, int dtype, void* stream);
+int thx_pgso2_vjp(const thx_pg_structure* s, const thx_pg_data* d, const void* w, int64_t ldw, void* grad_meas,
+                  void* grad_w_between, void* grad_prior_target, void* grad_w_prior, void* grad_log_radius_between,
+                  void* grad_log_radius_prior, int dtype, void* stream);
 
 /* ---- SO3 variables (rotation-only graphs): theseus/geometry/so3.py over torchlie's SO3 closed forms
  *      (torchlie/torchlie/functional/so3_impl.py:220-261 exp, :270-320 Jexp, :390-433 log, :442-479 Jlog; adjoint = R,
@@ -530,6 +539,12 @@ int thx_pgso3_unroll_vjp(const thx_pg_structure* s, const thx_pg_data* d, const 
                          const void* ellipsoidal_damping, void* grad_pose_i, void* grad_pose_j, void* grad_meas,
                          void* grad_w_between, void* grad_pose_prior, void* grad_prior_target, void* grad_w_prior,
                          void* grad_log_radius_between, void* grad_log_radius_prior, int dtype, const thx_lie_eps* eps, void* stream);
+/* The 1-dof twin (SO2: 2-element records [cos, sin], plain autograd through theseus/geometry/so2.py :206-235, Jlog = Ad = 1): same
+ * arguments without eps, 1-vectors for the weights (grad_w_between (E,B), grad_w_prior (K,B)). */
+int thx_pgso2_unroll_vjp(const thx_pg_structure* s, const thx_pg_data* d, const void* w, int64_t ldw, const void* delta, int64_t ldd,
+                         const void* ellipsoidal_damping, void* grad_pose_i, void* grad_pose_j, void* grad_meas,
+                         void* grad_w_between, void* grad_pose_prior, void* grad_prior_target, void* grad_w_prior,
+                         void* grad_log_radius_between, void* grad_log_radius_prior, int dtype, void* stream);
 
 /* ---- Bundle adjustment (BASELINE.json configs[3]; examples/bundle_adjustment.py:103-160): camera poses SE3 + Point3
  *      world points, costs = Reprojection (theseus/embodied/measurements/reprojection.py:54-94, dim 2; SE3.transform_from

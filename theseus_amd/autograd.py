@@ -27,7 +27,7 @@ def pg_vjp_grads(K, packed, t, w):
     B = t.poses.shape[1]
     E, Kp = packed.structure.num_edges, packed.structure.num_priors
     new = lambda *s: torch.empty(*s, dtype=w.dtype, device=w.device)  # noqa: E731
-    gs, dof = t.poses.shape[2:], packed.dof   # group record shape (3,4) | (4,) | (3,3), tangent size 6 | 3 | 3
+    gs, dof = t.poses.shape[2:], packed.dof   # group record shape (3,4) | (4,) | (3,3) | (2,), tangent size 6 | 3 | 3 | 1
     g_meas, g_wb = new(max(E, 1), B, *gs), new(max(E, 1), B, dof)
     g_tgt, g_wp = new(max(Kp, 1), B, *gs), new(max(Kp, 1), B, dof)
     g_lrb = new(max(E, 1), B, 1) if t.robust_between else None
@@ -90,7 +90,8 @@ class ImplicitStep(torch.autograd.Function):
 def compose_left_backward(K, group: str, X, delta, step: float, G):
     """grad w.r.t. X of X_new = X exp(step * delta) given G = grad_X_new (raw entries), as the reference's autograd produces it:
     SE3 / SO3 -- torchlie's Compose.backward (se3_impl.py:739-747, so3_impl.py:702-707): the plain matrix rule
-    [G_R E_R^T + G_t E_t^T | G_t] / G E^T; SE2 -- plain autograd through theseus/geometry/se2.py's compose on [x, y, cos, sin]."""
+    [G_R E_R^T + G_t E_t^T | G_t] / G E^T; SE2 / SO2 -- plain autograd through theseus/geometry/se2.py's compose on [x, y, cos, sin]
+    / so2.py's compose (:225-231) on [cos, sin]."""
     P, B = X.shape[:2]
     dof = delta.shape[1] // P
     xi = (step * delta).view(B, P, dof).transpose(0, 1).reshape(P * B, dof).contiguous()
@@ -100,6 +101,13 @@ def compose_left_backward(K, group: str, X, delta, step: float, G):
     if group == "SO3":
         E = K.so3_exp(xi).view(P, B, 3, 3)
         return G @ E.transpose(-1, -2)
+    if group == "SO2":
+        ec, es = K.so2_exp(xi).view(P, B, 2).unbind(-1)
+        gc, gs = G.unbind(-1)
+        # c' = c ec - s es,  s' = s ec + c es
+        return torch.stack([gc * ec + gs * es, -gc * es + gs * ec], -1)
+    if group != "SE2":
+        raise ValueError(f"compose_left_backward: unknown group {group}")
     E = K.se2_exp(xi).view(P, B, 4)
     ex, ey, ec, es = E.unbind(-1)
     gx, gy, gc, gs = G.unbind(-1)
@@ -108,7 +116,7 @@ def compose_left_backward(K, group: str, X, delta, step: float, G):
 
 
 class PGUnrolledIteration(torch.autograd.Function):
-    """One DIFFERENTIATED iteration of an SE3 / SE2 / SO3 pose graph (BackwardMode.UNROLL / TRUNCATED,
+    """One DIFFERENTIATED iteration of an SE3 / SE2 / SO3 / SO2 pose graph (BackwardMode.UNROLL / TRUNCATED,
     theseus/optimizer/nonlinear/nonlinear_least_squares.py:223-292: the Hessian is part of the graph):
     ``X_new = X exp(step * delta)``, ``delta = (H(X, theta) + lambda I)^-1 g(X, theta)``.  Forward: the optimizer's own kernels
     at the detached iterate (assemble, damped factorisation, solves, retraction).  Backward, given grad_X_new (raw 3 x 4 entries):
@@ -170,7 +178,7 @@ class PGUnrolledIteration(torch.autograd.Function):
         s = packed.structure
         E_, Kp = s.num_edges, s.num_priors
         new = lambda *sh: torch.zeros(*sh, dtype=dt, device=dev)  # noqa: E731
-        rec, dof = tuple(X.shape[2:]), packed.dof       # group record (3,4) | (4,) | (3,3), tangent size 6 | 3 | 3
+        rec, dof = tuple(X.shape[2:]), packed.dof       # group record (3,4) | (4,) | (3,3) | (2,), tangent size 6 | 3 | 3 | 1
         gpi, gpj, gm, gwb = new(max(E_, 1), B, *rec), new(max(E_, 1), B, *rec), new(max(E_, 1), B, *rec), new(max(E_, 1), B, dof)
         gpp, gt, gwp = new(max(Kp, 1), B, *rec), new(max(Kp, 1), B, *rec), new(max(Kp, 1), B, dof)
         glb = new(max(E_, 1), B, 1) if t.robust_between else None

@@ -169,6 +169,18 @@ def group_of(poses: torch.Tensor) -> str:
     return "SO3" if poses.shape[-1] == 3 else "SE3"
 
 
+_RECORD_GROUP = {(3, 4): "SE3", (3, 3): "SO3", (4,): "SE2", (2,): "SO2"}
+
+
+def vjp_group(records: torch.Tensor) -> str:
+    """The group of a (P|E|K, B, *record) buffer for the backward entry points: only an exact record shape names a group (no
+    fall-through to another group's kernel)."""
+    grp = _RECORD_GROUP.get(tuple(records.shape[2:]))
+    if grp is None:
+        raise ValueError(f"no VJP kernel for records of shape {tuple(records.shape[2:])}")
+    return grp
+
+
 @dataclass
 class PGTensors:
     """Per-call tensors of a pose-graph objective in the entity-major device layout."""
@@ -674,22 +686,19 @@ class HipKernels:
     # ---- implicit backward ----------------------------------------------------------------------
     def retract_vjp(self, poses, delta, step, grad_out, grad_delta):
         """grad_X_new -> grad_delta of X exp(step * delta); the group is read off the record shape."""
-        if group_of(poses) == "SO3":
-            P, B = poses.shape[:2]
-            dt = poses.dtype
-            _lib.check(self.lib.thx_so3_retract_vjp(_lib.ptr(poses), _lib.ptr(delta), delta.stride(0), float(step),
-                                                    _lib.ptr(grad_out), _lib.ptr(grad_delta), grad_delta.stride(0), P, B,
-                                                    _lib.dtype_code(dt), lie_eps(dt), _lib.stream_ptr(poses.device)),
-                       "thx_so3_retract_vjp")
-            return
-        if poses.dim() == 4:
+        grp = vjp_group(poses)
+        if grp == "SE3":
             return self.se3_retract_vjp(poses, delta, step, grad_out, grad_delta)
         P, B = poses.shape[:2]
         dt = poses.dtype
-        _lib.check(self.lib.thx_se2_retract_vjp(_lib.ptr(poses), _lib.ptr(delta), delta.stride(0), float(step),
-                                                _lib.ptr(grad_out), _lib.ptr(grad_delta), grad_delta.stride(0), P, B,
-                                                _lib.dtype_code(dt), se2_eps(dt), _lib.stream_ptr(poses.device)),
-                   "thx_se2_retract_vjp")
+        common = (_lib.ptr(poses), _lib.ptr(delta), delta.stride(0), float(step), _lib.ptr(grad_out), _lib.ptr(grad_delta),
+                  grad_delta.stride(0), P, B, _lib.dtype_code(dt))
+        if grp == "SO3":
+            _lib.check(self.lib.thx_so3_retract_vjp(*common, lie_eps(dt), _lib.stream_ptr(poses.device)), "thx_so3_retract_vjp")
+        elif grp == "SE2":
+            _lib.check(self.lib.thx_se2_retract_vjp(*common, se2_eps(dt), _lib.stream_ptr(poses.device)), "thx_se2_retract_vjp")
+        else:
+            _lib.check(self.lib.thx_so2_retract_vjp(*common, _lib.stream_ptr(poses.device)), "thx_so2_retract_vjp")
 
     def se3_retract_vjp(self, poses, delta, step, grad_out, grad_delta):
         P, B = poses.shape[:2]
@@ -700,34 +709,28 @@ class HipKernels:
                    "thx_se3_retract_vjp")
 
     def pg_vjp(self, s: DeviceStructure, t: PGTensors, w, g_meas, g_wb, g_tgt, g_wp, poses=None, g_lrb=None, g_lrp=None):
+        """thx_pg_vjp / thx_pg2_vjp / thx_pgso3_vjp / thx_pgso2_vjp (include/theseus_hip.h), chosen by the group of the records."""
         d = t.c_struct(poses)
         dt = w.dtype
-        if t.group == "SO3":
-            _lib.check(self.lib.thx_pgso3_vjp(s.c, d, _lib.ptr(w), w.stride(0), _lib.ptr(g_meas), _lib.ptr(g_wb),
-                                              _lib.ptr(g_tgt), _lib.ptr(g_wp), _lib.ptr(g_lrb), _lib.ptr(g_lrp),
-                                              _lib.dtype_code(dt), lie_eps(dt), _lib.stream_ptr(w.device)), "thx_pgso3_vjp")
-            return
-        if t.se2:
-            _lib.check(self.lib.thx_pg2_vjp(s.c, d, _lib.ptr(w), w.stride(0), _lib.ptr(g_meas), _lib.ptr(g_wb),
-                                            _lib.ptr(g_tgt), _lib.ptr(g_wp), _lib.ptr(g_lrb), _lib.ptr(g_lrp),
-                                            _lib.dtype_code(dt), se2_eps(dt), _lib.stream_ptr(w.device)), "thx_pg2_vjp")
-            return
-        _lib.check(self.lib.thx_pg_vjp(s.c, d, _lib.ptr(w), w.stride(0), _lib.ptr(g_meas), _lib.ptr(g_wb),
-                                       _lib.ptr(g_tgt), _lib.ptr(g_wp), _lib.ptr(g_lrb), _lib.ptr(g_lrp),
-                                       _lib.dtype_code(dt), lie_eps(dt),
-                                       _lib.stream_ptr(w.device)), "thx_pg_vjp")
+        grp = vjp_group(t.poses if poses is None else poses)
+        fn = {"SE3": "thx_pg_vjp", "SE2": "thx_pg2_vjp", "SO3": "thx_pgso3_vjp", "SO2": "thx_pgso2_vjp"}[grp]
+        eps = {"SE3": (lie_eps(dt),), "SE2": (se2_eps(dt),), "SO3": (lie_eps(dt),), "SO2": ()}[grp]
+        _lib.check(getattr(self.lib, fn)(s.c, d, _lib.ptr(w), w.stride(0), _lib.ptr(g_meas), _lib.ptr(g_wb), _lib.ptr(g_tgt),
+                                         _lib.ptr(g_wp), _lib.ptr(g_lrb), _lib.ptr(g_lrp), _lib.dtype_code(dt), *eps,
+                                         _lib.stream_ptr(w.device)), fn)
 
     def pg_unroll_vjp(self, s: DeviceStructure, t: PGTensors, w, delta, g_pose_i, g_pose_j, g_meas, g_wb, g_pose_p, g_tgt, g_wp,
                       poses=None, ell_damping=None, g_lrb=None, g_lrp=None):
-        """thx_pg_unroll_vjp / thx_pg2_unroll_vjp / thx_pgso3_unroll_vjp (include/theseus_hip.h): the per-cost backward of one
-        differentiated iteration of an SE3 / SE2 / SO3 pose graph."""
+        """thx_pg_unroll_vjp / thx_pg2_unroll_vjp / thx_pgso3_unroll_vjp / thx_pgso2_unroll_vjp (include/theseus_hip.h): the per-cost
+        backward of one differentiated iteration of an SE3 / SE2 / SO3 / SO2 pose graph."""
         dt = w.dtype
-        fn, eps = {"SE3": ("thx_pg_unroll_vjp", lie_eps), "SE2": ("thx_pg2_unroll_vjp", se2_eps),
-                   "SO3": ("thx_pgso3_unroll_vjp", lie_eps)}[t.group]
+        grp = vjp_group(t.poses if poses is None else poses)
+        fn = {"SE3": "thx_pg_unroll_vjp", "SE2": "thx_pg2_unroll_vjp", "SO3": "thx_pgso3_unroll_vjp", "SO2": "thx_pgso2_unroll_vjp"}[grp]
+        eps = {"SE3": (lie_eps(dt),), "SE2": (se2_eps(dt),), "SO3": (lie_eps(dt),), "SO2": ()}[grp]
         _lib.check(getattr(self.lib, fn)(s.c, t.c_struct(poses), _lib.ptr(w), w.stride(0), _lib.ptr(delta), delta.stride(0),
                                          _lib.ptr(ell_damping), _lib.ptr(g_pose_i), _lib.ptr(g_pose_j), _lib.ptr(g_meas), _lib.ptr(g_wb),
                                          _lib.ptr(g_pose_p), _lib.ptr(g_tgt), _lib.ptr(g_wp), _lib.ptr(g_lrb), _lib.ptr(g_lrp),
-                                         _lib.dtype_code(dt), eps(dt), _lib.stream_ptr(w.device)), fn)
+                                         _lib.dtype_code(dt), *eps, _lib.stream_ptr(w.device)), fn)
 
     # ---- dense solver ---------------------------------------------------------------------------
     def chol_factor(self, H, n, damping, ellipsoidal, damping_eps, L, panels, info, rhs=None, y=None):

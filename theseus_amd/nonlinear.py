@@ -678,9 +678,6 @@ class NonlinearLeastSquares(abc.ABC):
         if packed.group == "Euclidean":   # generic objectives: theseus_amd/euclidean.py (torch forms g, cached-factor solve)
             with torch.set_grad_enabled(outer_grad):
                 return packed.implicit_step(self, float(step), kwargs)
-        if packed.group not in ("SE3", "SE2", "SO3"):
-            raise NotImplementedError("HIP back end: backward_mode='implicit' is fused for SE3 / SE2 / SO3 pose graphs and "
-                                      f"bundle adjustment (got {packed.group}); there is no autograd/CPU fallback.")
         with torch.set_grad_enabled(outer_grad):
             packed.flush_variables()
             packed.sync(force=True)  # re-pack the auxiliary tensors WITH their autograd history

@@ -187,8 +187,9 @@ class _FusedUnrolledSolve(torch.autograd.Function):
 
 
 class _HipRetract(torch.autograd.Function):
-    """X_new = X exp(delta) on the packed pose buffer (thx_se3_retract / thx_se2_retract), differentiable w.r.t. delta:
-    the backward is thx_se3_retract_vjp / thx_se2_retract_vjp.  (X itself is the detached iterate of the no-grad loop.)"""
+    """X_new = X exp(delta) on the packed pose buffer (thx_se3_retract / thx_se2_retract / thx_so3_retract / thx_so2_retract),
+    differentiable w.r.t. delta: the backward is the group's thx_*_retract_vjp (HipKernels.retract_vjp picks it by the record shape).
+    (X itself is the detached iterate of the no-grad loop.)"""
 
     @staticmethod
     def forward(ctx, packed, poses, delta, mask):
