@@ -304,39 +304,38 @@ int thx_se3_retract(const void* poses, const void* delta, int64_t ldd, double st
  *          factorisation in the same workgroup) or SPLIT into an MFMA-only SYRK kernel and a one-wave-per-tile kernel that keeps
  *          the tile in registers (eight tiles per CU in their pivot chains instead of three).  The split pays from this many
  *          problems per launch on (the level schedule: problems x block columns of the level); 0 = always split, INT32_MAX =
- *          never; < 0: the default (2048, or the environment's THX_CHOL_SPLIT_DIAG_MIN read once at load time).
+ *          never; < 0: the default (2048).
  *        column_pairs: fp32 factorisations on dense factor frames of at least column_pairs_min_batch problems (and not on the
  *          right-looking schedule), two block columns at a time -- diag(j), tile (j+1, j), diag(j+1), then ONE workgroup per row tile
  *          i >= j+2 produces L_ij and L_i,j+1, streaming row panel L_i,0:j from HBM once for both; 1 on, 0 off, < 0: the default
- *          (on, or THX_CHOL_COLPAIR).  Bit-identical to the column-by-column schedule.
+ *          (on).  Bit-identical to the column-by-column schedule.
  *        right_looking_max_batch: factorisations (fp32 and fp64) on dense factor frames (no tile pattern, ld >= ntiles * THX_TILE) of at most
  *          this many problems take the RIGHT-LOOKING schedule -- per block column the tile factorisation, the substitutions and
  *          one workgroup per tile of the trailing matrix, each a single 128^3 product -- instead of the left-looking one whose
  *          serial K-loops leave the chip empty at 8 ... 64 problems (the reference's published batch range,
  *          evaluations/pose_graph_synthetic.sh:7).  Another summation order: the factor agrees with the left-looking one to
- *          rounding, not bit for bit.  0 = never; < 0: the default (THX_CHOL_RL_MAX_BATCH, else by dtype and size: fp32 64 problems and
+ *          rounding, not bit for bit.  0 = never; < 0: the default (by dtype and size: fp32 64 problems and
  *          fp64 40 up to 12 block columns, shrinking to 32 from 24 block columns on -- min(64, max(32, 768 / ntiles)) resp.
  *          min(40, max(32, 480 / ntiles))).
  *        hb_scatter_max_pieces: block-compact H (thx_hblock_layout) whose off-diagonal tiles hold at most this many pieces
  *          (layout.max_tile_pieces) has them ADDED to the tile's Schur update by the matrix cores; above, they are gathered through
- *          LDS (see thx_hblock_layout.max_tile_pieces; the same bits either way).  0 = always gather; < 0: the default (64, or
- *          THX_HB_SCATTER_MAX_PIECES).
+ *          LDS (see thx_hblock_layout.max_tile_pieces; the same bits either way).  0 = always gather; < 0: the default (64).
  *        f64_wide_max_ktiles: fp64 factorisations on the column-by-column schedule: the off-diagonal tiles of the first this many
  *          block columns (K-loops shorter than that many tiles) are produced by EIGHT-wave workgroups (16 rows of the tile per
  *          wave, four waves per SIMD) instead of four-wave ones -- the same arithmetic in the same order, bit-identical.  0 =
- *          never; < 0: the default (every column, or THX_F64_WIDE_MAX_KTILES).
+ *          never; < 0: the default (every column).
  *        f64_half_max_ktiles: fp64, column-by-column schedule on a dense factor frame: the off-diagonal tiles of the first this many
  *          block columns are produced as two HALF tiles (64 rows each) by four-wave workgroups that need 37 KB of LDS and 128
  *          VGPRs -- four per CU instead of two; takes precedence over f64_wide_max_ktiles for those columns.  Bit-identical.
- *          0 = never; < 0: the default (8, or THX_F64_HALF_MAX_KTILES).
+ *          0 = never; < 0: the default (8).
  *        column_pairs_min_batch: the column-pair schedule (column_pairs) is taken from this many problems per call on; 0 = at any
- *          batch; < 0: the default (128, or THX_CHOL_COLPAIR_MIN_BATCH).
+ *          batch; < 0: the default (128).
  *        right_looking_mode: the launch arrangement of the right-looking schedule -- 0: three dependent launches per block column
  *          (tile factorisation, substitutions, trailing update); 1: two -- the diagonal tile and the substitution tiles of column j
  *          take column j - 1's update themselves (one-tile K-loop), the rest of that update rides in the substitutions' launch, and
  *          block column 1 is read straight from H; 2: the diagonal tile takes its own update, the rest of the update runs on the
  *          library's second stream beside it.  The three sum in different orders (to rounding, not bit for bit).  < 0: the default
- *          (THX_CHOL_RL_LOOKAHEAD, else 1 for fp32 and 2 for fp64); > 2: 1. */
+ *          (1 for fp32, 2 for fp64); > 2: 1. */
 typedef struct {
   int32_t split_diag_min_batch;
   int32_t column_pairs;
@@ -358,7 +357,7 @@ typedef struct {
   int32_t right_looking;       /* 1: the right-looking schedule */
   int32_t right_looking_mode;  /* its launch arrangement (thx_chol_schedule.right_looking_mode), -1 when left-looking */
   int32_t split_diag;          /* 1: the diagonal phase as SYRK kernel + one-wave-per-tile kernel, 0: the fused chol_diag kernel */
-  int32_t nparts;              /* streams the batch is dealt over (1: the caller's alone) */
+  int32_t nparts;              /* streams the batch is dealt over (1: the caller's alone; 2 from 1024 problems on) */
   int32_t column_pairs;        /* 1: the column-pair schedule (chol_offdiag2_f32_kernel) */
   int32_t f64_half_cols;       /* fp64: block columns whose off-diagonal tiles come from chol_offdiag_f64h_kernel */
   int32_t f64_wide_cols;       /* fp64: ... from chol_offdiag_f64w8_kernel */
@@ -439,12 +438,6 @@ typedef struct {
   const int32_t* level_maxk_host; /* (nlevels) HOST: longest diagonal K-list (diag_kptr) among the level's block columns */
   const int32_t* ent_col;         /* DEVICE (entries): block column of entry e (col_ptr is not used by the level kernels) */
   const int32_t* tile_valid;      /* DEVICE (ntiles): rows / columns of tile j that are matrix (a multiple of the block size) */
-  const int32_t* level_stream_host; /* (nlevels) HOST or NULL: launch stream of level l -- 0 the caller's, 1 the library's second
-                                     * stream; + 4: both streams join in front of this level (the trunk of the elimination tree).
-                                     * A "level" then is one SUBTREE's share of a tree level: subtrees of the tile elimination tree
-                                     * do not see each other, so the two streams need no ordering against each other and one
-                                     * chain's diagonal phases (one busy wave per workgroup) run beside the other's off-diagonal
-                                     * tiles.  NULL: every level on the caller's stream.  Read by thx_chol_factor_levels only. */
 } thx_level_schedule;
 int thx_chol_factor_levels(const thx_hblock_layout* layout, const void* Hc, int64_t bstride, int32_t B, const void* damping,
                            int ellipsoidal, double damping_eps, void* L, void* Winv, int32_t* info, const void* rhs, void* y,

@@ -3,6 +3,8 @@ include/theseus_hip.h declares; host-side structure compiler and batch sharding 
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -35,6 +37,22 @@ def test_ctypes_binding_covers_the_header(lib_path):
     lib = _lib.load()
     assert lib.thx_abi_version() == _lib.ABI_VERSION
     assert lib.thx_last_error() is not None
+
+
+def test_library_reads_no_environment_and_has_no_build_switches(lib_path):
+    """Every schedule choice is a thx_chol_schedule field or follows from the call's arguments: the library imports no getenv, and
+    no source under theseus_amd/csrc selects code with a THX_ preprocessor switch."""
+    nm = shutil.which("nm") or shutil.which("llvm-nm")
+    assert nm, "needs nm (binutils) or llvm-nm"
+    undefined = subprocess.run([nm, "-D", "--undefined-only", lib_path], check=True, capture_output=True, text=True).stdout
+    imported = {line.split()[-1].split("@")[0] for line in undefined.splitlines() if line.strip()}
+    assert imported, "nm listed no imports"
+    assert not imported & {"getenv", "secure_getenv"}
+    csrc = os.path.join(ROOT, "theseus_amd", "csrc")
+    switches = [f"{name}:{k + 1}: {line.strip()}" for name in sorted(os.listdir(csrc))
+                for k, line in enumerate(open(os.path.join(csrc, name)).read().splitlines())
+                if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b.*\bTHX_", line)]
+    assert not switches, switches
 
 
 def test_bad_arguments_are_rejected_without_a_gpu(lib_path):

@@ -269,7 +269,7 @@ def test_level_schedule_emulated_on_the_host_solves_the_system():
 
 
 def test_subtree_groups_of_the_tile_elimination_tree():
-    """Stream groups for thx_level_schedule.level_stream_host: a band is one chain (no split); two chains towards a separator are
+    """Subtree groups of level_ordering: a band is one chain (no split); two chains towards a separator are
     groups 0 / 1 with the separator's chain as the trunk (-1); a subtree never shares a K-list with the other group."""
     from theseus_amd.sparse import _subtree_groups, _symbolic_tiles
     nt = 9

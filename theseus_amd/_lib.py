@@ -12,7 +12,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_int, c_int32, c_int
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# THESEUS_HIP_LIB overrides the in-tree build (kernel A/B experiments: tools/variants.sh)
+# THESEUS_HIP_LIB: load the library from another path instead of the in-tree build
 LIB_PATH = os.environ.get("THESEUS_HIP_LIB") or os.path.join(_HERE, "lib", "libtheseus_hip.so")
 
 THX_TILE = 128
@@ -21,7 +21,7 @@ THX_BA_ERR_CHUNKS = 256
 LOSS_NONE, LOSS_WELSCH, LOSS_HUBER, LOSS_HINGE = 0, 1, 2, 3  # THX_LOSS_* (theseus/core/robust_loss.py:33-62)
 LOSS_FLATTEN = 4  # THX_LOSS_FLATTEN: RobustCostFunction(flatten_dims=True), or-ed into a loss code
 LOSS_GEMAN_MCCLURE = 8  # THX_LOSS_GEMAN_MCCLURE (robust_loss.py:92-113; the radius entry carries log(mu * radius))
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 
 class LieEps(Structure):
@@ -74,8 +74,7 @@ class CholPlanInfo(Structure):  # thx_chol_plan_info: the schedule a dense-frame
 
 
 class LevelSchedule(Structure):  # thx_level_schedule: elimination-tree levels of a tile pattern (2 host + 2 device int32 tables)
-    _fields_ = [("nlevels", c_int32)] + [(k, c_void_p) for k in ("level_col_host", "level_ent_host", "level_maxk_host", "ent_col", "tile_valid",
-                                                                 "level_stream_host")]
+    _fields_ = [("nlevels", c_int32)] + [(k, c_void_p) for k in ("level_col_host", "level_ent_host", "level_maxk_host", "ent_col", "tile_valid")]
 
 
 class HBlockLayout(Structure):  # thx_hblock_layout: block-compact Hessian (device int32 tables)

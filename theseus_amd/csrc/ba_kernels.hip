@@ -77,12 +77,9 @@ __device__ __forceinline__ SE3<double> load_cam(const T* __restrict__ p) {
 // problems of ONE entity, so component i of all lanes is 512 contiguous bytes: every load / store instruction moves four full
 // 128-B lines.  With the record-per-lane layout (entity, B, component) a wave's 16-byte load of an 144-byte W record touched 72
 // lines and every line was touched by nine different instructions (ba_schur_block: 2.4-2.7 ms for 1.3 GB of W).
-#ifndef THX_BA_PLANAR
-#define THX_BA_PLANAR 1
-#endif
 template <int NC>
 __device__ __forceinline__ int64_t ws_at(int64_t entity, int i, int b, int B) {
-  return THX_BA_PLANAR ? (entity * NC + i) * (int64_t)B + b : (entity * (int64_t)B + b) * NC + i;
+  return (entity * NC + i) * (int64_t)B + b;
 }
 
 // everything one observation needs besides its two variables
@@ -146,10 +143,7 @@ ba_point_kernel(thx_ba_structure s, thx_ba_data d, double* __restrict__ Hpp, dou
     for (int i = 0; i < 6; ++i)
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        double wv = r.Jc[i] * r.Jp[j] + r.Jc[6 + i] * r.Jp[3 + j];
-#ifdef THX_EXP_W32   // numerics experiment: what an fp32 W workspace would do to fp32 problems (rounded on store, layout unchanged)
-        if (sizeof(T) == 4) wv = (double)(float)wv;
-#endif
+        const double wv = r.Jc[i] * r.Jp[j] + r.Jc[6 + i] * r.Jp[3 + j];
         W[ws_at<18>(o, 3 * i + j, b, B)] = wv;
       }
   }

@@ -35,7 +35,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <cstdlib>
 #include <mutex>
 #include <type_traits>
 #include <utility>
@@ -125,36 +124,6 @@ struct Engine<float> {
 #pragma unroll
       for (int j = 0; j < 16; ++j) a.v[i][j] = 0.f;
   }
-#ifdef THX_KLOOP_PIPE
-  // EXPERIMENT (round 4): the fragment reads software-pipelined by hand -- hipcc emits "ds_read_b128; s_waitcnt lgkmcnt(0); 4 MFMAs"
-  // per A fragment; here the read of fragment n + 1 is issued before the MFMAs of fragment n (a two-deep register ring, the four
-  // B fragments of the chunk loaded up front) and the order is pinned with sched_group_barrier (0x100 = DS read, 0x008 = MFMA).
-  static __device__ __forceinline__ void chunk(const float* sA, const float* sBw, Acc& acc, int lane) {
-    const int rl = lane & 31, g = lane >> 5;
-    float4 fb[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) fb[ks] = *reinterpret_cast<const float4*>(sBw + rl * 36 + 8 * ks + 4 * g);
-    auto ld = [&](int n) __attribute__((always_inline)) {   // fragment n = (ks, cb) = (n / 4, n % 4)
-      return *reinterpret_cast<const float4*>(sA + (32 * (n & 3) + rl) * 36 + 8 * (n >> 2) + 4 * g);
-    };
-    float4 ring[2];
-    ring[0] = ld(0);
-    __builtin_amdgcn_sched_group_barrier(0x100, 5, 0);
-#pragma unroll
-    for (int n = 0; n < 16; ++n) {
-      if (n + 1 < 16) ring[(n + 1) & 1] = ld(n + 1);
-      const float4 fa = ring[n & 1];
-      const float4 b = fb[n >> 2];
-      const int cb = n & 3;
-      acc.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.x, b.x, acc.v[cb], 0, 0, 0);
-      acc.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.y, b.y, acc.v[cb], 0, 0, 0);
-      acc.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.z, b.z, acc.v[cb], 0, 0, 0);
-      acc.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.w, b.w, acc.v[cb], 0, 0, 0);
-      if (n + 1 < 16) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-    }
-  }
-#else
   static __device__ __forceinline__ void chunk(const float* sA, const float* sBw, Acc& acc, int lane) {
     const int rl = lane & 31, g = lane >> 5;
 #pragma unroll
@@ -170,7 +139,6 @@ struct Engine<float> {
       }
     }
   }
-#endif
 
   // SYRK of the diagonal tile on the 36 lower 16x16 blocks of its 8x8 block grid, nine per wave: wave g owns block
   // rows 4+g (5+g blocks) and 3-g (4-g blocks) -- equal MFMA counts on all four SIMDs, 56 % of the full tile.
@@ -737,23 +705,6 @@ __device__ __forceinline__ void kloop_f(const T* __restrict__ Arows, int validA,
   auto step = [&](uint4 (&xa)[NP], uint4 (&xb)[NP], int kc) __attribute__((always_inline)) {
     // column of the chunk to prefetch: the K-list entry is fetched here so that its (scalar) load completes under the staging
     const int2 knext = kc + AHEAD < nk ? sof(kc + AHEAD) : make_int2(0, 0);
-#ifdef THX_EXP_NOSTAGE  // timing experiment: no register -> LDS staging and only one barrier per chunk (garbage results)
-    if (kc == 0) {
-#pragma unroll
-      for (int u = 0; u < NP; ++u) {
-        const int row = lrow + RPP * u;
-        *reinterpret_cast<uint4*>(sA + row * LDT + scol) = xa[u];
-        if (!SAME) *reinterpret_cast<uint4*>(sB + row * LDT + scol) = xb[u];
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < NP; ++u) {
-        asm volatile("" ::"v"(xa[u].x));  // the loads must still complete
-        if (!SAME) asm volatile("" ::"v"(xb[u].x));
-      }
-    }
-    __syncthreads();
-#else
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < NP; ++u) {
@@ -762,12 +713,7 @@ __device__ __forceinline__ void kloop_f(const T* __restrict__ Arows, int validA,
       if (!SAME && u < NPB) *reinterpret_cast<uint4*>(sB + row * LDT + scol) = xb[u];
     }
     __syncthreads();
-#endif
-#ifdef THX_EXP_NOLOAD
-    if (kc == 0 && kc + AHEAD < nk) gload(xa, xb, knext);  // timing experiment: operands are not streamed
-#else
     if (kc + AHEAD < nk) gload(xa, xb, knext);
-#endif
     if constexpr (GEMV) {
       if (gemv_y) {
         constexpr int HALF = C::KB / 2;
@@ -785,11 +731,7 @@ __device__ __forceinline__ void kloop_f(const T* __restrict__ Arows, int validA,
         }
       }
     }
-#ifdef THX_EXP_NOMFMA
-    if (K < 0) compute();  // timing experiment: no MFMAs (garbage results)
-#else
     compute();  // MFMAs on the staged chunk (sA / sB)
-#endif
   };
 #pragma unroll
   for (int a = 0; a < AHEAD; ++a)
@@ -911,116 +853,6 @@ __device__ __forceinline__ int potrf_reg(T (&a)[N]) {
   });
   return bad;
 }
-template <typename T>
-__device__ __forceinline__ int potrf32(T (&a)[32]) {
-  return potrf_reg<T, 32>(a);
-}
-
-// W = L^-1 for a 32x32 triangle stored row-major in LDS (row stride LDM): lane j (= lane & 31) computes column j of
-// W by forward substitution on e_j.  L[i][k] is wave uniform: it is read with broadcast ds_read_b128 (4 values per
-// instruction, into VGPRs) -- a v_readlane per value does not scale: hipcc hoists all 496 of them, runs out of SGPRs
-// and spills through v_writelane/v_readlane pairs (measured 30 cycles per term).  Row i+1 is loaded while row i is
-// being consumed.  Accumulation in A: fp64 for the fp64 path, float for fp32 -- W then carries the backward error of
-// an fp32 TRSM (columnwise ~32 eps |L|), which is what the sub-block solve it replaces would have.
-template <typename T, typename A, int LDM, int N>
-__device__ __forceinline__ void inv_tri(const T* Lss, A (&w)[N], int lane) {
-  constexpr int VEC = 16 / sizeof(T);
-  using V = std::conditional_t<sizeof(T) == 4, float4, double2>;
-  const int j = lane & (N - 1);
-  V cur[N / VEC], nxt[N / VEC];
-  cur[0] = *reinterpret_cast<const V*>(Lss);
-  static_for<N>([&](auto ii) __attribute__((always_inline)) {
-    constexpr int i = decltype(ii)::value;
-    if constexpr (i + 1 < N) {  // prefetch row i+1: entries 0 .. i+1
-#pragma unroll
-      for (int q = 0; q <= (i + 1) / VEC; ++q) nxt[q] = *reinterpret_cast<const V*>(Lss + (i + 1) * LDM + VEC * q);
-    }
-    auto at = [&](int k) __attribute__((always_inline)) -> A {
-      if constexpr (sizeof(T) == 4) {
-        const float4 v = cur[k >> 2];
-        return (A)((k & 3) == 0 ? v.x : (k & 3) == 1 ? v.y : (k & 3) == 2 ? v.z : v.w);
-      } else {
-        const double2 v = cur[k >> 1];
-        return (A)((k & 1) ? v.y : v.x);
-      }
-    };
-    const A lii = at(i);
-    A r = (A)(1.0f / (float)lii);
-    r = r * (A(2) - lii * r);
-    r = r * (A(2) - lii * r);
-    A s0 = (j == i) ? A(1) : A(0), s1 = A(0);
-    static_for<i>([&](auto kk) __attribute__((always_inline)) {
-      constexpr int k = decltype(kk)::value;
-      if constexpr (k & 1) s1 -= at(k) * w[k];
-      else s0 -= at(k) * w[k];
-    });
-    w[i] = (s0 + s1) * r;
-    if constexpr (i + 1 < N) {
-#pragma unroll
-      for (int q = 0; q <= (i + 1) / VEC; ++q) cur[q] = nxt[q];
-    }
-    // keep the rows in order: without this the compiler issues every LDS read first and the FMA chains sink below
-    // them (hundreds of spilled registers)
-    asm volatile("" : "+v"(w[i]) : : "memory");
-  });
-}
-template <typename T, typename A, int LDM>
-__device__ __forceinline__ void inv32(const T* Lss, A (&w)[32], int lane) {
-  inv_tri<T, A, LDM, 32>(Lss, w, lane);
-}
-
-// ------------------------------------------------------------------------------------------------
-// (The scheme of rounds 2-6, kept for A/B under -DTHX_POTRF_BLOCKED; the default is potrf_inv32_lanes below: 7 us less per tile,
-//  profiles/r6/ah_.)
-// One 32x32 diagonal sub-block, blocked 16 + 16 (executed by ONE wave): the in-register factorisation and the
-// substitution for the inverse cost ~N^2 dependent readlane/FMA steps each, so halving N and doing the coupling
-// with 16x16x16 MFMA products on the LDS block halves the serial chain of chol_diag:
-//   L00 = chol(S00), W00 = L00^-1, L10 = S10 W00^T, S11 -= L10 L10^T, L11 = chol(S11), W11 = L11^-1,
-//   W10 = -W11 (L10 W00);   on exit the block holds W_ss = [[W00, 0], [W10, W11]] and L_ss has gone to global memory.
-// 16x16 MFMA convention (both dtypes):  acc(n, m) += sum_k Aop[m][k] * B[n][k],  n = lane & 15 (row of the B block),
-// m = m_of(lane, i) for accumulator element i (fp32: 4 (lane >> 4) + i; fp64: (lane >> 4) + 4 i); TA reads A transposed.
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-struct Mma16;
-template <>
-struct Mma16<float> {
-  using Acc = f32x4;
-  static __device__ __forceinline__ int m_of(int lane, int i) { return 4 * (lane >> 4) + i; }
-  template <bool TA>
-  static __device__ __forceinline__ void mma(const float* A, const float* B, Acc& acc, int lane, float asign) {
-    constexpr int LDB = CT<float>::LDB;
-    const int x = lane & 15, kq = lane >> 4;
-    const float4 fb = *reinterpret_cast<const float4*>(B + x * LDB + 4 * kq);
-    float fa[4];
-    if constexpr (TA) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) fa[e] = A[(4 * kq + e) * LDB + x];
-    } else {
-      const float4 v = *reinterpret_cast<const float4*>(A + x * LDB + 4 * kq);
-      fa[0] = v.x; fa[1] = v.y; fa[2] = v.z; fa[3] = v.w;
-    }
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(asign * fa[0], fb.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(asign * fa[1], fb.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(asign * fa[2], fb.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(asign * fa[3], fb.w, acc, 0, 0, 0);
-  }
-};
-template <>
-struct Mma16<double> {
-  using Acc = f64x4;
-  static __device__ __forceinline__ int m_of(int lane, int i) { return (lane >> 4) + 4 * i; }
-  template <bool TA>
-  static __device__ __forceinline__ void mma(const double* A, const double* B, Acc& acc, int lane, double asign) {
-    constexpr int LDB = CT<double>::LDB;
-    const int x = lane & 15, kq = lane >> 4;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const double fa = TA ? A[(4 * e + kq) * LDB + x] : A[x * LDB + 4 * e + kq];
-      const double fb = B[x * LDB + 4 * e + kq];
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(asign * fa, fb, acc, 0, 0, 0);
-    }
-  }
-};
 
 // the wave's own LDS writes become visible to its reads
 __device__ __forceinline__ void wave_lds_fence() {
@@ -1031,142 +863,14 @@ __device__ __forceinline__ void wave_lds_fence() {
 // Dss: the 32 x LDB block in LDS (S_ss on entry, W_ss on exit); Lg: global address of L's element (first row of the
 // sub-block, first column of the sub-block), rows_valid = number of the sub-block's rows inside the matrix.
 // Returns the 1-based index (within the sub-block) of the first non-positive pivot, 0 if none.
+// The inverse comes for FREE: lanes 0..31 hold the rows of S_ss, lanes 32..63 the rows of the identity, and the factorisation's
+// column operations (column c scaled by 1/sqrt(pivot), column q -= column c * L[q][c]) run over all 64 lanes in the same
+// instructions.  S -> L = S U with U = L^-T, so the identity becomes U: lane 32 + r ends with a[q] = U[r][q] = W[q][r], exact
+// zeros for q < r -- column r of W = L^-1 without a second N^2 / 2 chain of dependent FMAs (the blocked 16 + 16 scheme it replaced
+// was 7 us per tile slower, profiles/r6/ah_).  One wave issues in order, so the chain's cost is its instruction count: 32 steps of
+// (pivot broadcast, rsqrt, scale) + 496 (readlane, fma) pairs.
 template <typename T>
-__device__ __forceinline__ int potrf_inv32_blocked(T* Dss, T* Lg, int64_t ld, int rows_valid, int lane) {
-  using C = CT<T>;
-  using V = typename C::V;
-  using M = Mma16<T>;
-  using WA = std::conditional_t<sizeof(T) == 8, double, float>;
-  constexpr int LDB = C::LDB;
-  T* Q00 = Dss;
-  T* Q01 = Dss + 16;
-  T* Q10 = Dss + 16 * LDB;
-  T* Q11 = Dss + 16 * LDB + 16;
-  const int r = lane & 15;
-  int bad = 0;
-  // row r of a 16x16 LDS quadrant -> registers
-  auto load_row = [&](const T* Q, T (&a)[16]) __attribute__((always_inline)) {
-    const V* rp = reinterpret_cast<const V*>(Q + r * LDB);
-#pragma unroll
-    for (int q = 0; q < 16 / C::VEC; ++q) {
-      const V v = rp[q];
-      if constexpr (sizeof(T) == 4) {
-        a[4 * q] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
-      } else {
-        a[2 * q] = v.x; a[2 * q + 1] = v.y;
-      }
-    }
-  };
-  // lower-triangular rows (zeros above the diagonal) -> the LDS quadrant and -> global memory (rows inside the matrix)
-  auto store_tri = [&](T* Q, T* G, int row_in_block, const T (&a)[16]) __attribute__((always_inline)) {
-    if (lane < 16) {
-      V* rp = reinterpret_cast<V*>(Q + r * LDB);
-      V* gp = reinterpret_cast<V*>(G + (int64_t)r * ld);
-      const bool g = row_in_block + r < rows_valid;
-#pragma unroll
-      for (int q = 0; q < 16 / C::VEC; ++q) {
-        V v;
-        if constexpr (sizeof(T) == 4)
-          v = make_float4(4 * q <= r ? a[4 * q] : 0.f, 4 * q + 1 <= r ? a[4 * q + 1] : 0.f,
-                          4 * q + 2 <= r ? a[4 * q + 2] : 0.f, 4 * q + 3 <= r ? a[4 * q + 3] : 0.f);
-        else
-          v = make_double2(2 * q <= r ? a[2 * q] : 0.0, 2 * q + 1 <= r ? a[2 * q + 1] : 0.0);
-        rp[q] = v;
-        if (g) gp[q] = v;
-      }
-    }
-  };
-  // column j = r of W (w[i] = W[i][j], zero above the diagonal) -> row-major into the quadrant
-  auto store_cols = [&](T* Q, const WA (&w)[16]) __attribute__((always_inline)) {
-    if (lane < 16) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) Q[i * LDB + r] = (T)w[i];
-    }
-  };
-  auto acc_zero = [&](typename M::Acc& acc) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i] = T(0);
-  };
-  auto acc_store = [&](const typename M::Acc& acc, T* Q) __attribute__((always_inline)) {
-    if constexpr (sizeof(T) == 4) {
-      *reinterpret_cast<float4*>(Q + r * LDB + 4 * (lane >> 4)) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) Q[r * LDB + M::m_of(lane, i)] = acc[i];
-    }
-  };
-
-  T a[16];
-  WA w[16];
-  typename M::Acc acc;
-  // ---- L00, W00 ----
-  load_row(Q00, a);
-  bad = potrf_reg<T, 16>(a);
-  store_tri(Q00, Lg, 0, a);
-  wave_lds_fence();
-  inv_tri<T, WA, LDB, 16>(Q00, w, lane);
-  __builtin_amdgcn_wave_barrier();
-  store_cols(Q00, w);
-  wave_lds_fence();
-  // ---- L10 = S10 W00^T ----
-  acc_zero(acc);
-  M::template mma<false>(Q00, Q10, acc, lane, T(1));
-  acc_store(acc, Q10);
-  if (16 + r < rows_valid) {  // L10 -> global
-    T* gp = Lg + (int64_t)(16 + r) * ld;
-    if constexpr (sizeof(T) == 4) {
-      *reinterpret_cast<float4*>(gp + 4 * (lane >> 4)) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) gp[M::m_of(lane, i)] = acc[i];
-    }
-  }
-  wave_lds_fence();
-  // ---- S11 -= L10 L10^T ----
-#pragma unroll
-  for (int i = 0; i < 4; ++i) acc[i] = Q11[r * LDB + M::m_of(lane, i)];
-  M::template mma<false>(Q10, Q10, acc, lane, T(-1));
-  acc_store(acc, Q11);
-  wave_lds_fence();
-  // ---- L11, W11 ----
-  load_row(Q11, a);
-  {
-    const int bad1 = potrf_reg<T, 16>(a);
-    if (bad == 0 && bad1 != 0) bad = 16 + bad1;
-  }
-  store_tri(Q11, Lg + 16 * ld + 16, 16, a);
-  wave_lds_fence();
-  inv_tri<T, WA, LDB, 16>(Q11, w, lane);
-  __builtin_amdgcn_wave_barrier();
-  store_cols(Q11, w);
-  wave_lds_fence();
-  // ---- W10 = -W11 (L10 W00): T1 = L10 W00 through the (otherwise zero) upper-right quadrant ----
-  acc_zero(acc);
-  M::template mma<true>(Q00, Q10, acc, lane, T(1));   // T1(n = row of L10, m = c) = sum_k W00[k][c] L10[n][k]
-  acc_store(acc, Q01);
-  wave_lds_fence();
-  acc_zero(acc);
-  M::template mma<true>(Q01, Q11, acc, lane, T(-1));  // W10(n, c) = -sum_k T1[k][c] W11[n][k]
-  acc_store(acc, Q10);
-  if (lane < 16) {  // upper-right quadrant back to zero: W_ss is used as a full 32x32 operand
-    V* rp = reinterpret_cast<V*>(Q01 + r * LDB);
-#pragma unroll
-    for (int q = 0; q < 16 / C::VEC; ++q) {
-      if constexpr (sizeof(T) == 4) rp[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-      else rp[q] = make_double2(0.0, 0.0);
-    }
-  }
-  return bad;
-}
-
-// The same contract as potrf_inv32_blocked with the inverse for FREE: lanes 0..31 hold the rows of S_ss, lanes 32..63 the rows
-// of the identity, and the factorisation's column operations (column c scaled by 1/sqrt(pivot), column q -= column c * L[q][c])
-// run over all 64 lanes in the same instructions.  S -> L = S U with U = L^-T, so the identity becomes U: lane 32 + r ends with
-// a[q] = U[r][q] = W[q][r], exact zeros for q < r -- column r of W = L^-1, what inv_tri produced with a second N^2 / 2 chain of
-// dependent FMAs, two LDS round trips and five 16 x 16 MFMA couplings around it.  One wave issues in order, so the chain's cost
-// is its instruction count: 32 steps of (pivot broadcast, rsqrt, scale) + 496 (readlane, fma) pairs.
-template <typename T>
-__device__ __forceinline__ int potrf_inv32_lanes(T* Dss, T* Lg, int64_t ld, int rows_valid, int lane) {
+__device__ __forceinline__ int potrf_inv32(T* Dss, T* Lg, int64_t ld, int rows_valid, int lane) {
   using C = CT<T>;
   using V = typename C::V;
   constexpr int LDB = C::LDB;
@@ -1206,14 +910,6 @@ __device__ __forceinline__ int potrf_inv32_lanes(T* Dss, T* Lg, int64_t ld, int 
     for (int q = 0; q < 32; ++q) Dss[q * LDB + r] = a[q];
   }
   return bad;
-}
-template <typename T>
-__device__ __forceinline__ int potrf_inv32(T* Dss, T* Lg, int64_t ld, int rows_valid, int lane) {
-#ifdef THX_POTRF_BLOCKED
-  return potrf_inv32_blocked<T>(Dss, Lg, ld, rows_valid, lane);
-#else
-  return potrf_inv32_lanes<T>(Dss, Lg, ld, rows_valid, lane);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1330,14 +1026,6 @@ struct HBPre {
   int rc[NPRE];   // (r << 8) | c inside the tile, -1: nothing
   int p0, cnt;
   int wmeta;      // lane l of every wave: piece_rc of the tile's piece l (hb_scatter: readlane)
-  __device__ __forceinline__ void empty() {   // (timing experiments)
-    p0 = cnt = wmeta = 0;
-#pragma unroll
-    for (int k = 0; k < NPRE; ++k) {
-      rc[k] = -1;
-      v[k] = T(0);
-    }
-  }
   // the tile's elements, in list order, -> LDS (element idx of the tile's run at list[idx]; the caller publishes them with a barrier)
   __device__ __forceinline__ void to_list(T* list, int tid) const {
 #pragma unroll
@@ -1453,14 +1141,6 @@ struct HBPre2 {
   int rc[NPRE];
   int p0, p1, cnt;   // first piece of tile 0 / of tile 1, elements of both
   int wmeta;         // (HBPre: lane l holds piece_rc of piece l of the run)
-  __device__ __forceinline__ void empty() {   // (timing experiments)
-    p0 = p1 = cnt = wmeta = 0;
-#pragma unroll
-    for (int k = 0; k < NPRE; ++k) {
-      rc[k] = -1;
-      v[k] = T(0);
-    }
-  }
   __device__ __forceinline__ void to_list(T* list, int tid) const {
 #pragma unroll
     for (int k = 0; k < NPRE; ++k)
@@ -1653,9 +1333,7 @@ __device__ __forceinline__ void hb_add(Acc& P, const Pre& pre, const HBlk& hb, i
   const int nreg = min(min(pre.cnt / bb, LIST0 / bb), 64);
   if (write_list) {
     pre.to_list(list, tid);
-#ifndef THX_EXP_NO_HBBARRIER   // (timing experiment, WRONG results)
     __syncthreads();
-#endif
   }
   hb_scatter(P, list, pre.wmeta, lo, min(hi, nreg), bd, wave, lane);
   if (hi > nreg) {   // (workgroup uniform)
@@ -1706,14 +1384,6 @@ chol_diag_kernel(const T* __restrict__ H, T* __restrict__ L, T* __restrict__ pan
   const int valid = tile_rows(pat, n, j);
 
   const bool fwd = rhs != nullptr;
-#ifdef THX_DIAG_PROF
-  long long stamps[24];
-  int nst = 0;
-#define THX_STAMP() stamps[nst++] = (long long)__builtin_readcyclecounter()
-#else
-#define THX_STAMP()
-#endif
-  THX_STAMP();
 
   // SYRK on the 36 lower 16x16 blocks of the tile, nine per wave (Engine<T>::syrk36)
   // tile-sparse: only the block columns k < j in which row panel j is non-zero
@@ -1753,9 +1423,6 @@ chol_diag_kernel(const T* __restrict__ H, T* __restrict__ L, T* __restrict__ pan
       hbp.load(hb, b, j, j, tid);
     }
   };
-#ifdef THX_OFF_PROLOGUE_FIRST   // the round-1 order (A/B timing)
-  prologue();
-#endif
   kloop_f<T, true, true, E::SYRK_LDT, (sizeof(T) == 8 && CT<T>::KB == 32)>(
       L + lmat + (lf.packed ? 0 : (int64_t)row0 * ld) + kcol0, valid, nullptr, 0, ldt, Kspan, tile, nullptr, tid,
       (fwd && !pat.rl) ? ybuf : nullptr, &tpart, [&]() __attribute__((always_inline)) {
@@ -1764,15 +1431,10 @@ chol_diag_kernel(const T* __restrict__ H, T* __restrict__ L, T* __restrict__ pan
     else if (wave == 2) E::template syrk36<2>(tile, acc, lane);
     else E::template syrk36<3>(tile, acc, lane);
   },
-#ifdef THX_OFF_PROLOGUE_FIRST
-  NoHook{}, klist, lf.packed ? pat.diag_s + pat.diag_kptr[j] : nullptr, nullptr, lf.pstride, ycompact);
-#else
   prologue, klist, lf.packed ? pat.diag_s + pat.diag_kptr[j] : nullptr, nullptr, lf.pstride, ycompact);
-#endif
 
   // ---- S = H_jj (+ damping on the diagonal) - acc -> LDS tile; identity padding outside the matrix ----
   __syncthreads();  // staging buffer is free
-  THX_STAMP();
   if (tid < TILE) vvec[tid] = (fwd && tid < valid) ? rhs[(int64_t)b * ldv + row0 + tid] : T(0);
   {
     const bool damp = damping != nullptr;
@@ -1796,86 +1458,15 @@ chol_diag_kernel(const T* __restrict__ H, T* __restrict__ L, T* __restrict__ pan
     }
   }
   __syncthreads();
-  THX_STAMP();
 
   // ---- blocked right-looking Cholesky on the LDS tile, 32-wide sub-blocks.  Afterwards the tile IS the
   //      solve panel: W_ss = L_ss^-1 on the diagonal sub-blocks, -L_us below them. ----
-#if defined(THX_SERIAL_WAVE_BID)
-  const int sw = (blockIdx.x >> 8) & 3;
-#else
-  const int sw = 0;
-#endif
   for (int sb = 0; sb < 4; ++sb) {
     T* Dss = tile + tblk<T>(sb, sb);
-#ifndef THX_POTRF_FLAT
-    if (wave == sw) {
-      THX_STAMP();
+    if (wave == 0) {
       const int bad = potrf_inv32<T>(Dss, Ljj + (int64_t)(32 * sb) * ldt + 32 * sb, ldt, valid - 32 * sb, lane);
       if (bad != 0 && lane == 0 && info[b] == 0) info[b] = row0 + 32 * sb + bad;
-      THX_STAMP();
     }
-#else  // the unblocked 32-step chain (kept for A/B timing)
-    if (wave == sw) {
-      T a[32];
-      {
-        const V* rp = reinterpret_cast<const V*>(Dss + (lane & 31) * C::LDB);
-#pragma unroll
-        for (int q = 0; q < 32 / C::VEC; ++q) {
-          const V v = rp[q];
-          if constexpr (sizeof(T) == 4) {
-            a[4 * q] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
-          } else {
-            a[2 * q] = v.x; a[2 * q + 1] = v.y;
-          }
-        }
-      }
-      THX_STAMP();
-      const int bad = potrf32<T>(a);
-      THX_STAMP();
-      if (bad != 0 && lane == 0 && info[b] == 0) info[b] = row0 + 32 * sb + bad;
-      // L_ss straight to global memory: one 32-element row per lane, zeros above the diagonal
-      const int lr = lane & 31, grow = 32 * sb + lr;
-      if (lane < 32 && grow < valid) {
-        V* gp = reinterpret_cast<V*>(Ljj + (int64_t)grow * ldt + 32 * sb);
-#pragma unroll
-        for (int q = 0; q < 32 / C::VEC; ++q) {
-          if constexpr (sizeof(T) == 4) {
-            gp[q] = make_float4(4 * q <= lr ? a[4 * q] : 0.f, 4 * q + 1 <= lr ? a[4 * q + 1] : 0.f,
-                                4 * q + 2 <= lr ? a[4 * q + 2] : 0.f, 4 * q + 3 <= lr ? a[4 * q + 3] : 0.f);
-          } else {
-            gp[q] = make_double2(2 * q <= lr ? a[2 * q] : 0.0, 2 * q + 1 <= lr ? a[2 * q + 1] : 0.0);
-          }
-        }
-      }
-      // L_ss back into its LDS block (zeros above the diagonal), then invert it from there
-      {
-        V* rp = reinterpret_cast<V*>(Dss + lr * C::LDB);
-        if (lane < 32) {
-#pragma unroll
-          for (int q = 0; q < 32 / C::VEC; ++q) {
-            if constexpr (sizeof(T) == 4) {
-              rp[q] = make_float4(4 * q <= lr ? a[4 * q] : 0.f, 4 * q + 1 <= lr ? a[4 * q + 1] : 0.f,
-                                  4 * q + 2 <= lr ? a[4 * q + 2] : 0.f, 4 * q + 3 <= lr ? a[4 * q + 3] : 0.f);
-            } else {
-              rp[q] = make_double2(2 * q <= lr ? a[2 * q] : 0.0, 2 * q + 1 <= lr ? a[2 * q + 1] : 0.0);
-            }
-          }
-        }
-        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the wave's LDS writes are visible to its reads
-        __builtin_amdgcn_wave_barrier();
-      }
-      using WA = std::conditional_t<sizeof(T) == 8, double, float>;
-      WA w[32];
-      THX_STAMP();
-      inv32<T, WA, C::LDB>(Dss, w, lane);
-      THX_STAMP();
-      __builtin_amdgcn_wave_barrier();
-      if (lane < 32) {
-#pragma unroll
-        for (int i = 0; i < 32; ++i) Dss[i * C::LDB + lr] = (T)w[i];  // W[i][lr]; zero for i < lr
-      }
-    }
-#endif
     __syncthreads();
     if (sb == 3) break;
     // L_us = S_us W_ss^T for the sub-blocks below (one per wave), stored negated
@@ -1907,7 +1498,6 @@ chol_diag_kernel(const T* __restrict__ H, T* __restrict__ L, T* __restrict__ pan
     __syncthreads();
   }
 
-  THX_STAMP();
   // ---- outputs: strictly-lower sub-blocks of L_jj (= -tile), the panel, y_j ----
   {  // (the panel's sub-blocks above the diagonal are never read -- chol_offdiag and the solves use the lower ten -- and
      //  are not written)
@@ -1947,19 +1537,10 @@ chol_diag_kernel(const T* __restrict__ H, T* __restrict__ L, T* __restrict__ pan
     __syncthreads();
     if (tid < valid) yout[(int64_t)b * ldv + row0 + tid] = vvec[tid];
   }
-#ifdef THX_DIAG_PROF
-  THX_STAMP();
-  __syncthreads();
-  if (tid == sw * 64) {
-    T* P = panel + ((int64_t)b * ntiles + j) * TILE * TILE;
-    for (int k = 1; k < nst; ++k) P[k] = (T)(stamps[k] - stamps[0]);
-    P[0] = (T)nst;
-  }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
-// The diagonal phase SPLIT in two kernels (default; THX_CHOL_FUSED_DIAG=1 selects chol_diag_kernel above):
+// The diagonal phase SPLIT in two kernels:
 //   chol_syrk_kernel : the MFMA half of chol_diag -- S = H_jj + damping - L_j,0:j L_j,0:j^T (36 lower 16x16 blocks, nine per wave),
 //                      riding on it g_j - L_j,0:j y -- written to the diagonal tile's place in the global factor / to y_j.
 //                      No serial phase: all four waves of all three resident workgroups issue MFMAs for the kernel's whole life.
@@ -1976,16 +1557,13 @@ struct SyrkSmem {
   static size_t bytes(int ypad) { return (size_t)Engine<T>::SYRK_STAGE * sizeof(T) + (size_t)ypad * sizeof(T); }
 };
 
-#ifndef THX_SYRK32_WAVES
-#define THX_SYRK32_WAVES 3
-#endif
-#ifndef THX_SYRK64_WAVES
-#define THX_SYRK64_WAVES 3   // waves per SIMD the fp64 block-compact SYRK is compiled for: 3 (168 VGPRs + 20 B of scratch) instead of 2
-                             // (200 VGPRs) takes 0.7 ms off the headline factorisation (87.9 / 88.0 -> 87.2 / 87.3 ms: its short
-                             // K-loops want a third workgroup per CU); 4 (128 VGPRs, 168 B of scratch) costs 2.7 ms (profiles/r6/ag_)
-#endif
+constexpr int SYRK32_WAVES = 3;
+// waves per SIMD the fp64 block-compact SYRK is compiled for: 3 (168 VGPRs + 20 B of scratch) instead of 2 (200 VGPRs) takes 0.7 ms
+// off the headline factorisation (87.9 / 88.0 -> 87.2 / 87.3 ms: its short K-loops want a third workgroup per CU); 4 (128 VGPRs,
+// 168 B of scratch) costs 2.7 ms (profiles/r6/ag_)
+constexpr int SYRK64_WAVES = 3;
 template <typename T, bool HB>
-__global__ void __launch_bounds__(256, sizeof(T) == 4 ? (HB ? THX_SYRK32_WAVES : 3) : (HB ? THX_SYRK64_WAVES : 2))
+__global__ void __launch_bounds__(256, sizeof(T) == 4 ? (HB ? SYRK32_WAVES : 3) : (HB ? SYRK64_WAVES : 2))
 chol_syrk_kernel(const T* __restrict__ H, T* __restrict__ L, const T* __restrict__ damping, int ellipsoidal, T damping_eps,
                  int n, int64_t ld, int j0, const T* __restrict__ rhs, T* __restrict__ yout, int64_t ldv, TilePat pat, HBlk hb) {
   using E = Engine<T>;
@@ -2076,11 +1654,9 @@ chol_syrk_kernel(const T* __restrict__ H, T* __restrict__ L, const T* __restrict
 
 __device__ __forceinline__ constexpr int bidx(int u, int v) { return u * (u + 1) / 2 + v; }
 
-#ifndef THX_POTRF_F64_WAVES_PER_SIMD
-#define THX_POTRF_F64_WAVES_PER_SIMD 1   // (experiment knob: 2 = at most 256 registers, the compiler spills the rest to scratch)
-#endif
+constexpr int POTRF_F64_WAVES_PER_SIMD = 1;   // (2 = at most 256 registers: the compiler spills the rest to scratch)
 template <typename T>
-__global__ void __launch_bounds__(64, sizeof(T) == 4 ? 2 : THX_POTRF_F64_WAVES_PER_SIMD)
+__global__ void __launch_bounds__(64, sizeof(T) == 4 ? 2 : POTRF_F64_WAVES_PER_SIMD)
 chol_potrf_kernel(T* __restrict__ L, T* __restrict__ panel, int32_t* __restrict__ info, int n, int64_t pstride, int64_t tile_off0,
                   int64_t ld, int j0, int ntiles, T* __restrict__ yout, int64_t ldv, const int32_t* __restrict__ tile_valid) {
   // (the diagonal tile of problem b starts at L + b * pstride + tile_off, row stride ld: dense frame or tile-packed factor;
@@ -2260,12 +1836,6 @@ chol_offdiag_f32_kernel(const float* __restrict__ H, float* __restrict__ L, cons
   float* sB = smem + 128 * 36;
   float* Pc = smem + OFF32_STAGE_FLOATS;
 
-#ifdef THX_OFF_PROF  // timing build (tools/prof/off_prof.py): cycle stamps overwrite the head of the output tile
-  long long st[7];
-  st[0] = (long long)__builtin_readcyclecounter();
-  st[5] = 0;
-  const long long wc0 = (long long)wall_clock64();
-#endif
   // ---- prefetch: panel sub-blocks (s,t), t <= s, then the H tile.  Issued from inside the K-loop's prologue, AFTER the
   //      loads of the first k-chunk: one exposed memory latency per workgroup instead of two (in-kernel stamps: 8.8-11.2 k
   //      cycles from kernel entry to the first MFMA, profiles/r2/a_offdiag_stamps.txt) ----
@@ -2276,11 +1846,7 @@ chol_offdiag_f32_kernel(const float* __restrict__ H, float* __restrict__ L, cons
   float4 hr[4][4];
   HBPre<float, HB ? HB_NPRE_OFF : 1> hbp;
   auto prologue = [&]() __attribute__((always_inline)) {
-#ifdef THX_EXP_NO_HBLOAD   // timing experiment (WRONG results): the off-diagonal tiles without their table / value loads
-    if constexpr (HB) hbp.empty();
-#else
     if constexpr (HB) hbp.load(hb, b, i, j, tid);
-#endif
     if constexpr (!HB) {
       const float* Hrow = H + mat + (int64_t)(row0 + (rvalid ? r : 0)) * ld + col0 + 4 * g;
 #pragma unroll
@@ -2303,30 +1869,15 @@ chol_offdiag_f32_kernel(const float* __restrict__ H, float* __restrict__ L, cons
       });
     }
   };
-#ifdef THX_OFF_PROLOGUE_FIRST   // the round-1 order (A/B timing): panel + H loads and the panel copy BEFORE the first chunk's loads
-  prologue();
-#endif
 
   Engine<float>::Acc P;
   Engine<float>::zero(P);
-#ifdef THX_OFF_PROF
-  st[1] = (long long)__builtin_readcyclecounter();
-#endif
   // (two LDS staging buffers with ONE barrier per k-chunk instead of one buffer with two -- panel copy moved behind the
   //  loop to keep 2 workgroups/CU -- measured the same 9.3-9.4 k cycles per chunk: the barriers are not the K-loop's limit)
   const float* Ap = L + lmat + (lf.packed ? 0 : (int64_t)col0 * ld) + kcol0;   // rows of block row j (operand A) / i (operand B)
   const float* Bp = L + lmat + (lf.packed ? 0 : (int64_t)row0 * ld) + kcol0;
   const int validA = upd ? tile_rows(pat, n, j) : TILE;   // (update: tile column k may be the LAST block row)
-#ifdef THX_OFF_PROLOGUE_FIRST
-  kloop<float, false>(Ap, validA, Bp, validB, ldt, Kspan, sA, sB, P, tid, nullptr, nullptr, NoHook{}, klist, ksa, ksb, lf.pstride);
-#else
   kloop<float, false>(Ap, validA, Bp, validB, ldt, Kspan, sA, sB, P, tid, nullptr, nullptr, prologue, klist, ksa, ksb, lf.pstride);
-#endif
-#ifdef THX_OFF_PROF
-  __builtin_amdgcn_sched_barrier(0);
-  st[2] = (long long)__builtin_readcyclecounter();
-  __builtin_amdgcn_sched_barrier(0);
-#endif
   if constexpr (HB) {
     // block-compact H: the tile's pieces are gathered into the (now free) staging buffers, 64 rows at a time, and read back in
     // the accumulator layout -- a few hundred elements instead of a 64 KB tile of zeros from HBM
@@ -2338,15 +1889,6 @@ chol_offdiag_f32_kernel(const float* __restrict__ H, float* __restrict__ L, cons
     for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
       for (int q = 0; q < 16; ++q) P.v[cb][q] = -P.v[cb][q];
-#ifdef THX_EXP_NO_HBLOAD
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {   // (full-entropy mantissas: a constant pattern draws less power under the cap)
-        const unsigned hsh = (unsigned)(tid * 64 + cb * 16 + q + 4099 * blockIdx.x) * 2654435761u;
-        P.v[cb][q] += ((lane & 1) ? 1e-3f : -1e-3f) * (1.f + (float)(hsh >> 8) * (1.f / 16777216.f));
-      }
-#endif
     if constexpr (HB == HB_MODE_SCATTER) {
       // a few pieces per tile (pose graphs): added by the matrix cores, see hb_scatter.  (hb_add's barrier also publishes the
       // panel copy -- also when the K-loop had no iterations)
@@ -2390,11 +1932,6 @@ chol_offdiag_f32_kernel(const float* __restrict__ H, float* __restrict__ L, cons
       }
     __syncthreads();  // panel copy visible (also when the K-loop had no iterations)
   }
-#ifdef THX_OFF_PROF
-  __builtin_amdgcn_sched_barrier(0);
-  st[5] = (long long)__builtin_readcyclecounter();   // P = H - sum done (block-compact H: the gather rounds)
-  __builtin_amdgcn_sched_barrier(0);
-#endif
   if (upd) {   // trailing update: the tile goes back as it is (a diagonal tile: its lower triangle, zeros above)
     if (rvalid) {
       float* Lrow = Lij + (int64_t)r * ldt + 4 * g;
@@ -2414,16 +1951,6 @@ chol_offdiag_f32_kernel(const float* __restrict__ H, float* __restrict__ L, cons
   }
   Engine<float>::Acc X;
   Engine<float>::zero(X);
-#ifdef THX_EXP_FULLINV   // timing experiment: the dataflow of a FULL 128 x 128 inverse in the panel, X_s = sum_{t <= s} W_st P_t --
-                         // the same ten block products without the dependent chain (garbage results with today's panel)
-  static_for<4>([&](auto is) __attribute__((always_inline)) {
-    constexpr int sb = decltype(is)::value;
-    static_for<sb + 1>([&](auto it) __attribute__((always_inline)) {
-      constexpr int tb = decltype(it)::value;
-      sub_mma_sw<sb, tb>(Pc, P, X, lane);
-    });
-  });
-#else
   static_for<4>([&](auto is) __attribute__((always_inline)) {
     constexpr int sb = decltype(is)::value;
     static_for<sb>([&](auto it) __attribute__((always_inline)) {
@@ -2432,12 +1959,6 @@ chol_offdiag_f32_kernel(const float* __restrict__ H, float* __restrict__ L, cons
     });
     sub_mma_sw<sb, sb>(Pc, P, X, lane);    // X_s  = W_ss P_s
   });
-#endif
-#ifdef THX_OFF_PROF
-  __builtin_amdgcn_sched_barrier(0);
-  st[3] = (long long)__builtin_readcyclecounter();
-  __builtin_amdgcn_sched_barrier(0);
-#endif
   if (rvalid) {
     float* Lrow = Lij + (int64_t)r * ldt + 4 * g;
 #pragma unroll
@@ -2461,22 +1982,6 @@ chol_offdiag_f32_kernel(const float* __restrict__ H, float* __restrict__ L, cons
     dot += __shfl_xor(dot, 32);
     if (g == 0 && rvalid) yb[row0 + r] -= dot;
   }
-#ifdef THX_OFF_PROF
-  __builtin_amdgcn_s_waitcnt(0);
-  st[4] = (long long)__builtin_readcyclecounter();
-  __syncthreads();
-  if (tid == 0) {
-    float* o = Lij;
-    for (int k = 1; k < 5; ++k) o[k] = (float)(st[k] - st[0]);
-    o[5] = (float)((long long)wall_clock64() - wc0);  // 100 MHz ticks
-    o[6] = (float)(st[5] - st[0]);
-    // where and when this workgroup ran (tools/prof/off_occupancy.py): raw 32-bit words
-    o[7] = __int_as_float((int)__builtin_amdgcn_s_getreg(((32 - 1) << 11) | 4));    // HW_REG_HW_ID
-    o[8] = __int_as_float((int)__builtin_amdgcn_s_getreg(((32 - 1) << 11) | 20));   // HW_REG_XCC_ID
-    o[9] = __int_as_float((int)(unsigned)wc0);
-    o[10] = __int_as_float((int)(unsigned)wall_clock64());
-  }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2565,11 +2070,7 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
   Engine<float>::zero(P1);
   const int nk = 4 * j;
   if (nk > 0) gload3(0);
-#ifdef THX_EXP_NO_HBLOAD
-  if constexpr (HB) hb2.empty();
-#else
   if constexpr (HB) hb2.load(hb, b, i, j, tid);
-#endif
   const float* sBw = sB + 32 * wave * 36;
   for (int kc = 0; kc < nk; ++kc) {
     __syncthreads();
@@ -2630,15 +2131,6 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
       for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
         for (int q = 0; q < 16; ++q) P.v[cb][q] = -P.v[cb][q];
-#ifdef THX_EXP_NO_HBLOAD
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const unsigned hsh = (unsigned)(tid * 64 + cb * 16 + q + 4099 * blockIdx.x + 77 * sel) * 2654435761u;
-          P.v[cb][q] += ((lane & 1) ? 1e-3f : -1e-3f) * (1.f + (float)(hsh >> 8) * (1.f / 16777216.f));
-        }
-#endif
       if constexpr (HB == HB_MODE_SCATTER) {
         // a few pieces per tile (pose graphs): added by the matrix cores, see hb_scatter.  Both tiles' values go to staging
         // buffer 0 as ONE list before tile (i, j)'s pieces are applied (the caller's barrier before panel_dma(j): the K-loop is
@@ -2845,23 +2337,10 @@ chol_offdiag_f64_kernel(const double* __restrict__ H, double* __restrict__ L, co
   double* sA = smem;
   double* sB = smem + 128 * CT<double>::LDT;
 
-#ifdef THX_OFF_PROF64   // timing build (tools/prof/off_prof64.py): cycle stamps overwrite the head of the output tile
-  long long st64[16];
-  for (int k = 0; k < 16; ++k) st64[k] = 0;
-  st64[0] = (long long)__builtin_readcyclecounter();
-  const long long wc64 = (long long)wall_clock64();
-#define THX_ST64(k) do { __builtin_amdgcn_sched_barrier(0); st64[k] = (long long)__builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define THX_ST64(k)
-#endif
   E::Acc P;
   E::zero(P);
   HBPre<double, HB ? HB_NPRE_OFF : 1> hbp;
-#ifdef THX_EXP_NO_HBLOAD
-  if constexpr (HB) hbp.empty();
-#else
   if constexpr (HB) hbp.load(hb, b, i, j, tid);
-#endif
   // panel sub-block q (row-major list of the lower triangle): block row SB[q], block column TB[q]
   const double* Pn = panel + ((int64_t)b * ntiles + j) * TILE * TILE;
   double* const smemE = smem + OFF64_STAGE / 8;
@@ -2888,7 +2367,6 @@ chol_offdiag_f64_kernel(const double* __restrict__ H, double* __restrict__ L, co
   // block-compact H: after the gather rounds), W_33 (sub-block 9) LDS-direct into sub-block 0's place in E once E has been read.
   // No panel data in registers: round 4 parked sub-blocks 5..9 (block-compact H) / W_33 (dense H) in VGPRs from here on and
   // hipcc spilled them -- 160 B per thread through scratch, 1 GB of extra HBM traffic per launch (profiles/r5/ab_, ac_).
-  THX_ST64(1);   // K-loop done
   if (!HB && !upd) {
     // dense H: 5..8 straight into the staging buffers (LDS-direct, no registers: the 128 VGPRs of the H tile are about to be in
     // flight) -- after a barrier: the K-loop ends on a chunk's MFMAs, a slower wave may still be reading its fragments
@@ -2920,7 +2398,6 @@ chol_offdiag_f64_kernel(const double* __restrict__ H, double* __restrict__ L, co
     constexpr int LDH = 130;
     static_assert(32 * LDH * 8 <= OFF64_STAGE, "a quarter of an H tile must fit in the staging buffers");
     __syncthreads();
-    THX_ST64(8);    // (sub-stamps 8..11: the first barrier -- the K-loop's last MFMAs drained --, then the gather rounds 1..3 begin)
     // P = -sum first, H_ij's pieces are ADDED
 #pragma unroll
     for (int h = 0; h < 2; ++h)
@@ -2928,31 +2405,14 @@ chol_offdiag_f64_kernel(const double* __restrict__ H, double* __restrict__ L, co
       for (int cb = 0; cb < 8; ++cb)
 #pragma unroll
         for (int rho = 0; rho < 4; ++rho) P.v[h][cb][rho] = -P.v[h][cb][rho];
-#ifdef THX_EXP_NO_HBLOAD
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int cb = 0; cb < 8; ++cb)
-#pragma unroll
-        for (int rho = 0; rho < 4; ++rho) {
-          const unsigned hsh = (unsigned)(tid * 64 + h * 32 + cb * 4 + rho + 4099 * blockIdx.x) * 2654435761u;
-          const unsigned h2 = hsh * 2246822519u + 1u;
-          P.v[h][cb][rho] += ((lane & 1) ? 1e-3 : -1e-3) * (1.0 + ((double)hsh * 4294967296.0 + (double)h2) * (1.0 / 18446744073709551616.0));
-        }
-#endif
     if constexpr (HB == HB_MODE_SCATTER) {
       // a few pieces per tile (pose graphs): added by the matrix cores, see hb_scatter
       static_assert((256 * HB_NPRE_OFF + 64 * 36) * 8 <= OFF64_STAGE, "list + overflow chunk inside the staging buffers");
       hb_add<double, E::Acc, decltype(hbp), 256 * HB_NPRE_OFF>(P, hbp, hb, b, smem, 0, hbp.cnt / (hb.bd * hb.bd), true, tid);
-#ifndef THX_EXP_NO_HBBARRIER   // (timing experiment, WRONG results)
       __syncthreads();   // the list has been read: panel sub-blocks 5..8 may take the staging buffers
-#endif
     } else {
 #pragma unroll
     for (int rd = 0; rd < 4; ++rd) {
-      if (rd == 1) THX_ST64(9);
-      if (rd == 2) THX_ST64(10);
-      if (rd == 3) THX_ST64(11);
       for (int k = tid; k < 32 * LDH / 2; k += 256) reinterpret_cast<double2*>(smem)[k] = make_double2(0.0, 0.0);
       __syncthreads();
       hbp.foreach(hb, b, tid, [&](int rr, int cc, double v) __attribute__((always_inline)) {
@@ -2988,7 +2448,6 @@ chol_offdiag_f64_kernel(const double* __restrict__ H, double* __restrict__ L, co
       }
   }
   }
-  THX_ST64(2);   // P = H - sum
   if (RL && upd) {   // trailing update: the tile goes back as it is (a diagonal tile: its lower triangle, zeros above)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -3022,7 +2481,6 @@ chol_offdiag_f64_kernel(const double* __restrict__ H, double* __restrict__ L, co
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
-  THX_ST64(3);   // panel staged and visible
   // ---- in-place substitution ----
   auto solve_diag = [&](auto is, const double* Wss) __attribute__((always_inline)) {
     constexpr int sb = decltype(is)::value;
@@ -3069,7 +2527,6 @@ chol_offdiag_f64_kernel(const double* __restrict__ H, double* __restrict__ L, co
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();                  // W_33 in place
   solve_diag(I3{}, smemE + 0 * 1024);
-  THX_ST64(4);   // substitution done
   // ---- store X (in P's registers) ----
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -3098,18 +2555,6 @@ chol_offdiag_f64_kernel(const double* __restrict__ H, double* __restrict__ L, co
       if (kq == 0 && r < validB) yb[row0 + r] -= dot;
     }
   }
-#ifdef THX_OFF_PROF64
-  __builtin_amdgcn_s_waitcnt(0);
-  st64[5] = (long long)__builtin_readcyclecounter();
-  __syncthreads();
-  if (tid == 0) {
-    double* o = Lij;
-    for (int k = 1; k < 6; ++k) o[k] = (double)(st64[k] - st64[0]);
-    o[6] = (double)((long long)wall_clock64() - wc64);  // 100 MHz ticks
-    for (int k = 8; k < 12; ++k) o[k] = (double)(st64[k] - st64[0]);
-  }
-#endif
-#undef THX_ST64
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3300,14 +2745,12 @@ chol_offdiag_f64w8_kernel(const double* __restrict__ H, double* __restrict__ L, 
 // of H, panel waits, ten dependent block products, stores) that two resident workgroups cannot overlap.  The price: each half
 // stages the whole column panel L_j (1.5x the operand traffic per tile product), the solve panel is not prefetched under the K-loop
 // but fetched afterwards, four sub-blocks at a time into the free staging buffers (three exposed round trips), one k-chunk in
-// flight instead of two.  Same MFMAs in the same order per element: bit-identical (tools/cmp_f64_half.py, tests/test_gpu_block_hessian.py).
+// flight instead of two.  Same MFMAs in the same order per element: bit-identical (tests/test_gpu_block_hessian.py).
 // MEASURED (profiles/r6/af_): n = 1536, batch 4096: 90.0 -> 88.5 ms with the first 6 - 8 block columns on this kernel (0.700 -> 0.711),
 // every further column gives 0.1 ms back (the K-loop with one chunk in flight and 1.5x the staging loses to the 8-wave kernel from
 // ~8 tiles on): thx_chol_schedule.f64_half_max_ktiles, default 8.
 // ------------------------------------------------------------------------------------------------
-#ifndef THX_F64H_AHEAD
-#define THX_F64H_AHEAD 1   // k-chunks in flight (2: 142 VGPRs wanted, spills -- see the header comment)
-#endif
+constexpr int F64H_AHEAD = 1;   // k-chunks in flight (2: 142 VGPRs wanted, spills -- see the header comment)
 template <int HB>
 __global__ void __launch_bounds__(256, 4)
 chol_offdiag_f64h_kernel(const double* __restrict__ H, double* __restrict__ L, const double* __restrict__ panel, int n,
@@ -3344,7 +2787,7 @@ chol_offdiag_f64h_kernel(const double* __restrict__ H, double* __restrict__ L, c
   const double* Pn = panel + ((int64_t)b * ntiles + j) * TILE * TILE;
   {
     const double* sBw = sB + 16 * wave * CT<double>::LDT;
-    kloop_f<double, false, false, CT<double>::LDT, false, NT, THX_F64H_AHEAD, 64>(
+    kloop_f<double, false, false, CT<double>::LDT, false, NT, F64H_AHEAD, 64>(
         L + mat + (int64_t)col0 * ld, TILE, L + mat + (int64_t)row0 * ld, validB, ld, Kspan, sA, sB, tid, nullptr, nullptr,
         [&]() __attribute__((always_inline)) {
           constexpr int LDT = CT<double>::LDT;
@@ -3432,7 +2875,6 @@ chol_offdiag_f64h_kernel(const double* __restrict__ H, double* __restrict__ L, c
   using I1 = std::integral_constant<int, 1>;
   using I2 = std::integral_constant<int, 2>;
   using I3 = std::integral_constant<int, 3>;
-#ifndef THX_F64H_RING
   // ---- the substitution in three panel phases of four / four / two sub-blocks through the staging buffers (each an exposed round
   //      trip, covered by the other three workgroups of the CU) ----
   panel_dma(0, 0, smem + 0 * 1024);
@@ -3460,54 +2902,6 @@ chol_offdiag_f64h_kernel(const double* __restrict__ H, double* __restrict__ L, c
   landed();
   update(I3{}, I2{}, smem + 0 * 1024);
   solve_diag(I3{}, smem + 1 * 1024);
-#else
-  // (-DTHX_F64H_RING, measured EQUAL: 87.99 / 88.03 against 87.92 / 88.13 ms, profiles/r6/af_ -- not the default: ten barriers for nothing)
-  // ---- the substitution with the panel's ten sub-blocks through a RING of four slots in the staging buffers: sub-block m lives in
-  //      slot m % 4; the first four are requested here, sub-block k + 3 at step k >= 1 -- right behind the barrier that proves every
-  //      wave has finished product k - 1, the previous tenant of that slot -- so a request has three products' time to land.  The
-  //      waits count instructions: loads return in order, two LDS-direct loads per thread and sub-block, and behind sub-block k
-  //      at most k + 1, k + 2 are in flight.  One exposed round trip instead of three. ----
-  panel_dma(0, 0, smem + 0 * 1024);
-  panel_dma(1, 0, smem + 1 * 1024);
-  panel_dma(1, 1, smem + 2 * 1024);
-  panel_dma(2, 0, smem + 3 * 1024);
-  asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  __syncthreads();
-  solve_diag(I0{}, smem + 0 * 1024);                 // product 0: (0,0)
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  __syncthreads();
-  panel_dma(2, 1, smem + 0 * 1024);                  // sub-block 4 -> slot 0
-  update(I1{}, I0{}, smem + 1 * 1024);               // product 1: (1,0)
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  __syncthreads();
-  panel_dma(2, 2, smem + 1 * 1024);                  // 5 -> slot 1
-  solve_diag(I1{}, smem + 2 * 1024);                 // product 2: (1,1)
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  __syncthreads();
-  panel_dma(3, 0, smem + 2 * 1024);                  // 6 -> slot 2
-  update(I2{}, I0{}, smem + 3 * 1024);               // product 3: (2,0)
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  __syncthreads();
-  panel_dma(3, 1, smem + 3 * 1024);                  // 7 -> slot 3
-  update(I2{}, I1{}, smem + 0 * 1024);               // product 4: (2,1)
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  __syncthreads();
-  panel_dma(3, 2, smem + 0 * 1024);                  // 8 -> slot 0
-  solve_diag(I2{}, smem + 1 * 1024);                 // product 5: (2,2)
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  __syncthreads();
-  panel_dma(3, 3, smem + 1 * 1024);                  // 9 -> slot 1
-  update(I3{}, I0{}, smem + 2 * 1024);               // product 6: (3,0)
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  __syncthreads();
-  update(I3{}, I1{}, smem + 3 * 1024);               // product 7: (3,1)
-  asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  __syncthreads();
-  update(I3{}, I2{}, smem + 0 * 1024);               // product 8: (3,2)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  solve_diag(I3{}, smem + 1 * 1024);                 // product 9: (3,3)
-#endif
   // ---- store X ----
   if (r < validB) {
     double* Lrow = Lij + (int64_t)r * ld + kq;
@@ -3854,22 +3248,12 @@ __global__ void vec_gather_kernel(const T* __restrict__ src, int64_t lds, T* __r
 
 constexpr size_t LDS_LIMIT = 160 * 1024;
 constexpr int FACTOR_NEEDS_FORWARD = 1000;   // factor_impl -> factor_then_forward: factor done, y = L^-1 rhs still to be computed
+constexpr int BWD_ROWS_MAX_BATCH = 32;       // solve_impl: the backward substitution block row by block row up to this batch
 
-// Defaults of the per-call schedule (thx_chol_schedule; a negative field / a NULL pointer selects them): read once from the
-// environment, never written afterwards -- the library keeps no mutable schedule state, two callers with different schedules in
-// one process do not see each other.
-static const int g_split_diag_min_default = [] {
-  const char* e = getenv("THX_CHOL_SPLIT_DIAG_MIN");
-  return e ? atoi(e) : 2048;
-}();
-static const int g_column_pairs_default = [] {
-  const char* e = getenv("THX_CHOL_COLPAIR");
-  return e ? atoi(e) : 1;
-}();
-static const int g_right_looking_max_default = [] {
-  const char* e = getenv("THX_CHOL_RL_MAX_BATCH");
-  return e ? atoi(e) : -1;   // (-1: by dtype and size, factor_impl)
-}();
+// Defaults of the per-call schedule (thx_chol_schedule; a negative field / a NULL pointer selects them).  The library keeps no
+// mutable schedule state: two callers with different schedules in one process do not see each other.
+constexpr int SPLIT_DIAG_MIN_DEFAULT = 2048;
+constexpr int COLUMN_PAIRS_DEFAULT = 1;
 
 // Launch-side state is kept PER DEVICE (a process may drive several GPUs, from several threads): the dynamic-LDS limits
 // raised with hipFuncSetAttribute, and the auxiliary stream + events of the two-stream schedule, which belong to the device
@@ -3878,9 +3262,15 @@ constexpr int MAX_DEVICES = 64;
 struct DeviceLaunchState {
   size_t attr_diag[2][2] = {{0, 0}, {0, 0}}, attr_syrk[2][2] = {{0, 0}, {0, 0}}, attr_solve[2] = {0, 0}, attr_bwd_rows[2] = {0, 0};   // [0] float, [1] double (x HB)
   bool attr_off = false;
-  hipStream_t aux[2] = {nullptr, nullptr};
-  hipEvent_t ev_fork = nullptr, ev_lag[2] = {nullptr, nullptr}, ev_join[2] = {nullptr, nullptr};
+  hipStream_t aux = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_lag = nullptr, ev_join = nullptr;
   hipEvent_t ev_diag = nullptr, ev_rest = nullptr;   // look-ahead schedule (one part): diag(j) done / rest of column j done
+  // the auxiliary stream and the events of the two-stream schedules, created on first use
+  void need_aux() {
+    if (aux) return;
+    hipStreamCreateWithFlags(&aux, hipStreamNonBlocking);
+    for (hipEvent_t* e : {&ev_fork, &ev_lag, &ev_join, &ev_diag, &ev_rest}) hipEventCreateWithFlags(e, hipEventDisableTiming);
+  }
 };
 static std::mutex g_launch_mutex;
 static DeviceLaunchState& launch_state() {
@@ -3890,69 +3280,35 @@ static DeviceLaunchState& launch_state() {
   return st[(dev >= 0 && dev < MAX_DEVICES) ? dev : 0];
 }
 
-// Environment defaults of the launch plan below (read once at load time, like the schedule defaults above).
 // how an off-diagonal tile takes its pieces of H: a few per tile (pose graphs) -> added by the matrix cores (hb_scatter); many (a
 // bundle adjustment's reduced camera system: up to 21 x 21 blocks per tile) or unknown -> gathered through LDS in rounds
-static const int g_hb_scatter_max_default = [] {
-  const char* e = getenv("THX_HB_SCATTER_MAX_PIECES");   // (0: always the gather rounds)
-  return e ? atoi(e) : 64;
-}();
+constexpr int HB_SCATTER_MAX_PIECES_DEFAULT = 64;
 // fp64: the first f64_wide_max block columns (K-loops shorter than that many tiles) take the 8-wave off-diagonal kernel
 // (chol_offdiag_f64w8_kernel).  Default: ALL of them -- measured +1.0 ... 1.3 % at batch 256 / 1024 / 4096 (n = 1536), growing with
 // the number of columns that use it (profiles/r6/ae_): four waves per SIMD serve the K-loop better than two; the early columns,
 // for which the kernel was written, gain nothing.
-static const int g_f64_wide_default = [] {
-  const char* e = getenv("THX_F64_WIDE_MAX_KTILES");   // (0: never)
-  return e ? atoi(e) : (1 << 30);
-}();
+constexpr int F64_WIDE_MAX_KTILES_DEFAULT = 1 << 30;
 // ... and the first f64_half_max of them (K-loops shorter than that many tiles) the HALF-TILE kernel (chol_offdiag_f64h_kernel, four
 // workgroups per CU): measured optimum 6 ... 8 at n = 1536 / batch 4096 (profiles/r6/af_: 90.0 -> 88.5 ms; all twelve columns 89.0)
-static const int g_f64_half_default = [] {
-  const char* e = getenv("THX_F64_HALF_MAX_KTILES");   // (0: never)
-  return e ? atoi(e) : 8;
-}();
-static const int g_split_min = [] {
-  const char* e = getenv("THX_CHOL_SPLIT_MIN");  // batch size from which the multi-stream schedule is used (0: never)
-  return e ? atoi(e) : 1024;
-}();
-// number of parts (streams): 2; THX_CHOL_PARTS=3 staggers three thirds (measured)
-static const int g_nparts_cfg = [] {
-  const char* e = getenv("THX_CHOL_PARTS");
-  const int v = e ? atoi(e) : 2;
-  return v < 2 ? 2 : (v > 3 ? 3 : v);
-}();
-static const bool g_lookahead_cfg = [] {
-  const char* e = getenv("THX_CHOL_LOOKAHEAD");
-  return e ? atoi(e) != 0 : true;
-}();
-// (dense frames: see the look-ahead in factor_impl -- experiment, default 0 = off)
-static const int g_dense_la_max = [] {
-  const char* e = getenv("THX_CHOL_LOOKAHEAD_DENSE_MAX_BATCH");
-  return e ? atoi(e) : 0;
-}();
-static const int g_rl_mode_default = [] {
-  const char* e = getenv("THX_CHOL_RL_LOOKAHEAD");
-  return e ? atoi(e) : -1;   // (-1: by dtype, plan_factor)
-}();
+constexpr int F64_HALF_MAX_KTILES_DEFAULT = 8;
+// batch size from which the batch is dealt over two streams (factor_impl)
+constexpr int SPLIT_MIN = 1024;
 // (pairs from 128 problems per call on: the pair schedule's chain per two columns is diag, head tile, diag, pair tiles -- one
 //  more dependent launch than two plain columns -- and below ~128 problems the launches are too small to pay for it: n = 1536,
 //  batch 8 / 16 / 32 / 64: 1.62 / 1.64 / 1.67 / 1.85 ms with pairs, 1.42 / 1.44 / 1.50 / 1.73 ms without; 128: 2.25 / 2.23; 256:
 //  3.25 / 3.30 -- profiles/r6/j_ab_small_batch.txt.  Bit-identical either way.)
-static const int g_pair_min_batch_default = [] {
-  const char* e = getenv("THX_CHOL_COLPAIR_MIN_BATCH");
-  return e ? atoi(e) : 128;
-}();
+constexpr int COLUMN_PAIRS_MIN_BATCH_DEFAULT = 128;
 
 // THE LAUNCH PLAN of a factorisation: every schedule decision factor_impl takes from its arguments, the per-call schedule and the
-// environment defaults -- in one place, so that thx_chol_plan reports exactly what a call with those arguments runs.
+// defaults above -- in one place, so that thx_chol_plan reports exactly what a call with those arguments runs.
 struct FactorPlan {
   int ntiles;
   int split_diag_min;    // (the level schedule decides per level with it)
   bool fused_diag;       // the diagonal phase as one kernel (else SYRK + potrf)
   int rl_max_batch;
-  bool split;            // the batch dealt over nparts streams
-  int nparts;
-  bool lookahead;        // one part, REST of a column on the second stream (tile-sparse with col_head_host, or the dense experiment)
+  bool split;            // the batch dealt over two streams
+  int nparts;            // 2 if split, else 1
+  bool lookahead;        // one part, REST of a column on the second stream (tile-sparse with col_head_host)
   bool rl;               // the right-looking schedule of small dense batches
   int rl_mode;           // its launch arrangement (0 | 1 | 2)
   bool rl_fwd_fused;     // ... with the forward substitution riding on it (else FACTOR_NEEDS_FORWARD)
@@ -3967,34 +3323,33 @@ static FactorPlan plan_factor(bool f64, int n, int64_t ld, int B, bool has_dampi
   const bool use_hb = hbp != nullptr;
   const bool packed = ld == 0;
   p.ntiles = (n + TILE - 1) / TILE;
-  const int hb_scatter_max = (sched && sched->hb_scatter_max_pieces >= 0) ? sched->hb_scatter_max_pieces : g_hb_scatter_max_default;
+  const int hb_scatter_max = (sched && sched->hb_scatter_max_pieces >= 0) ? sched->hb_scatter_max_pieces : HB_SCATTER_MAX_PIECES_DEFAULT;
   const bool hb_sc = use_hb && hbp->bd <= 6 && hbp->max_tile_pieces > 0 && hbp->max_tile_pieces <= hb_scatter_max;
   p.hbm = !use_hb ? 0 : (hb_sc ? HB_MODE_SCATTER : HB_MODE_ROUNDS);
-  p.f64_wide_max = (sched && sched->f64_wide_max_ktiles >= 0) ? sched->f64_wide_max_ktiles : g_f64_wide_default;
-  p.f64_half_max = (sched && sched->f64_half_max_ktiles >= 0) ? sched->f64_half_max_ktiles : g_f64_half_default;
+  p.f64_wide_max = (sched && sched->f64_wide_max_ktiles >= 0) ? sched->f64_wide_max_ktiles : F64_WIDE_MAX_KTILES_DEFAULT;
+  p.f64_half_max = (sched && sched->f64_half_max_ktiles >= 0) ? sched->f64_half_max_ktiles : F64_HALF_MAX_KTILES_DEFAULT;
   // diagonal phase: chol_syrk_kernel + chol_potrf_kernel from split_diag_min problems per call on (measured, n = 1536: fp32
   // 45.1 vs 46.0 ms at batch 4096, fp64 101.6 vs 105.2 ms; equal at batch 1024; 3.74 vs 3.51 ms at batch 256 -- the second
   // launch per column costs more than the chain there), else the fused chol_diag_kernel
-  p.split_diag_min = (sched && sched->split_diag_min_batch >= 0) ? sched->split_diag_min_batch : g_split_diag_min_default;
-  const int column_pairs = (sched && sched->column_pairs >= 0) ? sched->column_pairs : g_column_pairs_default;
-  const int pair_min_batch = (sched && sched->column_pairs_min_batch >= 0) ? sched->column_pairs_min_batch : g_pair_min_batch_default;
+  p.split_diag_min = (sched && sched->split_diag_min_batch >= 0) ? sched->split_diag_min_batch : SPLIT_DIAG_MIN_DEFAULT;
+  const int column_pairs = (sched && sched->column_pairs >= 0) ? sched->column_pairs : COLUMN_PAIRS_DEFAULT;
+  const int pair_min_batch =
+      (sched && sched->column_pairs_min_batch >= 0) ? sched->column_pairs_min_batch : COLUMN_PAIRS_MIN_BATCH_DEFAULT;
   // (default hand-over to the left-looking schedule, measured at 12 block columns with two launches per column, profiles/r6/ar_:
   //  fp32 right-looking wins through 64 problems -- batch 40 1.49 -> 1.16 ms, 64 1.66 -> 1.58 --, fp64 through 40; the update
   //  launches grow with the SQUARE of the block columns, so the limit shrinks with them, down to round 6's first 32)
   const int rl_auto = !f64 ? min(64, max(32, 768 / max(p.ntiles, 1))) : min(40, max(32, 480 / max(p.ntiles, 1)));
-  p.rl_max_batch = (sched && sched->right_looking_max_batch >= 0) ? sched->right_looking_max_batch
-                   : (g_right_looking_max_default >= 0 ? g_right_looking_max_default : rl_auto);
+  p.rl_max_batch = (sched && sched->right_looking_max_batch >= 0) ? sched->right_looking_max_batch : rl_auto;
   p.fused_diag = B < p.split_diag_min;
-  p.split = g_split_min > 0 && B >= g_split_min && p.ntiles > 1;
-  p.nparts = p.split ? g_nparts_cfg : 1;
+  p.split = B >= SPLIT_MIN && p.ntiles > 1;
+  p.nparts = p.split ? 2 : 1;
   if (ls) return p;   // (the level schedule: its own launch loop, per level)
-  const bool dense_la = !tp && !packed && B > p.rl_max_batch && B <= g_dense_la_max;
-  p.lookahead = g_lookahead_cfg && !p.split && p.ntiles > 2 && ((tp && tp->col_head_host != nullptr) || dense_la);
+  p.lookahead = !p.split && p.ntiles > 2 && tp && tp->col_head_host != nullptr;
   if (p.lookahead) return p;
   p.rl = !tp && !packed && !p.split && p.fused_diag && p.ntiles >= 3 && B <= p.rl_max_batch && ld >= (int64_t)p.ntiles * TILE &&
          (!use_hb || !has_damping || hbp->diag_blk);
   if (p.rl) {
-    const int m = (sched && sched->right_looking_mode >= 0) ? sched->right_looking_mode : g_rl_mode_default;
+    const int m = sched ? sched->right_looking_mode : -1;
     p.rl_mode = m < 0 ? (f64 ? 2 : 1) : (m > 2 ? 1 : m);
     p.rl_fwd_fused = has_rhs && (ldv % 4) == 0 && y_aligned16;
     return p;
@@ -4117,24 +3472,14 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
   };
   const bool split = P.split;
   const int nparts = P.nparts;
-  Half halves[3] = {{st, 0, B}, {st, 0, 0}, {st, 0, 0}};
+  Half halves[2] = {{st, 0, B}, {st, 0, 0}};
   if (split) {
-    if (!ds.ev_fork) hipEventCreateWithFlags(&ds.ev_fork, hipEventDisableTiming);
-    for (int k = 0; k + 1 < nparts; ++k)
-      if (!ds.aux[k]) {
-        hipStreamCreateWithFlags(&ds.aux[k], hipStreamNonBlocking);
-        hipEventCreateWithFlags(&ds.ev_lag[k], hipEventDisableTiming);
-        hipEventCreateWithFlags(&ds.ev_join[k], hipEventDisableTiming);
-      }
-    const int per = min((B / nparts + 7) / 8 * 8, B);  // (multiple of 8: the XCD-aware block map of chol_offdiag)
-    int b0 = 0;
-    for (int k = 0; k < nparts; ++k) {
-      const int nb = k + 1 < nparts ? min(per, B - b0) : B - b0;
-      halves[k] = {k == 0 ? st : ds.aux[k - 1], b0, nb};
-      b0 += nb;
-    }
+    ds.need_aux();
+    const int per = min((B / 2 + 7) / 8 * 8, B);  // (multiple of 8: the XCD-aware block map of chol_offdiag)
+    halves[0] = {st, 0, per};
+    halves[1] = {ds.aux, per, B - per};
     hipEventRecord(ds.ev_fork, st);
-    for (int k = 0; k + 1 < nparts; ++k) hipStreamWaitEvent(ds.aux[k], ds.ev_fork, 0);
+    hipStreamWaitEvent(ds.aux, ds.ev_fork, 0);
   }
   // (block-compact H: the half's problems start at h.b0 of the block list; H itself is not dereferenced)
   auto hb_of = [&](const Half& h) {
@@ -4224,98 +3569,19 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
   // ~log2(ntiles) of them under a nested-dissection ordering (theseus_amd/sparse.py:LevelPattern).
   if (ls) {
     pat.lpt = 1;   // (the level's entries are sorted longest K-list first; consecutive workgroups = the problems of one entry)
-    // TWO HALF BATCHES ON TWO STREAMS (THX_LEVEL_SPLIT_MIN=<problems> turns it on; default OFF): a level is SYRK (memory) -> potrf
-    // (one wave per tile in its pivot chain: latency) -> off-diagonal tiles (matrix cores); one half's potrf could run underneath the
-    // other half's off-diagonal launch (kernel trace at 4096 poses / batch 256: potrf 1.9 ms + SYRK 2.1 ms of a 9.3 ms
-    // factorisation with the matrix cores idle).  MEASURED, NOT A WIN (profiles/r6/c_bench_sparse_two_streams.txt: factor 9.00 vs
-    // 9.16 ms at batch 256, 2.81 vs 2.76 ms at batch 64; the LM iteration 14.3 vs 13.9 / 5.66 vs 5.61 ms): a level's launches are
-    // one to two rounds of workgroups, halving them halves the occupancy of each.  The halves are disjoint problems: no dependence
-    // between the streams, same arithmetic.
-    static const int level_split_min = [] {
-      const char* e = getenv("THX_LEVEL_SPLIT_MIN");
-      return e ? atoi(e) : 0;
-    }();
-    const bool two = level_split_min > 0 && B >= level_split_min && B >= 16;
-    Half hv[2] = {{st, 0, B}, {st, 0, 0}};
-    if (two) {
-      if (!ds.ev_fork) hipEventCreateWithFlags(&ds.ev_fork, hipEventDisableTiming);
-      if (!ds.aux[0]) {
-        hipStreamCreateWithFlags(&ds.aux[0], hipStreamNonBlocking);
-        hipEventCreateWithFlags(&ds.ev_lag[0], hipEventDisableTiming);
-        hipEventCreateWithFlags(&ds.ev_join[0], hipEventDisableTiming);
-      }
-      const int per = min((B / 2 + 7) / 8 * 8, B);
-      hv[0] = {st, 0, per};
-      hv[1] = {ds.aux[0], per, B - per};
-      hipEventRecord(ds.ev_fork, st);
-      hipStreamWaitEvent(ds.aux[0], ds.ev_fork, 0);
-    }
-    // SUBTREE STREAMS (level_stream_host; not together with the half-batch split): levels of group 1 on the second stream, one
-    // diagonal phase behind group 0, joined in front of the first trunk level
-    const int32_t* lstr = two ? nullptr : ls->level_stream_host;
-    static const bool chains_on = [] {
-      const char* e = getenv("THX_LEVEL_CHAINS");
-      return e ? atoi(e) != 0 : true;
-    }();
-    if (!chains_on) lstr = nullptr;
-    bool forked = false, lag_recorded = false, lag_waited = false;
-    if (lstr) {
-      if (!ds.ev_fork) hipEventCreateWithFlags(&ds.ev_fork, hipEventDisableTiming);
-      if (!ds.aux[0]) {
-        hipStreamCreateWithFlags(&ds.aux[0], hipStreamNonBlocking);
-        hipEventCreateWithFlags(&ds.ev_lag[0], hipEventDisableTiming);
-        hipEventCreateWithFlags(&ds.ev_join[0], hipEventDisableTiming);
-      }
-      hipEventRecord(ds.ev_fork, st);
-      hipStreamWaitEvent(ds.aux[0], ds.ev_fork, 0);
-      forked = true;
-    }
+    const Half h{st, 0, B};
     for (int l = 0; l < ls->nlevels; ++l) {
       const int j0 = ls->level_col_host[l], nc = ls->level_col_host[l + 1] - j0;
       const int e0 = ls->level_ent_host[l], ne = ls->level_ent_host[l + 1] - e0;
       if (nc <= 0) continue;
       const int yp = rhs ? ls->level_maxk_host[l] * TILE : 0;
-      if (lstr) {
-        const int code = lstr[l];
-        if (forked && (code & 4)) {   // the trunk: everything below it has to be there
-          hipEventRecord(ds.ev_join[0], ds.aux[0]);
-          hipStreamWaitEvent(st, ds.ev_join[0], 0);
-          forked = false;
-        }
-        const bool second = forked && (code & 3) == 1;
-        const Half h{second ? ds.aux[0] : st, 0, B};
-        const bool fused = (int64_t)B * nc < split_diag_min;
-        if (second && !lag_waited && lag_recorded) {   // group 1 starts one diagonal phase behind group 0
-          hipStreamWaitEvent(h.s, ds.ev_lag[0], 0);
-          lag_waited = true;
-        }
-        launch_diag_n(h, j0, nc, fused, fused ? DiagSmem<T>::bytes(yp) : SyrkSmem<T>::bytes(yp));
-        if (!second && forked && !lag_recorded) {
-          hipEventRecord(ds.ev_lag[0], st);
-          lag_recorded = true;
-        }
-        if (ne > 0) launch_off(h, j0, e0, ne);
-        continue;
-      }
-      for (int k = 0; k < (two ? 2 : 1); ++k) {
-        const Half& h = hv[k];
-        if (h.nb <= 0) continue;
-        // (the schedule of the diagonal phase follows the LAUNCH's workgroup count -- whole batch, so that a problem's arithmetic
-        //  does not depend on which half it is in)
-        const bool fused = (int64_t)B * nc < split_diag_min;
-        if (two && k == 1 && l == 0) hipStreamWaitEvent(h.s, ds.ev_lag[0], 0);   // half 1: one diagonal phase behind half 0
-        launch_diag_n(h, j0, nc, fused, fused ? DiagSmem<T>::bytes(yp) : SyrkSmem<T>::bytes(yp));
-        if (two && k == 0 && l == 0) hipEventRecord(ds.ev_lag[0], h.s);
-        if (ne > 0) launch_off(h, j0, e0, ne);
-      }
-    }
-    if (two || forked) {
-      hipEventRecord(ds.ev_join[0], ds.aux[0]);
-      hipStreamWaitEvent(st, ds.ev_join[0], 0);
+      const bool fused = (int64_t)B * nc < split_diag_min;
+      launch_diag_n(h, j0, nc, fused, fused ? DiagSmem<T>::bytes(yp) : SyrkSmem<T>::bytes(yp));
+      if (ne > 0) launch_off(h, j0, e0, ne);
     }
     return check_launch("thx_chol_factor_levels");
   }
-  // LOOK-AHEAD for batches that do not fill the chip (one part, i.e. B < THX_CHOL_SPLIT_MIN; THX_CHOL_LOOKAHEAD=0 turns it off).
+  // LOOK-AHEAD for batches that do not fill the chip (one part, i.e. B < SPLIT_MIN).
   // Left-looking: tile (i, j) needs rows i and j of the columns before j.  So the diagonal phase of column j + 1 needs, of column
   // j, only tile (j + 1, j) -- and at batch 256 that phase is B workgroups with one busy wave each (80 us on a 3072-column banded
   // system, 24 times).  Column j's off-diagonal launch is therefore split: HEAD = tile (j + 1, j) on the caller's stream, followed
@@ -4328,38 +3594,23 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
   // Measured (profiles/r4/c_ab_lookahead_small_batch_factor.txt, same box, two rounds): the banded reduced camera system of the
   // bundle-adjustment config (3072 columns, batch 256, 158 of 300 tiles) 6.82 -> 6.60 ms; DENSE frames do not gain (n = 1536:
   // batch 256 3.5 ms either way, batch 512 6.2 -> 6.4 ms; n = 3072 batch 256 21.6 -> 21.8 ms: REST(j) of a dense column is most
-  // of the launch, the dispatcher does not run the two queues side by side) -- so: tile-sparse only.
-  // DENSE frames between the right-looking schedule's batches and THX_CHOL_LOOKAHEAD_DENSE_MAX_BATCH problems (experiment, default
-  // 0 = off): the launches of a block column do not fill the chip there either (batch 64: diag(j) is 64 workgroups, REST(j)
-  // 64 (10 - j)).  MEASURED, NOT A WIN (profiles/r6/ai_: batch 64 1.66 -> 1.88 ms, 128 2.18 -> 2.22, 256 3.16 -> 3.27): the whole
-  // off-diagonal launch is one round of workgroups, HEAD(j) alone takes as long -- the chain is the serial K-loops.
-  const bool lookahead = P.lookahead;
-  static const bool lpt_cfg = [] {
-    const char* e = getenv("THX_CHOL_LPT");
-    return e ? atoi(e) != 0 : true;
-  }();
-  pat.lpt = (lookahead && lpt_cfg && tp) ? 1 : 0;
+  // of the launch, the dispatcher does not run the two queues side by side) -- so: tile-sparse only.  (Nor between the right-looking
+  // schedule's batches and 256 problems, profiles/r6/ai_: batch 64 1.66 -> 1.88 ms, 128 2.18 -> 2.22, 256 3.16 -> 3.27 -- the
+  // whole off-diagonal launch is one round of workgroups there, HEAD(j) alone takes as long.)
+  const bool lookahead = P.lookahead;   // (tile-sparse: tp is set)
+  pat.lpt = lookahead ? 1 : 0;
   if (lookahead) {
-    if (!ds.ev_fork) hipEventCreateWithFlags(&ds.ev_fork, hipEventDisableTiming);
-    if (!ds.ev_diag) {
-      hipEventCreateWithFlags(&ds.ev_diag, hipEventDisableTiming);
-      hipEventCreateWithFlags(&ds.ev_rest, hipEventDisableTiming);
-    }
-    if (!ds.aux[0]) {
-      hipStreamCreateWithFlags(&ds.aux[0], hipStreamNonBlocking);
-      hipEventCreateWithFlags(&ds.ev_lag[0], hipEventDisableTiming);
-      hipEventCreateWithFlags(&ds.ev_join[0], hipEventDisableTiming);
-    }
+    ds.need_aux();
     const Half h0 = halves[0];
-    const Half h1 = {ds.aux[0], 0, B};
+    const Half h1 = {ds.aux, 0, B};
     hipEventRecord(ds.ev_fork, st);
     hipStreamWaitEvent(h1.s, ds.ev_fork, 0);
     bool rest_pending = false;   // a REST launch whose completion the caller's stream has not waited for yet
     for (int j = 0; j < ntiles; ++j) {
       launch_diag(h0, j);
-      const int nrt = tp ? tp->col_count_host[j] : ntiles - 1 - j;
+      const int nrt = tp->col_count_host[j];
       if (nrt <= 0) continue;
-      const bool head = tp ? tp->col_head_host[j] != 0 : true;   // the launch's first tile is (j + 1, j)
+      const bool head = tp->col_head_host[j] != 0;   // the launch's first tile is (j + 1, j)
       const int n_head = head ? 1 : 0, n_rest = nrt - n_head;
       if (n_rest > 0) {
         hipEventRecord(ds.ev_diag, h0.s);
@@ -4369,9 +3620,9 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
         hipStreamWaitEvent(h0.s, ds.ev_rest, 0);
         rest_pending = false;
       }
-      if (n_head) launch_off(h0, j, tp ? 0 : j + 1, 1);
+      if (n_head) launch_off(h0, j, 0, 1);
       if (n_rest > 0) {
-        launch_off(h1, j, tp ? n_head : j + 1 + n_head, n_rest);
+        launch_off(h1, j, n_head, n_rest);
         hipEventRecord(ds.ev_rest, h1.s);
         rest_pending = true;
         if (!head) {   // no look-ahead for this column: diag(j + 1) needs a tile of this launch
@@ -4491,19 +3742,12 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
       // both.  Hides the whole update instead of the part the substitutions cover, for two event hops per column.
       // MEASURED (profiles/r6/ao_, n = 1536, factor + forward, plain / mode 1 / mode 2): fp32 batch 8 0.742 / 0.724 / 0.756 ms, 16:
       // 0.856 / 0.828 / 0.855, 32: 1.10 / 1.05 / 1.08; fp64 batch 8 1.53 / 1.42 / 1.34, 16: 1.77 / 1.66 / 1.60, 32: 2.41 / 2.28 / 2.19
-      // -- an fp32 update launch is as short as the event hops, an fp64 one twice as long.  THX_CHOL_RL_LOOKAHEAD = 0 | 1 | 2 forces a mode.
+      // -- an fp32 update launch is as short as the event hops, an fp64 one twice as long.  thx_chol_schedule.right_looking_mode forces
+      // a mode.
       hipStream_t sa = st;
       if (la == 2) {
-        if (!ds.ev_diag) {
-          hipEventCreateWithFlags(&ds.ev_diag, hipEventDisableTiming);
-          hipEventCreateWithFlags(&ds.ev_rest, hipEventDisableTiming);
-        }
-        if (!ds.aux[0]) {
-          hipStreamCreateWithFlags(&ds.aux[0], hipStreamNonBlocking);
-          hipEventCreateWithFlags(&ds.ev_lag[0], hipEventDisableTiming);
-          hipEventCreateWithFlags(&ds.ev_join[0], hipEventDisableTiming);
-        }
-        sa = ds.aux[0];
+        ds.need_aux();
+        sa = ds.aux;
       }
       TilePat pd = p1;
       pd.rl_la = 1;
@@ -4545,55 +3789,14 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
     }
   }
   const bool colpair = P.colpair;   // (from column_pairs_min_batch problems per call on, see plan_factor)
-  // STAGGERED PIPELINE (THX_CHOL_LAG_COLS=<columns>, THX_CHOL_PIPE=<parts per stream>; experiment, default off): the batch in
-  // 2 x PIPE parts, even parts one after the other on the caller's stream, odd parts on the auxiliary stream which starts LAG
-  // block columns behind -- so that one stream's early columns (short K-loops: substitution / store bound, 0.4 - 0.7 of peak per
-  // executed flop in fp64) share the CUs with the other stream's late columns (long K-loops: matrix-core bound) instead of with
-  // each other.  MEASURED, NOT A WIN (profiles/r6/ad_ab_staggered_streams.txt: fp64 91.7 ms -> 91.8 ... 94.7, fp32 43.7 -> 43.9 ... 45.9
-  // over LAG 4 / 6 / 8 x PIPE 1 / 2 / 4): two streams' kernels do not interleave on a CU finely enough.
-  static const int lag_cols = [] {
-    const char* e = getenv("THX_CHOL_LAG_COLS");
-    return e ? atoi(e) : 0;
-  }();
-  static const int pipe_parts = [] {
-    const char* e = getenv("THX_CHOL_PIPE");
-    const int v = e ? atoi(e) : 2;
-    return v < 1 ? 1 : (v > 8 ? 8 : v);
-  }();
-  if (split && nparts == 2 && lag_cols > 0 && lag_cols < ntiles && !tp) {
-    const int nq = 2 * pipe_parts;
-    const int per = min(((B + nq - 1) / nq + 7) / 8 * 8, B);
-    for (int q = 0; q < nq; ++q) {
-      const int b0 = q * per, nb = min(per, B - b0);
-      if (nb <= 0) break;
-      const Half h{(q & 1) ? ds.aux[0] : st, b0, nb};
-      if (q == 1) hipStreamWaitEvent(h.s, ds.ev_lag[0], 0);
-      for (int j = 0; j < ntiles;) {
-        const bool pair = colpair && j + 2 < ntiles;
-        launch_diag(h, j);
-        if (pair) {
-          launch_off(h, j, j + 1, 1);
-          launch_diag(h, j + 1);
-          launch_pair(h, j, j + 2, ntiles - 2 - j);
-        } else if (ntiles - 1 - j > 0) {
-          launch_off(h, j, j + 1, ntiles - 1 - j);
-        }
-        j += pair ? 2 : 1;
-        if (q == 0 && j >= lag_cols && j - (pair ? 2 : 1) < lag_cols) hipEventRecord(ds.ev_lag[0], h.s);
-      }
-    }
-    hipEventRecord(ds.ev_join[0], ds.aux[0]);
-    hipStreamWaitEvent(st, ds.ev_join[0], 0);
-    return check_launch("thx_chol_factor");
-  }
   for (int j = 0; j < ntiles;) {
     const bool pair = colpair && j + 2 < ntiles;
     for (int k = 0; k < nparts; ++k) {
       const Half& h = halves[k];
       if (h.nb <= 0) continue;
-      if (split && k > 0 && j == 0) hipStreamWaitEvent(h.s, ds.ev_lag[k - 1], 0);  // part k: one diagonal phase behind part k-1
+      if (split && k == 1 && j == 0) hipStreamWaitEvent(h.s, ds.ev_lag, 0);  // half 1: one diagonal phase behind half 0
       launch_diag(h, j);
-      if (split && k + 1 < nparts && j == 0) hipEventRecord(ds.ev_lag[k], h.s);
+      if (split && k == 0 && j == 0) hipEventRecord(ds.ev_lag, h.s);
       if (pair) {
         launch_off(h, j, j + 1, 1);
         launch_diag(h, j + 1);
@@ -4606,10 +3809,8 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
     j += pair ? 2 : 1;
   }
   if (split) {
-    for (int k = 0; k + 1 < nparts; ++k) {
-      hipEventRecord(ds.ev_join[k], ds.aux[k]);
-      hipStreamWaitEvent(st, ds.ev_join[k], 0);
-    }
+    hipEventRecord(ds.ev_join, ds.aux);
+    hipStreamWaitEvent(st, ds.ev_join, 0);
   }
   return check_launch("thx_chol_factor");
 }
@@ -4681,15 +3882,11 @@ static int solve_impl(const void* L, int64_t ld, int n, int B, const void* panel
     src = (const T*)x;  // the backward pass then runs in place
   }
   // small batches, dense frame: one launch per block row (chol_bwd_rows_kernel; bit-identical to chol_bwd_kernel) -- up to
-  // THX_CHOL_BWD_ROWS_MAX_BATCH problems per call (default 32).  A SMALL gain: chol_bwd_kernel's push already runs 256 threads
+  // BWD_ROWS_MAX_BATCH problems per call.  A SMALL gain: chol_bwd_kernel's push already runs 256 threads
   // x 8 loads deep (n = 1536, batch 8: 115 us; block rows: 101 us, twelve launches of 5.5 ... 9 us; no difference from 64
   // problems on, profiles/r6/o_ab_bwd_rows.txt) -- it is chol_fwd_kernel's row dots that take 0.46 ms at any batch size, and
   // the right-looking schedule fuses the forward substitution instead.
-  static const int bwd_rows_max = [] {
-    const char* e = getenv("THX_CHOL_BWD_ROWS_MAX_BATCH");
-    return e ? atoi(e) : 32;
-  }();
-  if (backward && !list && ntiles >= 3 && B <= bwd_rows_max && B <= 65535) {
+  if (backward && !list && ntiles >= 3 && B <= BWD_ROWS_MAX_BATCH) {
     if (src != (const T*)x)
       hipMemcpy2DAsync(x, (size_t)ldv * sizeof(T), src, (size_t)ldv * sizeof(T), (size_t)n * sizeof(T), (size_t)B,
                        hipMemcpyDeviceToDevice, st);

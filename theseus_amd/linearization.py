@@ -8,7 +8,6 @@ writes the block-sparse lower triangle of H = A^T A straight into a persistent d
 buffer (zero-filled once; the pattern is fixed) and g = A^T b into (B,n).
 """
 import abc
-import os
 from typing import List, Optional
 
 import torch
@@ -124,12 +123,12 @@ class HipLinearizationCore:
         # A^T A (undamped, lower triangle).  SE3 pose graphs on the HIP kernels keep it BLOCK-COMPACT: ``Hc`` (B, bstride), the
         # list of its non-zero 6 x 6 blocks (184 KB per problem at 256 poses / 1024 edges; the dense frame: 9.4 MB) -- assembly
         # writes whole 144-byte blocks, the Cholesky tiles gather their pieces.  ``H`` (B, ld, ld) is then materialised only if
-        # somebody reads it (``AtA``).  Everything else (SE2 / SO3, the test stand-in kernels, THX_DENSE_HESSIAN=1): dense frame.
+        # somebody reads it (``AtA``).  Everything else (SE2 / SO3, the test stand-in kernels, block_hessian=False): dense frame.
         self._H: Optional[torch.Tensor] = None
         self.Hc: Optional[torch.Tensor] = None
         self.hblocks = None                      # compiler.DeviceHessianBlocks when compact
         self.g: Optional[torch.Tensor] = None   # (B, n): A^T b
-        want = block_hessian if block_hessian is not None else os.environ.get("THX_DENSE_HESSIAN", "0") != "1"
+        want = block_hessian if block_hessian is not None else True
         self._compact = bool(want) and getattr(self.packed, "supports_block_hessian", lambda: False)()
         self._AtA_cache = None
         self._A = self._b = None

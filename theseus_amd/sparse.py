@@ -14,7 +14,6 @@ Dense ``n^3/3`` stops scaling beyond ~2-4 k poses (evaluations/pose_graph_synthe
   non-zero tiles only, each K-loop walking its list -- the work follows the fill instead of ``n^3/3``.  Storage stays the
   dense row-major frame (288 GB of HBM hold batch 64 of n = 12288 in fp32); tiles outside the pattern are never touched.
 """
-import os
 import re
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Type, Union
 
@@ -343,12 +342,11 @@ def _symbolic_tiles(lp: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
 
 
 def _subtree_groups(lp: np.ndarray) -> np.ndarray:
-    """Stream group of every block column for the level schedule's two chain streams: walk the tile elimination tree (parent of
+    """Subtree group of every block column (level_ordering sorts a level's columns by it): walk the tile elimination tree (parent of
     column j = its first non-zero row tile below the diagonal) down from the root(s) while a node has one child -- that path is
-    the TRUNK (group -1: launched after both streams have joined); at the first node with several children their subtrees are
-    dealt to groups 0 / 1, largest first onto the lighter group.  Subtrees do not see each other (a column's K-lists name its
-    descendants only), so the two groups' launches need no ordering against each other.  A tree that never branches (a band): all
-    columns in group 0, no trunk."""
+    the TRUNK (group -1); at the first node with several children their subtrees are dealt to groups 0 / 1, largest first onto
+    the lighter group.  Subtrees do not see each other (a column's K-lists name its descendants only).  A tree that never branches
+    (a band): all columns in group 0, no trunk."""
     nt = lp.shape[0]
     parent = np.full(nt, -1, dtype=np.int64)
     for j in range(nt):
@@ -380,7 +378,7 @@ def _subtree_groups(lp: np.ndarray) -> np.ndarray:
             v = stack.pop()
             group[v] = g
             stack.extend(children[v])
-    if min(load) == 0:                       # everything landed on one stream
+    if min(load) == 0:                       # everything landed in one group
         group[group >= 0] = 0
     return group
 
@@ -462,7 +460,7 @@ def tile_nested_dissection(num_vars: int, edges: Sequence[Tuple[int, int]], vars
             best = (cost, name, o, level, int(lp.sum()))
     cost, name, o, level, l_tiles = best
     o = o[np.argsort(level, kind="stable")]          # level by level (stable: a level keeps the candidate's internal order)
-    # ... and inside a level by stream group (LevelPattern splits every level into one launch pair per group)
+    # ... and inside a level by subtree group
     lp_l, level_l = _symbolic_tiles(np.tril(adj[np.ix_(o, o)]))
     grp = _subtree_groups(lp_l)
     o = o[np.lexsort((np.arange(nc), grp, level_l))]
@@ -505,38 +503,11 @@ class LevelPattern:
         self.lower, self.tree_level = lp, level
         self.tree_levels = int(level.max()) + 1
         self.tree_level_col = np.ascontiguousarray(np.searchsorted(level, np.arange(self.tree_levels + 1)).astype(np.int32))
-        # LAUNCH levels: a tree level is split by stream group when its columns are sorted by group (tile_nested_dissection does
-        # that) -- group 0 on the caller's stream, group 1 on the library's second stream, the trunk (-1) on the caller's stream
-        # after the join; the groups' subtrees do not see each other, so a level's two launch pairs are independent and the two
-        # streams drift apart: one chain's diagonal phase (one busy wave per workgroup) runs beside the other's off-diagonal tiles
-        group = _subtree_groups(lp)
-        key = level * 3 + (group + 1)
-        # ... only for CHAIN-like subtrees (at most two columns of a group on a tree level: the two-chain orders of a band, e.g. the
-        # reduced camera system of bundle adjustment): a bushy level cut in two is two half-size launches, which costs more than
-        # the overlap returns (4096 poses under nd1 at batch 8: factor 0.84 -> 0.98 ms with the split, 1.39 without the streams).
-        # Same-box A/B against ONE launch pair per tree level (profiles/r6/u_ab_subtree_streams.txt, three interleaved rounds):
-        # bundle adjustment under nd13: factor 6.66 - 6.73 vs 6.85 - 6.90 ms, but 11.08 - 11.42 vs 11.19 - 11.25 ms per linear solve
-        # inside the LM loop; 4096 poses under two chains (nd98) at batch 256: factor 7.91 vs 7.43 ms.  The trunk of the tree (the
-        # separator: seven serial block columns of the camera system) has nothing to overlap with.  Kept behind the switch.
-        widest = max((int(((level == lv) & (group == g)).sum()) for lv in range(int(level.max()) + 1) for g in (0, 1)), default=0)
-        if (np.any(np.diff(key) < 0) or widest > 2 or not (group == 1).any()     # (else: levels only, everything on one stream)
-                or os.environ.get("THX_LEVEL_SUBTREES", "0") != "1"):   # MEASURED, NOT A WIN: off unless THX_LEVEL_SUBTREES=1
-            group = np.zeros(nt, dtype=np.int64)
-            key = level * 3 + 1
-        _, plevel = np.unique(key, return_inverse=True)
-        self.group = group
-        level = plevel.astype(np.int64)
+        # one diagonal and one off-diagonal launch per level of the tile elimination tree
         self.level = level
-        nlev = int(level.max()) + 1
+        nlev = self.tree_levels
         self.nlevels = nlev
         level_col = np.searchsorted(level, np.arange(nlev + 1)).astype(np.int32)
-        # stream of every launch level: 0 | 1, +4 on the first trunk level (both streams join in front of it)
-        lstream = np.array([max(int(group[level_col[lv]]), 0) for lv in range(nlev)], dtype=np.int32)
-        trunk_lv = [lv for lv in range(nlev) if group[level_col[lv]] < 0]
-        if trunk_lv and (lstream == 1).any():
-            lstream[trunk_lv[0]] |= 4
-        self.level_stream = np.ascontiguousarray(lstream)
-        self.two_streams = bool((lstream & 3 == 1).any())
         diag_kptr, diag_k = [0], []
         for j in range(nt):
             diag_k += np.nonzero(lp[j, :j])[0].tolist()
@@ -577,13 +548,8 @@ class LevelPattern:
         self.level_ent = np.ascontiguousarray(np.asarray(level_ent, dtype=np.int32))
         dk = np.diff(np.asarray(diag_kptr))
         self.level_maxk = np.ascontiguousarray(np.array([dk[level_col[lv]:level_col[lv + 1]].max() for lv in range(nlev)], dtype=np.int32))
-        # the same tables per TREE level (the solves' schedule: a tree level = one or two consecutive launch levels)
-        first = np.searchsorted(level, self.tree_level_col[:-1])          # first launch level of every tree level
-        bounds = np.concatenate([level[self.tree_level_col[:-1]], [nlev]]).astype(np.int64)
-        self.tree_level_ent = np.ascontiguousarray(self.level_ent[bounds].astype(np.int32))
-        self.tree_level_maxk = np.ascontiguousarray(np.array([self.level_maxk[bounds[t]:bounds[t + 1]].max() for t in range(self.tree_levels)],
-                                                             dtype=np.int32))
-        del first
+        # (the solves walk the same levels)
+        self.tree_level_ent, self.tree_level_maxk = self.level_ent, self.level_maxk
         self.col_count = np.zeros(nt, dtype=np.int32)     # (host tables of the column-by-column schedule: not used)
         self.l_tiles = int(lp.sum())
         self.tile_products = len(tile_k) + len(diag_k) + self.l_tiles
@@ -629,15 +595,12 @@ class LevelPattern:
             ls.nlevels = self.nlevels
             ls.level_col_host, ls.level_ent_host = self.level_col.ctypes.data, self.level_ent.ctypes.data
             ls.level_maxk_host = self.level_maxk.ctypes.data
-            ls.level_stream_host = self.level_stream.ctypes.data if self.two_streams else None
             ls.ent_col, ls.tile_valid = t["ent_col"].data_ptr(), t["tile_valid"].data_ptr()
-            # the triangular solves walk TREE levels (a tree level's columns are contiguous: the stream groups only order them
-            # inside it) -- one launch per tree level and direction, on the caller's stream
+            # the triangular solves: one launch per tree level and direction
             lt = _lib.LevelSchedule()
             lt.nlevels = self.tree_levels
             lt.level_col_host = self.tree_level_col.ctypes.data
             lt.level_ent_host, lt.level_maxk_host = self.tree_level_ent.ctypes.data, self.tree_level_maxk.ctypes.data
-            lt.level_stream_host = None
             lt.ent_col, lt.tile_valid = t["ent_col"].data_ptr(), t["tile_valid"].data_ptr()
             vec = dict(pad_of_col=torch.from_numpy(self.pad_of_col).to(device), col_of_pad=torch.from_numpy(self.col_of_pad).to(device))
             self._dev[key] = (c, ls, t, vec, lt)
@@ -828,10 +791,9 @@ class HipSparseCholeskySolver(HipSparseCholeskyCore, LinearSolver):
         if linearization_kwargs.get("ordering") is None:
             kern = linearization_kwargs.get("kernels")
             levels_possible = (kern is None or hasattr(kern, "pg_assemble_blocks")) and linearization_kwargs.get("block_hessian") is not False \
-                and os.environ.get("THX_DENSE_HESSIAN", "0") != "1" and packed_factor is not False
-            method = os.environ.get("THX_SPARSE_ORDERING", ordering)
+                and packed_factor is not False
             linearization_kwargs["ordering"], tile_count, self.ordering_info = level_ordering(
-                objective, method=method if levels_possible else "rcm", batch_hint=batch_hint)
+                objective, method=ordering if levels_possible else "rcm", batch_hint=batch_hint)
         LinearSolver.__init__(self, objective, linearization_cls, linearization_kwargs)
         if tile_count is not None and not getattr(self.linearization, "_compact", False):
             # (the linearization did not take the block-compact path after all: the column-by-column schedule on an RCM order)

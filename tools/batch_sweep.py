@@ -8,6 +8,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import theseus_amd as th
+from theseus_amd.kernels import chol_plan
 from theseus_amd.utils import synthetic as syn
 
 P, E, iters, dtype, dev = 256, 1024, 10, torch.float32, "cuda"
@@ -44,8 +45,9 @@ for B in batches:
         torch.cuda.synchronize()
         fac = ev0.elapsed_time(ev1) / 5
     tf = B * n ** 3 / 3.0 / (fac * 1e-3) / 1e12
-    sched = "right-looking" if B <= int(os.environ.get("THX_CHOL_RL_MAX_BATCH", "64")) else ("left-looking" if B < 128 else ("left-looking, column pairs" if B < 1024 else
-                                                                            "left-looking, column pairs, two half-batch streams"))
+    plan = chol_plan(n, n, B, dtype)
+    sched = "right-looking" if plan["right_looking"] else ("left-looking" + (", column pairs" if plan["column_pairs"] else "") +
+                                                            (", two half-batch streams" if plan["nparts"] == 2 else ""))
     print(f"{B:6d} {best:16.3f} {B / best * 1e3:15.0f} {fac:10.3f} {tf:8.1f} {tf / 157.3:8.3f}  {sched}", flush=True)
     del sol, info, layer, opt, obj, inputs
     torch.cuda.empty_cache()

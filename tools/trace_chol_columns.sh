@@ -1,6 +1,6 @@
 #!/bin/bash
-# Per block COLUMN efficiency of the dense factorisation: rocprofv3 kernel trace of tools/bench_chol.py on ONE stream
-# (THX_CHOL_SPLIT_MIN=0: the launches of a call run one after the other), the last factor call's launches in order, and for every
+# Per block COLUMN efficiency of the dense factorisation: rocprofv3 kernel trace of tools/bench_chol.py (below 1024 problems per call
+# on ONE stream: the launches of a call run one after the other), the last factor call's launches in order, and for every
 # chol_offdiag launch the EXECUTED flops (K-loop 2 j t^3 + substitution 10/16 * 2 t^3 per tile, t = 128) over its duration.
 # usage: tools/trace_chol_columns.sh <tag> [n B dtype]         (tools/bench_chol.py: dense H frames)
 #        THX_COLS_BENCH=1 tools/trace_chol_columns.sh <tag> n B dtype   (bench.py at that batch / dtype: the LM loop's block-compact H)
@@ -8,14 +8,14 @@ set -u
 TAG=$1; shift
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/trace_cols_$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS=${@:-1536 4096 f32 2}
+ARGS=${@:-1536 512 f32 2}
 set -- $ARGS
 if [ -n "${THX_COLS_BENCH:-}" ]; then
   CMD="python $ROOT/bench.py --steps 3 --warmup 1 --batch $2 --dtype $3 --cpu-sample 0 --parity-sample 0 --no-sparse-leg --legs none"
 else
   CMD="python $ROOT/tools/bench_chol.py $ARGS"
 fi
-(cd /tmp && THX_CHOL_SPLIT_MIN=0 timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT -o run -- $CMD > $OUT/run.log 2>&1)
+(cd /tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT -o run -- $CMD > $OUT/run.log 2>&1)
 grep -v amdgpu.ids $OUT/run.log | tail -3
 python - $ARGS <<PY
 import csv, glob, sys
