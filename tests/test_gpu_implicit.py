@@ -49,24 +49,31 @@ def test_implicit_fp32_gradients_close_to_fp64_reference():
         assert (got - want).abs().max() <= 5e-3 * want.abs().max(), key
 
 
-@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
-def test_vjp_kernels_vs_oracle_autograd(dtype):
-    """thx_pg_vjp / thx_se3_retract_vjp on their own against torch autograd through the oracle (which is pinned to
+# (name, dtype) cases; the SE3 ones keep their original ids
+_VJP_CASES = [pytest.param(name, dt, id=(tag if name == "pg_f64_implicit_b" else f"{name}-{tag}"))
+              for name in ("pg_f64_implicit_b", "pg2_f64_implicit", "pg3_f64_implicit")
+              for dt, tag in ((torch.float64, "dtype0"), (torch.float32, "dtype1"))]
+
+
+@pytest.mark.parametrize("name,dtype", _VJP_CASES)
+def test_vjp_kernels_vs_oracle_autograd(name, dtype):
+    """thx_pg*_vjp / thx_*_retract_vjp of SE3, SE2 and SO3 on their own against torch autograd through the oracle (which is pinned to
     the reference's gradient conventions by tests/test_oracle_golden.py)."""
     from tests.gpu_helpers import to_device_problem
     from theseus_amd.kernels import default_kernels
     K = default_kernels()
     import contextlib
     from tests.helpers import f32_thresholds
-    g = load_golden("pg_f64_implicit_b")
+    g = load_golden(name)
     p, poses0, _ = golden_problem(g)
+    rec, dof = tuple(p.meas.shape[2:]), p.w_between.shape[-1]
     if dtype == torch.float32:  # same values as the kernel sees; the checker switches Taylor branches where fp32 does
         r32 = lambda x: x.float().double()  # noqa: E731
         p = dataclasses.replace(p, meas=r32(p.meas), w_between=r32(p.w_between), prior_target=r32(p.prior_target),
                                 w_prior=r32(p.w_prior))
         poses0 = r32(poses0)
     ctx = f32_thresholds() if dtype == torch.float32 else contextlib.nullcontext()
-    B, n = poses0.shape[0], 6 * p.num_poses
+    B, n = poses0.shape[0], dof * p.num_poses
     gen = torch.Generator().manual_seed(3)
     w = torch.randn(B, n, dtype=torch.float64, generator=gen)
     full = lambda a: a.expand(B, *a.shape[1:]).clone().requires_grad_(True)  # noqa: E731
@@ -83,8 +90,8 @@ def test_vjp_kernels_vs_oracle_autograd(dtype):
                               w_prior=cast(p.w_prior))
     s, t = to_device_problem(p_d, cast(poses0))
     E, Kp = s.num_edges, s.num_priors
-    outs = [torch.empty(E, B, 3, 4, dtype=dtype, device="cuda"), torch.empty(E, B, 6, dtype=dtype, device="cuda"),
-            torch.empty(Kp, B, 3, 4, dtype=dtype, device="cuda"), torch.empty(Kp, B, 6, dtype=dtype, device="cuda")]
+    outs = [torch.empty(E, B, *rec, dtype=dtype, device="cuda"), torch.empty(E, B, dof, dtype=dtype, device="cuda"),
+            torch.empty(Kp, B, *rec, dtype=dtype, device="cuda"), torch.empty(Kp, B, dof, dtype=dtype, device="cuda")]
     K.pg_vjp(s.on("cuda"), t, cast(w).cuda(), *outs)
     tol = 1e-9 if dtype == torch.float64 else 5e-7  # fp32: same inputs, fp64 registers, output rounded once
     for got, want in zip(outs, ref):
@@ -92,13 +99,13 @@ def test_vjp_kernels_vs_oracle_autograd(dtype):
         assert (got.cpu().double() - want).abs().max() <= tol * want.abs().max()
     # retract VJP
     delta = 0.3 * torch.randn(B, n, dtype=torch.float64, generator=gen)
-    gout = torch.randn(B, p.num_poses, 3, 4, dtype=torch.float64, generator=gen)
+    gout = torch.randn(B, p.num_poses, *rec, dtype=torch.float64, generator=gen)
     if dtype == torch.float32:
         delta, gout = delta.float().double(), gout.float().double()
     d = delta.clone().requires_grad_(True)
     with ctx:
         (gref,) = torch.autograd.grad(opg.retract(poses0, d * 0.75), d, gout)
     gd = torch.empty(B, n, dtype=dtype, device="cuda")
-    K.se3_retract_vjp(cast(poses0).transpose(0, 1).contiguous().cuda(), cast(delta).cuda(), 0.75,
-                      cast(gout).transpose(0, 1).contiguous().cuda(), gd)
+    K.retract_vjp(cast(poses0).transpose(0, 1).contiguous().cuda(), cast(delta).cuda(), 0.75,
+                  cast(gout).transpose(0, 1).contiguous().cuda(), gd)
     assert (gd.cpu().double() - gref).abs().max() <= (1e-10 if dtype == torch.float64 else 5e-7) * gref.abs().max()

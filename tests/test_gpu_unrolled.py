@@ -46,9 +46,18 @@ def test_differentiating_through_the_iterations_of_se2_and_so3_pose_graphs_on_th
     run_pg_unrolled(th, load_golden(fixture), tag, "cuda")
 
 
-@pytest.mark.parametrize("dtype", ["f64", "f32"])
-def test_unroll_vjp_kernel_against_autograd_through_the_oracle(dtype):
-    """thx_pg_unroll_vjp on its own: per-cost gradients of phi = -(J w).(r + J delta) for random w, delta against torch autograd
+# (name, dtype) cases; the SE3 ones keep their original ids.  SE2 fp64: the kernel's w_between gradient is 2.4e-7 from the
+# oracle's (4e-10 of the largest entry), above the 1e-10 bound that SE3 and SO3 meet; the same with the library built before
+# the backward kernels were templated, so it is a known gap between kernel and oracle, kept visible here.
+_SE2_F64_GAP = pytest.mark.xfail(strict=True, reason="SE2 fp64 unrolled w_between: 4e-10 relative to the oracle, bound 1e-10")
+_UNROLL_CASES = [pytest.param(name, dt, id=(dt if name == "pg_f64_unrolled" else f"{name}-{dt}"),
+                              marks=(_SE2_F64_GAP,) if (name, dt) == ("pg2_f64_unrolled", "f64") else ())
+                 for name in ("pg_f64_unrolled", "pg2_f64_unrolled", "pg3_f64_unrolled") for dt in ("f64", "f32")]
+
+
+@pytest.mark.parametrize("name,dtype", _UNROLL_CASES)
+def test_unroll_vjp_kernel_against_autograd_through_the_oracle(name, dtype):
+    """thx_pg*_unroll_vjp of SE3, SE2 and SO3 on its own: per-cost gradients of phi = -(J w).(r + J delta) for random w, delta against torch autograd
     through the oracle's Between / Local formulas (tests/oracle_kernels.py:pg_unroll_vjp): fp64 to rounding; fp32 storage
     (double arithmetic inside, the same fp32-rounded inputs on both sides, fp32 Taylor thresholds) to the output's rounding."""
     import contextlib
@@ -58,13 +67,14 @@ def test_unroll_vjp_kernel_against_autograd_through_the_oracle(dtype):
     from tests.helpers import f32_thresholds, golden_problem
     from tests.oracle_kernels import OracleKernels
     from theseus_amd.kernels import default_kernels
-    g = load_golden("pg_f64_unrolled")
+    g = load_golden(name)
     p, poses0, _ = golden_problem({**g, "opt_kwargs": "{}"})
+    rec, dof = tuple(p.meas.shape[2:]), p.w_between.shape[-1]
     dt = torch.float64 if dtype == "f64" else torch.float32
     r = (lambda x: x) if dtype == "f64" else (lambda x: x.float().double())
     p = dataclasses.replace(p, meas=r(p.meas), w_between=r(p.w_between), prior_target=r(p.prior_target), w_prior=r(p.w_prior))
     poses0 = r(poses0)
-    B, n = poses0.shape[0], 6 * p.num_poses
+    B, n = poses0.shape[0], dof * p.num_poses
     gen = torch.Generator().manual_seed(3)
     w, d = (r(torch.randn(B, n, dtype=torch.float64, generator=gen)) for _ in range(2))
     cast = lambda x: x.to(dt)  # noqa: E731
@@ -72,7 +82,7 @@ def test_unroll_vjp_kernel_against_autograd_through_the_oracle(dtype):
     s, t = to_device_problem(p_d, cast(poses0))
     s64, t64 = to_device_problem(p, poses0, device="cpu")
     E, Kp = s.num_edges, s.num_priors
-    shapes = [(E, B, 3, 4), (E, B, 3, 4), (E, B, 3, 4), (E, B, 6), (Kp, B, 3, 4), (Kp, B, 3, 4), (Kp, B, 6)]
+    shapes = [(E, B, *rec), (E, B, *rec), (E, B, *rec), (E, B, dof), (Kp, B, *rec), (Kp, B, *rec), (Kp, B, dof)]
     got = [torch.zeros(*sh, dtype=dt, device="cuda") for sh in shapes]
     default_kernels().pg_unroll_vjp(s.on("cuda"), t, cast(w).cuda(), cast(d).cuda(), *got)
     want = [torch.zeros(*sh, dtype=torch.float64) for sh in shapes]

@@ -15,7 +15,7 @@ struct SO3m {
 };
 
 // log (+ Jlog = b w w^T + a I + hat(w)/2, sine / cosine taken from the matrix, d_near_zero switch): so3_impl.py:390-479.
-// On any scalar type: the implicit backward evaluates it on dual numbers (vjpso3_kernels.hip).
+// On any scalar type: the implicit backward evaluates it on dual numbers (pg_vjp_kernels.hip).
 template <typename S>
 __device__ __forceinline__ void so3_log_jlog(const S* R, const thx::Eps<S>& eps, S* w, S* J, bool want_jac) {
   S theta, sine, cosine;

@@ -61,7 +61,7 @@ struct UG_SO3 {
   }
   static __device__ __forceinline__ void log_jlog(const X<UD3>& E, const EpsU& eps, UD3* xi, UD3* J) {
     so3_log_jlog<UD3>(E.R, eps, xi, J, true);
-    // torchlie's log backward: d xi = Jlog vee2(E^T dE) / 2  (vjpso3_kernels.hip follows the same rule)
+    // torchlie's log backward: d xi = Jlog vee2(E^T dE) / 2  (pg_vjp_kernels.hip: cost_vjp_so3 follows the same rule)
     double R[9], dR[9], M[9], u[3], jv[9], dxi[3];
 #pragma unroll
     for (int i = 0; i < 9; ++i) {

@@ -1,6 +1,6 @@
-// SE3 cost-term VJP shared by the pose-graph (vjp_kernels.hip) and the bundle-adjustment (ba_vjp_kernels.hip) backward
+// SE3 cost-term VJP shared by the pose-graph (pg_vjp_kernels.hip) and the bundle-adjustment (ba_vjp_kernels.hip) backward
 // kernels: gradient of  phi = - sum_r m_r(x, log_radius) s_r^2 (Jlog(E) q)_r log(E)_r ,  E = Z^-1 C, w.r.t. the 12 raw entries of
-// Z, the 6 weights s and log_radius (m_r: one factor for the cost, or one per row with flatten_dims) -- see vjp_kernels.hip for the derivation and the torchlie backward semantics it follows.
+// Z, the 6 weights s and log_radius (m_r: one factor for the cost, or one per row with flatten_dims) -- see pg_vjp_kernels.hip for the derivation and the torchlie backward semantics it follows.
 #pragma once
 #include "common.cuh"
 #include "dual.cuh"

@@ -1,4 +1,4 @@
-// Backward maths of SO2 pose graphs (planar rotation-only graphs, theseus/geometry/so2.py): the 1-dof twins of vjp2_kernels.hip's
+// Backward maths of SO2 pose graphs (planar rotation-only graphs, theseus/geometry/so2.py): the 1-dof twins of pg_vjp_kernels.hip's
 // cost_vjp2 (BackwardMode.IMPLICIT) and unroll_g3.cuh's unroll3_vjp (UNROLL / TRUNCATED).  so2.py has no custom backward: every
 // derivative is plain autograd through its closed forms -- compose by the angle-addition formulas (:225-231), inverse (cos, -sin)
 // (:233-235), log = atan2(sin, cos) (:206-223), exp = (cos theta, sin theta) (:167-186) -- so every derivative here is the dual part

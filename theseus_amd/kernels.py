@@ -6,7 +6,7 @@ stand-in injected by tests/; nothing in this package provides such a stand-in.
 """
 import dataclasses
 from dataclasses import dataclass
-from typing import Optional
+from typing import Callable, Optional
 
 import torch
 
@@ -160,25 +160,39 @@ def chol_plan(n, ld, B, dtype, damping=True, rhs=True, ldv=None, layout=None, sc
     return {k: int(getattr(out, k)) for k, _ in _lib.CholPlanInfo._fields_}
 
 
-GROUP_RECORD = {"SE3": (12, 6), "SO3": (9, 3), "SE2": (4, 3), "SO2": (2, 1)}   # (scalars per record, dof)
+@dataclass(frozen=True)
+class PGGroup:
+    """The C ABI entry points of one pose-graph group: thx_<pg>_{assemble,error,jacobians,vjp,unroll_vjp} and
+    thx_<elem>_{retract,retract_vjp}, with the Taylor thresholds ``eps`` (None: the group has none)."""
+
+    name: str
+    pg: str
+    elem: str
+    eps: Optional[Callable]
+    rec: int    # scalars per record
+    dof: int
+
+    def eps_args(self, dtype) -> tuple:
+        return () if self.eps is None else (self.eps(dtype),)
 
 
-def group_of(poses: torch.Tensor) -> str:
-    if poses.dim() == 3:
-        return "SO2" if poses.shape[-1] == 2 else "SE2"
-    return "SO3" if poses.shape[-1] == 3 else "SE3"
+_SE3 = PGGroup("SE3", "pg", "se3", lie_eps, 12, 6)
+PG_GROUPS = {(3, 4): _SE3, (4,): PGGroup("SE2", "pg2", "se2", se2_eps, 4, 3), (3, 3): PGGroup("SO3", "pgso3", "so3", lie_eps, 9, 3),
+             (2,): PGGroup("SO2", "pgso2", "so2", None, 2, 1)}
 
 
-_RECORD_GROUP = {(3, 4): "SE3", (3, 3): "SO3", (4,): "SE2", (2,): "SO2"}
+def record_group(records: torch.Tensor) -> PGGroup:
+    """The group of a (P|E|K, B, *record) buffer, for the forward and the backward entry points alike: only an exact record shape
+    names a group (no fall-through to another group's kernel)."""
+    grp = PG_GROUPS.get(tuple(records.shape[2:]))
+    if grp is None:
+        raise ValueError(f"no VJP kernel (and no forward kernel) for records of shape {tuple(records.shape[2:])}")
+    return grp
 
 
 def vjp_group(records: torch.Tensor) -> str:
-    """The group of a (P|E|K, B, *record) buffer for the backward entry points: only an exact record shape names a group (no
-    fall-through to another group's kernel)."""
-    grp = _RECORD_GROUP.get(tuple(records.shape[2:]))
-    if grp is None:
-        raise ValueError(f"no VJP kernel for records of shape {tuple(records.shape[2:])}")
-    return grp
+    """The name ("SE3", "SE2", "SO3", "SO2") of the group record_group reads off the buffer."""
+    return record_group(records).name
 
 
 @dataclass
@@ -208,13 +222,9 @@ class PGTensors:
         return self.poses.shape[1]
 
     @property
-    def se2(self) -> bool:
-        return self.poses.dim() == 3 and self.poses.shape[-1] == 4
-
-    @property
     def group(self) -> str:
         """Read off the record shape: SE3 (3,4), SO3 (3,3), SE2 (4,), SO2 (2,)."""
-        return group_of(self.poses)
+        return vjp_group(self.poses)
 
     def c_struct(self, poses: Optional[torch.Tensor] = None) -> _lib.PGData:
         poses = self.poses if poses is None else poses
@@ -230,11 +240,11 @@ class PGTensors:
             setattr(d, name, _lib.ptr(t, name).value if t.numel() else None)
             setattr(d, name + "_bstride", width if nb == B else 0)
 
-        gw, dof = GROUP_RECORD[group_of(poses)]
-        put("meas", self.meas, gw)
-        put("w_between", self.w_between, dof)
-        put("prior_target", self.prior_target, gw)
-        put("w_prior", self.w_prior, dof)
+        grp = record_group(poses)
+        put("meas", self.meas, grp.rec)
+        put("w_between", self.w_between, grp.dof)
+        put("prior_target", self.prior_target, grp.rec)
+        put("w_prior", self.w_prior, grp.dof)
         for role in ("between", "prior"):
             kind = getattr(self, "robust_" + role)
             setattr(d, "robust_" + role, int(kind))
@@ -421,28 +431,14 @@ class HipKernels:
         self._so2_op(4, X, None, A, None)
         return A
 
-    # ---- pose graph (SE3 records (3,4) -> thx_pg_*, SE2 records (4,) -> thx_pg2_*, SO3 records (3,3) -> thx_pgso3_*, SO2 records
-    #      (2,) -> thx_pgso2_*) ----
+    # ---- pose graph: the entry points of the group the record shape names (PG_GROUPS) ----
+    def _call(self, fn, *args):
+        _lib.check(getattr(self.lib, fn)(*args), fn)
+
     def pg_assemble(self, s: DeviceStructure, t: PGTensors, H, g, poses=None):
-        d = t.c_struct(poses)
-        dt = H.dtype
-        if t.group == "SO2":
-            _lib.check(self.lib.thx_pgso2_assemble(s.c, d, _lib.ptr(H, "H"), H.shape[-1], _lib.ptr(g, "g"),
-                                                   _lib.dtype_code(dt), _lib.stream_ptr(H.device)), "thx_pgso2_assemble")
-            return
-        if t.group == "SO3":
-            _lib.check(self.lib.thx_pgso3_assemble(s.c, d, _lib.ptr(H, "H"), H.shape[-1], _lib.ptr(g, "g"),
-                                                   _lib.dtype_code(dt), lie_eps(dt), _lib.stream_ptr(H.device)),
-                       "thx_pgso3_assemble")
-            return
-        if t.se2:
-            _lib.check(self.lib.thx_pg2_assemble(s.c, d, _lib.ptr(H, "H"), H.shape[-1], _lib.ptr(g, "g"),
-                                                 _lib.dtype_code(dt), se2_eps(dt), _lib.stream_ptr(H.device)),
-                       "thx_pg2_assemble")
-            return
-        _lib.check(self.lib.thx_pg_assemble(s.c, d, _lib.ptr(H, "H"), H.shape[-1], _lib.ptr(g, "g"),
-                                            _lib.dtype_code(dt), lie_eps(dt), _lib.stream_ptr(H.device)),
-                   "thx_pg_assemble")
+        grp, dt = record_group(t.poses if poses is None else poses), H.dtype
+        self._call(f"thx_{grp.pg}_assemble", s.c, t.c_struct(poses), _lib.ptr(H, "H"), H.shape[-1], _lib.ptr(g, "g"),
+                   _lib.dtype_code(dt), *grp.eps_args(dt), _lib.stream_ptr(H.device))
 
     # ---- block-compact Hessian (include/theseus_hip.h: thx_hblock_layout; theseus_amd/compiler.py:HessianBlocks) ----
     def pg_assemble_blocks(self, s: DeviceStructure, t: PGTensors, hb, Hc, g, poses=None):
@@ -499,71 +495,27 @@ class HipKernels:
                                            dst.shape[0], _lib.dtype_code(src.dtype), _lib.stream_ptr(src.device)), "thx_vec_gather")
 
     def pg_error(self, s: DeviceStructure, t: PGTensors, partials, err, poses=None):
-        d = t.c_struct(poses)
-        dt = err.dtype
-        if t.group == "SO2":
-            _lib.check(self.lib.thx_pgso2_error(s.c, d, _lib.ptr(partials), _lib.ptr(err), _lib.dtype_code(dt),
-                                                _lib.stream_ptr(err.device)), "thx_pgso2_error")
-            return
-        if t.group == "SO3":
-            _lib.check(self.lib.thx_pgso3_error(s.c, d, _lib.ptr(partials), _lib.ptr(err), _lib.dtype_code(dt),
-                                                lie_eps(dt), _lib.stream_ptr(err.device)), "thx_pgso3_error")
-            return
-        if t.se2:
-            _lib.check(self.lib.thx_pg2_error(s.c, d, _lib.ptr(partials), _lib.ptr(err), _lib.dtype_code(dt),
-                                              se2_eps(dt), _lib.stream_ptr(err.device)), "thx_pg2_error")
-            return
-        _lib.check(self.lib.thx_pg_error(s.c, d, _lib.ptr(partials), _lib.ptr(err), _lib.dtype_code(dt), lie_eps(dt),
-                                         _lib.stream_ptr(err.device)), "thx_pg_error")
+        grp, dt = record_group(t.poses if poses is None else poses), err.dtype
+        self._call(f"thx_{grp.pg}_error", s.c, t.c_struct(poses), _lib.ptr(partials), _lib.ptr(err), _lib.dtype_code(dt),
+                   *grp.eps_args(dt), _lib.stream_ptr(err.device))
 
     def pg_jacobians(self, s: DeviceStructure, t: PGTensors, J0, J1, eb, Jp, ep, poses=None):
-        d = t.c_struct(poses)
-        dt = t.poses.dtype
-        if t.group == "SO2":
-            _lib.check(self.lib.thx_pgso2_jacobians(s.c, d, _lib.ptr(J0), _lib.ptr(J1), _lib.ptr(eb), _lib.ptr(Jp), _lib.ptr(ep),
-                                                    _lib.dtype_code(dt), _lib.stream_ptr(t.poses.device)), "thx_pgso2_jacobians")
-            return
-        if t.group == "SO3":
-            _lib.check(self.lib.thx_pgso3_jacobians(s.c, d, _lib.ptr(J0), _lib.ptr(J1), _lib.ptr(eb), _lib.ptr(Jp),
-                                                    _lib.ptr(ep), _lib.dtype_code(dt), lie_eps(dt),
-                                                    _lib.stream_ptr(t.poses.device)), "thx_pgso3_jacobians")
-            return
-        if t.se2:
-            _lib.check(self.lib.thx_pg2_jacobians(s.c, d, _lib.ptr(J0), _lib.ptr(J1), _lib.ptr(eb), _lib.ptr(Jp),
-                                                  _lib.ptr(ep), _lib.dtype_code(dt), se2_eps(dt),
-                                                  _lib.stream_ptr(t.poses.device)), "thx_pg2_jacobians")
-            return
-        _lib.check(self.lib.thx_pg_jacobians(s.c, d, _lib.ptr(J0), _lib.ptr(J1), _lib.ptr(eb), _lib.ptr(Jp),
-                                             _lib.ptr(ep), _lib.dtype_code(dt), lie_eps(dt),
-                                             _lib.stream_ptr(t.poses.device)), "thx_pg_jacobians")
+        grp, dt = record_group(t.poses if poses is None else poses), t.poses.dtype
+        self._call(f"thx_{grp.pg}_jacobians", s.c, t.c_struct(poses), _lib.ptr(J0), _lib.ptr(J1), _lib.ptr(eb), _lib.ptr(Jp),
+                   _lib.ptr(ep), _lib.dtype_code(dt), *grp.eps_args(dt), _lib.stream_ptr(t.poses.device))
+
+    def _retract(self, grp: PGGroup, poses, delta, step, ignore_mask, out):
+        P, B = poses.shape[:2]
+        dt = poses.dtype
+        self._call(f"thx_{grp.elem}_retract", _lib.ptr(poses), _lib.ptr(delta), delta.stride(0), float(step), _lib.ptr(ignore_mask),
+                   _lib.ptr(out), P, B, _lib.dtype_code(dt), *grp.eps_args(dt), _lib.stream_ptr(poses.device))
 
     def retract(self, poses, delta, step, ignore_mask, out):
         """X <- X exp(step * delta) on the packed pose buffer; the group is read off the record shape."""
-        grp = group_of(poses)
-        if grp == "SE3":
-            return self.se3_retract(poses, delta, step, ignore_mask, out)
-        P, B = poses.shape[:2]
-        dt = poses.dtype
-        if grp == "SO2":
-            _lib.check(self.lib.thx_so2_retract(_lib.ptr(poses), _lib.ptr(delta), delta.stride(0), float(step),
-                                                _lib.ptr(ignore_mask), _lib.ptr(out), P, B, _lib.dtype_code(dt),
-                                                _lib.stream_ptr(poses.device)), "thx_so2_retract")
-            return
-        if grp == "SO3":
-            _lib.check(self.lib.thx_so3_retract(_lib.ptr(poses), _lib.ptr(delta), delta.stride(0), float(step),
-                                                _lib.ptr(ignore_mask), _lib.ptr(out), P, B, _lib.dtype_code(dt),
-                                                lie_eps(dt), _lib.stream_ptr(poses.device)), "thx_so3_retract")
-            return
-        _lib.check(self.lib.thx_se2_retract(_lib.ptr(poses), _lib.ptr(delta), delta.stride(0), float(step),
-                                            _lib.ptr(ignore_mask), _lib.ptr(out), P, B, _lib.dtype_code(dt),
-                                            se2_eps(dt), _lib.stream_ptr(poses.device)), "thx_se2_retract")
+        self._retract(record_group(poses), poses, delta, step, ignore_mask, out)
 
     def se3_retract(self, poses, delta, step, ignore_mask, out):
-        P, B = poses.shape[:2]
-        dt = poses.dtype
-        _lib.check(self.lib.thx_se3_retract(_lib.ptr(poses), _lib.ptr(delta), delta.stride(0), float(step),
-                                            _lib.ptr(ignore_mask), _lib.ptr(out), P, B, _lib.dtype_code(dt),
-                                            lie_eps(dt), _lib.stream_ptr(poses.device)), "thx_se3_retract")
+        self._retract(_SE3, poses, delta, step, ignore_mask, out)
 
     # ---- bundle adjustment (csrc/ba_kernels.hip) --------------------------------------------------
     def ba_assemble(self, s, t, Hcc, Hpp, W, gd, g, diag):
@@ -684,53 +636,36 @@ class HipKernels:
         self._keepalive = (hterm_d, gterm_d)
 
     # ---- implicit backward ----------------------------------------------------------------------
+    def _retract_vjp(self, grp: PGGroup, poses, delta, step, grad_out, grad_delta):
+        P, B = poses.shape[:2]
+        dt = poses.dtype
+        self._call(f"thx_{grp.elem}_retract_vjp", _lib.ptr(poses), _lib.ptr(delta), delta.stride(0), float(step), _lib.ptr(grad_out),
+                   _lib.ptr(grad_delta), grad_delta.stride(0), P, B, _lib.dtype_code(dt), *grp.eps_args(dt),
+                   _lib.stream_ptr(poses.device))
+
     def retract_vjp(self, poses, delta, step, grad_out, grad_delta):
         """grad_X_new -> grad_delta of X exp(step * delta); the group is read off the record shape."""
-        grp = vjp_group(poses)
-        if grp == "SE3":
-            return self.se3_retract_vjp(poses, delta, step, grad_out, grad_delta)
-        P, B = poses.shape[:2]
-        dt = poses.dtype
-        common = (_lib.ptr(poses), _lib.ptr(delta), delta.stride(0), float(step), _lib.ptr(grad_out), _lib.ptr(grad_delta),
-                  grad_delta.stride(0), P, B, _lib.dtype_code(dt))
-        if grp == "SO3":
-            _lib.check(self.lib.thx_so3_retract_vjp(*common, lie_eps(dt), _lib.stream_ptr(poses.device)), "thx_so3_retract_vjp")
-        elif grp == "SE2":
-            _lib.check(self.lib.thx_se2_retract_vjp(*common, se2_eps(dt), _lib.stream_ptr(poses.device)), "thx_se2_retract_vjp")
-        else:
-            _lib.check(self.lib.thx_so2_retract_vjp(*common, _lib.stream_ptr(poses.device)), "thx_so2_retract_vjp")
+        self._retract_vjp(record_group(poses), poses, delta, step, grad_out, grad_delta)
 
     def se3_retract_vjp(self, poses, delta, step, grad_out, grad_delta):
-        P, B = poses.shape[:2]
-        dt = poses.dtype
-        _lib.check(self.lib.thx_se3_retract_vjp(_lib.ptr(poses), _lib.ptr(delta), delta.stride(0), float(step),
-                                                _lib.ptr(grad_out), _lib.ptr(grad_delta), grad_delta.stride(0), P, B,
-                                                _lib.dtype_code(dt), lie_eps(dt), _lib.stream_ptr(poses.device)),
-                   "thx_se3_retract_vjp")
+        self._retract_vjp(_SE3, poses, delta, step, grad_out, grad_delta)
 
     def pg_vjp(self, s: DeviceStructure, t: PGTensors, w, g_meas, g_wb, g_tgt, g_wp, poses=None, g_lrb=None, g_lrp=None):
         """thx_pg_vjp / thx_pg2_vjp / thx_pgso3_vjp / thx_pgso2_vjp (include/theseus_hip.h), chosen by the group of the records."""
-        d = t.c_struct(poses)
-        dt = w.dtype
-        grp = vjp_group(t.poses if poses is None else poses)
-        fn = {"SE3": "thx_pg_vjp", "SE2": "thx_pg2_vjp", "SO3": "thx_pgso3_vjp", "SO2": "thx_pgso2_vjp"}[grp]
-        eps = {"SE3": (lie_eps(dt),), "SE2": (se2_eps(dt),), "SO3": (lie_eps(dt),), "SO2": ()}[grp]
-        _lib.check(getattr(self.lib, fn)(s.c, d, _lib.ptr(w), w.stride(0), _lib.ptr(g_meas), _lib.ptr(g_wb), _lib.ptr(g_tgt),
-                                         _lib.ptr(g_wp), _lib.ptr(g_lrb), _lib.ptr(g_lrp), _lib.dtype_code(dt), *eps,
-                                         _lib.stream_ptr(w.device)), fn)
+        grp, dt = record_group(t.poses if poses is None else poses), w.dtype
+        self._call(f"thx_{grp.pg}_vjp", s.c, t.c_struct(poses), _lib.ptr(w), w.stride(0), _lib.ptr(g_meas), _lib.ptr(g_wb),
+                   _lib.ptr(g_tgt), _lib.ptr(g_wp), _lib.ptr(g_lrb), _lib.ptr(g_lrp), _lib.dtype_code(dt), *grp.eps_args(dt),
+                   _lib.stream_ptr(w.device))
 
     def pg_unroll_vjp(self, s: DeviceStructure, t: PGTensors, w, delta, g_pose_i, g_pose_j, g_meas, g_wb, g_pose_p, g_tgt, g_wp,
                       poses=None, ell_damping=None, g_lrb=None, g_lrp=None):
         """thx_pg_unroll_vjp / thx_pg2_unroll_vjp / thx_pgso3_unroll_vjp / thx_pgso2_unroll_vjp (include/theseus_hip.h): the per-cost
         backward of one differentiated iteration of an SE3 / SE2 / SO3 / SO2 pose graph."""
-        dt = w.dtype
-        grp = vjp_group(t.poses if poses is None else poses)
-        fn = {"SE3": "thx_pg_unroll_vjp", "SE2": "thx_pg2_unroll_vjp", "SO3": "thx_pgso3_unroll_vjp", "SO2": "thx_pgso2_unroll_vjp"}[grp]
-        eps = {"SE3": (lie_eps(dt),), "SE2": (se2_eps(dt),), "SO3": (lie_eps(dt),), "SO2": ()}[grp]
-        _lib.check(getattr(self.lib, fn)(s.c, t.c_struct(poses), _lib.ptr(w), w.stride(0), _lib.ptr(delta), delta.stride(0),
-                                         _lib.ptr(ell_damping), _lib.ptr(g_pose_i), _lib.ptr(g_pose_j), _lib.ptr(g_meas), _lib.ptr(g_wb),
-                                         _lib.ptr(g_pose_p), _lib.ptr(g_tgt), _lib.ptr(g_wp), _lib.ptr(g_lrb), _lib.ptr(g_lrp),
-                                         _lib.dtype_code(dt), *eps, _lib.stream_ptr(w.device)), fn)
+        grp, dt = record_group(t.poses if poses is None else poses), w.dtype
+        self._call(f"thx_{grp.pg}_unroll_vjp", s.c, t.c_struct(poses), _lib.ptr(w), w.stride(0), _lib.ptr(delta), delta.stride(0),
+                   _lib.ptr(ell_damping), _lib.ptr(g_pose_i), _lib.ptr(g_pose_j), _lib.ptr(g_meas), _lib.ptr(g_wb), _lib.ptr(g_pose_p),
+                   _lib.ptr(g_tgt), _lib.ptr(g_wp), _lib.ptr(g_lrb), _lib.ptr(g_lrp), _lib.dtype_code(dt), *grp.eps_args(dt),
+                   _lib.stream_ptr(w.device))
 
     # ---- dense solver ---------------------------------------------------------------------------
     def chol_factor(self, H, n, damping, ellipsoidal, damping_eps, L, panels, info, rhs=None, y=None):
