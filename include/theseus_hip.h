@@ -236,7 +236,18 @@ typedef struct {
                             * to 64 (pose graphs: ~15 blocks per tile) they are ADDED to the tile's Schur update by the matrix cores
                             * (a rank-bd MFMA per piece, one barrier); above (a bundle adjustment's reduced camera system: up to
                             * 21 x 21 blocks per tile) or unknown they are gathered through LDS.  Same results either way. */
+  const int32_t* l_mask;   /* DEVICE (ntiles, 4 * ntiles) or NULL: the structurally non-zero 32 x 32 sub-blocks of the natural-order
+                            * factor L -- bit s of l_mask[t * 4 * ntiles + c] is set when the sub-block of rows [128 t + 32 s, +32) and
+                            * columns [32 c, +32) of tril(L) can be non-zero (thx_hblock_fill_mask).  The fp32 column-by-column
+                            * dense-frame factorisation skips the K-loop block products whose operand sub-block is zero there
+                            * (thx_chol_schedule.skip_zero_blocks); every other schedule ignores it.  NULL = no skipping. */
 } thx_hblock_layout;
+/*      thx_hblock_fill_mask: HOST-ONLY (no device is touched) -- the table behind thx_hblock_layout.l_mask.  blocks: host (nblocks, 2)
+ *      int32 pairs (row variable p, column variable q), q <= p, the non-zero bd x bd blocks of tril(H) in any order.  Runs the
+ *      natural-order symbolic Cholesky at variable granularity (elimination tree grown row by row, row structure by walking it:
+ *      O(|L|)) and writes mask (host int32, ntiles x 4 * ntiles, ntiles = ceil(nvars * bd / THX_TILE)) in the layout of l_mask:
+ *      a sub-block is marked when any variable block of L's fill overlaps it (sub-blocks wholly outside the matrix stay 0). */
+int thx_hblock_fill_mask(int32_t nvars, int32_t bd, int32_t nblocks, const int32_t* blocks, int32_t* mask);
 int thx_pg_assemble_blocks(const thx_pg_structure* s, const thx_pg_data* d, const thx_hblock_layout* layout, void* Hc,
                            int64_t bstride, void* g, int dtype, const thx_lie_eps* eps, void* stream);
 int thx_hblocks_expand(const thx_hblock_layout* layout, const void* Hc, int64_t bstride, int32_t B, void* H, int64_t ld,
@@ -335,7 +346,12 @@ int thx_se3_retract(const void* poses, const void* delta, int64_t ldd, double st
  *          take column j - 1's update themselves (one-tile K-loop), the rest of that update rides in the substitutions' launch, and
  *          block column 1 is read straight from H; 2: the diagonal tile takes its own update, the rest of the update runs on the
  *          library's second stream beside it.  The three sum in different orders (to rounding, not bit for bit).  < 0: the default
- *          (1 for fp32, 2 for fp64); > 2: 1. */
+ *          (1 for fp32, 2 for fp64); > 2: 1.
+ *        skip_zero_blocks: fp32 factorisations of a block-compact H on the column-by-column schedule (thx_chol_factor_hblocks, no tile
+ *          pattern, not right-looking) whose layout carries l_mask leave out the K-loop MFMAs of every 32 x 32 output block whose row
+ *          or column operand sub-block of L is structurally zero at that k-chunk (the column-pair kernel, chol_offdiag2_f32_kernel).
+ *          The skipped products are exact zeros: the factor is the same (up to the sign of a zero).  1 on, 0 off, < 0: the default
+ *          (on). */
 typedef struct {
   int32_t split_diag_min_batch;
   int32_t column_pairs;
@@ -345,6 +361,7 @@ typedef struct {
   int32_t f64_half_max_ktiles;
   int32_t column_pairs_min_batch;
   int32_t right_looking_mode;
+  int32_t skip_zero_blocks;
 } thx_chol_schedule;
 
 /* ---- thx_chol_plan: HOST-ONLY query (no device is touched, no GPU needed) -- the schedule a DENSE-frame factorisation

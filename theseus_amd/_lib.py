@@ -21,7 +21,7 @@ THX_BA_ERR_CHUNKS = 256
 LOSS_NONE, LOSS_WELSCH, LOSS_HUBER, LOSS_HINGE = 0, 1, 2, 3  # THX_LOSS_* (theseus/core/robust_loss.py:33-62)
 LOSS_FLATTEN = 4  # THX_LOSS_FLATTEN: RobustCostFunction(flatten_dims=True), or-ed into a loss code
 LOSS_GEMAN_MCCLURE = 8  # THX_LOSS_GEMAN_MCCLURE (robust_loss.py:92-113; the radius entry carries log(mu * radius))
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 
 class LieEps(Structure):
@@ -65,7 +65,8 @@ class TilePattern(Structure):  # thx_tile_pattern: tile-level symbolic factorisa
 class CholSchedule(Structure):  # thx_chol_schedule: per-call schedule of the factorisations (negative = the library default)
     _fields_ = [("split_diag_min_batch", c_int32), ("column_pairs", c_int32), ("right_looking_max_batch", c_int32),
                 ("hb_scatter_max_pieces", c_int32), ("f64_wide_max_ktiles", c_int32),
-                ("f64_half_max_ktiles", c_int32), ("column_pairs_min_batch", c_int32), ("right_looking_mode", c_int32)]
+                ("f64_half_max_ktiles", c_int32), ("column_pairs_min_batch", c_int32), ("right_looking_mode", c_int32),
+                ("skip_zero_blocks", c_int32)]
 
 
 class CholPlanInfo(Structure):  # thx_chol_plan_info: the schedule a dense-frame factorisation takes (thx_chol_plan, host only)
@@ -79,7 +80,19 @@ class LevelSchedule(Structure):  # thx_level_schedule: elimination-tree levels o
 
 class HBlockLayout(Structure):  # thx_hblock_layout: block-compact Hessian (device int32 tables)
     _fields_ = [(k, c_int32) for k in ("nblocks", "bd", "nvars", "ntiles")] + [
-        (k, c_void_p) for k in ("diag_blk", "inc_blk", "tile_ptr", "piece_blk", "piece_rc")] + [("max_tile_pieces", c_int32)]
+        (k, c_void_p) for k in ("diag_blk", "inc_blk", "tile_ptr", "piece_blk", "piece_rc")] + [("max_tile_pieces", c_int32),
+                                                                                               ("l_mask", c_void_p)]
+
+
+def hblock_fill_mask(blocks, nvars: int, bd: int):
+    """thx_hblock_fill_mask (host only): the (ntiles, 4 * ntiles) int32 table of thx_hblock_layout.l_mask for the lower block
+    pattern ``blocks`` ((nblocks, 2) pairs (row variable, column variable))."""
+    import numpy as np
+    b = np.ascontiguousarray(np.asarray(blocks, dtype=np.int32).reshape(-1, 2))
+    ntiles = (nvars * bd + THX_TILE - 1) // THX_TILE
+    mask = np.zeros((ntiles, 4 * ntiles), dtype=np.int32)
+    check(load().thx_hblock_fill_mask(nvars, bd, b.shape[0], b.ctypes.data, mask.ctypes.data), "thx_hblock_fill_mask")
+    return mask
 
 
 def max_offdiag_tile_pieces(tile_ptr, ntiles: int) -> int:
@@ -205,6 +218,7 @@ _SIGNATURES = {
     "thx_chol_factor_hblocks": [POINTER(HBlockLayout), c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int, c_double, c_void_p,
                                 c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, POINTER(TilePattern), c_int, c_void_p,
                                 POINTER(CholSchedule)],
+    "thx_hblock_fill_mask": [c_int32, c_int32, c_int32, c_void_p, c_void_p],
     "thx_chol_plan": [c_int32, c_int64, c_int32, c_int, c_int, c_int, c_int64, POINTER(HBlockLayout), POINTER(CholSchedule),
                       POINTER(CholPlanInfo)],
     "thx_chol_factor_levels": [POINTER(HBlockLayout), c_void_p, c_int64, c_int32, c_void_p, c_int, c_double, c_void_p, c_void_p,

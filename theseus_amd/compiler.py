@@ -181,6 +181,14 @@ class HessianBlocks:
         self.elems = self.nblocks * d * d
         self.bstride = (self.elems + 3) // 4 * 4     # elements per problem (16-byte aligned in fp32)
         self._dev = {}
+        self._l_mask = None
+
+    def l_mask(self) -> np.ndarray:
+        """(ntiles, 4 * ntiles) int32: bit s of [t, c] set when the 32x32 sub-block (rows 128 t + 32 s, columns 32 c) of the
+        natural-order Cholesky factor can be non-zero (thx_hblock_fill_mask, host only)."""
+        if self._l_mask is None:
+            self._l_mask = _lib.hblock_fill_mask(self.blocks, self.nvars, self.bd)
+        return self._l_mask
 
     def on(self, device) -> "DeviceHessianBlocks":
         key = str(device)
@@ -231,4 +239,7 @@ class DeviceHessianBlocks:
         for f in self._FIELDS:
             setattr(c, f, self.t[f].data_ptr())
         c.max_tile_pieces = _lib.max_offdiag_tile_pieces(hb.tile_ptr, hb.ntiles)
+        # the structurally non-zero 32x32 sub-blocks of the natural-order factor (thx_hblock_layout.l_mask), once per layout and device
+        self.t["l_mask"] = torch.from_numpy(hb.l_mask()).to(device)
+        c.l_mask = self.t["l_mask"].data_ptr()
         self.c = c

@@ -38,6 +38,7 @@
 #include <mutex>
 #include <type_traits>
 #include <utility>
+#include <vector>
 
 namespace thx {
 
@@ -1012,6 +1013,9 @@ struct HBlk {
   const int32_t* piece_rc;
   const int32_t* diag_blk;   // (nvars) block id of variable v's diagonal block (the right-looking schedule's damping pass; may be null)
   int max_tile_pieces;       // thx_hblock_layout.max_tile_pieces (host side: picks the off-diagonal kernels' HB mode); 0: unknown
+  // thx_hblock_layout.l_mask: (ntiles, 4 * ntiles) 4-bit masks of the structurally non-zero 32-row sub-blocks of tile t at 32-column
+  // chunk c -- set by factor_impl only for the fp32 column-by-column dense-frame schedule (FactorPlan.zskip), nullptr otherwise
+  const int32_t* l_mask;
 };
 
 // The pieces of lower tile (ti, tj) of problem b -- f(r, c, value), (r, c) relative to the tile origin and inside the tile; the
@@ -2072,7 +2076,26 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
   if (nk > 0) gload3(0);
   if constexpr (HB) hb2.load(hb, b, i, j, tid);
   const float* sBw = sB + 32 * wave * 36;
+  // Structurally zero 32x32 sub-blocks of L (HBlk.l_mask, nullptr: none): per k-chunk the 4-bit masks of tiles j, j + 1 (the
+  // column side: operand A sub-block cb, the same for the four waves) and of row tile i (the row side: this wave's operand B
+  // sub-block).  An MFMA of an all-zero operand adds exact zeros: its output block's products are left out (wave-uniform
+  // branches), every accumulator still receives the others in the same order.  Scalar loads through the constant address space
+  // (as kloop_f's K-list), one chunk ahead: issued with the chunk's operand prefetch, they complete under the MFMAs.
+  typedef const int32_t __attribute__((address_space(4))) * lmask_t;
+  const lmask_t lm = (lmask_t)(uintptr_t)hb.l_mask;
+  const int nch = 4 * ntiles;
+  const int wv = __builtin_amdgcn_readfirstlane(wave);
+  int nm0 = 15, nm1 = 15, nmi = 15;   // the masks of the next chunk
+  auto lmask_load = [&](int kc) __attribute__((always_inline)) {
+    if (lm) {
+      nm0 = lm[j * nch + kc];
+      nm1 = lm[(j + 1) * nch + kc];
+      nmi = lm[i * nch + kc];
+    }
+  };
+  if (nk > 0) lmask_load(0);
   for (int kc = 0; kc < nk; ++kc) {
+    const int m0 = nm0, m1 = nm1, mi = nmi;
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -2082,13 +2105,24 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
       *reinterpret_cast<uint4*>(sB + row * 36 + 4 * lc) = qb[u];
     }
     __syncthreads();
-    if (kc + 1 < nk) gload3(kc + 1);
+    if (kc + 1 < nk) {
+      gload3(kc + 1);
+      lmask_load(kc + 1);
+    }
+    if (!((mi >> wv) & 1)) continue;   // this wave's rows of L_i are zero at the chunk: nothing to add
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const float4 fb = *reinterpret_cast<const float4*>(sBw + rl * 36 + 8 * ks + 4 * g);
+      float4 fa0[4], fa1[4];
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb) {
-        const float4 fa = *reinterpret_cast<const float4*>(sA0 + (32 * cb + rl) * 36 + 8 * ks + 4 * g);
+        fa0[cb] = *reinterpret_cast<const float4*>(sA0 + (32 * cb + rl) * 36 + 8 * ks + 4 * g);
+        fa1[cb] = *reinterpret_cast<const float4*>(sA1 + (32 * cb + rl) * 36 + 8 * ks + 4 * g);
+      }
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) {
+        if (!((m0 >> cb) & 1)) continue;
+        const float4 fa = fa0[cb];
         P0.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.x, fb.x, P0.v[cb], 0, 0, 0);
         P0.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.y, fb.y, P0.v[cb], 0, 0, 0);
         P0.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.z, fb.z, P0.v[cb], 0, 0, 0);
@@ -2096,7 +2130,8 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
       }
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb) {
-        const float4 fa = *reinterpret_cast<const float4*>(sA1 + (32 * cb + rl) * 36 + 8 * ks + 4 * g);
+        if (!((m1 >> cb) & 1)) continue;
+        const float4 fa = fa1[cb];
         P1.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.x, fb.x, P1.v[cb], 0, 0, 0);
         P1.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.y, fb.y, P1.v[cb], 0, 0, 0);
         P1.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.z, fb.z, P1.v[cb], 0, 0, 0);
@@ -3313,6 +3348,7 @@ struct FactorPlan {
   int rl_mode;           // its launch arrangement (0 | 1 | 2)
   bool rl_fwd_fused;     // ... with the forward substitution riding on it (else FACTOR_NEEDS_FORWARD)
   bool colpair;          // the column-pair schedule (left-looking, fp32)
+  bool zskip;            // the off-diagonal K-loops skip structurally zero 32x32 sub-blocks (HBlk.l_mask; fp32 left-looking dense frame)
   int hbm;               // the off-diagonal kernels' HB template argument: 0 dense H, HB_MODE_SCATTER, HB_MODE_ROUNDS
   int f64_wide_max, f64_half_max;
 };
@@ -3355,6 +3391,7 @@ static FactorPlan plan_factor(bool f64, int n, int64_t ld, int B, bool has_dampi
     return p;
   }
   p.colpair = column_pairs != 0 && !f64 && !tp && !packed && B >= pair_min_batch;
+  p.zskip = !f64 && !tp && !packed && use_hb && hbp->l_mask != nullptr && (!sched || sched->skip_zero_blocks != 0);
   return p;
 }
 
@@ -3364,9 +3401,10 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
                        const thx_tile_pattern* tp = nullptr, const HBlk* hbp = nullptr, const thx_level_schedule* ls = nullptr,
                        const thx_chol_schedule* sched = nullptr) {
   const bool use_hb = hbp != nullptr;
-  const HBlk hb = use_hb ? *hbp : HBlk{nullptr, 0, 0, nullptr, nullptr, nullptr};
   const FactorPlan P = plan_factor(sizeof(T) == 8, n, ld, B, damping != nullptr, rhs != nullptr, ldv,
                                    (reinterpret_cast<uintptr_t>(y) % 16) == 0, tp, hbp, ls, sched);
+  HBlk hb = use_hb ? *hbp : HBlk{nullptr, 0, 0, nullptr, nullptr, nullptr};
+  if (!P.zskip) hb.l_mask = nullptr;   // (every other schedule, and skipping switched off: the kernels see no mask)
   const int f64_wide_max = P.f64_wide_max, f64_half_max = P.f64_half_max;
   const int ntiles = P.ntiles;
   TilePat pat{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr};
@@ -4012,7 +4050,8 @@ int thx_chol_factor_hblocks(const thx_hblock_layout* layout, const void* Hc, int
     return fail("thx_chol_factor_hblocks: incomplete tile pattern");
   if ((rhs == nullptr) != (y == nullptr) || (rhs && ldv < n)) return fail("thx_chol_factor_hblocks: rhs / y / ldv");
   if (rhs && rhs == y) return fail("thx_chol_factor_hblocks: y must not alias rhs");
-  const HBlk hb{Hc, bstride, layout->bd, layout->tile_ptr, layout->piece_blk, layout->piece_rc, layout->diag_blk, layout->max_tile_pieces};
+  const HBlk hb{Hc, bstride, layout->bd, layout->tile_ptr, layout->piece_blk, layout->piece_rc, layout->diag_blk, layout->max_tile_pieces,
+                layout->l_mask};
   THX_DISPATCH(dtype,
                return factor_then_forward<float>(nullptr, ld, n, B, damping, ellipsoidal, damping_eps, L, Winv, info, rhs, y, ldv,
                                          as_stream(stream), pattern, &hb, nullptr, schedule),
@@ -4045,6 +4084,47 @@ int thx_chol_plan(int32_t n, int64_t ld, int32_t B, int dtype, int has_damping, 
   out->f64_half_cols = half;
   out->f64_wide_cols = f64_lanes ? std::max(0, std::min(p.f64_wide_max, cols) - half) : 0;
   out->forward_fused = has_rhs && (!p.rl || p.rl_fwd_fused);
+  return 0;
+}
+
+// Natural-order symbolic Cholesky of the variable-block pattern (Liu's row-subtree walk: row p of L is the union of the elimination-tree
+// paths from the columns q < p of row p of H up to p; the tree grows as the rows are visited), reduced to the l_mask table.
+int thx_hblock_fill_mask(int32_t nvars, int32_t bd, int32_t nblocks, const int32_t* blocks, int32_t* mask) {
+  if (nvars <= 0 || bd <= 0 || nblocks < 0 || (nblocks > 0 && !blocks) || !mask) return fail("thx_hblock_fill_mask: bad arguments");
+  const int64_t n = (int64_t)nvars * bd;
+  if (n > (int64_t)1 << 24) return fail("thx_hblock_fill_mask: matrix too large");
+  const int ntiles = (int)((n + TILE - 1) / TILE), nch = 4 * ntiles;
+  std::vector<int32_t> rptr(nvars + 1, 0), rcol;
+  for (int32_t e = 0; e < nblocks; ++e) {
+    const int32_t p = blocks[2 * e], q = blocks[2 * e + 1];
+    if (p < 0 || p >= nvars || q < 0 || q > p) return fail("thx_hblock_fill_mask: a block outside tril(H)");
+    if (q < p) ++rptr[p + 1];
+  }
+  for (int32_t v = 0; v < nvars; ++v) rptr[v + 1] += rptr[v];
+  rcol.resize(rptr[nvars]);
+  {
+    std::vector<int32_t> fill(rptr.begin(), rptr.end() - 1);
+    for (int32_t e = 0; e < nblocks; ++e)
+      if (blocks[2 * e + 1] < blocks[2 * e]) rcol[fill[blocks[2 * e]]++] = blocks[2 * e + 1];
+  }
+  std::fill(mask, mask + (int64_t)ntiles * nch, 0);
+  // block (p, q) of L, q <= p: every 32 x 32 sub-block (R, C), R >= C, that its rows / columns overlap
+  auto mark = [&](int32_t p, int32_t q) {
+    const int64_t r0 = (int64_t)p * bd, c0 = (int64_t)q * bd;
+    for (int64_t R = r0 / 32; R <= (r0 + bd - 1) / 32; ++R)
+      for (int64_t C = c0 / 32; C <= std::min((c0 + bd - 1) / 32, R); ++C) mask[(R / 4) * nch + C] |= 1 << (R % 4);
+  };
+  std::vector<int32_t> parent(nvars, -1), flag(nvars, -1);
+  for (int32_t p = 0; p < nvars; ++p) {
+    flag[p] = p;
+    mark(p, p);
+    for (int32_t e = rptr[p]; e < rptr[p + 1]; ++e)
+      for (int32_t k = rcol[e]; flag[k] != p; k = parent[k]) {
+        if (parent[k] < 0) parent[k] = p;
+        flag[k] = p;
+        mark(p, k);
+      }
+  }
   return 0;
 }
 

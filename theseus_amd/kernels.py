@@ -269,7 +269,7 @@ class HipKernels:
         self.lib = _lib.load()
         # per-call schedule of the factorisations (include/theseus_hip.h: thx_chol_schedule), handed to every thx_chol_factor* call
         # of THIS kernels object: -1 = the library default.  The library itself keeps no schedule state.
-        self.chol_schedule = _lib.CholSchedule(-1, -1, -1, -1, -1, -1, -1, -1)
+        self.chol_schedule = _lib.CholSchedule(*([-1] * len(_lib.CholSchedule._fields_)))
 
     def _sched(self):
         import ctypes
