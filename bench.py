@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""bench.py -- LM problem-iterations/s on the synthetic SE3 pose graph (BASELINE.json configs[1]) + every other BASELINE config
-as a leg of the same JSON line.
+"""bench.py -- LM problem-iterations/s on the synthetic SE3 pose graph (BASELINE.json configs[1]); with `--full`, every other
+BASELINE config as a leg of the same JSON line.
 
 A "step" is ONE Levenberg-Marquardt iteration over the whole batch (linearize -> damp + Cholesky
 factor + solve -> retract -> error), i.e. one pass of the hot path over one batch of synthetic
@@ -9,8 +9,11 @@ tolerances 0 so nothing exits early -- same trick as the reference's examples/po
 the timed region is bracketed by barrier + torch.cuda.synchronize and the max over ranks is reported.
 value = n_gpus * B * K / time  (problem-iterations per second, whole job).
 
-The headline (`metric` / `value` / `roofline` / `cpu_baseline` / `parity` at the top level) is BASELINE.json configs[1]:
-256 poses / 1024 edges, batch 4096 per GPU, fp32, LM + dense Cholesky.  Under `"configs"` the same line carries
+The headline (`metric` / `value` / `roofline` at the top level) is BASELINE.json configs[1]: 256 poses / 1024 edges, batch 4096
+per GPU, fp32, LM + dense Cholesky.  A plain run does only what the headline needs: set up, warm up, time the steps, write
+`--dump-outputs`, print the line.  `--full` adds everything else the benchmark measures: `cpu_baseline` (--cpu-sample 128),
+`parity` against the exact evaluation (--parity-sample 32; either can also be asked for without --full), the same workload through
+the tile-sparse solver (`tile_sparse`) and, when the headline configuration is run unmodified, under `"configs"` the same line carries
   N = 1 : "fp64_b4096"       configs[2]'s dtype and per-GPU share (32768 / 8 problems) on one GPU,
           "ba_512_8192_32768_b256"   configs[3] (bundle adjustment, Schur complement + tile-sparse Cholesky),
           "implicit_b1024"   configs[4] (forward LM + implicit backward through TheseusLayer),
@@ -18,7 +21,8 @@ The headline (`metric` / `value` / `roofline` / `cpu_baseline` / `parity` at the
                              backward on the generic path; reports correctness against the closed form, ~1 s),
   N > 1 : "strong_f64_32768" configs[2] itself: 32768 fp64 problems sharded over the N GPUs (strong scaling), each rank's
           share solved in sub-batches of 4096, one all_gather of the solved poses,
-each with its own value / ms_per_step / roofline / parity / cpu_baseline (`--legs none` skips them), summarised (leg_summary).
+each with its own value / ms_per_step / roofline / parity / cpu_baseline (`--legs none` skips them, `--legs fp64,ba,...` picks
+some without --full), summarised (leg_summary).
 
 `--dump-outputs DIR` writes what the headline's last timed call returned (solved poses, final cost per problem) as .npy files:
 the inputs are seeded, so two builds run with the same arguments can be compared output for output.
@@ -338,7 +342,7 @@ LEG_TABLES = ("phases_ms_per_call", "hbm_bound_kernels")   # per-kernel tables: 
 def leg_summary(x, prose=48):
     """A leg as it rides under "configs": its numbers and short labels, without the per-kernel tables, the prose longer than
     ``prose`` characters and the null fields, floats to 6 digits.  Eight full legs made a 21 kB line; summarised the whole line
-    stays near 12 kB.  A leg's full record is its own configuration run alone (bench.py --dtype f64 / --implicit / ...,
+    stays near 12 kB.  A leg's full record is its own configuration run alone (bench.py --full --dtype f64 / --implicit / ...,
     tools/bench_ba.py, tools/bench_sparse.py)."""
     def keep(k, v):
         return k not in LEG_TABLES and v is not None and not (isinstance(v, str) and len(v) > prose and k != "error")
@@ -1152,19 +1156,26 @@ def main():
                     help="dense: HipCholeskySolver (n^3/3 per problem); sparse: HipSparseCholeskySolver -- the same tile kernels "
                          "under a reverse Cuthill-McKee variable ordering, skipping the tiles of L (and the K-loop blocks) that "
                          "are structurally zero")
-    ap.add_argument("--cpu-sample", type=int, default=128, help="problems in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the benchmark measures besides the headline: the CPU baseline, the exact-parity sub-sample, "
+                         "the tile-sparse second measurement and, for the unmodified headline configuration, every other "
+                         "BASELINE config under 'configs'.  Off (default): set up, warm up, time the steps, dump, print")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="problems in the CPU-baseline sample (0 = skip; default: 128 with --full, else 0)")
     ap.add_argument("--cpu-chunk", type=int, default=32, help="problems per CPU-baseline chunk")
     ap.add_argument("--cpu-iters", type=int, default=3)
-    ap.add_argument("--parity-sample", type=int, default=32, help="problems in the exact-parity sub-sample (0 = skip)")
+    ap.add_argument("--parity-sample", type=int, default=None,
+                    help="problems in the exact-parity sub-sample (0 = skip; default: 32 with --full, else 0)")
     ap.add_argument("--no-sparse-leg", action="store_true",
-                    help="skip the second measurement of the same workload with the tile-sparse solver (reported under "
-                         "'tile_sparse' next to the dense headline)")
+                    help="with --full, skip the second measurement of the same workload with the tile-sparse solver (reported "
+                         "under 'tile_sparse' next to the dense headline)")
     ap.add_argument("--implicit", action="store_true",
                     help="BASELINE.json configs[4]: forward LM + implicit backward (one backward linear solve) through "
                          "TheseusLayer; measurement tensors require grad; a step = one LM iteration of the forward")
     ap.add_argument("--legs", default="auto",
-                    help="the other BASELINE configs under 'configs' in the same line: 'auto' (default: all of them when the "
-                         "headline configuration is run unmodified), 'none', or a comma list of fp64,ba,implicit,strong")
+                    help="the other BASELINE configs under 'configs' in the same line: 'auto' (default: with --full, all of them "
+                         "when the headline configuration is run unmodified; else none), 'none', or a comma list of "
+                         "fp64,ba,implicit,simple,sparse,small,strong,dropin")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the headline's last timed LM call returned -- DIR/poses.npy "
                          "(batch, poses, 3, 4) and DIR/last_err.npy (batch,), run dtype, at most 64 MB (a fixed seeded sample "
@@ -1175,6 +1186,10 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help=argparse.SUPPRESS)
     ap.add_argument("--strong-total", type=int, default=32768, help=argparse.SUPPRESS)   # (the strong leg's job size; tests)
     args = ap.parse_args()
+    if args.cpu_sample is None:
+        args.cpu_sample = 128 if args.full else 0
+    if args.parity_sample is None:
+        args.parity_sample = 32 if args.full else 0
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         respawn_under_torchrun(args.gpus)
@@ -1207,15 +1222,16 @@ def main():
     head = SimpleNamespace(poses=args.poses, edges=args.edges, batch=args.batch, total_batch=args.total_batch, steps=args.steps,
                            warmup=args.warmup, dtype=args.dtype, damping=args.damping, adaptive=args.adaptive,
                            solver=args.solver, implicit=args.implicit, cpu_sample=args.cpu_sample, cpu_chunk=args.cpu_chunk,
-                           cpu_iters=args.cpu_iters, parity_sample=args.parity_sample, sparse_leg=not args.no_sparse_leg,
+                           cpu_iters=args.cpu_iters, parity_sample=args.parity_sample, sparse_leg=args.full and not args.no_sparse_leg,
                            dump_outputs=args.dump_outputs)
     result = pg_run(head, ctx)
 
     # ---- the other BASELINE configs, as legs of the same line ----
     unmodified = (args.dtype == "f32" and args.solver == "dense" and not args.implicit and args.total_batch == 0
                   and not args.adaptive and args.poses == 256 and args.edges == 1024 and args.batch == 4096)
+    auto = args.legs == "auto" and args.full     # (a plain run carries no legs)
     if args.legs == "auto":
-        legs = (["fp64", "ba", "implicit", "simple", "sparse", "small"] if world == 1 else ["strong"]) if (unmodified and on_gpu) else []
+        legs = (["fp64", "ba", "implicit", "simple", "sparse", "small"] if world == 1 else ["strong"]) if (auto and unmodified and on_gpu) else []
     elif args.legs == "none":
         legs = []
     else:
@@ -1252,14 +1268,14 @@ def main():
         leg("implicit_b1024", lambda: pg_run(variant(implicit=True, batch=min(1024, args.batch), sparse_leg=False,
                                                      cpu_sample=min(args.cpu_sample, 4), parity_sample=min(args.parity_sample, 4)),
                                              ctx))
-    if not os.environ.get("THX_REFERENCE_ROOT") and world == 1 and not standin and legs and ("dropin" in legs or args.legs == "auto"):
+    if not os.environ.get("THX_REFERENCE_ROOT") and world == 1 and not standin and legs and ("dropin" in legs or auto):
         # (the REAL theseus loop over theseus_amd.plugin cannot run without a copy of the reference; recorded:
         #  profiles/r6/z_bench_dropin_leg.json, profiles/r6/z_pytest_plugin_cuda.txt)
         configs["dropin_real_theseus_loop"] = leg_summary({
             "skipped": "reference absent (no THX_REFERENCE_ROOT)",
             "recorded": {"fraction_of_mirror_loop": [0.909, 0.949], "tests_on_cuda": "43 passed",
                          "source": "profiles/r6/z_bench_dropin_leg.json"}})
-    if os.environ.get("THX_REFERENCE_ROOT") and world == 1 and not standin and ("dropin" in legs or args.legs == "auto"):
+    if os.environ.get("THX_REFERENCE_ROOT") and world == 1 and not standin and ("dropin" in legs or auto):
         # the DROP-IN on hardware: the REAL theseus loop (its Objective / LevenbergMarquardt / TheseusLayer) with theseus_amd.plugin
         # behind it on the headline workload, next to theseus_amd's own loop on the same inputs (tools/dropin_bench.py; only where
         # a copy of the reference is importable: tools/dropin_gpu.sh stages one for a single gpurun call)

@@ -48,10 +48,10 @@ def test_single_rank_default():
 
 
 def test_gpus_2_with_the_default_rank0_legs_does_not_hang():
-    """The driver runs `bench.py --gpus N --steps K --warmup W` with nothing else: the rank-0-only legs (CPU baseline, parity
-    sub-sample) must not run the sharded loop's collectives on rank 0 alone while the other ranks sit in the final barrier --
-    at N > 1 they are skipped (they belong to the N = 1 line)."""
-    seam = [a for a in SEAM if a not in ("--cpu-sample", "--parity-sample", "0")] + ["--cpu-iters", "1"]
+    """`bench.py --gpus N --full` with no sample sizes given: the rank-0-only legs (CPU baseline, parity sub-sample) must not
+    run the sharded loop's collectives on rank 0 alone while the other ranks sit in the final barrier -- at N > 1 they are
+    skipped (they belong to the N = 1 line)."""
+    seam = [a for a in SEAM if a not in ("--cpu-sample", "--parity-sample", "0")] + ["--cpu-iters", "1", "--full"]
     r = _bench("--gpus", "2", "--batch", "3", seam=seam)
     assert r["n_gpus"] == 2 and "cpu_baseline" not in r and "parity" not in r
     r1 = _bench("--batch", "3", seam=seam)
@@ -70,6 +70,16 @@ def test_gpus_2_emits_the_strong_scaling_leg_in_the_same_line():
     assert leg["rank_ms_per_step"]["min"] <= leg["rank_ms_per_step"]["max"]
 
 
+def test_plain_run_is_the_headline_alone():
+    """`bench.py --gpus N --steps K --warmup W` with nothing else: the headline and its dumped outputs, no CPU baseline, no parity
+    sub-sample, no tile-sparse measurement, no legs -- those come with --full."""
+    seam = [a for a in SEAM if a not in ("--cpu-sample", "--parity-sample", "0")]
+    for gpus in ("1", "2"):
+        r = _bench("--gpus", gpus, "--batch", "3", seam=seam)
+        assert r["n_gpus"] == int(gpus) and r["iters_done"] == 2 and r["ms_per_step"] > 0
+        assert not {"cpu_baseline", "speedup_vs_cpu", "parity", "tile_sparse", "configs"} & set(r)
+
+
 def test_single_rank_legs_ride_in_the_same_line():
     r = _bench("--batch", "2", "--legs", "fp64")
     assert r["n_gpus"] == 1 and r["configs"]["fp64_b4096"]["dtype"] == "f64" and r["configs"]["fp64_b4096"]["iters_done"] == 2
@@ -85,7 +95,7 @@ def test_config0_leg_rides_in_the_line():
 
 
 def test_gpus_8_is_the_drivers_command_shape():
-    """The driver's 8-GPU line is `bench.py --gpus 8 --steps K --warmup W` and nothing else: eight ranks, the weak-scaling headline
+    """The driver's full 8-GPU line is `bench.py --gpus 8 --steps K --warmup W --full`: eight ranks, the weak-scaling headline
     (every rank its own batch, one all_gather of eight shards) AND the strong-scaling leg in the same line, in the shape of
     configs[2] -- 32768 / 8 = 4096 per rank in sub-batches -- scaled down: 32 problems, 4 per rank, 2 sub-batches of 2, every rank
     in every collective.  Stand-in kernels over gloo: what is checked is that the path is correct by construction -- it cannot

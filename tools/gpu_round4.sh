@@ -1,13 +1,13 @@
 #!/bin/bash
 # Round 4's measurement set in ONE gpurun call (outputs under gpurun_out/<tag>/; copy what is to be judged into profiles/r4/): the
-# GPU test suite, the default bench.py line (headline + all legs) the way the driver runs it, and -- when a scratch copy of the
+# GPU test suite, the full bench.py line (--full: headline + all legs), and -- when a scratch copy of the
 # reference was staged (tools/dropin_stage.sh) -- the plugin's tests on the HIP kernels and the drop-in leg of bench.py.
 # Every command under its own timeout.
 set -u
 TAG=${1:-r4z}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 ulimit -c 0
 timeout 900 python -m pytest tests -m gpu -q --maxfail=20 -p no:cacheprovider > $OUT/pytest_gpu.txt 2>&1; tail -3 $OUT/pytest_gpu.txt
-( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err ) 2> $OUT/bench_default.time
+( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_default.json 2> $OUT/bench_default.err ) 2> $OUT/bench_default.time
 tail -3 $OUT/bench_default.time; wc -c $OUT/bench_default.json
 if [ -d _refcopy ]; then
   export THX_REFERENCE_ROOT=$(pwd)/_refcopy THX_PLUGIN_DEVICE=cuda
