@@ -500,6 +500,29 @@ int thx_chol_factor_hblocks(const thx_hblock_layout* layout, const void* Hc, int
                             int32_t* info, const void* rhs, void* y, int64_t ldv, const thx_tile_pattern* pattern, int dtype,
                             void* stream, const thx_chol_schedule* schedule);
 
+/* ---- LinearSolver.solve() with pivoted LU: replaces DenseSolver._apply_damping + LUDenseSolver._solve_sytem
+ *      (linear/dense_solver.py:125-141: torch.linalg.lu_factor + torch.linalg.lu_solve).  For systems that are not numerically
+ *      positive definite (a gauge-free graph without damping, an indefinite or non-symmetric AtA assigned from outside).
+ *      thx_lu_factor: P (M + damping) = L U with partial (row) pivoting, out of place (M stays undamped, as for thx_chol_factor).
+ *        symmetric_lower != 0: M is the (B, ld, ld) frame thx_pg_assemble / thx_block_assemble write, only its lower triangle is
+ *          read and mirrored; == 0: M is a full contiguous (B, n, n) matrix, used as is;
+ *        damping / ellipsoidal / damping_eps: as thx_chol_factor;
+ *        LU: (B, ld, ld) frame, ld % 32 == 0, every element written (unit-lower L below the diagonal, U on and above it, identity
+ *          in rows / columns n..ld-1); piv: (B, n) int32, row k was exchanged with row piv[k] (0-based getrf convention, ties of
+ *          |value| to the lowest row); info: (B) int32, 0 = ok, k + 1 = U(k, k) is exactly zero for the first such k (getrf
+ *          convention; the factorisation of that item goes on without dividing, the other items are not affected).
+ *        Limit: n <= 4096 and ld <= 4096, refused before any launch.
+ *      thx_lu_solve_forward: y = L^-1 P rhs; thx_lu_solve_backward: x = U^-1 y; thx_lu_solve: x = (M + damping)^-1 rhs with a
+ *        cached factor.  rhs / y / x are (B, n) with row stride ldv; the output may alias the input. */
+int thx_lu_factor(const void* M, int64_t ld, int32_t n, int32_t B, int symmetric_lower, const void* damping, int ellipsoidal,
+                  double damping_eps, void* LU, int32_t* piv, int32_t* info, int dtype, void* stream);
+int thx_lu_solve_forward(const void* LU, int64_t ld, int32_t n, int32_t B, const int32_t* piv, const void* rhs, void* y,
+                         int64_t ldv, int dtype, void* stream);
+int thx_lu_solve_backward(const void* LU, int64_t ld, int32_t n, int32_t B, const void* y, void* x, int64_t ldv, int dtype,
+                          void* stream);
+int thx_lu_solve(const void* LU, int64_t ld, int32_t n, int32_t B, const int32_t* piv, const void* rhs, void* x, int64_t ldv,
+                 int dtype, void* stream);
+
 /* ---- Implicit backward (BackwardMode.IMPLICIT, nonlinear/nonlinear_least_squares.py:121-135,265-292): the
  *      grad-enabled last step is X_new = X exp(step * delta), delta = H^-1 g(theta) with H detached
  *      (dense_linearization.py:61).  The backward pass is

@@ -17,11 +17,12 @@ LIB_PATH = os.environ.get("THESEUS_HIP_LIB") or os.path.join(_HERE, "lib", "libt
 
 THX_TILE = 128
 THX_ERR_CHUNKS = 128
+THX_LU_MAX_N = 4096  # largest system of thx_lu_factor (include/theseus_hip.h)
 THX_BA_ERR_CHUNKS = 256
 LOSS_NONE, LOSS_WELSCH, LOSS_HUBER, LOSS_HINGE = 0, 1, 2, 3  # THX_LOSS_* (theseus/core/robust_loss.py:33-62)
 LOSS_FLATTEN = 4  # THX_LOSS_FLATTEN: RobustCostFunction(flatten_dims=True), or-ed into a loss code
 LOSS_GEMAN_MCCLURE = 8  # THX_LOSS_GEMAN_MCCLURE (robust_loss.py:92-113; the radius entry carries log(mu * radius))
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 
 class LieEps(Structure):
@@ -231,6 +232,11 @@ _SIGNATURES = {
                        c_void_p],
     "thx_chol_solve_backward": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                 c_void_p],
+    "thx_lu_factor": [c_void_p, c_int64, c_int32, c_int32, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int,
+                      c_void_p],
+    "thx_lu_solve_forward": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],
+    "thx_lu_solve_backward": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_int, c_void_p],
+    "thx_lu_solve": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],
     "thx_se3_retract_vjp": [c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int,
                             POINTER(LieEps), c_void_p],
     "thx_pg_vjp": [POINTER(PGStructure), POINTER(PGData), c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,

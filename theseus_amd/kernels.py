@@ -779,6 +779,35 @@ class HipKernels:
                                                     y.stride(0), _lib.dtype_code(L.dtype), _lib.stream_ptr(L.device)),
                    "thx_chol_solve_backward")
 
+    # ---- dense pivoted LU (include/theseus_hip.h: thx_lu_factor) --------------------------------------
+    def lu_factor(self, M, n, damping, ellipsoidal, damping_eps, LU, piv, info, symmetric_lower=True):
+        """P (M + damping) = L U.  ``symmetric_lower``: M is a (B, ld, ld) frame whose lower triangle is mirrored; otherwise a full
+        contiguous (B, n, n) matrix.  ``LU`` (B, ld, ld), ``piv`` (B, n) int32 and ``info`` (B) int32 are overwritten entirely."""
+        B, ld = LU.shape[0], LU.shape[-1]
+        if tuple(M.shape) != ((B, ld, ld) if symmetric_lower else (B, n, n)):
+            raise ValueError(f"lu_factor: M has shape {tuple(M.shape)}")
+        if M.dtype != LU.dtype or piv.dtype != torch.int32 or info.dtype != torch.int32 or tuple(piv.shape) != (B, n):
+            raise ValueError("lu_factor: M / LU of one dtype, piv (B, n) int32, info (B) int32")
+        _lib.check(self.lib.thx_lu_factor(_lib.ptr(M, "M"), ld, n, B, int(bool(symmetric_lower)), _lib.ptr(damping),
+                                          int(bool(ellipsoidal)), float(damping_eps), _lib.ptr(LU, "LU"), _lib.ptr(piv, "piv"),
+                                          _lib.ptr(info, "info"), _lib.dtype_code(LU.dtype), _lib.stream_ptr(LU.device)),
+                   "thx_lu_factor")
+
+    def lu_solve_forward(self, LU, n, piv, rhs, y):
+        B, ld = LU.shape[0], LU.shape[-1]
+        _lib.check(self.lib.thx_lu_solve_forward(_lib.ptr(LU), ld, n, B, _lib.ptr(piv), _lib.ptr(rhs), _lib.ptr(y), rhs.stride(0),
+                                                 _lib.dtype_code(LU.dtype), _lib.stream_ptr(LU.device)), "thx_lu_solve_forward")
+
+    def lu_solve_backward(self, LU, n, y, x):
+        B, ld = LU.shape[0], LU.shape[-1]
+        _lib.check(self.lib.thx_lu_solve_backward(_lib.ptr(LU), ld, n, B, _lib.ptr(y), _lib.ptr(x), y.stride(0),
+                                                  _lib.dtype_code(LU.dtype), _lib.stream_ptr(LU.device)), "thx_lu_solve_backward")
+
+    def lu_solve(self, LU, n, piv, rhs, x):
+        B, ld = LU.shape[0], LU.shape[-1]
+        _lib.check(self.lib.thx_lu_solve(_lib.ptr(LU), ld, n, B, _lib.ptr(piv), _lib.ptr(rhs), _lib.ptr(x), rhs.stride(0),
+                                         _lib.dtype_code(LU.dtype), _lib.stream_ptr(LU.device)), "thx_lu_solve")
+
     def diag(self, H, n, d):
         B, ld = H.shape[0], H.shape[-1]
         _lib.check(self.lib.thx_diag(_lib.ptr(H), ld, n, B, _lib.ptr(d), d.stride(0), _lib.dtype_code(H.dtype),

@@ -1,10 +1,12 @@
-"""`LinearSolver` plugin surface + the HIP dense Cholesky solver.
+"""`LinearSolver` plugin surface + the HIP dense Cholesky and pivoted-LU solvers.
 
 ABC contract: theseus/optimizer/linear/linear_solver.py:15-37.  ``HipCholeskySolver`` replaces
 ``CholeskyDenseSolver`` (theseus/optimizer/linear/dense_solver.py:20-161): damping semantics of
 ``DenseSolver._apply_damping`` (:38-64, out of place), ``torch.linalg.cholesky`` +
 ``torch.cholesky_solve`` (:159-161) become one batched tiled HIP factorisation + two triangular
 solves; a non positive-definite system raises ``RuntimeError`` like ``torch.linalg.cholesky`` does.
+``HipLUSolver`` replaces ``LUDenseSolver`` (dense_solver.py:125-141) for systems that are not numerically positive
+definite: ``torch.linalg.lu_factor`` + ``lu_solve`` become thx_lu_factor + thx_lu_solve*.
 """
 import abc
 import warnings
@@ -206,6 +208,93 @@ class HipCholeskySolver(HipCholeskyCore, LinearSolver):
         self._core_init()
 
     # theseus/optimizer/linear/dense_solver.py:84-123
+    def solve(self, damping: Optional[Union[float, torch.Tensor]] = None, ellipsoidal_damping: bool = True,
+              damping_eps: float = 1e-8, check_info: bool = True, **kwargs) -> torch.Tensor:
+        return self._solve(damping, ellipsoidal_damping, damping_eps, check_info)
+
+
+class HipLUCore(HipCholeskyCore):
+    """Back-end half of the pivoted-LU solver: the surface of ``HipCholeskyCore`` that the loops and the autograd nodes call, on
+    thx_lu_factor / thx_lu_solve* (include/theseus_hip.h).  P (AtA + damping) = L U; the factor is (``LU``, ``piv``).  The backward
+    solves of the differentiated modes use the same factor: AtA + damping is symmetric."""
+
+    def _core_init(self):
+        self.K = self.linearization.K
+        self.LU = self.piv = self.info = self._y = None
+        self._lam = self._frame = None
+        self.factor_version = 0
+
+    def _ensure_buffers(self):
+        lin = self.linearization
+        g = lin.g
+        B, n = g.shape[0], lin.n
+        if n > _lib.THX_LU_MAX_N:
+            raise RuntimeError(f"HipLUSolver: systems of up to {_lib.THX_LU_MAX_N} unknowns (got {n})")
+        shape = (B, lin.ld, lin.ld)
+        if self.LU is None or tuple(self.LU.shape) != shape or self.LU.device != g.device or self.LU.dtype != g.dtype \
+                or self.piv.shape[1] != n:
+            # (every buffer is written entirely by the kernels: no initial contents needed)
+            self.LU = torch.empty(shape, dtype=g.dtype, device=g.device)
+            self.piv = torch.empty(B, n, dtype=torch.int32, device=g.device)
+            self._y = torch.empty(B, n, dtype=g.dtype, device=g.device)
+            self.info = torch.zeros(B, dtype=torch.int32, device=g.device)
+            self._lam = torch.empty(B, dtype=g.dtype, device=g.device)
+            self._frame = None
+
+    def _factor_call(self, lam, ellipsoidal_damping, damping_eps, rhs, y, pattern=None):
+        lin = self.linearization
+        full = getattr(lin, "full_matrix", None)   # a system handed over as plain tensors: any square matrix, used as it is
+        if full is not None:
+            self.K.lu_factor(full.contiguous(), lin.n, lam, ellipsoidal_damping, damping_eps, self.LU, self.piv, self.info,
+                             symmetric_lower=False)
+        elif getattr(lin, "_compact", False):
+            # block-compact Hessian: one extra pass expands it into a dense frame (blocks are rewritten each time, the zeros
+            # between them are written once)
+            if self._frame is None:
+                self._frame = torch.zeros_like(self.LU)
+            self.K.hblocks_expand(lin.hblocks, lin.Hc, self._frame)
+            self.K.lu_factor(self._frame, lin.n, lam, ellipsoidal_damping, damping_eps, self.LU, self.piv, self.info)
+        else:
+            self.K.lu_factor(lin.H, lin.n, lam, ellipsoidal_damping, damping_eps, self.LU, self.piv, self.info)
+        if rhs is not None:
+            self.K.lu_solve_forward(self.LU, lin.n, self.piv, rhs, y)
+
+    def factor_snapshot(self):
+        return self.LU.clone(), self.piv.clone()
+
+    def solve_with_snapshot(self, snapshot, rhs: torch.Tensor) -> torch.Tensor:
+        LU, piv = snapshot
+        rhs = rhs.contiguous()
+        x = torch.empty_like(rhs)
+        self.K.lu_solve(LU, self.linearization.n, piv, rhs, x)
+        return x
+
+    def _substitute(self, rhs, x, backward_only: bool):
+        """x = U^-1 rhs (``backward_only``: rhs is the y of ``factorize``) or (AtA + damping)^-1 rhs with the current factor."""
+        if backward_only:
+            self.K.lu_solve_backward(self.LU, self.linearization.n, rhs, x)
+        else:
+            self.K.lu_solve(self.LU, self.linearization.n, self.piv, rhs, x)
+
+    def check_info(self):
+        bad = self.info.nonzero()
+        if bad.numel():
+            b = int(bad[0])
+            raise RuntimeError(f"linalg.solve: (Batch element {b}): The solver failed because the input matrix is singular.")
+
+
+class HipLUSolver(HipLUCore, LinearSolver):
+    def __init__(self, objective: Objective, linearization_cls: Optional[Type[Linearization]] = None,
+                 linearization_kwargs: Optional[Dict[str, Any]] = None, check_singular: bool = False, **kwargs):
+        linearization_cls = linearization_cls or HipLinearization
+        if not (isinstance(linearization_cls, type) and issubclass(linearization_cls, HipLinearization)):
+            raise RuntimeError("HipLUSolver only works with theseus_amd.HipLinearization, "
+                               f"but {linearization_cls} was provided.")
+        LinearSolver.__init__(self, objective, linearization_cls, linearization_kwargs)
+        self._check_singular = check_singular
+        self._core_init()
+
+    # theseus/optimizer/linear/dense_solver.py:84-123,125-141
     def solve(self, damping: Optional[Union[float, torch.Tensor]] = None, ellipsoidal_damping: bool = True,
               damping_eps: float = 1e-8, check_info: bool = True, **kwargs) -> torch.Tensor:
         return self._solve(damping, ellipsoidal_damping, damping_eps, check_info)

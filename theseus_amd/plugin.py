@@ -34,6 +34,7 @@ import torch
 import theseus as th
 from theseus.optimizer import Linearization as _RefLinearization
 from theseus.optimizer.linear import CholeskyDenseSolver as _RefCholeskyDenseSolver
+from theseus.optimizer.linear import LUDenseSolver as _RefLUDenseSolver
 from theseus.optimizer.linear import LinearSolver as _RefLinearSolver
 
 from theseus.global_params import _THESEUS_GLOBAL_PARAMS as _REF_GLOBAL_PARAMS
@@ -41,7 +42,7 @@ from theseus.global_params import _THESEUS_GLOBAL_PARAMS as _REF_GLOBAL_PARAMS
 from .generic import BlockAssembler
 from .autograd import detached_tensors, pg_vjp_grads
 from .kernels import default_kernels, round_up
-from .linear_solver import HipCholeskyCore
+from .linear_solver import HipCholeskyCore, HipLUCore
 from .linearization import HipLinearizationCore
 from .packed import UnsupportedObjective
 from . import kernels as _kernels
@@ -578,6 +579,7 @@ class _TensorSystem:
 
     def __init__(self, K):
         self.K, self.H, self.g, self.n, self.ld = K, None, None, 0, 0
+        self.full_matrix = None   # the matrix as handed over (the LU solver reads it as it is: it need not be symmetric)
 
     def load(self, AtA: torch.Tensor, Atb: torch.Tensor):
         if AtA.ndim != 3 or AtA.shape[1] != AtA.shape[2]:
@@ -589,6 +591,7 @@ class _TensorSystem:
         self.H[:, :n, :n].copy_(AtA.detach())
         self.g = Atb.detach().reshape(B, n).contiguous()
         self.n, self.ld = n, ld
+        self.full_matrix = AtA.detach()
 
     def diagonal(self) -> torch.Tensor:
         d = torch.empty(self.g.shape[0], self.n, dtype=self.g.dtype, device=self.g.device)
@@ -695,6 +698,62 @@ class HipCholeskySolver(HipCholeskyCore, _RefCholeskyDenseSolver):
 
     def _solve_sytem(self, Atb: torch.Tensor, AtA: torch.Tensor) -> torch.Tensor:  # abstract in DenseSolver
         raise NotImplementedError("HipCholeskySolver.solve() factorises its linearization's packed Hessian")
+
+
+class _TensorSystemLUSolver(HipLUCore):
+    def __init__(self, K, check_singular: bool):
+        self.linearization = _TensorSystem(K)
+        self._check_singular = check_singular
+        self._core_init()
+
+
+class HipLUSolver(HipLUCore, _RefLUDenseSolver):
+    """Replaces ``th.LUDenseSolver`` (theseus/optimizer/linear/dense_solver.py:125-141) -- the solver for systems that are not
+    numerically positive definite.  Subclasses the reference's class (LM's isinstance whitelists) and calls
+    ``LinearSolver.__init__`` directly, as ``HipCholeskySolver`` above and for the same reason."""
+
+    def __init__(self, objective: th.Objective, linearization_cls: Optional[Type[_RefLinearization]] = None,
+                 linearization_kwargs: Optional[Dict[str, Any]] = None, check_singular: bool = False, **kwargs):
+        linearization_cls = linearization_cls or HipLinearization
+        if not (isinstance(linearization_cls, type) and issubclass(linearization_cls, HipLinearization)):
+            raise RuntimeError("HipLUSolver only works with theseus_amd.plugin.HipLinearization, "
+                               f"but {linearization_cls} was provided.")
+        _RefLinearSolver.__init__(self, objective, linearization_cls, linearization_kwargs)
+        self._check_singular = check_singular
+        self._core_init()
+
+    def solve(self, damping: Optional[Union[float, torch.Tensor]] = None, ellipsoidal_damping: bool = True,
+              damping_eps: float = 1e-8, **kwargs) -> torch.Tensor:
+        # the dispatch of HipCholeskySolver.solve; a singular system = RuntimeError = FAIL status under no_grad
+        lin = self.linearization
+        if not isinstance(lin, HipLinearization) or lin._ext_AtA is not None or lin._ext_Atb is not None:
+            return self._solve_tensor_system(lin.AtA, lin.Atb, damping, ellipsoidal_damping, damping_eps)
+        if damping is not None and isinstance(damping, torch.Tensor) and damping.ndim > 1:
+            raise ValueError("Damping must be a float or a 1-D tensor.")
+        if getattr(lin, "_unroll", None) is not None and torch.is_grad_enabled():
+            return _FusedUnrolledSolve.apply(self, damping, ellipsoidal_damping, damping_eps, *lin._unroll)
+        g = lin._g_graph
+        if g is not None and torch.is_grad_enabled():
+            Hg = getattr(lin, "_H_graph", None)
+            if Hg is not None:
+                return _UnrolledFactorSolve.apply(self, damping, ellipsoidal_damping, damping_eps, Hg, g)
+            return _CachedFactorSolve.apply(self, damping, ellipsoidal_damping, damping_eps, g)
+        return self._solve(damping, ellipsoidal_damping, damping_eps, check_info=True)
+
+    def _solve_tensor_system(self, AtA, Atb, damping, ellipsoidal_damping, damping_eps) -> torch.Tensor:
+        """``solve()`` on whatever ``linearization.AtA`` / ``.Atb`` return: the matrix is factorised as it is (general mode of
+        thx_lu_factor).  Gradients through it assume a symmetric system, as ``_UnrolledFactorSolve`` does."""
+        sub = getattr(self, "_tensor_solver", None)
+        if sub is None:
+            sub = self._tensor_solver = _TensorSystemLUSolver(self.K, self._check_singular)
+        sub.linearization.load(AtA, Atb)
+        if torch.is_grad_enabled() and (AtA.requires_grad or Atb.requires_grad):
+            return _UnrolledFactorSolve.apply(sub, damping, ellipsoidal_damping, damping_eps, AtA,
+                                              Atb.reshape(AtA.shape[0], AtA.shape[1]))
+        return sub._solve(damping, ellipsoidal_damping, damping_eps, check_info=True)
+
+    def _solve_sytem(self, Atb: torch.Tensor, AtA: torch.Tensor) -> torch.Tensor:  # abstract in DenseSolver
+        raise NotImplementedError("HipLUSolver.solve() factorises its linearization's packed Hessian")
 
 
 # ---- large pose graphs (theseus_amd/sparse.py): tile-sparse Cholesky under a fill-reducing ordering ----------------------------
