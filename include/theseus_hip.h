@@ -494,6 +494,19 @@ int thx_chol_solve_backward(const void* L, int64_t ld, int32_t n, int32_t B, con
                             void* x, int64_t ldv, int dtype, void* stream);
 int thx_chol_solve(const void* L, int64_t ld, int32_t n, int32_t B, const void* Winv, const void* rhs,
                    void* x, int64_t ldv, int dtype, void* stream);
+/*      thx_chol_solve_multi: the same solves for a BLOCK of right-hand sides per problem -- what TheseusLayer.compute_samples
+ *        (theseus/theseus_layer.py:99-135: delta + L^-T y for n_samples normal draws y, the sampling step of LEO,
+ *        examples/state_estimation_2d.py:319) and marginal covariances (blocks of H^-1: solves against unit vectors) need from the
+ *        factor the optimiser holds.  L (B, ld, ld) and Winv exactly as thx_chol_factor* leave them on a DENSE factor frame
+ *        (ld >= n, ld % 32 == 0, both 16-byte aligned), whichever schedule wrote them.  rhs / x: (B, nrhs, n), one vector per row:
+ *        element (b, s, i) at b * bstride + s * ldv + i, ldv >= n, bstride >= nrhs * ldv; x may alias rhs.
+ *        which (the codes of thx_chol_solve_levels) = 0: x = (L L^T)^-1 rhs, 1: x = L^-T rhs, 2: x = L^-1 rhs.
+ *        One workgroup per (problem, group of 32 vectors) streams L once per substitution, products on the matrix cores; the
+ *        block of vectors stays in x, so there is no limit on n or nrhs.  Rows / columns n..ld-1 of the frame are never used,
+ *        nothing outside nrhs rows of n elements is read or written, and a vector's result does not depend on the other vectors
+ *        of the call.  Agrees with thx_chol_solve to rounding (another summation order). */
+int thx_chol_solve_multi(const void* L, int64_t ld, int32_t n, int32_t B, const void* Winv, const void* rhs, void* x, int32_t nrhs,
+                         int64_t ldv, int64_t bstride, int which, int dtype, void* stream);
 /*      (block-compact Hessian, see thx_hblock_layout) */
 int thx_chol_factor_hblocks(const thx_hblock_layout* layout, const void* Hc, int64_t bstride, int32_t n, int32_t B,
                             const void* damping, int ellipsoidal, double damping_eps, void* L, int64_t ld, void* Winv,

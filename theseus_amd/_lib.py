@@ -22,7 +22,7 @@ THX_BA_ERR_CHUNKS = 256
 LOSS_NONE, LOSS_WELSCH, LOSS_HUBER, LOSS_HINGE = 0, 1, 2, 3  # THX_LOSS_* (theseus/core/robust_loss.py:33-62)
 LOSS_FLATTEN = 4  # THX_LOSS_FLATTEN: RobustCostFunction(flatten_dims=True), or-ed into a loss code
 LOSS_GEMAN_MCCLURE = 8  # THX_LOSS_GEMAN_MCCLURE (robust_loss.py:92-113; the radius entry carries log(mu * radius))
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 
 class LieEps(Structure):
@@ -232,6 +232,8 @@ _SIGNATURES = {
                        c_void_p],
     "thx_chol_solve_backward": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                 c_void_p],
+    "thx_chol_solve_multi": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int, c_int,
+                             c_void_p],
     "thx_lu_factor": [c_void_p, c_int64, c_int32, c_int32, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int,
                       c_void_p],
     "thx_lu_solve_forward": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],

@@ -19,7 +19,7 @@ from . import _lib
 from .core import Objective, Variable
 from .compiler import PoseGraphStructure
 from .kernels import PGTensors, default_kernels, fast_approx_local_jacobians, round_up
-from .linear_solver import LinearSolver
+from .linear_solver import DenseCholeskyOnly, LinearSolver
 from .linearization import Linearization, VariableOrdering
 from .packed import (UnsupportedObjective, _AuxDeepStamp, _aux_vars, _kind, _opt_deep_stamp, _radius_vars, _unwrap_robust,
                      _views_deep_stamp, _weight_diag)
@@ -707,7 +707,7 @@ class _SchurBlockList:
         return self._dev[key]
 
 
-class HipSchurSolverCore:
+class HipSchurSolverCore(DenseCholeskyOnly):
     """(H + damping) delta = g of a bundle-adjustment linearization by block elimination of the points + the tiled dense
     Cholesky on the reduced camera system.  Same ``solve`` contract and failure behaviour as ``HipCholeskySolver``."""
 

@@ -779,6 +779,28 @@ class HipKernels:
                                                     y.stride(0), _lib.dtype_code(L.dtype), _lib.stream_ptr(L.device)),
                    "thx_chol_solve_backward")
 
+    def chol_solve_multi(self, L, n, panels, rhs, x, which=0):
+        """thx_chol_solve_multi: ``rhs`` / ``x`` (B, nrhs, n), one vector per row (unit stride along n, any row / batch strides
+        that do not overlap); which = 0: (L L^T)^-1 rhs, 1: L^-T rhs, 2: L^-1 rhs.  ``x`` may be ``rhs``."""
+        B, ld = L.shape[0], L.shape[-1]
+        nt = (n + _lib.THX_TILE - 1) // _lib.THX_TILE
+        if L.dim() != 3 or L.shape[1] != ld or tuple(panels.shape) != (B, nt, _lib.THX_TILE, _lib.THX_TILE):
+            raise ValueError(f"chol_solve_multi: L {tuple(L.shape)} / panels {tuple(panels.shape)} are not a dense factor frame of order {n}")
+        if rhs.dim() != 3 or rhs.shape[0] != B or rhs.shape[2] != n or rhs.shape[1] < 1 or x.shape != rhs.shape:
+            raise ValueError(f"chol_solve_multi: rhs {tuple(rhs.shape)} / x {tuple(x.shape)} must both be (B = {B}, nrhs >= 1, n = {n})")
+        if not (L.dtype == panels.dtype == rhs.dtype == x.dtype):
+            raise ValueError("chol_solve_multi: L, panels, rhs and x must have one dtype")
+        if rhs.stride() != x.stride() or rhs.stride(2) != 1:
+            raise ValueError("chol_solve_multi: rhs and x need the same strides, unit stride along n")
+        for t, name in ((rhs, "rhs"), (x, "x")):
+            if not t.is_cuda:
+                raise RuntimeError(f"{name} must live on a HIP device (got {t.device}); there is no CPU fallback")
+        nrhs, ldv = rhs.shape[1], (rhs.stride(1) if rhs.shape[1] > 1 else max(rhs.stride(1), n))
+        bstride = rhs.stride(0) if B > 1 else max(rhs.stride(0), nrhs * ldv)
+        _lib.check(self.lib.thx_chol_solve_multi(_lib.ptr(L, "L"), ld, n, B, _lib.ptr(panels, "panels"), _lib.c_void_p(rhs.data_ptr()),
+                                                 _lib.c_void_p(x.data_ptr()), nrhs, ldv, bstride, int(which), _lib.dtype_code(L.dtype),
+                                                 _lib.stream_ptr(L.device)), "thx_chol_solve_multi")
+
     # ---- dense pivoted LU (include/theseus_hip.h: thx_lu_factor) --------------------------------------
     def lu_factor(self, M, n, damping, ellipsoidal, damping_eps, LU, piv, info, symmetric_lower=True):
         """P (M + damping) = L U.  ``symmetric_lower``: M is a (B, ld, ld) frame whose lower triangle is mirrored; otherwise a full

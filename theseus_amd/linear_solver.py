@@ -9,8 +9,9 @@ solves; a non positive-definite system raises ``RuntimeError`` like ``torch.lina
 definite: ``torch.linalg.lu_factor`` + ``lu_solve`` become thx_lu_factor + thx_lu_solve*.
 """
 import abc
+import math
 import warnings
-from typing import Any, Dict, Optional, Type, Union
+from typing import Any, Dict, Optional, Sequence, Type, Union
 
 import torch
 
@@ -121,6 +122,85 @@ class HipCholeskyCore:
         else:
             self.K.chol_solve(self.L, self.linearization.n, self.panels, rhs, x)
 
+    # ---- blocks of right-hand sides on the cached factor (thx_chol_solve_multi): posterior samples, marginal covariances ----------
+    def _factor_owner(self) -> "HipCholeskyCore":
+        """The core that holds the factor ``solve()`` left (theseus_amd/plugin.py: a system handed over as tensors has its own)."""
+        return self
+
+    def _factorize_undamped(self) -> "HipCholeskyCore":
+        """L L^T = AtA of the linearization as it stands; returns the core that holds it."""
+        self.factorize(None)
+        self.check_info()
+        return self
+
+    def solve_multi_with_factor(self, rhs: torch.Tensor, which: int = 0) -> torch.Tensor:
+        """``rhs`` (B, k, n), one vector per row, against the CURRENT factor: which = 0: (L L^T)^-1 rhs, 1: L^-T rhs, 2: L^-1 rhs
+        (the codes of thx_chol_solve_levels).  Every group of 32 vectors reads L once per substitution.  Returns a new tensor."""
+        own = self._factor_owner()
+        if own is None or own.L is None or own.factor_version == 0:
+            raise RuntimeError("solve_multi_with_factor: nothing has been factorised yet (solve() or factorize() first).")
+        n = own.linearization.n
+        if rhs.dim() != 3 or rhs.shape[0] != own.L.shape[0] or rhs.shape[2] != n or rhs.shape[1] < 1:
+            raise ValueError(f"solve_multi_with_factor: rhs must be (B = {own.L.shape[0]}, k >= 1, n = {n}), got {tuple(rhs.shape)}")
+        x = rhs.detach().to(own.L.dtype).clone(memory_format=torch.contiguous_format)
+        own.K.chol_solve_multi(own.L, n, own.panels, x, x, which=which)
+        return x
+
+    @torch.no_grad()
+    def sample_deltas(self, n_samples: int = 10, temperature: float = 1.0, noise: Optional[torch.Tensor] = None,
+                      generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """The ``delta_samples`` of TheseusLayer.compute_samples (theseus/theseus_layer.py:110-123), (B, n, n_samples): draws from
+        N(delta, (AtA / temperature)^-1) as  delta + sqrt(temperature) L^-T y  with delta = ``solve()`` (undamped, on the
+        linearization as it stands) and L the factor that solve just left -- the reference factorises AtA / temperature a second
+        time, densely.  ``noise``: y as (n, n_samples), shared by the batch as in the reference, or (B, n, n_samples); None: drawn
+        with ``generator``.  The result is a permuted view of the kernel's (B, n_samples, n) output."""
+        if not temperature > 0:
+            raise ValueError(f"sample_deltas: temperature must be positive, got {temperature}")
+        if int(n_samples) < 1:
+            raise ValueError(f"sample_deltas: n_samples must be at least 1, got {n_samples}")
+        delta = self.solve()
+        own = self._factor_owner()
+        B, n = delta.shape
+        if noise is None:
+            noise = torch.randn(n, int(n_samples), generator=generator, device=delta.device, dtype=delta.dtype)
+        if noise.dim() == 2 and tuple(noise.shape) == (n, n_samples):
+            y = noise.t().unsqueeze(0).expand(B, n_samples, n)
+        elif noise.dim() == 3 and tuple(noise.shape) == (B, n, n_samples):
+            y = noise.transpose(1, 2)
+        else:
+            raise ValueError(f"sample_deltas: noise must be ({n}, {n_samples}) or ({B}, {n}, {n_samples}), got {tuple(noise.shape)}")
+        y = y.to(device=delta.device, dtype=delta.dtype).clone(memory_format=torch.contiguous_format)
+        own.K.chol_solve_multi(own.L, n, own.panels, y, y, which=1)
+        y.mul_(math.sqrt(float(temperature))).add_(delta.unsqueeze(1))
+        return y.transpose(1, 2)
+
+    @torch.no_grad()
+    def marginal_covariance(self, var_names: Sequence[str]) -> torch.Tensor:
+        """(B, d, d): the rows and columns of (AtA)^-1 at the columns of the named optimisation variables, in the order given --
+        their joint marginal covariance in the tangent space at the linearization point.  Factorises undamped and solves against
+        the d unit vectors of those columns (one thx_chol_solve_multi call)."""
+        lin = self.linearization
+        names = list(var_names)
+        if len(set(names)) != len(names):
+            raise ValueError(f"marginal_covariance: repeated variable names in {names}")
+        cols = []
+        for name in names:
+            try:
+                k = lin.ordering.index_of(name)
+            except KeyError:
+                raise ValueError(f"marginal_covariance: {name!r} is not an optimisation variable of the objective") from None
+            cols.extend(range(lin.var_start_cols[k], lin.var_start_cols[k] + lin.var_dims[k]))
+        if not cols:
+            raise ValueError("marginal_covariance: no variables named")
+        own = self._factorize_undamped()
+        B, n, d = own.L.shape[0], own.linearization.n, len(cols)
+        idx = torch.tensor(cols, dtype=torch.long, device=own.L.device)
+        E = torch.zeros(B, d, n, dtype=own.L.dtype, device=own.L.device)
+        E[:, torch.arange(d, device=idx.device), idx] = 1
+        own.K.chol_solve_multi(own.L, n, own.panels, E, E, which=0)
+        C = E[:, :, idx]
+        return (C + C.transpose(1, 2)) / 2
+
     def check_info(self):
         bad = self.info.nonzero()
         if bad.numel():
@@ -213,7 +293,23 @@ class HipCholeskySolver(HipCholeskyCore, LinearSolver):
         return self._solve(damping, ellipsoidal_damping, damping_eps, check_info)
 
 
-class HipLUCore(HipCholeskyCore):
+def _dense_cholesky_only(name: str):
+    def method(self, *args, **kwargs):
+        raise NotImplementedError(f"{type(self).__name__}.{name}: blocks of right-hand sides, posterior samples and marginal "
+                                  "covariances need the dense factor frame of HipCholeskySolver (thx_chol_solve_multi).")
+    method.__name__ = name
+    return method
+
+
+class DenseCholeskyOnly:
+    """Mixed in FIRST by the cores whose factor is not a dense Cholesky frame (pivoted LU, tile-packed / pattern / level factors,
+    the Schur solver): the multi-right-hand-side surface of ``HipCholeskyCore`` raises instead of reading a frame they lack."""
+    solve_multi_with_factor = _dense_cholesky_only("solve_multi_with_factor")
+    sample_deltas = _dense_cholesky_only("sample_deltas")
+    marginal_covariance = _dense_cholesky_only("marginal_covariance")
+
+
+class HipLUCore(DenseCholeskyOnly, HipCholeskyCore):
     """Back-end half of the pivoted-LU solver: the surface of ``HipCholeskyCore`` that the loops and the autograd nodes call, on
     thx_lu_factor / thx_lu_solve* (include/theseus_hip.h).  P (AtA + damping) = L U; the factor is (``LU``, ``piv``).  The backward
     solves of the differentiated modes use the same factor: AtA + damping is symmetric."""

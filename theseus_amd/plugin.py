@@ -696,6 +696,20 @@ class HipCholeskySolver(HipCholeskyCore, _RefCholeskyDenseSolver):
                                               Atb.reshape(AtA.shape[0], AtA.shape[1]))
         return sub._solve(damping, ellipsoidal_damping, damping_eps, check_info=True)
 
+    def _external_system(self) -> bool:
+        lin = self.linearization
+        return not isinstance(lin, HipLinearization) or lin._ext_AtA is not None or lin._ext_Atb is not None
+
+    def _factor_owner(self):
+        # (a system handed over as tensors is factorised by the tensor solver's core: None until solve() has built it)
+        return getattr(self, "_tensor_solver", None) if self._external_system() else self
+
+    def _factorize_undamped(self):
+        if self._external_system():   # (the system is loaded into the tensor solver's frame by solve(), which factorises it undamped)
+            self.solve()
+            return self._tensor_solver
+        return HipCholeskyCore._factorize_undamped(self)
+
     def _solve_sytem(self, Atb: torch.Tensor, AtA: torch.Tensor) -> torch.Tensor:  # abstract in DenseSolver
         raise NotImplementedError("HipCholeskySolver.solve() factorises its linearization's packed Hessian")
 

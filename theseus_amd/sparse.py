@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from .core import Objective
-from .linear_solver import HipCholeskyCore, LinearSolver
+from .linear_solver import DenseCholeskyOnly, HipCholeskyCore, LinearSolver
 from .linearization import HipLinearization, Linearization, VariableOrdering
 
 TILE = _lib.THX_TILE
@@ -642,7 +642,7 @@ class _LevelLayout:
         self.c, self._base = c, base
 
 
-class HipSparseCholeskyCore(HipCholeskyCore):
+class HipSparseCholeskyCore(DenseCholeskyOnly, HipCholeskyCore):
     """HipCholeskyCore whose factorisation follows the tile pattern of its linearization."""
 
     levels = False   # True: LevelPattern + thx_chol_factor_levels / thx_chol_solve_levels (elimination-tree parallelism)
