@@ -7,7 +7,13 @@
   * failure reporting: info is LAPACK's (torch.linalg.cholesky_ex of the damped fp64 matrix) for a non-positive pivot in block
     column 0, 1, a late one, the partial last tile, and a NaN off the diagonal -- and the other problems of the batch keep their bits;
   * stale and poisoned buffers: the LM reuses L across iterations and allocates the panels / vectors with torch.empty -- a factor
-    must not depend on what they held."""
+    must not depend on what they held;
+  * the dynamic-LDS limits, which the library raises kernel by kernel where it launches: one process in which every limit has to
+    grow from call to call (a child process, so that no earlier test has raised them)."""
+import os
+import subprocess
+import sys
+
 import pytest
 import torch
 
@@ -278,3 +284,59 @@ def test_factor_does_not_depend_on_stale_buffers(sched):
     assert torch.equal(Pf[mask], Ps[mask])
     assert torch.equal(yf, ys) and torch.equal(xf, xs)
     assert not torch.isnan(xs).any()
+
+
+# ---- dynamic-LDS limits that must grow within one process --------------------------------------------------------------------------
+# The library raises a kernel's dynamic-LDS limit next to its launch and remembers per kernel how far.  The diagonal phase's LDS
+# grows with n when the forward substitution is fused (its y buffer), the solves' with n (the whole vector): n = 128, 384, 640 in
+# this order make every later call need more than any call before it.  B = 2: left-looking at one tile, right-looking from three
+# tiles on (the dense-frame chol_diag instance, block rows in the backward substitution); B = 160: left-looking, in column pairs
+# in fp32, the one-workgroup solves; then 384 x 8, right-looking again after the larger left-looking calls.
+GROW_STEPS = [(128, 2), (384, 2), (640, 2), (128, 160), (384, 160), (640, 160), (384, 8)]
+
+
+def _growing_limits_child():
+    from theseus_amd.kernels import HipKernels
+    K = HipKernels()
+    for dtype in (F64, F32):
+        f32 = dtype == F32
+        tol_L, tol_x = (2e-5, 2e-3) if f32 else (1e-13, 1e-10)      # (as test_right_looking_modes_vs_lapack)
+        for n, B in GROW_STEPS:
+            ld = n
+            p = K.chol_plan(n, ld, B, dtype, damping=False, rhs=True, ldv=n)
+            assert p["right_looking"] == int(n >= 384 and B <= 8), (n, B, p)
+            assert p["column_pairs"] == int(f32 and B == 160), (n, B, p)
+            M = _spd(B, n, dtype, seed=13 * n + B)
+            H = _frame(M, ld)
+            rhs = _vec(B, n, n, dtype)
+            rhs.copy_(torch.randn(B, n, dtype=F64, device="cuda", generator=torch.Generator(device="cuda").manual_seed(n + B)).to(dtype))
+            L, panels, y, x, info = (torch.zeros_like(H), torch.zeros(B, (n + 127) // 128, 128, 128, dtype=dtype, device="cuda"),
+                                     _vec(B, n, n, dtype), _vec(B, n, n, dtype), torch.zeros(B, dtype=torch.int32, device="cuda"))
+            x2 = _vec(B, n, n, dtype)
+            K.chol_factor(H, n, None, False, 0.0, L, panels, info, rhs=rhs, y=y)      # thx_chol_factor_forward
+            K.chol_solve(L, n, panels, rhs, x)                                        # thx_chol_solve
+            K.chol_solve_backward(L, n, panels, y, x2)                                # (y, through the backward substitution)
+            torch.cuda.synchronize()
+            assert int(info.abs().sum()) == 0, (n, B, info)
+            sample = sorted({0, B // 2, B - 1})
+            Lref = torch.linalg.cholesky(M[sample].double().cpu())                    # (LAPACK, fp64, on the host)
+            xref = torch.cholesky_solve(rhs[sample].double().cpu().unsqueeze(2), Lref).squeeze(2)
+            eL = float((torch.tril(L[sample, :n, :n]).double().cpu() - Lref).abs().max() / Lref.abs().max())
+            ex = float((x[sample].double().cpu() - xref).abs().max() / xref.abs().max())
+            ey = float((x2[sample].double().cpu() - xref).abs().max() / xref.abs().max())
+            print(f"{'f32' if f32 else 'f64'} n={n} B={B}: L {eL:.3e} (< {tol_L}), x {ex:.3e}, x from y {ey:.3e} (< {tol_x})", flush=True)
+            assert eL < tol_L and ex < tol_x and ey < tol_x, (n, B, eL, ex, ey)
+    print("GROWING-LIMITS-OK")
+
+
+def test_lds_limits_grow_within_a_process():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    out = subprocess.run([sys.executable, "-m", "tests.test_gpu_chol_schedules"], cwd=root, env=env, capture_output=True, text=True,
+                         timeout=300)
+    print(out.stdout)
+    assert out.returncode == 0 and "GROWING-LIMITS-OK" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
+
+
+if __name__ == "__main__":
+    _growing_limits_child()

@@ -451,7 +451,7 @@ def _chol_vs_lapack(K, dtype, n, B, fused):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 def test_chol_two_stream_half_batch_schedule(K, dtype):
     """Batches of 1024 problems or more are factorised as two halves on two streams (chol_kernels.hip:
-    factor_impl).  An odd batch of 1029 with per-problem damping and the fused forward substitution: every problem must
+    run_left_looking).  An odd batch of 1029 with per-problem damping and the fused forward substitution: every problem must
     come out as if it had been solved alone -- checked against LAPACK on a sample across both halves."""
     from tests.gpu_helpers import factor_and_solve
     from theseus_amd.kernels import round_up

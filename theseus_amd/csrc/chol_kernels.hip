@@ -3290,13 +3290,10 @@ constexpr int BWD_ROWS_MAX_BATCH = 32;       // solve_impl: the backward substit
 constexpr int SPLIT_DIAG_MIN_DEFAULT = 2048;
 constexpr int COLUMN_PAIRS_DEFAULT = 1;
 
-// Launch-side state is kept PER DEVICE (a process may drive several GPUs, from several threads): the dynamic-LDS limits
-// raised with hipFuncSetAttribute, and the auxiliary stream + events of the two-stream schedule, which belong to the device
-// they were created on.
+// Launch-side state is kept PER DEVICE (a process may drive several GPUs, from several threads): the auxiliary stream + events of
+// the two-stream schedules, which belong to the device they were created on, and the dynamic-LDS limits (launch_lds).
 constexpr int MAX_DEVICES = 64;
 struct DeviceLaunchState {
-  size_t attr_diag[2][2] = {{0, 0}, {0, 0}}, attr_syrk[2][2] = {{0, 0}, {0, 0}}, attr_solve[2] = {0, 0}, attr_bwd_rows[2] = {0, 0};   // [0] float, [1] double (x HB)
-  bool attr_off = false;
   hipStream_t aux = nullptr;
   hipEvent_t ev_fork = nullptr, ev_lag = nullptr, ev_join = nullptr;
   hipEvent_t ev_diag = nullptr, ev_rest = nullptr;   // look-ahead schedule (one part): diag(j) done / rest of column j done
@@ -3308,11 +3305,39 @@ struct DeviceLaunchState {
   }
 };
 static std::mutex g_launch_mutex;
-static DeviceLaunchState& launch_state() {
-  static DeviceLaunchState st[MAX_DEVICES];
+static int current_device() {
   int dev = 0;
   hipGetDevice(&dev);
-  return st[(dev >= 0 && dev < MAX_DEVICES) ? dev : 0];
+  return (dev >= 0 && dev < MAX_DEVICES) ? dev : 0;
+}
+static DeviceLaunchState& launch_state(int dev) {
+  static DeviceLaunchState st[MAX_DEVICES];
+  return st[dev];
+}
+
+// Launches Kernel with `smem` bytes of dynamic LDS, first raising the kernel's limit on device `dev` (current_device()) if it does
+// not stand that high yet: remembered per kernel instance (one instance of this template each) and per device, so a kernel cannot
+// be launched without its limit.  Only under g_launch_mutex.
+template <auto Kernel, typename... A>
+static void launch_lds(int dev, dim3 grid, dim3 block, size_t smem, hipStream_t s, A... args) {
+  static size_t have[MAX_DEVICES] = {};
+  if (smem > have[dev]) {
+    hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    have[dev] = smem;
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, smem, s, args...);
+}
+
+// a run-time value as a template argument: f(std::integral_constant<...>{})
+template <typename F>
+static void with_bool(bool b, F&& f) {
+  b ? f(std::true_type{}) : f(std::false_type{});
+}
+template <typename F>
+static void with_hb_mode(int hbm, F&& f) {   // (FactorPlan.hbm: the off-diagonal kernels' HB template argument)
+  if (hbm == 0) f(std::integral_constant<int, 0>{});
+  else if (hbm == HB_MODE_SCATTER) f(std::integral_constant<int, HB_MODE_SCATTER>{});
+  else f(std::integral_constant<int, HB_MODE_ROUNDS>{});
 }
 
 // how an off-diagonal tile takes its pieces of H: a few per tile (pose graphs) -> added by the matrix cores (hb_scatter); many (a
@@ -3336,18 +3361,18 @@ constexpr int COLUMN_PAIRS_MIN_BATCH_DEFAULT = 128;
 
 // THE LAUNCH PLAN of a factorisation: every schedule decision factor_impl takes from its arguments, the per-call schedule and the
 // defaults above -- in one place, so that thx_chol_plan reports exactly what a call with those arguments runs.
+enum class Schedule { Levels, LookAhead, RightLooking, LeftLooking };   // run_levels, run_lookahead, run_right_looking, run_left_looking
 struct FactorPlan {
+  Schedule schedule;
   int ntiles;
   int split_diag_min;    // (the level schedule decides per level with it)
   bool fused_diag;       // the diagonal phase as one kernel (else SYRK + potrf)
   int rl_max_batch;
-  bool split;            // the batch dealt over two streams
+  bool split;            // (left-looking) the batch dealt over two streams
   int nparts;            // 2 if split, else 1
-  bool lookahead;        // one part, REST of a column on the second stream (tile-sparse with col_head_host)
-  bool rl;               // the right-looking schedule of small dense batches
-  int rl_mode;           // its launch arrangement (0 | 1 | 2)
+  int rl_mode;           // (right-looking) its launch arrangement (0 | 1 | 2)
   bool rl_fwd_fused;     // ... with the forward substitution riding on it (else FACTOR_NEEDS_FORWARD)
-  bool colpair;          // the column-pair schedule (left-looking, fp32)
+  bool colpair;          // (left-looking) the column-pair schedule (fp32)
   bool zskip;            // the off-diagonal K-loops skip structurally zero 32x32 sub-blocks (HBlk.l_mask; fp32 left-looking dense frame)
   int hbm;               // the off-diagonal kernels' HB template argument: 0 dense H, HB_MODE_SCATTER, HB_MODE_ROUNDS
   int f64_wide_max, f64_half_max;
@@ -3379,478 +3404,441 @@ static FactorPlan plan_factor(bool f64, int n, int64_t ld, int B, bool has_dampi
   p.fused_diag = B < p.split_diag_min;
   p.split = B >= SPLIT_MIN && p.ntiles > 1;
   p.nparts = p.split ? 2 : 1;
-  if (ls) return p;   // (the level schedule: its own launch loop, per level)
-  p.lookahead = !p.split && p.ntiles > 2 && tp && tp->col_head_host != nullptr;
-  if (p.lookahead) return p;
-  p.rl = !tp && !packed && !p.split && p.fused_diag && p.ntiles >= 3 && B <= p.rl_max_batch && ld >= (int64_t)p.ntiles * TILE &&
-         (!use_hb || !has_damping || hbp->diag_blk);
-  if (p.rl) {
+  p.schedule = Schedule::Levels;
+  if (ls) return p;   // (its own launch loop, per level)
+  p.schedule = Schedule::LookAhead;
+  if (!p.split && p.ntiles > 2 && tp && tp->col_head_host != nullptr) return p;
+  p.schedule = Schedule::RightLooking;
+  if (!tp && !packed && !p.split && p.fused_diag && p.ntiles >= 3 && B <= p.rl_max_batch && ld >= (int64_t)p.ntiles * TILE &&
+      (!use_hb || !has_damping || hbp->diag_blk)) {
     const int m = sched ? sched->right_looking_mode : -1;
     p.rl_mode = m < 0 ? (f64 ? 2 : 1) : (m > 2 ? 1 : m);
     p.rl_fwd_fused = has_rhs && (ldv % 4) == 0 && y_aligned16;
     return p;
   }
+  p.schedule = Schedule::LeftLooking;
   p.colpair = column_pairs != 0 && !f64 && !tp && !packed && B >= pair_min_batch;
   p.zskip = !f64 && !tp && !packed && use_hb && hbp->l_mask != nullptr && (!sched || sched->skip_zero_blocks != 0);
   return p;
 }
 
+struct Half { hipStream_t s; int b0, nb; };   // some of the batch on one stream: problems [b0, b0 + nb)
+
+// ONE FACTORISATION BEING ENQUEUED: the call's arguments, its plan and what every schedule derives from them, with the launches
+// the schedules share as members.  Built by factor_impl under g_launch_mutex; the four run_* functions below hold the schedules.
+template <typename T>
+struct FactorLaunch {
+  const void* H; int64_t ld; int n, B; const void* damping; int ellipsoidal; double eps;   // (factor_impl's arguments)
+  void* L; void* panel; int32_t* info; const void* rhs; void* y; int64_t ldv; hipStream_t st;
+  const thx_tile_pattern* tp; const thx_level_schedule* ls;
+  FactorPlan P;
+  TilePat pat;
+  bool use_hb;
+  HBlk hb;                    // (l_mask only with P.zskip: under every other schedule, and with skipping switched off, the kernels see no mask)
+  bool packed;                // ld == 0: L is the TILE-PACKED factor (B, nslots, TILE, TILE) of the pattern
+  int64_t hstride, lstride;   // elements per problem: the H frame (dense H only; never packed), L
+  size_t dsm;                 // dynamic LDS of the diagonal phase P.fused_diag selects, with the whole y buffer if there is a rhs
+  int dev; DeviceLaunchState& ds;   // current_device() and its launch_state
+
+  // the half's first problem in L, in the panels and in the dense H frame (block-compact H: the half's problems start at h.b0 of the
+  // block list; H itself is not dereferenced)
+  T* L_of(const Half& h) const { return (T*)L + (int64_t)h.b0 * lstride; }
+  T* panel_of(const Half& h) const { return (T*)panel + (int64_t)h.b0 * P.ntiles * TILE * TILE; }
+  const T* H_of(const Half& h) const { return use_hb ? nullptr : (const T*)H + (int64_t)h.b0 * hstride; }
+  HBlk hb_of(const Half& h) const {
+    HBlk x = hb;
+    if (use_hb) x.blocks = static_cast<const T*>(hb.blocks) + (int64_t)h.b0 * hb.bstride;
+    return x;
+  }
+
+  // row tiles [i_first, i_first + nrt) of block column j (tile-sparse / levels: entries of the pattern), one workgroup each
+  void off(const Half& h, int j, int i_first, int nrt) const {
+    const int ntiles = P.ntiles, Bpad = (h.nb + 7) / 8 * 8;
+    with_hb_mode(P.hbm, [&](auto mode) {
+      constexpr int M = decltype(mode)::value;
+      if constexpr (sizeof(T) == 4) {
+        launch_lds<chol_offdiag_f32_kernel<M>>(dev, dim3(Bpad * nrt), dim3(256), OFF32_SMEM, h.s, H_of(h), L_of(h), panel_of(h), n, ld, j,
+                                               ntiles, i_first, nrt, h.nb, pat, hb_of(h));
+      } else {
+        if constexpr (M != HB_MODE_ROUNDS) {
+          if (!tp && !packed && j < P.f64_half_max) {   // (half tiles, four workgroups per CU, for the short K-loops)
+            launch_lds<chol_offdiag_f64h_kernel<M>>(dev, dim3(Bpad * nrt * 2), dim3(256), OFF64_STAGE, h.s, H_of(h), L_of(h), panel_of(h),
+                                                    n, ld, j, ntiles, i_first, nrt, h.nb, pat, hb_of(h));
+            return;
+          }
+          if (!tp && j < P.f64_wide_max) {   // (dense schedule: column j's K-loops are j tiles long)
+            launch_lds<chol_offdiag_f64w8_kernel<M>>(dev, dim3(Bpad * nrt), dim3(512), OFF64_SMEM, h.s, H_of(h), L_of(h), panel_of(h), n,
+                                                     ld, j, ntiles, i_first, nrt, h.nb, pat, hb_of(h));
+            return;
+          }
+        }
+        launch_lds<chol_offdiag_f64_kernel<M>>(dev, dim3(Bpad * nrt), dim3(256), OFF64_SMEM, h.s, H_of(h), L_of(h), panel_of(h), n, ld, j,
+                                               ntiles, i_first, nrt, h.nb, pat, hb_of(h));
+      }
+    });
+  }
+
+  // tiles (i, j) and (i, j + 1) of row tiles [i_first, i_first + nrt) in one workgroup each (chol_offdiag2_f32_kernel)
+  void pair(const Half& h, int j, int i_first, int nrt) const {
+    if constexpr (sizeof(T) == 4)
+      with_hb_mode(P.hbm, [&](auto mode) {
+        launch_lds<chol_offdiag2_f32_kernel<decltype(mode)::value>>(dev, dim3((h.nb + 7) / 8 * 8 * nrt), dim3(256), OFF2_SMEM, h.s, H_of(h),
+                                                                    L_of(h), panel_of(h), n, ld, j, P.ntiles, i_first, nrt, h.nb, hb_of(h));
+      });
+  }
+
+  // the diagonal phase of block column j (nc > 1: the level schedule -- block columns [j, j + nc) in one launch, blockIdx.y the
+  // column; `fused` / `smem`: which of the two diagonal schedules this launch takes, see FactorPlan.fused_diag)
+  void diag(const Half& h, int j, int nc, bool fused, size_t smem) const {
+    const int ntiles = P.ntiles;
+    const T* rh = rhs ? (const T*)rhs + (int64_t)h.b0 * ldv : nullptr;
+    T* yh = y ? (T*)y + (int64_t)h.b0 * ldv : nullptr;
+    const T* dh = damping ? (const T*)damping + h.b0 : nullptr;
+    with_bool(use_hb, [&](auto hbk) {
+      constexpr bool HB = decltype(hbk)::value;
+      if (fused)
+        launch_lds<chol_diag_kernel<T, HB>>(dev, dim3(h.nb, nc), dim3(256), smem, h.s, H_of(h), L_of(h), panel_of(h), dh, ellipsoidal, (T)eps,
+                                            info + h.b0, n, ld, j, ntiles, rh, yh, ldv, pat, hb_of(h));
+      else
+        launch_lds<chol_syrk_kernel<T, HB>>(dev, dim3(h.nb, nc), dim3(256), smem, h.s, H_of(h), L_of(h), dh, ellipsoidal, (T)eps, n, ld, j, rh,
+                                            yh, ldv, pat, hb_of(h));
+    });
+    if (!fused) {
+      const int64_t tile_off = packed ? (int64_t)j * TILE * TILE : (int64_t)j * TILE * ld + (int64_t)j * TILE;
+      hipLaunchKernelGGL(chol_potrf_kernel<T>, dim3(h.nb, nc), dim3(64), 0, h.s, L_of(h), panel_of(h), info + h.b0, n, lstride,
+                         tile_off, packed ? (int64_t)TILE : ld, j, ntiles, rh ? yh : nullptr, ldv, pat.tile_valid);
+    }
+  }
+  void diag(const Half& h, int j) const { diag(h, j, 1, P.fused_diag, dsm); }
+};
+
+// LEVEL SCHEDULE (thx_chol_factor_levels): the block columns of one elimination-tree level do not depend on each other (a column
+// needs, of the earlier columns, only those in which its own row panel is non-zero: its descendants in the tree) and the host
+// numbered the columns level by level -- so: ONE diagonal launch and ONE off-diagonal launch per level, B x (columns of the
+// level) and B x (entries of the level) workgroups.  A banded ordering's chain of ntiles dependent launch pairs becomes
+// ~log2(ntiles) of them under a nested-dissection ordering (theseus_amd/sparse.py:LevelPattern).
+template <typename T>
+static int run_levels(const FactorLaunch<T>& c) {
+  const thx_level_schedule* ls = c.ls;
+  const Half h{c.st, 0, c.B};
+  for (int l = 0; l < ls->nlevels; ++l) {
+    const int j0 = ls->level_col_host[l], nc = ls->level_col_host[l + 1] - j0;
+    const int e0 = ls->level_ent_host[l], ne = ls->level_ent_host[l + 1] - e0;
+    if (nc <= 0) continue;
+    // with the fused forward substitution a column keeps only its K-list's blocks of y in LDS: the launch of level l is sized for
+    // the longest K-list of that level (level_maxk_host)
+    const int yp = c.rhs ? ls->level_maxk_host[l] * TILE : 0;
+    const bool fused = (int64_t)c.B * nc < c.P.split_diag_min;   // (both diagonal schedules may be taken, level by level)
+    c.diag(h, j0, nc, fused, fused ? DiagSmem<T>::bytes(yp) : SyrkSmem<T>::bytes(yp));
+    if (ne > 0) c.off(h, j0, e0, ne);
+  }
+  return check_launch("thx_chol_factor_levels");
+}
+
+// LOOK-AHEAD for batches that do not fill the chip (one part, i.e. B < SPLIT_MIN).
+// Left-looking: tile (i, j) needs rows i and j of the columns before j.  So the diagonal phase of column j + 1 needs, of column
+// j, only tile (j + 1, j) -- and at batch 256 that phase is B workgroups with one busy wave each (80 us on a 3072-column banded
+// system, 24 times).  Column j's off-diagonal launch is therefore split: HEAD = tile (j + 1, j) on the caller's stream, followed
+// at once by diag(j + 1); REST = the other row tiles on the auxiliary stream, concurrent with both.  Dependencies:
+//   REST(j)  after diag(j)                     (event ev_diag; the earlier HEADs precede diag(j) on the caller's stream)
+//   HEAD(j)  after diag(j) and REST(j - 1)     (row j + 1 of column j - 1 is a REST tile: event ev_rest)
+//   diag(j+1) after HEAD(j) [stream order] -- its other inputs, rows j + 1 of columns < j, were waited for by HEAD(j).
+// Tile-sparse: only if the host put tile (j + 1, j) FIRST in column j's entry list (col_head_host); otherwise the column runs
+// as before (diag(j + 1) waits for all of column j).  Same kernels, same arithmetic: bit-identical results.
+// Measured (profiles/r4/c_ab_lookahead_small_batch_factor.txt, same box, two rounds): the banded reduced camera system of the
+// bundle-adjustment config (3072 columns, batch 256, 158 of 300 tiles) 6.82 -> 6.60 ms; DENSE frames do not gain (n = 1536:
+// batch 256 3.5 ms either way, batch 512 6.2 -> 6.4 ms; n = 3072 batch 256 21.6 -> 21.8 ms: REST(j) of a dense column is most
+// of the launch, the dispatcher does not run the two queues side by side) -- so: tile-sparse only.  (Nor between the right-looking
+// schedule's batches and 256 problems, profiles/r6/ai_: batch 64 1.66 -> 1.88 ms, 128 2.18 -> 2.22, 256 3.16 -> 3.27 -- the
+// whole off-diagonal launch is one round of workgroups there, HEAD(j) alone takes as long.)
+template <typename T>
+static int run_lookahead(const FactorLaunch<T>& c) {
+  const thx_tile_pattern* tp = c.tp;
+  DeviceLaunchState& ds = c.ds;
+  ds.need_aux();
+  const Half h0{c.st, 0, c.B}, h1{ds.aux, 0, c.B};
+  hipEventRecord(ds.ev_fork, c.st);
+  hipStreamWaitEvent(h1.s, ds.ev_fork, 0);
+  bool rest_pending = false;   // a REST launch whose completion the caller's stream has not waited for yet
+  for (int j = 0; j < c.P.ntiles; ++j) {
+    c.diag(h0, j);
+    const int nrt = tp->col_count_host[j];
+    if (nrt <= 0) continue;
+    const bool head = tp->col_head_host[j] != 0;   // the launch's first tile is (j + 1, j)
+    const int n_head = head ? 1 : 0, n_rest = nrt - n_head;
+    if (n_rest > 0) {
+      hipEventRecord(ds.ev_diag, h0.s);
+      hipStreamWaitEvent(h1.s, ds.ev_diag, 0);
+    }
+    if (rest_pending) {   // HEAD(j) / the next diagonal phase read REST(j - 1)'s tiles
+      hipStreamWaitEvent(h0.s, ds.ev_rest, 0);
+      rest_pending = false;
+    }
+    if (n_head) c.off(h0, j, 0, 1);
+    if (n_rest > 0) {
+      c.off(h1, j, n_head, n_rest);
+      hipEventRecord(ds.ev_rest, h1.s);
+      rest_pending = true;
+      if (!head) {   // no look-ahead for this column: diag(j + 1) needs a tile of this launch
+        hipStreamWaitEvent(h0.s, ds.ev_rest, 0);
+        rest_pending = false;
+      }
+    }
+  }
+  if (rest_pending) hipStreamWaitEvent(c.st, ds.ev_rest, 0);
+  return check_launch("thx_chol_factor");
+}
+
+// RIGHT-LOOKING SCHEDULE for SMALL dense batches (dense L frame without a tile pattern, whole tiles inside the frame, up to
+// thx_chol_schedule.right_looking_max_batch problems).  Left-looking, block column j is two dependent launches whose workgroups
+// walk K-loops of j tiles -- the diagonal one with ONE workgroup per problem: at 8 ... 64 problems the chip is 3 ... 25 % occupied
+// and a factorisation is the sum of those serial K-loops (n = 1536, batch 8: 1.62 ms, 0.04 of the MFMA peak).  Here every tile
+// product is its own workgroup: per block column  chol_diag (the tile factorisation alone) -> chol_offdiag as the substitution
+// alone, B (ntiles - 1 - j) tiles -> chol_offdiag as the trailing update, B m (m + 1) / 2 tiles each receiving ONE product; the
+// working matrix lives in the L frame (first touched by column 0's update, which reads H), the damping of the later diagonal
+// tiles is added once after that update.  Same tile kernels, another summation order: the factor differs from the left-looking
+// one in the last bits (tests: against LAPACK and against the left-looking solution).  The forward substitution runs as its
+// own kernel afterwards.
+// (c by value: with the forward substitution fused, y starts as a copy of g and from then on is the kernels' rhs -- c.rhs = y;
+// without it the caller runs the forward substitution on the ORIGINAL rhs afterwards, FACTOR_NEEDS_FORWARD)
+template <typename T>
+static int run_right_looking(FactorLaunch<T> c) {
+  DeviceLaunchState& ds = c.ds;
+  const hipStream_t st = c.st;
+  const int n = c.n, B = c.B, ntiles = c.P.ntiles, hbm = c.P.hbm, dev = c.dev, Bpad = (B + 7) / 8 * 8;
+  const int64_t ld = c.ld, ldv = c.ldv;
+  const bool use_hb = c.use_hb;
+  const HBlk& hb = c.hb;
+  const TilePat& pat = c.pat;
+    // forward substitution riding on the schedule (vectors with 16-byte rows; else its own kernel afterwards, FACTOR_NEEDS_FORWARD): y starts
+    // as a copy of g; chol_diag(j) turns block j into y_j in place, the substitution tiles of column j update the blocks below
+  const bool fwd_fused = c.P.rl_fwd_fused;
+  if (fwd_fused) {
+    hipMemcpy2DAsync(c.y, (size_t)ldv * sizeof(T), c.rhs, (size_t)ldv * sizeof(T), (size_t)n * sizeof(T), (size_t)B, hipMemcpyDeviceToDevice, st);
+    c.rhs = c.y;
+  }
+  TilePat p0 = pat, p1 = pat;
+  p1.rl = 1;
+  if (fwd_fused) {
+    p0.rl_y = p1.rl_y = c.y;
+    p0.rl_ldv = p1.rl_ldv = ldv;
+  }
+  const HBlk nohb{nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0};
+  const T* H = (const T*)c.H;
+  T *L = (T*)c.L, *panel = (T*)c.panel;
+  const T* Lc = L;
+  const T* yc = fwd_fused ? (const T*)c.y : nullptr;
+  T* yw = fwd_fused ? (T*)c.y : nullptr;
+  // (the later columns run the dense-frame instance of chol_diag on the L frame whatever H is)
+  const size_t dsm_rl = fwd_fused ? c.dsm : DiagSmem<T>::bytes(0);
+  // one chol_offdiag launch: nrt workgroup slots per problem (row tiles / update tiles), H from the block list, the dense H
+  // frame or the L frame.  Not FactorLaunch::off: unsplit, the RL instance in fp64, never the half-tile / eight-wave kernels.
+  auto off = [&](bool hbsrc, const T* Hsrc, int jarg, int i_first, int nrt, const TilePat& pp, hipStream_t so = nullptr) {
+    if (!so) so = st;
+    with_hb_mode(hbsrc ? hbm : 0, [&](auto mode) {
+      constexpr int M = decltype(mode)::value;
+      if constexpr (sizeof(T) == 4)
+        launch_lds<chol_offdiag_f32_kernel<M>>(dev, dim3(Bpad * nrt), dim3(256), OFF32_SMEM, so, (const float*)(M ? nullptr : Hsrc),
+                                               (float*)L, (const float*)panel, n, ld, jarg, ntiles, i_first, nrt, B, pp, M ? hb : nohb);
+      else
+        launch_lds<chol_offdiag_f64_kernel<M, true>>(dev, dim3(Bpad * nrt), dim3(256), OFF64_SMEM, so,
+                                                     (const double*)(M ? nullptr : Hsrc), (double*)L, (const double*)panel, n, ld, jarg,
+                                                     ntiles, i_first, nrt, B, pp, M ? hb : nohb);
+    });
+  };
+  auto upd = [&](int jc, bool first) {
+    const int m = ntiles - 1 - jc;
+    TilePat pu = pat;
+    pu.rl = 2 + jc;
+    off(first && use_hb, first ? H : Lc, jc, 0, m * (m + 1) / 2, pu);
+  };
+  auto damp = [&](int d0) {   // the damping of the diagonal elements d >= d0, once the first trailing update has written them
+    if (c.damping && n > d0)
+      hipLaunchKernelGGL(rl_damp_kernel<T>, dim3((n - d0 + 255) / 256, B), dim3(256), 0, st, L, ld, H, ld, hb, (const T*)c.damping,
+                         c.ellipsoidal, (T)c.eps, d0, n);
+  };
+  const int la = c.P.rl_mode;
+  // block column 0: the kernels as they are (no earlier columns), reading H
+  c.diag(Half{st, 0, B}, 0, 1, true, c.dsm);   // (with a right-hand side: y_0 = W_00 g_0 -- kept when the forward substitution is fused)
+  off(use_hb, H, 0, 1, ntiles - 1, p0);
+  int jstart = 1;
+  if (la == 1) {
+      // (mode 1) block column 1 the same way, straight from H: chol_diag(1) and the substitution tiles (i, 1) read their tile of H
+      // (block list or dense frame; the diagonal tile with its damping) and take column 0's update through the one-tile K-loop;
+      // column 0's update of the tiles right of column 1 -- which moves H into the L frame -- rides with the substitutions.
+      // (The plain schedule's update(0) is 66 tiles per problem at 12 block columns: 528 workgroups at batch 8, 16 more than one round.)
+    TilePat pd1 = p0;
+    pd1.rl = 1;
+    pd1.rl_la = 1;
+    with_bool(use_hb, [&](auto hbk) {
+      constexpr bool HB = decltype(hbk)::value;
+      launch_lds<chol_diag_kernel<T, HB>>(dev, dim3(B, 1), dim3(256), dsm_rl, st, HB ? (const T*)nullptr : H, L, panel,
+                                          (const T*)c.damping, c.ellipsoidal, (T)c.eps, c.info, n, ld, 1, ntiles, yc, yw, ldv, pd1,
+                                          HB ? hb : nohb);
+    });
+    const int nsub = ntiles - 2;
+    TilePat pc1 = pd1;
+    pc1.rl_nsub = nsub;
+    off(use_hb, H, 1, 2, nsub + nsub * (nsub + 1) / 2, pc1);
+    damp(2 * TILE);
+    jstart = 2;
+  } else {
+    upd(0, true);
+    damp(TILE);
+  }
+    // MODE 1, TWO LAUNCHES PER BLOCK COLUMN (TilePat.rl_la / rl_nsub; fp32's default; mode 0: the three launches of the plain schedule).
+    // The chain per column was diag -> substitutions -> trailing update, although the next diagonal phase and the next
+    // substitutions need only ONE block column of that update.  From block column 2 on every tile of column j takes column
+    // j - 1's update ITSELF -- chol_diag(j) and the substitution tiles (i, j) run a K-loop over the one tile of column j - 1, the
+    // left-looking kernels' own path -- and the rest of that update (tiles (i, k), j < k <= i: needed from column j + 1 on) rides
+    // in the SAME chol_offdiag launch as column j's substitutions, as extra workgroup slots:
+    //   diag(j) [own update]  ->  { substitutions (i, j) [own update]  +  update of column j - 1 on the tiles right of column j }
+    // No second stream, no events.  Another summation order for the tiles' last update (one K-loop product added before the
+    // substitution instead of a read-modify-write before it): to rounding, as the schedule itself.
+    // MODE 2, the second stream (fp64's default): only chol_diag(j) takes its own update; update(j - 1) is launched without tile
+    // (j, j) (first slot skipped) on the library's second stream and runs BESIDE diag(j); the substitutions of column j wait for
+    // both.  Hides the whole update instead of the part the substitutions cover, for two event hops per column.
+    // MEASURED (profiles/r6/ao_, n = 1536, factor + forward, plain / mode 1 / mode 2): fp32 batch 8 0.742 / 0.724 / 0.756 ms, 16:
+    // 0.856 / 0.828 / 0.855, 32: 1.10 / 1.05 / 1.08; fp64 batch 8 1.53 / 1.42 / 1.34, 16: 1.77 / 1.66 / 1.60, 32: 2.41 / 2.28 / 2.19
+    // -- an fp32 update launch is as short as the event hops, an fp64 one twice as long.  thx_chol_schedule.right_looking_mode forces
+    // a mode.
+  hipStream_t sa = st;
+  if (la == 2) {
+    ds.need_aux();
+    sa = ds.aux;
+  }
+  TilePat pd = p1;
+  pd.rl_la = 1;
+  bool upd_pending = false;   // (mode 2) an update launch on the second stream that the caller's stream has not waited for yet
+  for (int j = jstart; j < ntiles; ++j) {
+    launch_lds<chol_diag_kernel<T, false>>(dev, dim3(B, 1), dim3(256), dsm_rl, st, Lc, L, panel, (const T*)nullptr, 0, T(0), c.info, n,
+                                           ld, j, ntiles, yc, yw, ldv, (la && j >= 2) ? pd : p1, nohb);
+    if (j + 1 == ntiles) break;
+    if (la == 0) {
+      off(false, Lc, j, j + 1, ntiles - 1 - j, p1);
+      upd(j, false);
+    } else if (la == 1) {   // (from column 2 on: column 1 ran straight from H above)
+      const int nsub = ntiles - 1 - j;
+      TilePat pc = pd;
+      pc.rl_nsub = nsub;
+      off(false, Lc, j, j + 1, nsub + nsub * (nsub + 1) / 2, pc);
+    } else {
+      if (upd_pending) {   // the substitutions read the tiles update(j - 1) wrote
+        hipStreamWaitEvent(st, ds.ev_rest, 0);
+        upd_pending = false;
+      }
+      off(false, Lc, j, j + 1, ntiles - 1 - j, p1);
+      const int m = ntiles - 1 - j, nslots = m * (m + 1) / 2 - 1;   // (slot 0 = tile (j + 1, j + 1): left to diag(j + 1))
+      if (nslots > 0) {
+        hipEventRecord(ds.ev_diag, st);
+        hipStreamWaitEvent(sa, ds.ev_diag, 0);
+        TilePat pu = pat;
+        pu.rl = 2 + j;
+        off(false, Lc, j, 1, nslots, pu, sa);
+        hipEventRecord(ds.ev_rest, sa);
+        upd_pending = true;
+      }
+    }
+  }
+  if (upd_pending) hipStreamWaitEvent(st, ds.ev_rest, 0);
+  if (int r = check_launch("thx_chol_factor (right-looking)")) return r;
+  return (c.rhs && !fwd_fused) ? FACTOR_NEEDS_FORWARD : 0;   // (the caller runs the forward substitution as its own kernel)
+}
+
+// LEFT-LOOKING, column by column: plain, in column pairs (P.colpair, see plan_factor) and, from SPLIT_MIN problems on, two streams:
+// One half of the batch per stream, the second half one diagonal phase behind the first: the latency-bound serial part
+// of chol_diag (one wave per workgroup busy, §4.1) and the tail of every launch of one half run underneath the MFMA-bound
+// chol_offdiag of the other half.  The halves touch disjoint memory; the auxiliary stream forks from / joins the
+// caller's stream through events.  (Overlapping diag(j+1) with the rest of column j of the SAME problems had gained
+// nothing: column j+1 needs all of column j, so there is no slack to fill.)
+template <typename T>
+static int run_left_looking(const FactorLaunch<T>& c) {
+  const thx_tile_pattern* tp = c.tp;
+  DeviceLaunchState& ds = c.ds;
+  const int B = c.B, ntiles = c.P.ntiles;
+  const bool split = c.P.split;
+  Half halves[2] = {{c.st, 0, B}, {c.st, 0, 0}};
+  if (split) {
+    ds.need_aux();
+    const int per = min((B / 2 + 7) / 8 * 8, B);  // (multiple of 8: the XCD-aware block map of chol_offdiag)
+    halves[0] = {c.st, 0, per};
+    halves[1] = {ds.aux, per, B - per};
+    hipEventRecord(ds.ev_fork, c.st);
+    hipStreamWaitEvent(ds.aux, ds.ev_fork, 0);
+  }
+  for (int j = 0; j < ntiles;) {
+    const bool pair = c.P.colpair && j + 2 < ntiles;
+    for (int k = 0; k < c.P.nparts; ++k) {
+      const Half& h = halves[k];
+      if (h.nb <= 0) continue;
+      if (split && k == 1 && j == 0) hipStreamWaitEvent(h.s, ds.ev_lag, 0);  // half 1: one diagonal phase behind half 0
+      c.diag(h, j);
+      if (split && k == 0 && j == 0) hipEventRecord(ds.ev_lag, h.s);
+      if (pair) {
+        c.off(h, j, j + 1, 1);
+        c.diag(h, j + 1);
+        c.pair(h, j, j + 2, ntiles - 2 - j);
+        continue;
+      }
+      const int nrt = tp ? tp->col_count_host[j] : ntiles - 1 - j;   // (tile-sparse: the column's non-zero row tiles)
+      if (nrt > 0) c.off(h, j, tp ? 0 : j + 1, nrt);
+    }
+    j += pair ? 2 : 1;
+  }
+  if (split) {
+    hipEventRecord(ds.ev_join, ds.aux);
+    hipStreamWaitEvent(c.st, ds.ev_join, 0);
+  }
+  return check_launch("thx_chol_factor");
+}
+
+// Checks what the kernels cannot, plans, and enqueues the plan's schedule -- holding g_launch_mutex for the whole enqueue (the
+// auxiliary stream / events and the LDS limits are shared).  Nothing below may call solve_impl, which takes the lock itself.
 template <typename T>
 static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damping, int ellipsoidal, double eps,
                        void* L, void* panel, int32_t* info, const void* rhs, void* y, int64_t ldv, hipStream_t st,
                        const thx_tile_pattern* tp = nullptr, const HBlk* hbp = nullptr, const thx_level_schedule* ls = nullptr,
                        const thx_chol_schedule* sched = nullptr) {
   const bool use_hb = hbp != nullptr;
+  const bool packed = ld == 0;   // L is the TILE-PACKED factor (B, nslots, TILE, TILE) of the pattern
   const FactorPlan P = plan_factor(sizeof(T) == 8, n, ld, B, damping != nullptr, rhs != nullptr, ldv,
                                    (reinterpret_cast<uintptr_t>(y) % 16) == 0, tp, hbp, ls, sched);
-  HBlk hb = use_hb ? *hbp : HBlk{nullptr, 0, 0, nullptr, nullptr, nullptr};
-  if (!P.zskip) hb.l_mask = nullptr;   // (every other schedule, and skipping switched off: the kernels see no mask)
-  const int f64_wide_max = P.f64_wide_max, f64_half_max = P.f64_half_max;
   const int ntiles = P.ntiles;
-  TilePat pat{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr};
-  // ld == 0: L is the TILE-PACKED factor (B, nslots, TILE, TILE) of the pattern
-  const bool packed = ld == 0;
   if (packed && (!tp || tp->nslots <= 0 || !tp->tile_sa || !tp->tile_sb || !tp->diag_s))
     return fail("thx_chol_factor: a tile-packed factor (ld = 0) needs a tile pattern with slot tables");
-  if (tp) {
-    if (tp->ntiles != ntiles) return fail("thx_chol_factor_sparse: the tile pattern was built for another matrix order");
-    pat = TilePat{tp->col_ptr, tp->col_row, tp->tile_kptr, tp->tile_k, tp->diag_kptr, tp->diag_k,
-                  packed ? tp->tile_sa : nullptr, packed ? tp->tile_sb : nullptr, packed ? tp->diag_s : nullptr,
-                  packed ? tp->nslots : 0, 0, ls ? ls->ent_col : nullptr, ls ? ls->tile_valid : nullptr};
-  }
-  const int64_t hstride = (int64_t)ld * ld;                                            // H frame (dense H only; never packed)
-  const int64_t lstride = packed ? (int64_t)tp->nslots * TILE * TILE : (int64_t)ld * ld;   // elements of L per problem
+  if (tp && tp->ntiles != ntiles) return fail("thx_chol_factor_sparse: the tile pattern was built for another matrix order");
+  const int64_t lstride = packed ? (int64_t)tp->nslots * TILE * TILE : (int64_t)ld * ld;
   if (packed && lstride * (int64_t)sizeof(T) > 0x7fffffffLL)
     return fail("thx_chol_factor: tile-packed factor larger than 2 GB per problem");
-  const int split_diag_min = P.split_diag_min;
-  const bool fused_diag = P.fused_diag;
-  const size_t dsm = fused_diag ? DiagSmem<T>::bytes(rhs ? ntiles * TILE : 0) : SyrkSmem<T>::bytes(rhs ? ntiles * TILE : 0);
+  const size_t dsm = P.fused_diag ? DiagSmem<T>::bytes(rhs ? ntiles * TILE : 0) : SyrkSmem<T>::bytes(rhs ? ntiles * TILE : 0);
   if (dsm > LDS_LIMIT) return fail("thx_chol_factor: n too large for the fused forward substitution (LDS)");
   if (ls && (!packed || !use_hb)) return fail("thx_chol_factor_levels: tile-packed factor + block-compact H");
-  // level schedule + fused forward substitution: a column keeps only its K-list's blocks of y in LDS -- the launch of level l is
-  // sized for the longest K-list of that level (level_maxk_host)
-  size_t ls_smem_max = 0;
-  if (ls) {
+  if (ls && rhs)   // (run_levels sizes the launch of level l for the longest K-list of that level)
     for (int l = 0; l < ls->nlevels; ++l) {
-      const int yp = rhs ? ls->level_maxk_host[l] * TILE : 0;
-      ls_smem_max = std::max(ls_smem_max, std::max(DiagSmem<T>::bytes(yp), SyrkSmem<T>::bytes(yp)));
+      const int yp = ls->level_maxk_host[l] * TILE;
+      if (std::max(DiagSmem<T>::bytes(yp), SyrkSmem<T>::bytes(yp)) > LDS_LIMIT)
+        return fail("thx_chol_factor_levels: K-list too long for the fused forward substitution (LDS)");
     }
-    if (ls_smem_max > LDS_LIMIT) return fail("thx_chol_factor_levels: K-list too long for the fused forward substitution (LDS)");
-  }
-  std::lock_guard<std::mutex> guard(g_launch_mutex);   // (the whole enqueue: the auxiliary stream / events are shared)
-  DeviceLaunchState& ds = launch_state();
-  constexpr int ti = sizeof(T) == 8;
-  if (ls) {   // (both diagonal schedules may be taken, level by level; no y buffer: well below the default limit, raised anyway)
-    const size_t d0 = ls_smem_max, s0 = ls_smem_max;
-    if (d0 > ds.attr_diag[ti][1]) {
-      hipFuncSetAttribute(reinterpret_cast<const void*>(chol_diag_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)d0);
-      ds.attr_diag[ti][1] = d0;
-    }
-    if (s0 > ds.attr_syrk[ti][1]) {
-      hipFuncSetAttribute(reinterpret_cast<const void*>(chol_syrk_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s0);
-      ds.attr_syrk[ti][1] = s0;
-    }
-  }
-  if (fused_diag && dsm > ds.attr_diag[ti][use_hb]) {
-    hipFuncSetAttribute(use_hb ? reinterpret_cast<const void*>(chol_diag_kernel<T, true>)
-                               : reinterpret_cast<const void*>(chol_diag_kernel<T, false>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)dsm);
-    ds.attr_diag[ti][use_hb] = dsm;
-  }
-  if (!fused_diag && dsm > ds.attr_syrk[ti][use_hb]) {
-    hipFuncSetAttribute(use_hb ? reinterpret_cast<const void*>(chol_syrk_kernel<T, true>)
-                               : reinterpret_cast<const void*>(chol_syrk_kernel<T, false>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)dsm);
-    ds.attr_syrk[ti][use_hb] = dsm;
-  }
-  if (!ds.attr_off) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag_f32_kernel<0>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, OFF32_SMEM);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag_f32_kernel<1>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, OFF32_SMEM);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag_f32_kernel<2>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, OFF32_SMEM);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag2_f32_kernel<0>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, OFF2_SMEM);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag2_f32_kernel<1>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, OFF2_SMEM);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag2_f32_kernel<2>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, OFF2_SMEM);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag_f64_kernel<0>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, OFF64_SMEM);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag_f64_kernel<1>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, OFF64_SMEM);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag_f64_kernel<2>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, OFF64_SMEM);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag_f64_kernel<0, true>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, OFF64_SMEM);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag_f64_kernel<1, true>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, OFF64_SMEM);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag_f64_kernel<2, true>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, OFF64_SMEM);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag_f64h_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                        OFF64_STAGE);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag_f64h_kernel<HB_MODE_SCATTER>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, OFF64_STAGE);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag_f64w8_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                        OFF64_SMEM);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(chol_offdiag_f64w8_kernel<HB_MODE_SCATTER>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, OFF64_SMEM);
-    ds.attr_off = true;
-  }
+  // (lpt: the level's / column's entries are sorted longest K-list first; consecutive workgroups = the problems of one entry)
+  const int lpt = (P.schedule == Schedule::Levels || P.schedule == Schedule::LookAhead) ? 1 : 0;
+  TilePat pat{};
+  if (tp)
+    pat = TilePat{tp->col_ptr, tp->col_row, tp->tile_kptr, tp->tile_k, tp->diag_kptr, tp->diag_k,
+                  packed ? tp->tile_sa : nullptr, packed ? tp->tile_sb : nullptr, packed ? tp->diag_s : nullptr,
+                  packed ? tp->nslots : 0, lpt, ls ? ls->ent_col : nullptr, ls ? ls->tile_valid : nullptr};
+  HBlk hb = use_hb ? *hbp : HBlk{};
+  if (!P.zskip) hb.l_mask = nullptr;
+  std::lock_guard<std::mutex> guard(g_launch_mutex);
+  const int dev = current_device();
+  const FactorLaunch<T> c{H, ld, n, B, damping, ellipsoidal, eps, L, panel, info, rhs, y, ldv, st, tp, ls, P, pat, use_hb, hb, packed,
+                          (int64_t)ld * ld, lstride, dsm, dev, launch_state(dev)};
   hipMemsetAsync(info, 0, sizeof(int32_t) * (size_t)B, st);
-  // One half of the batch per stream, the second half one diagonal phase behind the first: the latency-bound serial part
-  // of chol_diag (one wave per workgroup busy, §4.1) and the tail of every launch of one half run underneath the MFMA-bound
-  // chol_offdiag of the other half.  The halves touch disjoint memory; the auxiliary stream forks from / joins the
-  // caller's stream through events.  (Overlapping diag(j+1) with the rest of column j of the SAME problems had gained
-  // nothing: column j+1 needs all of column j, so there is no slack to fill.)
-  struct Half {
-    hipStream_t s;
-    int b0, nb;
-  };
-  const bool split = P.split;
-  const int nparts = P.nparts;
-  Half halves[2] = {{st, 0, B}, {st, 0, 0}};
-  if (split) {
-    ds.need_aux();
-    const int per = min((B / 2 + 7) / 8 * 8, B);  // (multiple of 8: the XCD-aware block map of chol_offdiag)
-    halves[0] = {st, 0, per};
-    halves[1] = {ds.aux, per, B - per};
-    hipEventRecord(ds.ev_fork, st);
-    hipStreamWaitEvent(ds.aux, ds.ev_fork, 0);
+  switch (P.schedule) {
+    case Schedule::Levels: return run_levels(c);
+    case Schedule::LookAhead: return run_lookahead(c);
+    case Schedule::RightLooking: return run_right_looking(c);
+    default: return run_left_looking(c);
   }
-  // (block-compact H: the half's problems start at h.b0 of the block list; H itself is not dereferenced)
-  auto hb_of = [&](const Half& h) {
-    HBlk x = hb;
-    if (use_hb) x.blocks = static_cast<const T*>(hb.blocks) + (int64_t)h.b0 * hb.bstride;
-    return x;
-  };
-  const int hbm = P.hbm;   // the off-diagonal kernels' HB template argument
-  auto launch_off = [&](const Half& h, int j, int i_first, int nrt) {
-    const int Bpad = (h.nb + 7) / 8 * 8;
-    const int64_t mo = (int64_t)h.b0 * lstride, po = (int64_t)h.b0 * ntiles * TILE * TILE;
-    const T* Hh = use_hb ? nullptr : (const T*)H + (int64_t)h.b0 * hstride;
-    auto go = [&](auto mode) {
-      constexpr int M = decltype(mode)::value;
-      if constexpr (sizeof(T) == 4) {
-        hipLaunchKernelGGL(chol_offdiag_f32_kernel<M>, dim3(Bpad * nrt), dim3(256), OFF32_SMEM, h.s, (const float*)Hh, (float*)L + mo,
-                           (const float*)panel + po, n, ld, j, ntiles, i_first, nrt, h.nb, pat, hb_of(h));
-      } else {
-        if constexpr (M != HB_MODE_ROUNDS) {
-          if (!tp && !packed && j < f64_half_max) {   // (half tiles, four workgroups per CU, for the short K-loops)
-            hipLaunchKernelGGL(chol_offdiag_f64h_kernel<M>, dim3(Bpad * nrt * 2), dim3(256), OFF64_STAGE, h.s, (const double*)Hh,
-                               (double*)L + mo, (const double*)panel + po, n, ld, j, ntiles, i_first, nrt, h.nb, pat, hb_of(h));
-            return;
-          }
-          if (!tp && j < f64_wide_max) {   // (dense schedule: column j's K-loops are j tiles long)
-            hipLaunchKernelGGL(chol_offdiag_f64w8_kernel<M>, dim3(Bpad * nrt), dim3(512), OFF64_SMEM, h.s, (const double*)Hh,
-                               (double*)L + mo, (const double*)panel + po, n, ld, j, ntiles, i_first, nrt, h.nb, pat, hb_of(h));
-            return;
-          }
-        }
-        hipLaunchKernelGGL(chol_offdiag_f64_kernel<M>, dim3(Bpad * nrt), dim3(256), OFF64_SMEM, h.s, (const double*)Hh, (double*)L + mo,
-                           (const double*)panel + po, n, ld, j, ntiles, i_first, nrt, h.nb, pat, hb_of(h));
-      }
-    };
-    if (hbm == 0) go(std::integral_constant<int, 0>{});
-    else if (hbm == HB_MODE_SCATTER) go(std::integral_constant<int, HB_MODE_SCATTER>{});
-    else go(std::integral_constant<int, HB_MODE_ROUNDS>{});
-  };
-  // tiles (i, j) and (i, j + 1) of row tiles [i_first, i_first + nrt) in one workgroup each (chol_offdiag2_f32_kernel)
-  auto launch_pair = [&](const Half& h, int j, int i_first, int nrt) {
-    if constexpr (sizeof(T) == 4) {
-      const int Bpad = (h.nb + 7) / 8 * 8;
-      const int64_t mo = (int64_t)h.b0 * lstride, po = (int64_t)h.b0 * ntiles * TILE * TILE;
-      const float* Hh = use_hb ? nullptr : (const float*)H + (int64_t)h.b0 * hstride;
-      auto go = [&](auto mode) {
-        constexpr int M = decltype(mode)::value;
-        hipLaunchKernelGGL(chol_offdiag2_f32_kernel<M>, dim3(Bpad * nrt), dim3(256), OFF2_SMEM, h.s, Hh, (float*)L + mo,
-                           (const float*)panel + po, n, ld, j, ntiles, i_first, nrt, h.nb, hb_of(h));
-      };
-      if (hbm == 0) go(std::integral_constant<int, 0>{});
-      else if (hbm == HB_MODE_SCATTER) go(std::integral_constant<int, HB_MODE_SCATTER>{});
-      else go(std::integral_constant<int, HB_MODE_ROUNDS>{});
-    }
-  };
-  // (nc > 1: the level schedule -- block columns [j, j + nc) in one launch, blockIdx.y the column; `fused` / `smem`: which of the
-  //  two diagonal schedules this launch takes, see fused_diag)
-  auto launch_diag_n = [&](const Half& h, int j, int nc, bool fused, size_t smem) {
-    const int64_t mo = (int64_t)h.b0 * lstride, po = (int64_t)h.b0 * ntiles * TILE * TILE;
-    const T* rh = rhs ? (const T*)rhs + (int64_t)h.b0 * ldv : nullptr;
-    T* yh = y ? (T*)y + (int64_t)h.b0 * ldv : nullptr;
-    const T* dh = damping ? (const T*)damping + h.b0 : nullptr;
-    const T* Hh = use_hb ? nullptr : (const T*)H + (int64_t)h.b0 * hstride;
-    if (fused) {
-      if (use_hb)
-        hipLaunchKernelGGL((chol_diag_kernel<T, true>), dim3(h.nb, nc), dim3(256), smem, h.s, Hh, (T*)L + mo, (T*)panel + po,
-                           dh, ellipsoidal, (T)eps, info + h.b0, n, ld, j, ntiles, rh, yh, ldv, pat, hb_of(h));
-      else
-        hipLaunchKernelGGL((chol_diag_kernel<T, false>), dim3(h.nb, nc), dim3(256), smem, h.s, Hh, (T*)L + mo, (T*)panel + po,
-                           dh, ellipsoidal, (T)eps, info + h.b0, n, ld, j, ntiles, rh, yh, ldv, pat, hb_of(h));
-    } else {
-      if (use_hb)
-        hipLaunchKernelGGL((chol_syrk_kernel<T, true>), dim3(h.nb, nc), dim3(256), smem, h.s, Hh, (T*)L + mo, dh, ellipsoidal,
-                           (T)eps, n, ld, j, rh, yh, ldv, pat, hb_of(h));
-      else
-        hipLaunchKernelGGL((chol_syrk_kernel<T, false>), dim3(h.nb, nc), dim3(256), smem, h.s, Hh, (T*)L + mo, dh, ellipsoidal,
-                           (T)eps, n, ld, j, rh, yh, ldv, pat, hb_of(h));
-      const int64_t tile_off = packed ? (int64_t)j * TILE * TILE : (int64_t)j * TILE * ld + (int64_t)j * TILE;
-      hipLaunchKernelGGL(chol_potrf_kernel<T>, dim3(h.nb, nc), dim3(64), 0, h.s, (T*)L + mo, (T*)panel + po, info + h.b0, n, lstride,
-                         tile_off, packed ? (int64_t)TILE : ld, j, ntiles, rh ? yh : nullptr, ldv, pat.tile_valid);
-    }
-  };
-  auto launch_diag = [&](const Half& h, int j) { launch_diag_n(h, j, 1, fused_diag, dsm); };
-  // LEVEL SCHEDULE (thx_chol_factor_levels): the block columns of one elimination-tree level do not depend on each other (a column
-  // needs, of the earlier columns, only those in which its own row panel is non-zero: its descendants in the tree) and the host
-  // numbered the columns level by level -- so: ONE diagonal launch and ONE off-diagonal launch per level, B x (columns of the
-  // level) and B x (entries of the level) workgroups.  A banded ordering's chain of ntiles dependent launch pairs becomes
-  // ~log2(ntiles) of them under a nested-dissection ordering (theseus_amd/sparse.py:LevelPattern).
-  if (ls) {
-    pat.lpt = 1;   // (the level's entries are sorted longest K-list first; consecutive workgroups = the problems of one entry)
-    const Half h{st, 0, B};
-    for (int l = 0; l < ls->nlevels; ++l) {
-      const int j0 = ls->level_col_host[l], nc = ls->level_col_host[l + 1] - j0;
-      const int e0 = ls->level_ent_host[l], ne = ls->level_ent_host[l + 1] - e0;
-      if (nc <= 0) continue;
-      const int yp = rhs ? ls->level_maxk_host[l] * TILE : 0;
-      const bool fused = (int64_t)B * nc < split_diag_min;
-      launch_diag_n(h, j0, nc, fused, fused ? DiagSmem<T>::bytes(yp) : SyrkSmem<T>::bytes(yp));
-      if (ne > 0) launch_off(h, j0, e0, ne);
-    }
-    return check_launch("thx_chol_factor_levels");
-  }
-  // LOOK-AHEAD for batches that do not fill the chip (one part, i.e. B < SPLIT_MIN).
-  // Left-looking: tile (i, j) needs rows i and j of the columns before j.  So the diagonal phase of column j + 1 needs, of column
-  // j, only tile (j + 1, j) -- and at batch 256 that phase is B workgroups with one busy wave each (80 us on a 3072-column banded
-  // system, 24 times).  Column j's off-diagonal launch is therefore split: HEAD = tile (j + 1, j) on the caller's stream, followed
-  // at once by diag(j + 1); REST = the other row tiles on the auxiliary stream, concurrent with both.  Dependencies:
-  //   REST(j)  after diag(j)                     (event ev_diag; the earlier HEADs precede diag(j) on the caller's stream)
-  //   HEAD(j)  after diag(j) and REST(j - 1)     (row j + 1 of column j - 1 is a REST tile: event ev_rest)
-  //   diag(j+1) after HEAD(j) [stream order] -- its other inputs, rows j + 1 of columns < j, were waited for by HEAD(j).
-  // Tile-sparse: only if the host put tile (j + 1, j) FIRST in column j's entry list (col_head_host); otherwise the column runs
-  // as before (diag(j + 1) waits for all of column j).  Same kernels, same arithmetic: bit-identical results.
-  // Measured (profiles/r4/c_ab_lookahead_small_batch_factor.txt, same box, two rounds): the banded reduced camera system of the
-  // bundle-adjustment config (3072 columns, batch 256, 158 of 300 tiles) 6.82 -> 6.60 ms; DENSE frames do not gain (n = 1536:
-  // batch 256 3.5 ms either way, batch 512 6.2 -> 6.4 ms; n = 3072 batch 256 21.6 -> 21.8 ms: REST(j) of a dense column is most
-  // of the launch, the dispatcher does not run the two queues side by side) -- so: tile-sparse only.  (Nor between the right-looking
-  // schedule's batches and 256 problems, profiles/r6/ai_: batch 64 1.66 -> 1.88 ms, 128 2.18 -> 2.22, 256 3.16 -> 3.27 -- the
-  // whole off-diagonal launch is one round of workgroups there, HEAD(j) alone takes as long.)
-  const bool lookahead = P.lookahead;   // (tile-sparse: tp is set)
-  pat.lpt = lookahead ? 1 : 0;
-  if (lookahead) {
-    ds.need_aux();
-    const Half h0 = halves[0];
-    const Half h1 = {ds.aux, 0, B};
-    hipEventRecord(ds.ev_fork, st);
-    hipStreamWaitEvent(h1.s, ds.ev_fork, 0);
-    bool rest_pending = false;   // a REST launch whose completion the caller's stream has not waited for yet
-    for (int j = 0; j < ntiles; ++j) {
-      launch_diag(h0, j);
-      const int nrt = tp->col_count_host[j];
-      if (nrt <= 0) continue;
-      const bool head = tp->col_head_host[j] != 0;   // the launch's first tile is (j + 1, j)
-      const int n_head = head ? 1 : 0, n_rest = nrt - n_head;
-      if (n_rest > 0) {
-        hipEventRecord(ds.ev_diag, h0.s);
-        hipStreamWaitEvent(h1.s, ds.ev_diag, 0);
-      }
-      if (rest_pending) {   // HEAD(j) / the next diagonal phase read REST(j - 1)'s tiles
-        hipStreamWaitEvent(h0.s, ds.ev_rest, 0);
-        rest_pending = false;
-      }
-      if (n_head) launch_off(h0, j, 0, 1);
-      if (n_rest > 0) {
-        launch_off(h1, j, n_head, n_rest);
-        hipEventRecord(ds.ev_rest, h1.s);
-        rest_pending = true;
-        if (!head) {   // no look-ahead for this column: diag(j + 1) needs a tile of this launch
-          hipStreamWaitEvent(h0.s, ds.ev_rest, 0);
-          rest_pending = false;
-        }
-      }
-    }
-    if (rest_pending) hipStreamWaitEvent(st, ds.ev_rest, 0);
-    return check_launch("thx_chol_factor");
-  }
-  // RIGHT-LOOKING SCHEDULE for SMALL dense batches (dense L frame without a tile pattern, whole tiles inside the frame, up to
-  // thx_chol_schedule.right_looking_max_batch problems).  Left-looking, block column j is two dependent launches whose workgroups
-  // walk K-loops of j tiles -- the diagonal one with ONE workgroup per problem: at 8 ... 64 problems the chip is 3 ... 25 % occupied
-  // and a factorisation is the sum of those serial K-loops (n = 1536, batch 8: 1.62 ms, 0.04 of the MFMA peak).  Here every tile
-  // product is its own workgroup: per block column  chol_diag (the tile factorisation alone) -> chol_offdiag as the substitution
-  // alone, B (ntiles - 1 - j) tiles -> chol_offdiag as the trailing update, B m (m + 1) / 2 tiles each receiving ONE product; the
-  // working matrix lives in the L frame (first touched by column 0's update, which reads H), the damping of the later diagonal
-  // tiles is added once after that update.  Same tile kernels, another summation order: the factor differs from the left-looking
-  // one in the last bits (tests: against LAPACK and against the left-looking solution).  The forward substitution runs as its
-  // own kernel afterwards.
-  {
-    if (P.rl) {
-      if (dsm > ds.attr_diag[ti][0]) {   // (the later columns run the dense-frame instance on the L frame whatever H is)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(chol_diag_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dsm);
-        ds.attr_diag[ti][0] = dsm;
-      }
-      const Half h{st, 0, B};
-      const int Bpad = (B + 7) / 8 * 8;
-      // forward substitution riding on the schedule (vectors with 16-byte rows; else its own kernel afterwards, FACTOR_NEEDS_FORWARD): y starts
-      // as a copy of g; chol_diag(j) turns block j into y_j in place, the substitution tiles of column j update the blocks below
-      const bool fwd_fused = P.rl_fwd_fused;
-      if (fwd_fused) {
-        hipMemcpy2DAsync(y, (size_t)ldv * sizeof(T), rhs, (size_t)ldv * sizeof(T), (size_t)n * sizeof(T), (size_t)B, hipMemcpyDeviceToDevice, st);
-        rhs = y;
-      }
-      TilePat p0 = pat, p1 = pat;
-      p1.rl = 1;
-      if (fwd_fused) {
-        p0.rl_y = p1.rl_y = y;
-        p0.rl_ldv = p1.rl_ldv = ldv;
-      }
-      const HBlk nohb{nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, 0};
-      const T* Lc = (const T*)L;
-      const T* yc = fwd_fused ? (const T*)y : nullptr;
-      const size_t dsm0 = DiagSmem<T>::bytes(0);
-      // one chol_offdiag launch: nrt workgroup slots per problem (row tiles / update tiles), H from the block list, the dense H
-      // frame or the L frame
-      auto off = [&](bool hbsrc, const T* Hsrc, int jarg, int i_first, int nrt, const TilePat& pp, hipStream_t so = nullptr) {
-        if (!so) so = st;
-        auto go = [&](auto mode) {
-          constexpr int M = decltype(mode)::value;
-          if constexpr (sizeof(T) == 4)
-            hipLaunchKernelGGL(chol_offdiag_f32_kernel<M>, dim3(Bpad * nrt), dim3(256), OFF32_SMEM, so, (const float*)(M ? nullptr : Hsrc),
-                               (float*)L, (const float*)panel, n, ld, jarg, ntiles, i_first, nrt, B, pp, M ? hb : nohb);
-          else
-            hipLaunchKernelGGL((chol_offdiag_f64_kernel<M, true>), dim3(Bpad * nrt), dim3(256), OFF64_SMEM, so,
-                               (const double*)(M ? nullptr : Hsrc), (double*)L, (const double*)panel, n, ld, jarg, ntiles, i_first, nrt, B,
-                               pp, M ? hb : nohb);
-        };
-        if (!hbsrc) go(std::integral_constant<int, 0>{});
-        else if (hbm == HB_MODE_SCATTER) go(std::integral_constant<int, HB_MODE_SCATTER>{});
-        else go(std::integral_constant<int, HB_MODE_ROUNDS>{});
-      };
-      auto upd = [&](int jc, bool first) {
-        const int m = ntiles - 1 - jc;
-        TilePat pu = pat;
-        pu.rl = 2 + jc;
-        off(first && use_hb, first ? (const T*)H : Lc, jc, 0, m * (m + 1) / 2, pu);
-      };
-      const int la = P.rl_mode;
-      // block column 0: the kernels as they are (no earlier columns), reading H
-      launch_diag_n(h, 0, 1, true, dsm);   // (with a right-hand side: y_0 = W_00 g_0 -- kept when the forward substitution is fused)
-      off(use_hb, (const T*)H, 0, 1, ntiles - 1, p0);
-      int jstart = 1;
-      if (la == 1) {
-        // (mode 1) block column 1 the same way, straight from H: chol_diag(1) and the substitution tiles (i, 1) read their tile of H
-        // (block list or dense frame; the diagonal tile with its damping) and take column 0's update through the one-tile K-loop;
-        // column 0's update of the tiles right of column 1 -- which moves H into the L frame -- rides with the substitutions.
-        // (The plain schedule's update(0) is 66 tiles per problem at 12 block columns: 528 workgroups at batch 8, 16 more than one round.)
-        TilePat pd1 = p0;
-        pd1.rl = 1;
-        pd1.rl_la = 1;
-        if (use_hb)
-          hipLaunchKernelGGL((chol_diag_kernel<T, true>), dim3(B, 1), dim3(256), fwd_fused ? dsm : dsm0, st, (const T*)nullptr, (T*)L,
-                             (T*)panel, (const T*)damping, ellipsoidal, (T)eps, info, n, ld, 1, ntiles, yc, (T*)(fwd_fused ? y : nullptr),
-                             ldv, pd1, hb);
-        else
-          hipLaunchKernelGGL((chol_diag_kernel<T, false>), dim3(B, 1), dim3(256), fwd_fused ? dsm : dsm0, st, (const T*)H, (T*)L,
-                             (T*)panel, (const T*)damping, ellipsoidal, (T)eps, info, n, ld, 1, ntiles, yc, (T*)(fwd_fused ? y : nullptr),
-                             ldv, pd1, nohb);
-        const int nsub = ntiles - 2;
-        TilePat pc1 = pd1;
-        pc1.rl_nsub = nsub;
-        off(use_hb, (const T*)H, 1, 2, nsub + nsub * (nsub + 1) / 2, pc1);
-        if (damping && n > 2 * TILE)
-          hipLaunchKernelGGL(rl_damp_kernel<T>, dim3((n - 2 * TILE + 255) / 256, B), dim3(256), 0, st, (T*)L, ld, (const T*)H, ld, hb,
-                             (const T*)damping, ellipsoidal, (T)eps, 2 * TILE, n);
-        jstart = 2;
-      } else {
-        upd(0, true);
-        if (damping)
-          hipLaunchKernelGGL(rl_damp_kernel<T>, dim3((n - TILE + 255) / 256, B), dim3(256), 0, st, (T*)L, ld, (const T*)H, ld, hb,
-                             (const T*)damping, ellipsoidal, (T)eps, TILE, n);
-      }
-      // MODE 1, TWO LAUNCHES PER BLOCK COLUMN (TilePat.rl_la / rl_nsub; fp32's default; mode 0: the three launches of the plain schedule).
-      // The chain per column was diag -> substitutions -> trailing update, although the next diagonal phase and the next
-      // substitutions need only ONE block column of that update.  From block column 2 on every tile of column j takes column
-      // j - 1's update ITSELF -- chol_diag(j) and the substitution tiles (i, j) run a K-loop over the one tile of column j - 1, the
-      // left-looking kernels' own path -- and the rest of that update (tiles (i, k), j < k <= i: needed from column j + 1 on) rides
-      // in the SAME chol_offdiag launch as column j's substitutions, as extra workgroup slots:
-      //   diag(j) [own update]  ->  { substitutions (i, j) [own update]  +  update of column j - 1 on the tiles right of column j }
-      // No second stream, no events.  Another summation order for the tiles' last update (one K-loop product added before the
-      // substitution instead of a read-modify-write before it): to rounding, as the schedule itself.
-      // MODE 2, the second stream (fp64's default): only chol_diag(j) takes its own update; update(j - 1) is launched without tile
-      // (j, j) (first slot skipped) on the library's second stream and runs BESIDE diag(j); the substitutions of column j wait for
-      // both.  Hides the whole update instead of the part the substitutions cover, for two event hops per column.
-      // MEASURED (profiles/r6/ao_, n = 1536, factor + forward, plain / mode 1 / mode 2): fp32 batch 8 0.742 / 0.724 / 0.756 ms, 16:
-      // 0.856 / 0.828 / 0.855, 32: 1.10 / 1.05 / 1.08; fp64 batch 8 1.53 / 1.42 / 1.34, 16: 1.77 / 1.66 / 1.60, 32: 2.41 / 2.28 / 2.19
-      // -- an fp32 update launch is as short as the event hops, an fp64 one twice as long.  thx_chol_schedule.right_looking_mode forces
-      // a mode.
-      hipStream_t sa = st;
-      if (la == 2) {
-        ds.need_aux();
-        sa = ds.aux;
-      }
-      TilePat pd = p1;
-      pd.rl_la = 1;
-      bool upd_pending = false;   // (mode 2) an update launch on the second stream that the caller's stream has not waited for yet
-      for (int j = jstart; j < ntiles; ++j) {
-        hipLaunchKernelGGL((chol_diag_kernel<T, false>), dim3(B, 1), dim3(256), fwd_fused ? dsm : dsm0, st, Lc, (T*)L,
-                           (T*)panel, (const T*)nullptr, 0, T(0), info, n, ld, j, ntiles, yc, (T*)(fwd_fused ? y : nullptr), ldv,
-                           (la && j >= 2) ? pd : p1, nohb);
-        if (j + 1 == ntiles) break;
-        if (la == 0) {
-          off(false, Lc, j, j + 1, ntiles - 1 - j, p1);
-          upd(j, false);
-        } else if (la == 1) {   // (from column 2 on: column 1 ran straight from H above)
-          const int nsub = ntiles - 1 - j;
-          TilePat pc = pd;
-          pc.rl_nsub = nsub;
-          off(false, Lc, j, j + 1, nsub + nsub * (nsub + 1) / 2, pc);
-        } else {
-          if (upd_pending) {   // the substitutions read the tiles update(j - 1) wrote
-            hipStreamWaitEvent(st, ds.ev_rest, 0);
-            upd_pending = false;
-          }
-          off(false, Lc, j, j + 1, ntiles - 1 - j, p1);
-          const int m = ntiles - 1 - j, nslots = m * (m + 1) / 2 - 1;   // (slot 0 = tile (j + 1, j + 1): left to diag(j + 1))
-          if (nslots > 0) {
-            hipEventRecord(ds.ev_diag, st);
-            hipStreamWaitEvent(sa, ds.ev_diag, 0);
-            TilePat pu = pat;
-            pu.rl = 2 + j;
-            off(false, Lc, j, 1, nslots, pu, sa);
-            hipEventRecord(ds.ev_rest, sa);
-            upd_pending = true;
-          }
-        }
-      }
-      if (upd_pending) hipStreamWaitEvent(st, ds.ev_rest, 0);
-      if (int r = check_launch("thx_chol_factor (right-looking)")) return r;
-      return (rhs && !fwd_fused) ? FACTOR_NEEDS_FORWARD : 0;   // (the caller runs the forward substitution as its own kernel)
-    }
-  }
-  const bool colpair = P.colpair;   // (from column_pairs_min_batch problems per call on, see plan_factor)
-  for (int j = 0; j < ntiles;) {
-    const bool pair = colpair && j + 2 < ntiles;
-    for (int k = 0; k < nparts; ++k) {
-      const Half& h = halves[k];
-      if (h.nb <= 0) continue;
-      if (split && k == 1 && j == 0) hipStreamWaitEvent(h.s, ds.ev_lag, 0);  // half 1: one diagonal phase behind half 0
-      launch_diag(h, j);
-      if (split && k == 0 && j == 0) hipEventRecord(ds.ev_lag, h.s);
-      if (pair) {
-        launch_off(h, j, j + 1, 1);
-        launch_diag(h, j + 1);
-        launch_pair(h, j, j + 2, ntiles - 2 - j);
-        continue;
-      }
-      const int nrt = tp ? tp->col_count_host[j] : ntiles - 1 - j;   // (tile-sparse: the column's non-zero row tiles)
-      if (nrt > 0) launch_off(h, j, tp ? 0 : j + 1, nrt);
-    }
-    j += pair ? 2 : 1;
-  }
-  if (split) {
-    hipEventRecord(ds.ev_join, ds.aux);
-    hipStreamWaitEvent(st, ds.ev_join, 0);
-  }
-  return check_launch("thx_chol_factor");
 }
 
 template <typename T>
@@ -3861,62 +3849,50 @@ static int solve_impl(const void* L, int64_t ld, int n, int B, const void* panel
   const bool list = tp != nullptr;
   const size_t sm = solve_smem<T>(list ? 0 : ntiles * TILE);
   if (sm > LDS_LIMIT) return fail("thx_chol_solve: n too large for the LDS plan (thx_chol_solve_sparse has no limit)");
-  {
-    std::lock_guard<std::mutex> guard(g_launch_mutex);
-    size_t& attr = launch_state().attr_solve[sizeof(T) == 8];
-    if (sm > attr) {
-      hipFuncSetAttribute(reinterpret_cast<const void*>(chol_fwd_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)sm);
-      hipFuncSetAttribute(reinterpret_cast<const void*>(chol_bwd_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)sm);
-      hipFuncSetAttribute(reinterpret_cast<const void*>(chol_fwd_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)sm);
-      hipFuncSetAttribute(reinterpret_cast<const void*>(chol_bwd_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)sm);
-      attr = sm;
-    }
-  }
   const bool packed = ld == 0;
   if (packed && (!list || !tp->row_slot || tp->nslots <= 0))
     return fail("thx_chol_solve: a tile-packed factor (ld = 0) needs thx_chol_solve_sparse and a pattern with slot tables");
+  if (ls && !list) return fail("thx_chol_solve_levels: needs the tile pattern");
   RowPat rp{list ? tp->row_ptr : nullptr, list ? tp->row_tile : nullptr, packed ? tp->row_slot : nullptr, packed ? tp->nslots : 0,
             -1, ls ? ls->tile_valid : nullptr};
+  std::lock_guard<std::mutex> guard(g_launch_mutex);   // (the LDS limits; not recursive -- see factor_then_forward)
+  const int dev = current_device();
   const T* src = (const T*)rhs;
+  auto copy_to_x = [&] {   // the backward substitution runs in place
+    if (src != (const T*)x)
+      hipMemcpy2DAsync(x, (size_t)ldv * sizeof(T), src, (size_t)ldv * sizeof(T), (size_t)n * sizeof(T), (size_t)B,
+                       hipMemcpyDeviceToDevice, st);
+  };
   if (ls) {
     // LEVEL SCHEDULE: one launch per elimination-tree level, one workgroup per (problem, block row of the level) -- forward bottom
     // up (a row pulls from its descendants' blocks of y), backward top down (a row pushes into its descendants' blocks of x)
-    if (!list) return fail("thx_chol_solve_levels: needs the tile pattern");
     if (forward) {
       for (int l = 0; l < ls->nlevels; ++l) {
         rp.j0 = ls->level_col_host[l];
         const int nc = ls->level_col_host[l + 1] - rp.j0;
         if (nc > 0)
-          hipLaunchKernelGGL((chol_fwd_kernel<T, true>), dim3(B, nc), dim3(256), sm, st, (const T*)L, (const T*)panel, src, (T*)x, n,
-                             ld, ldv, ntiles, rp);
+          launch_lds<chol_fwd_kernel<T, true>>(dev, dim3(B, nc), dim3(256), sm, st, (const T*)L, (const T*)panel, src, (T*)x, n, ld, ldv,
+                                               ntiles, rp);
       }
       src = (const T*)x;
     }
     if (backward) {
-      if (src != (const T*)x)
-        hipMemcpy2DAsync(x, (size_t)ldv * sizeof(T), src, (size_t)ldv * sizeof(T), (size_t)n * sizeof(T), (size_t)B,
-                         hipMemcpyDeviceToDevice, st);
+      copy_to_x();
       for (int l = ls->nlevels - 1; l >= 0; --l) {
         rp.j0 = ls->level_col_host[l];
         const int nc = ls->level_col_host[l + 1] - rp.j0;
         if (nc > 0)
-          hipLaunchKernelGGL((chol_bwd_kernel<T, true>), dim3(B, nc), dim3(256), sm, st, (const T*)L, (const T*)panel, (const T*)x,
-                             (T*)x, n, ld, ldv, ntiles, rp);
+          launch_lds<chol_bwd_kernel<T, true>>(dev, dim3(B, nc), dim3(256), sm, st, (const T*)L, (const T*)panel, (const T*)x, (T*)x, n,
+                                               ld, ldv, ntiles, rp);
       }
     }
     return check_launch("thx_chol_solve_levels");
   }
   if (forward) {
-    if (list)
-      hipLaunchKernelGGL((chol_fwd_kernel<T, true>), dim3(B), dim3(256), sm, st, (const T*)L, (const T*)panel, src, (T*)x, n,
-                         ld, ldv, ntiles, rp);
-    else
-      hipLaunchKernelGGL((chol_fwd_kernel<T, false>), dim3(B), dim3(256), sm, st, (const T*)L, (const T*)panel, src, (T*)x, n,
-                         ld, ldv, ntiles, rp);
+    with_bool(list, [&](auto lk) {
+      launch_lds<chol_fwd_kernel<T, decltype(lk)::value>>(dev, dim3(B), dim3(256), sm, st, (const T*)L, (const T*)panel, src, (T*)x, n,
+                                                          ld, ldv, ntiles, rp);
+    });
     src = (const T*)x;  // the backward pass then runs in place
   }
   // small batches, dense frame: one launch per block row (chol_bwd_rows_kernel; bit-identical to chol_bwd_kernel) -- up to
@@ -3925,31 +3901,18 @@ static int solve_impl(const void* L, int64_t ld, int n, int B, const void* panel
   // problems on, profiles/r6/o_ab_bwd_rows.txt) -- it is chol_fwd_kernel's row dots that take 0.46 ms at any batch size, and
   // the right-looking schedule fuses the forward substitution instead.
   if (backward && !list && ntiles >= 3 && B <= BWD_ROWS_MAX_BATCH) {
-    if (src != (const T*)x)
-      hipMemcpy2DAsync(x, (size_t)ldv * sizeof(T), src, (size_t)ldv * sizeof(T), (size_t)n * sizeof(T), (size_t)B,
-                       hipMemcpyDeviceToDevice, st);
+    copy_to_x();
     const size_t smr = solve_smem<T>(0);
-    {
-      std::lock_guard<std::mutex> guard(g_launch_mutex);
-      size_t& attr = launch_state().attr_bwd_rows[sizeof(T) == 8];
-      if (smr > attr) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(chol_bwd_rows_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smr);
-        attr = smr;
-      }
-    }
     for (int jb = ntiles; jb >= 1; --jb)
-      hipLaunchKernelGGL((chol_bwd_rows_kernel<T>), dim3(jb < ntiles ? jb : 1, B), dim3(256), smr, st, (const T*)L, (const T*)panel,
-                         (T*)x, n, ld, ldv, ntiles, jb);
+      launch_lds<chol_bwd_rows_kernel<T>>(dev, dim3(jb < ntiles ? jb : 1, B), dim3(256), smr, st, (const T*)L, (const T*)panel, (T*)x, n,
+                                          ld, ldv, ntiles, jb);
     return check_launch("thx_chol_solve (block rows)");
   }
-  if (backward) {
-    if (list)
-      hipLaunchKernelGGL((chol_bwd_kernel<T, true>), dim3(B), dim3(256), sm, st, (const T*)L, (const T*)panel, src, (T*)x, n,
-                         ld, ldv, ntiles, rp);
-    else
-      hipLaunchKernelGGL((chol_bwd_kernel<T, false>), dim3(B), dim3(256), sm, st, (const T*)L, (const T*)panel, src, (T*)x, n,
-                         ld, ldv, ntiles, rp);
-  }
+  if (backward)
+    with_bool(list, [&](auto lk) {
+      launch_lds<chol_bwd_kernel<T, decltype(lk)::value>>(dev, dim3(B), dim3(256), sm, st, (const T*)L, (const T*)panel, src, (T*)x, n,
+                                                          ld, ldv, ntiles, rp);
+    });
   return check_launch("thx_chol_solve");
 }
 
@@ -3977,6 +3940,28 @@ static int check_factor_args(const void* H, const void* L, const void* panel, co
   return 0;
 }
 
+// the tile-pattern tables every tile-sparse factorisation reads
+static int check_pattern(const thx_tile_pattern* pattern, const char* who) {
+  if (!pattern || !pattern->col_ptr || !pattern->col_row || !pattern->tile_kptr || !pattern->tile_k || !pattern->diag_kptr ||
+      !pattern->diag_k || !pattern->col_count_host)
+    return fail(who, ": incomplete tile pattern");
+  return 0;
+}
+
+// the right-hand side and its forward-substituted vector: both or (unless `required`) neither, of at least n elements, not aliased
+static int check_rhs(const void* rhs, const void* y, int64_t ldv, int n, const char* who, bool required = false,
+                     const char* what = ": rhs / y / ldv") {
+  if (required ? (!rhs || !y || ldv < n) : ((rhs == nullptr) != (y == nullptr) || (rhs && ldv < n))) return fail(who, what);
+  if (rhs && rhs == y) return fail(who, ": y must not alias rhs");
+  return 0;
+}
+
+// the kernels' view of a block-compact Hessian: the layout's tables and the value buffer (B, bstride)
+static HBlk hblk_from(const thx_hblock_layout* layout, const void* Hc, int64_t bstride) {
+  return HBlk{Hc, bstride, layout->bd, layout->tile_ptr, layout->piece_blk, layout->piece_rc, layout->diag_blk, layout->max_tile_pieces,
+              layout->l_mask};
+}
+
 int thx_chol_factor(const void* H, int64_t ld, int32_t n, int32_t B, const void* damping, int ellipsoidal,
                     double damping_eps, void* L, void* Winv, int32_t* info, int dtype, void* stream, const thx_chol_schedule* schedule) {
   if (int r = check_factor_args(H, L, Winv, info, n, B, ld)) return r;
@@ -3992,8 +3977,7 @@ int thx_chol_factor_forward(const void* H, int64_t ld, int32_t n, int32_t B, con
                             double damping_eps, void* L, void* Winv, int32_t* info, const void* rhs, void* y,
                             int64_t ldv, int dtype, void* stream, const thx_chol_schedule* schedule) {
   if (int r = check_factor_args(H, L, Winv, info, n, B, ld)) return r;
-  if (!rhs || !y || ldv < n) return fail("thx_chol_factor_forward: rhs / y / ldv");
-  if (rhs == y) return fail("thx_chol_factor_forward: y must not alias rhs");
+  if (int r = check_rhs(rhs, y, ldv, n, "thx_chol_factor_forward", true)) return r;
   THX_DISPATCH(dtype,
                return factor_then_forward<float>(H, ld, n, B, damping, ellipsoidal, damping_eps, L, Winv, info, rhs, y, ldv,
                                          as_stream(stream), nullptr, nullptr, nullptr, schedule),
@@ -4007,11 +3991,8 @@ int thx_chol_factor_sparse(const void* H, int64_t ld, int32_t n, int32_t B, cons
                            const thx_tile_pattern* pattern, int dtype, void* stream, const thx_chol_schedule* schedule) {
   if (int r = check_factor_args(H, L, Winv, info, n, B, ld)) return r;
   if (ld == 0) return fail("thx_chol_factor_sparse: H is a dense frame here (ld >= n); the tile-packed factor goes with thx_chol_factor_hblocks");
-  if (!pattern || !pattern->col_ptr || !pattern->col_row || !pattern->tile_kptr || !pattern->tile_k || !pattern->diag_kptr ||
-      !pattern->diag_k || !pattern->col_count_host)
-    return fail("thx_chol_factor_sparse: incomplete tile pattern");
-  if ((rhs == nullptr) != (y == nullptr) || (rhs && ldv < n)) return fail("thx_chol_factor_sparse: rhs / y / ldv");
-  if (rhs && rhs == y) return fail("thx_chol_factor_sparse: y must not alias rhs");
+  if (int r = check_pattern(pattern, "thx_chol_factor_sparse")) return r;
+  if (int r = check_rhs(rhs, y, ldv, n, "thx_chol_factor_sparse")) return r;
   THX_DISPATCH(dtype,
                return factor_impl<float>(H, ld, n, B, damping, ellipsoidal, damping_eps, L, Winv, info, rhs, y, ldv,
                                          as_stream(stream), pattern, nullptr, nullptr, schedule),
@@ -4045,13 +4026,10 @@ int thx_chol_factor_hblocks(const thx_hblock_layout* layout, const void* Hc, int
   if (int r = check_factor_args(Hc, L, Winv, info, n, B, ld)) return r;
   if (layout->ntiles != (n + TILE - 1) / TILE || layout->nvars * layout->bd != n || bstride < (int64_t)layout->nblocks * layout->bd * layout->bd)
     return fail("thx_chol_factor_hblocks: the block layout is not this matrix's");
-  if (pattern && (!pattern->col_ptr || !pattern->col_row || !pattern->tile_kptr || !pattern->tile_k || !pattern->diag_kptr ||
-                  !pattern->diag_k || !pattern->col_count_host))
-    return fail("thx_chol_factor_hblocks: incomplete tile pattern");
-  if ((rhs == nullptr) != (y == nullptr) || (rhs && ldv < n)) return fail("thx_chol_factor_hblocks: rhs / y / ldv");
-  if (rhs && rhs == y) return fail("thx_chol_factor_hblocks: y must not alias rhs");
-  const HBlk hb{Hc, bstride, layout->bd, layout->tile_ptr, layout->piece_blk, layout->piece_rc, layout->diag_blk, layout->max_tile_pieces,
-                layout->l_mask};
+  if (pattern)
+    if (int r = check_pattern(pattern, "thx_chol_factor_hblocks")) return r;
+  if (int r = check_rhs(rhs, y, ldv, n, "thx_chol_factor_hblocks")) return r;
+  const HBlk hb = hblk_from(layout, Hc, bstride);
   THX_DISPATCH(dtype,
                return factor_then_forward<float>(nullptr, ld, n, B, damping, ellipsoidal, damping_eps, L, Winv, info, rhs, y, ldv,
                                          as_stream(stream), pattern, &hb, nullptr, schedule),
@@ -4067,23 +4045,24 @@ int thx_chol_plan(int32_t n, int64_t ld, int32_t B, int dtype, int has_damping, 
   if (has_rhs && ldv < n) return fail("thx_chol_plan: ldv < n");
   if (dtype != THX_F32 && dtype != THX_F64) return fail("bad dtype");
   if (layout && layout->ntiles != (n + TILE - 1) / TILE) return fail("thx_chol_plan: the block layout is not this matrix's");
-  const HBlk hb{nullptr, 0, layout ? layout->bd : 0, nullptr, nullptr, nullptr, layout ? layout->diag_blk : nullptr,
-                layout ? layout->max_tile_pieces : 0};
+  HBlk hb = layout ? hblk_from(layout, nullptr, 0) : HBlk{};   // (no data pointers: the plan reads bd, diag_blk, max_tile_pieces)
+  hb.l_mask = nullptr;                                         // (skipping zero sub-blocks is not part of the report)
   const FactorPlan p = plan_factor(dtype == THX_F64, n, ld, B, has_damping != 0, has_rhs != 0, ldv, true, nullptr,
                                    layout ? &hb : nullptr, nullptr, schedule);
-  out->right_looking = p.rl;
-  out->right_looking_mode = p.rl ? p.rl_mode : -1;
+  const bool rl = p.schedule == Schedule::RightLooking;
+  out->right_looking = rl;
+  out->right_looking_mode = rl ? p.rl_mode : -1;
   out->split_diag = !p.fused_diag;
   out->nparts = p.nparts;
   out->column_pairs = p.colpair;
   // (fp64 off-diagonal launches of the column-by-column schedule: block columns 0 .. ntiles - 2; the half-tile kernel first, then the
-  //  eight-wave one -- launch_off; neither takes the LDS gather rounds of a block list)
+  //  eight-wave one -- FactorLaunch::off; neither takes the LDS gather rounds of a block list)
   const int cols = p.ntiles - 1;
-  const bool f64_lanes = dtype == THX_F64 && !p.rl && p.hbm != HB_MODE_ROUNDS;
+  const bool f64_lanes = dtype == THX_F64 && !rl && p.hbm != HB_MODE_ROUNDS;
   const int half = f64_lanes ? std::max(0, std::min(p.f64_half_max, cols)) : 0;
   out->f64_half_cols = half;
   out->f64_wide_cols = f64_lanes ? std::max(0, std::min(p.f64_wide_max, cols) - half) : 0;
-  out->forward_fused = has_rhs && (!p.rl || p.rl_fwd_fused);
+  out->forward_fused = has_rhs && (!rl || p.rl_fwd_fused);
   return 0;
 }
 
@@ -4155,9 +4134,10 @@ int thx_chol_factor_levels(const thx_hblock_layout* layout, const void* Hc, int6
   if (layout->ntiles != pattern->ntiles || bstride < (int64_t)layout->nblocks * layout->bd * layout->bd)
     return fail("thx_chol_factor_levels: the block layout is not this pattern's");
   const int n = pattern->ntiles * TILE;   // (the padded order: every tile is whole, tile_valid says how much of it is matrix)
-  if ((rhs == nullptr) != (y == nullptr) || (rhs && ldv < n)) return fail("thx_chol_factor_levels: rhs / y are vectors of the PADDED order (ldv >= ntiles * THX_TILE)");
-  if (rhs && rhs == y) return fail("thx_chol_factor_levels: y must not alias rhs");
-  const HBlk hb{Hc, bstride, layout->bd, layout->tile_ptr, layout->piece_blk, layout->piece_rc, nullptr, layout->max_tile_pieces};
+  if (int r = check_rhs(rhs, y, ldv, n, "thx_chol_factor_levels", false, ": rhs / y are vectors of the PADDED order (ldv >= ntiles * THX_TILE)"))
+    return r;
+  HBlk hb = hblk_from(layout, Hc, bstride);
+  hb.diag_blk = hb.l_mask = nullptr;   // (the level schedule has no right-looking damping pass and skips no sub-blocks)
   THX_DISPATCH(dtype,
                return factor_impl<float>(nullptr, 0, n, B, damping, ellipsoidal, damping_eps, L, Winv, info, rhs, y, ldv,
                                          as_stream(stream), pattern, &hb, schedule, chol_schedule),
