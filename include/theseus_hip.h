@@ -288,6 +288,42 @@ int thx_block_assemble(const thx_block_target* h_targets, const thx_block_term* 
                        const int32_t* g_elem2target, int32_t n_g_elems, void* H, int64_t ld, void* g, int64_t ldg,
                        int32_t B, int dtype, void* stream);
 
+/* ---- 2D motion planning (examples/motion_planning_2d.py): the whole cost family of a trajectory objective in one launch.
+ *      terms[t] (DEVICE array built by the host, sorted by kind) is one cost function on the (B, n) Euclidean state x:
+ *        THX_TRAJ2_COLLISION  Collision2D on a Point2 (theseus/embodied/collision/collision.py:44-73 over
+ *                             SignedDistanceField2D.signed_distance, signed_distance_field.py:163-241), ScaleCostWeight;
+ *                             aux = sdf_data (rows x cols, row major), sdf_origin (2), sdf_cell_size (1), cost_eps (1), scale (1)
+ *        THX_TRAJ2_GP         GPMotionModel with dof 2 (theseus/embodied/motionmodel/double_integrator.py:48-80) weighted by
+ *                             GPCostWeight (:131-152), formed here as chol(M)^T (x) chol(Qc_inv)^T with
+ *                             M = [[12/dt^3, -6/dt^2], [-6/dt^2, 4/dt]];  aux = the cost's dt (1), the weight's dt (1), Qc_inv (2 x 2)
+ *        THX_TRAJ2_PRIOR      Difference on a 2-dof Euclidean variable (theseus/embodied/misc/local_cost_fn.py:16-75);
+ *                             aux = target (2), weight (wdim = 1: ScaleCostWeight, 2: DiagonalCostWeight)
+ *      aux[k] are device pointers of the run's dtype, aux_bstride[k] their element batch strides (0 = shared by all problems).
+ *      thx_traj2_eval writes, per term and problem, the WEIGHTED Jacobian blocks (what weighted_jacobians_error returns,
+ *      core/cost_function.py:107-122) and the weighted error:  block s of term t (dim x 2, row major) of problem b starts
+ *      (j_off + 2 * dim * s) * B + 2 * dim * b elements into J (each block is a contiguous (B, dim, 2) tensor:
+ *      thx_block_term / thx_grad_term can point at it), j_total = blocks' elements per problem;  e is (B, m) with row stride
+ *      lde, the term's rows from row0 (the objective's row order).  Terms whose rows, columns or blocks fall outside
+ *      m / n / j_total are skipped.  thx_traj2_error: err[b] = 0.5 * sum of the squared weighted errors, one launch, fixed
+ *      reduction order, sums in fp64.  Both compute in the run's dtype with the reference's operation order for the cell
+ *      coordinates, the bounds test and the distance > eps test. */
+#define THX_TRAJ2_COLLISION 0
+#define THX_TRAJ2_GP 1
+#define THX_TRAJ2_PRIOR 2
+typedef struct {
+  int32_t kind, row0;
+  int32_t col[4]; /* first state column of each optimisation variable of the cost (unused: -1) */
+  int32_t rows, cols; /* collision: the grid's size */
+  int64_t j_off;
+  const void* aux[5];
+  int64_t aux_bstride[5];
+  int32_t wdim, pad_;
+} thx_traj2_term;
+int thx_traj2_eval(const thx_traj2_term* terms, int32_t n_terms, const void* x, int64_t ldx, int32_t n, void* J,
+                   int64_t j_total, void* e, int64_t lde, int32_t m, int32_t B, int dtype, void* stream);
+int thx_traj2_error(const thx_traj2_term* terms, int32_t n_terms, const void* x, int64_t ldx, int32_t n, void* err,
+                    int32_t B, int dtype, void* stream);
+
 /* ---- Objective.error_metric(): 0.5 * ||weighted error||^2 per problem (core/objective.py:37-38,
  *      562-641).  `partials` is a (B, THX_ERR_CHUNKS) scratch; the reduction order is fixed
  *      (deterministic).  err is (B). */

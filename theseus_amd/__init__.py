@@ -17,6 +17,8 @@ from .nonlinear import (BackwardMode, Dogleg, GaussNewton, LevenbergMarquardt, N
                         NonlinearOptimizerInfo, NonlinearOptimizerStatus, TrustRegion)
 from .packed import PackedPoseGraph, UnsupportedObjective  # noqa: F401
 from .ba import HipSchurLinearization, HipSchurSolver, PackedBA  # noqa: F401
+from . import embodied as eb  # noqa: F401
+from .embodied import PackedTrajectory2D  # noqa: F401
 
 # names a reference user would reach for on this path
 CholeskyDenseSolver = HipCholeskySolver

@@ -658,6 +658,16 @@ class Difference(CostFunction):
     def error(self):
         return self.target.local(self.var)
 
+    def jacobians(self):
+        """Euclidean variables only (local(a, b) = b - a: the identity, theseus/geometry/vector.py:150-160); the Lie-group priors
+        are evaluated by the fused pose-graph kernels."""
+        if "Vector" not in {c.__name__ for c in type(self.var).__mro__}:
+            raise NotImplementedError(f"Difference.jacobians(): torch Jacobians exist for Euclidean variables only; got "
+                                      f"{type(self.var).__name__} ({self.var.name}).")
+        err = self.error()
+        d = err.shape[1]
+        return [torch.eye(d, dtype=err.dtype, device=err.device).expand(err.shape[0], d, d)], err
+
     def dim(self):
         return self.var.dof()
 

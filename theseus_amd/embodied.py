@@ -1,0 +1,418 @@
+"""2D motion planning on theseus_amd's own API (``theseus_amd.eb``, as the reference's ``th.eb``): torch restatements of
+  SignedDistanceField2D   theseus/embodied/collision/signed_distance_field.py:16-247
+  Collision2D             theseus/embodied/collision/collision.py:17-92 (Point2 poses, the identity robot model)
+  DoubleIntegrator        theseus/embodied/motionmodel/double_integrator.py:14-91 (Euclidean variables)
+  GPCostWeight            :94-176
+  GPMotionModel           :179-202
+They implement ``error`` / ``jacobians`` / ``weighted_jacobians_error``, so an objective made of them runs through the generic
+path (theseus_amd/euclidean.py: PackedEuclidean) with every backward mode; an objective made ONLY of Collision2D, GPMotionModel
+and 2-dof Difference priors is evaluated by the fused kernels of csrc/traj_kernels.hip (PackedTrajectory2D below), for which these
+classes are the fallback and the differentiable twin.
+"""
+from typing import List, Optional, Union
+
+import numpy as np
+import torch
+
+from . import _lib
+from .core import CostFunction, CostWeight, Point2, Variable, Vector
+from .euclidean import PackedEuclidean, _is_euclidean
+
+
+def _as_variable(x, dtype=None, name=None) -> Variable:
+    if isinstance(x, Variable):
+        return x
+    if not isinstance(x, torch.Tensor):
+        x = torch.tensor(float(x), dtype=dtype or torch.get_default_dtype())
+    return Variable(x, name=name)
+
+
+def _names(obj):
+    return {c.__name__ for c in type(obj).__mro__}
+
+
+class SignedDistanceField2D:
+    """A batch of grids ``sdf_data`` (B|1, rows, cols) with ``origin`` (B|1, 2) the position of cell (0, 0) and ``cell_size``
+    (B|1, 1); x runs along the columns, y along the rows (signed_distance_field.py:163-188)."""
+
+    def __init__(self, origin: Union[Point2, torch.Tensor], cell_size: Union[float, torch.Tensor, Variable],
+                 sdf_data: Optional[Union[torch.Tensor, Variable]] = None, occupancy_map=None,
+                 occupancy_threshold: float = 0.75, sdf_boundary_value: float = 0.0):
+        if occupancy_map is not None:
+            raise NotImplementedError("SignedDistanceField2D(occupancy_map=...) is out of scope on this back end (the reference "
+                                      "runs scipy's distance transform on the host, signed_distance_field.py:51-102): pass sdf_data.")
+        if sdf_data is None:
+            raise ValueError("Either sdf_data or argument occupancy_map should be provided.")
+        self.update_data(origin, sdf_data, cell_size)
+        self.sdf_boundary_value = sdf_boundary_value
+
+    @staticmethod
+    def convert_origin(origin) -> Point2:
+        if isinstance(origin, Point2):
+            return origin
+        if not isinstance(origin, torch.Tensor):
+            raise ValueError("Argument origin to SignedDistanceField2D must be either a tensor or a Point2 variable.")
+        try:
+            return Point2(tensor=origin if origin.ndim == 2 else origin.view(1, -1))
+        except ValueError:
+            raise ValueError("Argument origin to SignedDistanceField2D must be a batch of 2D tensors.") from None
+
+    @staticmethod
+    def convert_cell_size(cell_size) -> Variable:
+        if not isinstance(cell_size, Variable):
+            if not isinstance(cell_size, torch.Tensor):
+                if not isinstance(cell_size, float):
+                    raise ValueError("Argument cell_size must be either a Variable, tensor, or float.")
+                cell_size = torch.tensor(cell_size)
+            return Variable(cell_size.view(-1, 1))
+        if not (cell_size.ndim == 1 or (cell_size.ndim == 2 and cell_size.shape[1] == 1)):
+            raise ValueError("Argument cell_size must be a batch of 0D or 1D tensors.")
+        return cell_size
+
+    @staticmethod
+    def convert_sdf_data(sdf_data) -> Variable:
+        sdf_data = _as_variable(sdf_data)
+        if sdf_data.ndim != 3:
+            raise ValueError("Argument sdf_data to SignedDistanceField2D must be a batch of matrices.")
+        return sdf_data
+
+    def update_data(self, origin, sdf_data, cell_size):
+        self.origin = self.convert_origin(origin)
+        self.cell_size = self.convert_cell_size(cell_size)
+        self.sdf_data = self.convert_sdf_data(sdf_data)
+
+    def signed_distance(self, points: torch.Tensor):
+        """points (B, 2, P) -> distances (B, P), Jacobians (B, P, 2) = [d/dpx, d/dpy] (signed_distance_field.py:163-241)."""
+        origin, cell = self.origin.tensor.unsqueeze(-1), self.cell_size.tensor.view(-1, 1)
+        sdf = self.sdf_data.tensor
+        R, C = sdf.shape[1], sdf.shape[2]
+        px, py = points[:, 0], points[:, 1]
+        oob = (px < origin[:, 0]) | (px > (origin[:, 0] + (C - 1.0) * cell)) | (py < origin[:, 1]) | (py > (origin[:, 1] + (R - 1.0) * cell))
+        cols, rows = (px - origin[:, 0]) / cell, (py - origin[:, 1]) / cell
+        lr, lc = torch.floor(rows), torch.floor(cols)
+        hr, hc = lr + 1.0, lc + 1.0
+        lri, hri = lr.long().clamp(0, R - 1), hr.long().clamp(0, R - 1)
+        lci, hci = lc.long().clamp(0, C - 1), hc.long().clamp(0, C - 1)
+        B = max(points.shape[0], sdf.shape[0])
+        flat = sdf.reshape(sdf.shape[0], -1).expand(B, -1)
+
+        def at(r, c):
+            return flat.gather(1, (r * C + c).expand(B, -1))
+        sll, shl, slh, shh = at(lri, lci), at(hri, lci), at(lri, hci), at(hri, hci)
+        hrd, hcd, lrd, lcd = hr - rows, hc - cols, rows - lr, cols - lc
+        dist = hrd * hcd * sll + lrd * hcd * shl + hrd * lcd * slh + lrd * lcd * shh
+        jac1 = (hrd * (slh - sll) + lrd * (shh - shl)) / cell
+        jac2 = (hcd * (shl - sll) + lcd * (shh - slh)) / cell
+        oob = oob.expand_as(dist)
+        dist = torch.where(oob, torch.full_like(dist, self.sdf_boundary_value), dist)
+        zero = torch.zeros_like(dist)
+        return dist, torch.stack([torch.where(oob, zero, jac1), torch.where(oob, zero, jac2)], dim=2)
+
+    def to(self, *args, **kwargs):
+        for v in (self.cell_size, self.origin, self.sdf_data):
+            v.to(*args, **kwargs)
+
+
+class Collision2D(CostFunction):
+    """error = clamp(cost_eps - d(pose), min=0), Jacobian = -dd/dpose where d <= cost_eps (collision.py:44-73)."""
+
+    def __init__(self, pose: Point2, sdf_origin, sdf_data, sdf_cell_size, cost_eps, cost_weight: CostWeight,
+                 name: Optional[str] = None):
+        if not isinstance(pose, Point2):
+            if "SE2" in _names(pose):
+                raise ValueError("Collision2D on an SE2 pose is out of scope on this back end: use a Point2 pose.")
+            raise ValueError("Collision2D only accepts Point2 or SE2 poses.")
+        super().__init__(cost_weight, name)
+        self.pose = pose
+        self.sdf_origin = SignedDistanceField2D.convert_origin(sdf_origin)
+        self.sdf_data = SignedDistanceField2D.convert_sdf_data(sdf_data)
+        self.sdf_cell_size = SignedDistanceField2D.convert_cell_size(sdf_cell_size)
+        self.cost_eps = _as_variable(cost_eps, dtype=pose.dtype)
+        if self.cost_eps.tensor.ndim != 2:
+            self.cost_eps._tensor = self.cost_eps.tensor.view(-1, 1)
+
+    def optim_vars(self):
+        return [self.pose]
+
+    def aux_vars(self):
+        return [self.sdf_origin, self.sdf_data, self.sdf_cell_size, self.cost_eps] + self.weight.aux_vars()
+
+    def dim(self) -> int:
+        return 1
+
+    def _distances(self):
+        # (the variables are read at every evaluation: Objective.update may have replaced their tensors)
+        sdf = SignedDistanceField2D(self.sdf_origin, self.sdf_cell_size, self.sdf_data)
+        return sdf.signed_distance(self.pose.tensor.view(-1, 2, 1))
+
+    def error(self) -> torch.Tensor:
+        return (self.cost_eps.tensor.view(-1, 1) - self._distances()[0]).clamp(min=0)
+
+    def jacobians(self):
+        dist, jac = self._distances()
+        eps = self.cost_eps.tensor.view(-1, 1)
+        jac = torch.where((dist > eps).unsqueeze(2), torch.zeros_like(jac), jac)
+        return [-jac], (eps - dist).clamp(min=0)
+
+
+class GPCostWeight(CostWeight):
+    """The (B|1, 2 dof, 2 dof) matrix U = chol(W)^T, W = [[12/dt^3, -6/dt^2], [-6/dt^2, 4/dt]] (x) Qc_inv
+    (double_integrator.py:131-152); differentiable in Qc_inv and dt."""
+
+    def __init__(self, Qc_inv: Union[Variable, torch.Tensor], dt: Union[float, Variable, torch.Tensor], name: Optional[str] = None):
+        super().__init__(name)
+        Qc_inv = _as_variable(Qc_inv)
+        dt = _as_variable(dt, dtype=Qc_inv.dtype)
+        if dt.tensor.squeeze().ndim > 1:
+            raise ValueError("dt must be a 0-D or 1-D tensor.")
+        if dt.tensor.ndim != 2:
+            dt._tensor = dt.tensor.view(-1, 1)
+        if not (dt.tensor > 0).all():
+            raise ValueError("dt must be greater than 0.")
+        if Qc_inv.ndim not in (2, 3):
+            raise ValueError("Qc_inv must be a single matrix or a batch of matrices.")
+        if Qc_inv.shape[-2] != Qc_inv.shape[-1]:
+            raise ValueError("Qc_inv must contain square matrices.")
+        if Qc_inv.ndim == 2:
+            Qc_inv._tensor = Qc_inv.tensor.unsqueeze(0)
+        try:
+            torch.linalg.cholesky(Qc_inv.tensor)
+        except RuntimeError:
+            raise ValueError("Qc_inv must be positive definite.") from None
+        self.Qc_inv, self.dt = Qc_inv, dt
+
+    def aux_vars(self):
+        return [self.Qc_inv, self.dt]
+
+    def sqrt_diag(self, dim):
+        raise NotImplementedError("GPCostWeight is a full matrix: it weights through weight_jacobians_and_error()")
+
+    def cost_weight_matrix(self) -> torch.Tensor:
+        Q, dt = self.Qc_inv.tensor, self.dt.tensor.view(-1, 1, 1)
+        q11, q12, q22 = 12.0 * dt.pow(-3.0) * Q, -6.0 * dt.pow(-2.0) * Q, 4.0 * dt.reciprocal() * Q
+        W = torch.cat([torch.cat([q11, q12], dim=2), torch.cat([q12, q22], dim=2)], dim=1)
+        return torch.linalg.cholesky(W.transpose(-2, -1)).transpose(-2, -1)
+
+    def weight_error(self, error: torch.Tensor) -> torch.Tensor:
+        return (self.cost_weight_matrix() @ error.unsqueeze(2)).squeeze(2)
+
+    def weight_jacobians_and_error(self, jacobians: List[torch.Tensor], error: torch.Tensor):
+        U = self.cost_weight_matrix()
+        return [U @ j for j in jacobians], (U @ error.unsqueeze(2)).squeeze(2)
+
+
+class DoubleIntegrator(CostFunction):
+    """error = [pose2 - pose1 - dt vel1 ; vel2 - vel1] on Euclidean variables (double_integrator.py:48-80)."""
+
+    def __init__(self, pose1: Vector, vel1: Vector, pose2: Vector, vel2: Vector, dt, cost_weight: CostWeight,
+                 name: Optional[str] = None):
+        super().__init__(cost_weight, name)
+        for v in (pose1, vel1, pose2, vel2):
+            if not _is_euclidean(v):
+                raise ValueError(f"DoubleIntegrator: the variables must be Euclidean (Vector / Point2 / Point3) on this back end; got "
+                                 f"{type(v).__name__} ({v.name}).")
+        dof = pose1.dof()
+        if not (vel1.dof() == pose2.dof() == vel2.dof() == dof):
+            raise ValueError("All variables for a DoubleIntegrator must have the same dimension.")
+        self.dt = _as_variable(dt, dtype=pose1.dtype)
+        if self.dt.tensor.squeeze().ndim > 1:
+            raise ValueError("dt data must be a 0-D or 1-D tensor with numel in {1, batch_size}.")
+        if self.dt.tensor.ndim != 2:
+            self.dt._tensor = self.dt.tensor.view(-1, 1)
+        self.pose1, self.vel1, self.pose2, self.vel2 = pose1, vel1, pose2, vel2
+
+    def optim_vars(self):
+        return [self.pose1, self.vel1, self.pose2, self.vel2]
+
+    def aux_vars(self):
+        aux = [self.dt]
+        return aux + [v for v in self.weight.aux_vars() if v is not self.dt]
+
+    def dim(self) -> int:
+        return 2 * self.pose1.dof()
+
+    def error(self) -> torch.Tensor:
+        dt = self.dt.tensor.view(-1, 1)
+        return torch.cat([self.pose1.local(self.pose2) - dt * self.vel1.tensor, self.vel2.tensor - self.vel1.tensor], dim=1)
+
+    def jacobians(self):
+        err = self.error()
+        B, dof = err.shape[0], self.pose1.dof()
+        eye = torch.eye(dof, dtype=err.dtype, device=err.device).expand(B, dof, dof)
+        zero = torch.zeros_like(eye)
+        dt = self.dt.tensor.view(-1, 1, 1)
+        return [torch.cat([-eye, zero], dim=1), torch.cat([-dt * eye, -eye], dim=1), torch.cat([eye, zero], dim=1),
+                torch.cat([zero, eye], dim=1)], err
+
+    def weighted_error(self) -> torch.Tensor:
+        if hasattr(self.weight, "weight_error"):
+            return self.weight.weight_error(self.error())
+        return super().weighted_error()
+
+    def weighted_jacobians_error(self):
+        if hasattr(self.weight, "weight_jacobians_and_error"):
+            return self.weight.weight_jacobians_and_error(*self.jacobians())
+        return super().weighted_jacobians_error()
+
+
+class GPMotionModel(DoubleIntegrator):
+    def __init__(self, pose1: Vector, vel1: Vector, pose2: Vector, vel2: Vector, dt, cost_weight: GPCostWeight,
+                 name: Optional[str] = None):
+        if not isinstance(cost_weight, GPCostWeight):
+            raise ValueError("GPMotionModel only accepts cost weights of type GPCostWeight. For other weight types, consider "
+                             "using DoubleIntegrator instead.")
+        super().__init__(pose1, vel1, pose2, vel2, dt, cost_weight, name=name)
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# the packed family: csrc/traj_kernels.hip
+# --------------------------------------------------------------------------------------------------------------------------------
+TRAJ2_TERM = np.dtype([("kind", "<i4"), ("row0", "<i4"), ("col", "<i4", (4,)), ("rows", "<i4"), ("cols", "<i4"), ("j_off", "<i8"),
+                       ("aux", "<u8", (5,)), ("aux_bstride", "<i8", (5,)), ("wdim", "<i4"), ("pad", "<i4")])
+assert TRAJ2_TERM.itemsize == 128
+
+
+def _traj2_kind(c):
+    """THX_TRAJ2_* of a cost function the fused kernels cover, else None."""
+    names, w = _names(c), _names(c.weight)
+    if "Collision2D" in names and "ScaleCostWeight" in w and "Point2" in _names(c.pose):
+        return _lib.TRAJ2_COLLISION
+    if "GPMotionModel" in names and "GPCostWeight" in w and c.pose1.dof() == 2:
+        return _lib.TRAJ2_GP
+    if "Difference" in names and ("ScaleCostWeight" in w or "DiagonalCostWeight" in w) and _is_euclidean(c.var) and c.var.dof() == 2:
+        return _lib.TRAJ2_PRIOR
+    return None
+
+
+class PackedTrajectory2D(PackedEuclidean):
+    """PackedEuclidean whose NON-differentiated evaluation is fused: ``assemble(graph=False)`` = thx_traj2_eval into persistent
+    block buffers + thx_block_assemble on them, ``error_metric`` = thx_traj2_error.  The term table holds device pointers of the
+    auxiliary tensors themselves (an SDF grid shared by every collision cost is one tensor, stored once); it is rebuilt when
+    somebody replaces one of them.  Everything differentiated (``assemble(graph=True)``, ``unrolled_step``) is the parent's."""
+
+    _DIMS = {_lib.TRAJ2_COLLISION: 1, _lib.TRAJ2_GP: 4, _lib.TRAJ2_PRIOR: 2}
+
+    def __init__(self, objective, kernels=None, order=None):
+        from .kernels import default_kernels
+        from .packed import UnsupportedObjective
+        K = kernels or default_kernels()
+        if not hasattr(K, "traj2_eval"):
+            raise UnsupportedObjective("these kernels have no fused trajectory evaluation")
+        kinds = [_traj2_kind(c) for c in objective.cost_functions.values()]
+        if not kinds or any(k is None for k in kinds):
+            raise UnsupportedObjective("HIP backend, fused 2D motion planning: every cost must be a Collision2D on a Point2 with a "
+                                       "ScaleCostWeight, a GPMotionModel with dof 2 or a Difference on a 2-dof Euclidean variable "
+                                       "with a Scale / DiagonalCostWeight.")
+        super().__init__(objective, K, order)
+        self.kinds = kinds
+        rows, r, joff, j = [], 0, [], 0
+        for c, k in zip(self.costs, kinds):
+            rows.append(r)
+            joff.append(j)
+            r += c.dim()
+            j += 2 * c.dim() * len(self.cost_vars[len(rows) - 1])
+        self.rows, self.joff, self.j_total = rows, joff, j
+        self.term_order = sorted(range(len(self.costs)), key=lambda c: kinds[c])   # (stable: by kind, then the objective's order)
+        self._aux_refs = self._aux_key = self._table = None
+        self._aux_stamp = -1
+        self._J = self._e = self._Jv = self._ev = None
+        self._asm_cache = {}
+
+    # ---- the term table ------------------------------------------------------------------------------------------------------
+    def _term_aux(self, c, kind):
+        if kind == _lib.TRAJ2_COLLISION:
+            return [c.sdf_data, c.sdf_origin, c.sdf_cell_size, c.cost_eps, c.weight.scale]
+        if kind == _lib.TRAJ2_GP:
+            return [c.dt, c.weight.dt, c.weight.Qc_inv]
+        return [c.target, c.weight.scale if "ScaleCostWeight" in _names(c.weight) else c.weight.diagonal]
+
+    def _sync_aux(self, deep: bool = False):
+        if self._table is not None and not deep and self._aux_stamp == Variable._global_updates:
+            return
+        dev, dt, B = self._state.device, self._state.dtype, self._state.shape[0]
+        tensors = [[a.tensor for a in self._term_aux(c, k)] for c, k in zip(self.costs, self.kinds)]
+        key = tuple((id(t), t.data_ptr(), t.shape[0]) for ts in tensors for t in ts) + (str(dev), B)
+        self._aux_stamp = Variable._global_updates
+        if self._table is not None and key == self._aux_key:
+            return
+        table = np.zeros(len(self.costs), TRAJ2_TERM)
+        refs = []
+        for slot, c in enumerate(self.term_order):
+            cost, kind, ts = self.costs[c], self.kinds[c], tensors[c]
+            row = table[slot]
+            row["kind"], row["row0"], row["j_off"] = kind, self.rows[c], self.joff[c]
+            cols = [self.cols[k][0] for k in self.cost_vars[c]]
+            row["col"] = cols + [-1] * (4 - len(cols))
+            expect = {_lib.TRAJ2_COLLISION: (None, 2, 1, 1, 1), _lib.TRAJ2_GP: (1, 1, 4), _lib.TRAJ2_PRIOR: (2, None)}[kind]
+            for k, (t, width) in enumerate(zip(ts, expect)):
+                per = t[0].numel()
+                if t.device != dev or t.dtype != dt:
+                    raise RuntimeError(f"{cost.name}: an auxiliary tensor lives on {t.device} / {t.dtype}, the state on {dev} / {dt}; "
+                                       "there is no CPU fallback")
+                if t.shape[0] not in (1, B) or (width is not None and per != width):
+                    raise ValueError(f"{cost.name}: auxiliary tensor of shape {tuple(t.shape)} does not fit batch {B}")
+                td = t.detach()
+                if not td.is_contiguous():
+                    td = td.contiguous()
+                    key = None   # (a private copy: look again at the next call)
+                refs.append(td)
+                row["aux"][k], row["aux_bstride"][k] = td.data_ptr(), per if t.shape[0] > 1 else 0
+            if kind == _lib.TRAJ2_COLLISION:
+                row["rows"], row["cols"] = ts[0].shape[1], ts[0].shape[2]
+            elif kind == _lib.TRAJ2_PRIOR:
+                wdim = ts[1][0].numel()
+                if wdim not in (1, 2):
+                    raise ValueError("This cost needs a 2-dimensional DiagonalCostWeight.")
+                row["wdim"] = wdim
+        self._table = torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).to(dev)
+        self._aux_refs, self._aux_key = (tensors, refs), key
+        if key is None:
+            self._aux_stamp = -1
+
+    def sync(self, force: bool = False, deep: bool = False):
+        super().sync(force, deep)
+        self._sync_aux(deep or force)
+
+    def _buffers(self):
+        B, dev, dt = self._state.shape[0], self._state.device, self._state.dtype
+        if self._J is None or self._e.shape[0] != B or self._e.device != dev or self._e.dtype != dt:
+            self._J = torch.zeros(self.j_total * B, dtype=dt, device=dev)
+            self._e = torch.zeros(B, self.m, dtype=dt, device=dev)
+            self._Jv, self._ev = [], []
+            for c, cost in enumerate(self.costs):
+                d, o = cost.dim(), self.joff[c]
+                self._Jv.append([self._J[(o + 2 * d * s) * B:(o + 2 * d * (s + 1)) * B].view(B, d, 2) for s in range(len(self.cost_vars[c]))])
+                self._ev.append(self._e[:, self.rows[c]:self.rows[c] + d])
+            self._asm_cache = {}
+
+    def _differentiated(self) -> bool:
+        return torch.is_grad_enabled() and any(v.tensor.requires_grad for v in self._tracked())
+
+    def _eval(self, state=None):
+        """thx_traj2_eval at ``state`` (default: the current one) -> (Jacobian block views, error views) of the persistent buffers"""
+        self.sync()
+        self._buffers()
+        self.K.traj2_eval(self._table, len(self.costs), self._state if state is None else state, self.n, self._J, self.j_total,
+                          self._e)
+        return self._Jv, self._ev
+
+    # ---- the overrides --------------------------------------------------------------------------------------------------------
+    def weighted_blocks(self):
+        if self._differentiated():
+            return super().weighted_blocks()
+        return self._eval()
+
+    def assemble(self, H: torch.Tensor, g: torch.Tensor, graph: bool = False):
+        if graph:
+            return super().assemble(H, g, graph=True)
+        Jv, ev = self._eval()
+        self.K.block_assemble_strided(self.asm, Jv, ev, H, g, self._asm_cache)
+        self._blocks = (Jv, ev)
+        return None
+
+    def error_metric(self, state=None, out: Optional[torch.Tensor] = None, poses=None):
+        self.sync()
+        x = state if state is not None else (poses if poses is not None else self._state)
+        err = out if out is not None else torch.empty(x.shape[0], dtype=x.dtype, device=x.device)
+        self.K.traj2_error(self._table, len(self.costs), x.detach(), self.n, err)
+        return err

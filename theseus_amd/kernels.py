@@ -4,6 +4,7 @@
 that does not depend on a GPU (batch sharding, LM control flow) can be unit-tested on CPU with a
 stand-in injected by tests/; nothing in this package provides such a stand-in.
 """
+import ctypes
 import dataclasses
 from dataclasses import dataclass
 from typing import Callable, Optional
@@ -634,6 +635,47 @@ class HipKernels:
             _lib.dtype_code(ref.dtype), _lib.stream_ptr(dev)), "thx_block_assemble")
         # keep the uploaded tables alive until the stream has consumed them
         self._keepalive = (hterm_d, gterm_d)
+
+    def block_assemble_strided(self, asm, jacobians, errors, H, g, cache):
+        """``block_assemble`` on PERSISTENT block tensors (views of buffers a kernel fills: every block row-major dim x dof, any
+        batch stride): the term tables are built and uploaded once per set of buffers and kept in the caller's ``cache``."""
+        import numpy as np
+        dev = H.device
+        key = (jacobians[0][0].data_ptr(), errors[0].data_ptr(), H.shape[0], str(dev))
+        if cache.get("key") != key:
+            for t in [J for Js in jacobians for J in Js] + list(errors):
+                if not t.is_cuda or t.stride(-1) != 1 or (t.ndim == 3 and t.stride(1) != t.shape[2]):
+                    raise RuntimeError("block_assemble_strided: blocks must be row-major tensors on a HIP device")
+            up = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1)).to(dev)  # noqa: E731
+            cache["tables"] = tuple(up(a) for a in asm.term_tables(jacobians, errors))
+            cache["key"] = key
+        ht_d, he2t_d, gt_d, ge2t_d = asm._static(dev)
+        hterm_d, gterm_d = cache["tables"]
+        _lib.check(self.lib.thx_block_assemble(
+            _lib.ptr(ht_d), _lib.ptr(hterm_d), _lib.ptr(he2t_d), asm.n_h_elems, _lib.ptr(gt_d), _lib.ptr(gterm_d), _lib.ptr(ge2t_d),
+            asm.n_g_elems, _lib.ptr(H), H.shape[-1], _lib.ptr(g), g.stride(0), H.shape[0], _lib.dtype_code(H.dtype),
+            _lib.stream_ptr(dev)), "thx_block_assemble")
+
+    # ---- 2D motion planning (csrc/traj_kernels.hip) ------------------------------------------------
+    def traj2_eval(self, table, n_terms, x, n, J, j_total, e):
+        """table: uint8 device tensor of ``n_terms`` thx_traj2_term; x (B, >= n) state; J flat block buffer (j_total * B); e (B, m)."""
+        B = x.shape[0]
+        if x.stride(1) != 1 or J.numel() < j_total * B or e.shape[0] != B or J.dtype != x.dtype or e.dtype != x.dtype:
+            raise ValueError("traj2_eval: state / block buffers do not fit")
+        if not x.is_cuda:
+            raise RuntimeError(f"traj2_eval: the state must live on a HIP device (got {x.device}); there is no CPU fallback")
+        _lib.check(self.lib.thx_traj2_eval(_lib.ptr(table), int(n_terms), ctypes.c_void_p(x.data_ptr()), x.stride(0), int(n), _lib.ptr(J),
+                                           int(j_total), _lib.ptr(e), e.stride(0), e.shape[1], B, _lib.dtype_code(x.dtype),
+                                           _lib.stream_ptr(x.device)), "thx_traj2_eval")
+
+    def traj2_error(self, table, n_terms, x, n, err):
+        B = x.shape[0]
+        if x.stride(1) != 1 or err.shape != (B,) or err.dtype != x.dtype:
+            raise ValueError("traj2_error: state / output do not fit")
+        if not x.is_cuda:
+            raise RuntimeError(f"traj2_error: the state must live on a HIP device (got {x.device}); there is no CPU fallback")
+        _lib.check(self.lib.thx_traj2_error(_lib.ptr(table), int(n_terms), ctypes.c_void_p(x.data_ptr()), x.stride(0), int(n),
+                                            _lib.ptr(err), B, _lib.dtype_code(x.dtype), _lib.stream_ptr(x.device)), "thx_traj2_error")
 
     # ---- implicit backward ----------------------------------------------------------------------
     def _retract_vjp(self, grp: PGGroup, poses, delta, step, grad_out, grad_delta):

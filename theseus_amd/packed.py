@@ -695,8 +695,9 @@ class PackedPoseGraph:
 
 def packed_for(objective: Objective, kernels=None, order=None):
     """Get (or build) the packed representation attached to an objective (``order``: variable names in column order): the fused
-    pose-graph one, or -- Euclidean variables with cost functions that hand over their Jacobian blocks -- the generic one of
-    theseus_amd/euclidean.py."""
+    pose-graph one, the fused 2D motion-planning one (theseus_amd/embodied.py: PackedTrajectory2D), or -- Euclidean variables with
+    cost functions that hand over their Jacobian blocks -- the generic one of theseus_amd/euclidean.py."""
+    from .embodied import PackedTrajectory2D
     from .euclidean import PackedEuclidean
     p = getattr(objective, "_packed", None)
     order = tuple(order) if order is not None else tuple(objective.optim_vars.keys())
@@ -708,7 +709,10 @@ def packed_for(objective: Objective, kernels=None, order=None):
             if not isinstance(objective, Objective):   # the reference's own Objective: theseus_amd/plugin.py has its generic path
                 raise
             try:
-                p = PackedEuclidean(objective, kernels, order)
+                try:
+                    p = PackedTrajectory2D(objective, kernels, order)
+                except UnsupportedObjective:
+                    p = PackedEuclidean(objective, kernels, order)
             except UnsupportedObjective:
                 raise fused_error from None
         objective._packed = p
