@@ -1,4 +1,4 @@
-"""The arithmetic of potrf_inv32_lanes (theseus_amd/csrc/chol_kernels.hip) restated in numpy, operation for operation: the in-register
+"""The arithmetic of potrf_inv32_lanes (theseus_amd/csrc/chol_potrf.cuh) restated in numpy, operation for operation: the in-register
 Cholesky of a 32 x 32 diagonal sub-block works by COLUMN operations on rows held one per lane; the wave's other 32 lanes hold the rows of
 the identity and take the same operations, which turns them into L^-T -- column r of W = L^-1 in lane 32 + r, exact zeros above the
 diagonal.  No GPU: this pins the scheme (and its fp32 error level) the kernel relies on; the kernel itself is checked against LAPACK

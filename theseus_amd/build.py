@@ -4,6 +4,7 @@ hipcc cross-compiles without a GPU.  The .so is git-ignored but travels to the G
 gpurun snapshot.  Usage:  python -m theseus_amd.build [--force]
 """
 import os
+import re
 import subprocess
 import sys
 
@@ -12,7 +13,6 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libtheseus_hip.so")
 SOURCES = ["pg_kernels.hip", "chol_kernels.hip", "pg_vjp_kernels.hip", "block_kernels.hip", "pg2_kernels.hip", "ba_kernels.hip", "pgso3_kernels.hip", "pgso2_kernels.hip", "ba_vjp_kernels.hip", "vjp_unroll_ba_kernels.hip", "lu_kernels.hip", "multi_solve_kernels.hip", "traj_kernels.hip"]
-HEADERS = ["lie.cuh", "lie_se2.cuh", "lie_so3.cuh", "pg3_generic.cuh", "vjp_se3.cuh", "unroll_se3.cuh", "unroll_g3.cuh", "unroll_ba.cuh", "vjp_so2.cuh", "dual.cuh", "robust.cuh", "common.cuh", os.path.join("..", "..", "include", "theseus_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-pass-failed"]
 
 
@@ -20,16 +20,29 @@ def _mtime(p):
     return os.path.getmtime(p) if os.path.exists(p) else 0.0
 
 
+def deps(path):
+    """`path` and every file it reaches through `#include "..."` lines, each resolved against the including file's folder."""
+    seen, todo = set(), [os.path.normpath(path)]
+    while todo:
+        f = todo.pop()
+        if f in seen:
+            continue
+        seen.add(f)
+        with open(f) as fh:
+            for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', fh.read(), re.M):
+                todo.append(os.path.normpath(os.path.join(os.path.dirname(f), inc)))
+    return seen
+
+
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    newest_hdr = max(_mtime(os.path.join(CSRC, h)) for h in HEADERS)
     objs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(LIBDIR, src.replace(".hip", ".o"))
         objs.append(o)
-        if force or _mtime(o) < max(_mtime(s), newest_hdr):
+        if force or _mtime(o) < max(_mtime(d) for d in deps(s)):
             cmd = [hipcc, *FLAGS, "-c", s, "-o", o]
             if verbose:
                 print("[theseus_amd.build]", " ".join(cmd), flush=True)

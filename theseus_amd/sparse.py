@@ -3,7 +3,7 @@
 numeric factorisation + solve per iteration, damping added to the diagonal, the factor kept for the backward pass).
 
 Dense ``n^3/3`` stops scaling beyond ~2-4 k poses (evaluations/pose_graph_synthetic.sh sweeps to 4096).  Here the
-"supernodes" are the 128-wide tile columns of the MFMA Cholesky (csrc/chol_kernels.hip):
+"supernodes" are the 128-wide tile columns of the MFMA Cholesky (csrc/chol_kernels.hip, tiles: csrc/chol_tiles.cuh):
 
 * a fill-reducing VARIABLE ORDERING (reverse Cuthill-McKee on the pose graph: a SLAM graph -- odometry chain + local loop
   closures -- becomes banded) is handed to the linearization as its ``VariableOrdering``: the packed pose buffer, the

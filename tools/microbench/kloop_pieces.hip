@@ -1,6 +1,6 @@
 // The factorisation's fp32 K-loop rebuilt piece by piece, to see which piece costs what against the bare MFMA rate
 // (tools/microbench/mfma_sustained.hip).  One workgroup = 4 waves, each wave a 32 x 128 slab of a 128 x 128 product, k-chunks
-// of 32 staged in LDS with row stride 36 words (the layout of Engine<float>::chunk in theseus_amd/csrc/chol_kernels.hip).
+// of 32 staged in LDS with row stride 36 words (the layout of Engine<float>::chunk in theseus_amd/csrc/chol_engine.cuh).
 //   mode 0: fragment reads + MFMAs, the four MFMAs of one accumulator consecutive (dependent), as the kernel writes them
 //   mode 1: the same with the four accumulators interleaved (consecutive MFMAs independent)
 //   mode 2: mode 0 + the K-loop's two barriers per chunk
