@@ -324,6 +324,43 @@ int thx_traj2_eval(const thx_traj2_term* terms, int32_t n_terms, const void* x, 
 int thx_traj2_error(const thx_traj2_term* terms, int32_t n_terms, const void* x, int64_t ldx, int32_t n, void* err,
                     int32_t B, int dtype, void* stream);
 
+/* ---- Planar pushing on SE2 (examples/tactile_pose_estimation.py): the cost family of the pose estimator in one launch.
+ *      terms[t] (DEVICE array built by the host, sorted by kind) is one cost function on the pose-major SE2 state x (V, B, 4)
+ *      = [x, y, cos, sin]; pose[s] = index of the cost's s-th optimisation variable in it (its tangent columns: 3 pose[s] ...):
+ *        THX_PUSH2_QSP      QuasiStaticPushingPlanar (theseus/embodied/motionmodel/quasi_static_pushing_planar.py), dim 3;
+ *                           variables obj1, obj2, eff1, eff2;  aux = c_square (1), weight (wdim)
+ *        THX_PUSH2_MFB      MovingFrameBetween on SE2 (theseus/embodied/measurements/moving_frame_between.py), dim 3;
+ *                           variables frame1, frame2, pose1, pose2;  aux = measurement (4), weight (wdim)
+ *        THX_PUSH2_CONTACT  EffectorObjectContactPlanar (theseus/embodied/collision/eff_obj_contact.py), dim 1; variables obj, eff;
+ *                           aux = sdf_data (rows x cols, row major), sdf_origin (2), sdf_cell_size (1), eff_radius (1), weight (1)
+ *        THX_PUSH2_PRIOR    Difference on SE2 (theseus/embodied/misc/local_cost_fn.py:16-75), dim 3;  aux = target (4), weight (wdim)
+ *      wdim = 1: ScaleCostWeight, 3: DiagonalCostWeight.  aux[k] are device pointers of the run's dtype, aux_bstride[k] their
+ *      element batch strides (0 = shared by all problems).
+ *      thx_push2_eval writes, per term and problem, the WEIGHTED Jacobian blocks and the weighted error:  block s of term t
+ *      (dim x 3, row major) of problem b starts (j_off + 3 * dim * s) * B + 3 * dim * b elements into J (each block is a
+ *      contiguous (B, dim, 3) tensor: thx_block_term / thx_grad_term can point at it), j_total = blocks' elements per problem;
+ *      e is (B, m) with row stride lde, the term's rows from row0 (the objective's row order).  Terms whose rows, pose indices
+ *      or blocks fall outside m / V / j_total are skipped.  thx_push2_error: err[b] = 0.5 * sum of the squared weighted errors,
+ *      one launch, fixed reduction order, sums in fp64.  Both compute in the run's dtype with contraction off; x must be aligned
+ *      to one record (4 elements). */
+#define THX_PUSH2_QSP 0
+#define THX_PUSH2_MFB 1
+#define THX_PUSH2_CONTACT 2
+#define THX_PUSH2_PRIOR 3
+typedef struct {
+  int32_t kind, row0;
+  int32_t pose[4]; /* index of each optimisation variable of the cost in the state (unused: -1) */
+  int32_t rows, cols; /* contact: the grid's size */
+  int64_t j_off;
+  const void* aux[5];
+  int64_t aux_bstride[5];
+  int32_t wdim, pad_;
+} thx_push2_term;
+int thx_push2_eval(const thx_push2_term* terms, int32_t n_terms, const void* x, int32_t V, void* J, int64_t j_total, void* e,
+                   int64_t lde, int32_t m, int32_t B, int dtype, const thx_se2_eps* eps, void* stream);
+int thx_push2_error(const thx_push2_term* terms, int32_t n_terms, const void* x, int32_t V, void* err, int32_t B, int dtype,
+                    const thx_se2_eps* eps, void* stream);
+
 /* ---- Objective.error_metric(): 0.5 * ||weighted error||^2 per problem (core/objective.py:37-38,
  *      562-641).  `partials` is a (B, THX_ERR_CHUNKS) scratch; the reduction order is fixed
  *      (deterministic).  err is (B). */

@@ -659,9 +659,18 @@ class Difference(CostFunction):
         return self.target.local(self.var)
 
     def jacobians(self):
-        """Euclidean variables only (local(a, b) = b - a: the identity, theseus/geometry/vector.py:150-160); the Lie-group priors
-        are evaluated by the fused pose-graph kernels."""
-        if "Vector" not in {c.__name__ for c in type(self.var).__mro__}:
+        """Euclidean variables (local(a, b) = b - a: the identity, theseus/geometry/vector.py:150-160) and SE2 (the Jacobian of
+        log, by the differentiable torch functions of theseus_amd/se2_torch.py); the other Lie-group priors are evaluated by the
+        fused pose-graph kernels only."""
+        names = {c.__name__ for c in type(self.var).__mro__}
+        if "SE2" in names:
+            from . import se2_torch
+            from .kernels import fast_approx_local_jacobians
+            err, (_, jlog) = se2_torch.local(self.target.tensor, self.var.tensor, jac=True)
+            if fast_approx_local_jacobians():   # local_cost_fn.py:43-57
+                jlog = torch.eye(3, dtype=err.dtype, device=err.device).expand(err.shape[0], 3, 3)
+            return [jlog], err
+        if "Vector" not in names:
             raise NotImplementedError(f"Difference.jacobians(): torch Jacobians exist for Euclidean variables only; got "
                                       f"{type(self.var).__name__} ({self.var.name}).")
         err = self.error()

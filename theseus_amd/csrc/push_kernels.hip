@@ -1,0 +1,378 @@
+// Planar pushing on SE2 (examples/tactile_pose_estimation.py of the reference): the cost family of the pose estimator's objective --
+// QuasiStaticPushingPlanar (theseus/embodied/motionmodel/quasi_static_pushing_planar.py), MovingFrameBetween
+// (theseus/embodied/measurements/moving_frame_between.py), EffectorObjectContactPlanar (theseus/embodied/collision/
+// eff_obj_contact.py over SignedDistanceField2D.signed_distance, signed_distance_field.py:163-241) and Difference priors on SE2
+// (theseus/embodied/misc/local_cost_fn.py:16-75) -- evaluated by ONE launch instead of one torch call chain per cost object.
+//
+// thx_push2_eval: one thread per (term, problem), problems fastest; the host sorts the terms by kind, so a wave takes one branch
+// except where two kinds meet.  The state is pose-major (V, B, 4): the wave's loads of one pose are consecutive 16-byte (fp32) /
+// 32-byte (fp64) records, each loaded as one vector.  A thread writes the WEIGHTED Jacobian blocks and the weighted error where
+// thx_block_assemble's term tables point.
+// thx_push2_error: one workgroup per problem; thread i sums the squares of terms i, i + 256, ... in fp64, then a fixed-order tree
+// over the workgroup -- deterministic, one launch, no atomics.
+//
+// Everything runs in the run's dtype with contraction off (the pragma below covers the SE2 helpers included after it) and in the
+// reference's operation order wherever a branch is decided (grid bounds, floor, d < r, Taylor switches, atan2 arguments), so a kink
+// lands where the torch classes of theseus_amd/embodied.py put it.  Registers only; LDS: the reduction of thx_push2_error.
+#pragma clang fp contract(off)
+#include "common.cuh"
+#include "lie_se2.cuh"
+
+namespace thx {
+
+constexpr int kPushErrThreads = 256;
+
+template <typename T>
+__device__ __forceinline__ T paux(const thx_push2_term& tm, int k, int b, int i = 0) {
+  return static_cast<const T*>(tm.aux[k])[(int64_t)b * tm.aux_bstride[k] + i];
+}
+
+// one pose record as ONE vector load (the record is 4 * sizeof(T) aligned: checked on the host)
+__device__ __forceinline__ SE2<float> load_pose(const float* __restrict__ x, int64_t rec) {
+  const float4 v = reinterpret_cast<const float4*>(x)[rec];
+  return SE2<float>{v.x, v.y, v.z, v.w};
+}
+__device__ __forceinline__ SE2<double> load_pose(const double* __restrict__ x, int64_t rec) {
+  const double4 v = reinterpret_cast<const double4*>(x)[rec];
+  return SE2<double>{v.x, v.y, v.z, v.w};
+}
+
+template <typename T>
+__device__ __forceinline__ SE2<T> aux_pose(const thx_push2_term& tm, int k, int b) {
+  const T* p = static_cast<const T*>(tm.aux[k]) + (int64_t)b * tm.aux_bstride[k];
+  return SE2<T>{p[0], p[1], p[2], p[3]};
+}
+
+// the 1 | 3 row weights of a Scale / DiagonalCostWeight at aux slot k
+template <typename T>
+__device__ __forceinline__ void row_weights(const thx_push2_term& tm, int k, int b, T* w) {
+  w[0] = paux<T>(tm, k, b, 0);
+  w[1] = tm.wdim == 3 ? paux<T>(tm, k, b, 1) : w[0];
+  w[2] = tm.wdim == 3 ? paux<T>(tm, k, b, 2) : w[0];
+}
+
+// R^T p (so2.py: unrotate = rotate with (cos, -sin))
+template <typename T>
+__device__ __forceinline__ void unrotate(T c, T s, T px, T py, T& rx, T& ry) {
+  const T ns = -s;
+  rx = c * px - ns * py;
+  ry = ns * px + c * py;
+}
+
+// between with the reference's Jacobian of the first argument: Ad(B^-1) (-Ad(A))  (lie_group.py:125-136,162-178); the second is I
+template <typename T>
+__device__ __forceinline__ void between_j0(const SE2<T>& A, const SE2<T>& B, SE2<T>& D, T* J0, bool want_jac) {
+  SE2<T> Ai, Bi;
+  se2_inv(A, Ai);
+  se2_mul(Ai, B, D);
+  if (!want_jac) return;
+  se2_inv(B, Bi);
+  T AdB[9], AdA[9];
+  se2_adjoint(Bi, AdB);
+  se2_adjoint(A, AdA);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) AdA[i] = -AdA[i];
+  mat3_mul(AdB, AdA, J0);
+}
+
+// D V - Vp of Zhou et al. (quasi_static_pushing_planar.py): weighted error (3) and the four weighted 3 x 3 blocks
+// (obj1, obj2, eff1, eff2), block s at J + s * jstep
+template <typename T>
+__device__ __forceinline__ void qsp_term(const thx_push2_term& tm, const SE2<T>& o1, const SE2<T>& o2, const SE2<T>& e1,
+                                         const SE2<T>& e2, int b, T* __restrict__ e, T* __restrict__ J, int64_t jstep) {
+  const T c2 = paux<T>(tm, 0, b);
+  T w[3];
+  row_weights<T>(tm, 1, b, w);
+  // contact point (eff2's xy) in the object's frame: se2.py transform_to
+  T px, py;
+  unrotate(o2.c, o2.s, e2.x - o2.x, e2.y - o2.y, px, py);
+  // V: the object's velocity in its own frame and the rotation of obj1^-1 obj2
+  T vx, vy;
+  unrotate(o2.c, o2.s, o2.x - o1.x, o2.y - o1.y, vx, vy);
+  SE2<T> o1i, od;
+  se2_inv(o1, o1i);
+  se2_mul(o1i, o2, od);
+  const T om = t_atan2(od.s, od.c);
+  // Vp: the contact point's velocity in the object's frame
+  T ux, uy;
+  unrotate(o2.c, o2.s, e2.x - e1.x, e2.y - e1.y, ux, uy);
+  const T D[3][3] = {{T(1), T(0), -py}, {T(0), T(1), px}, {-py, px, -c2}};
+  const T V[3] = {vx, vy, om};
+  const T Vp[3] = {ux, uy, T(0)};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) e[i] = ((D[i][0] * V[0] + D[i][1] * V[1] + D[i][2] * V[2]) - Vp[i]) * w[i];
+  if (!J) return;
+  // R2^T R(X) for X = obj1, obj2, eff1, eff2: d(unrotated xy difference) / d(X's translation part of the tangent)
+  auto rtr = [&](const SE2<T>& X, T* A) {
+    A[0] = o2.c * X.c + o2.s * X.s;
+    A[1] = o2.c * -X.s + o2.s * X.c;
+    A[2] = -o2.s * X.c + o2.c * X.s;
+    A[3] = -o2.s * -X.s + o2.c * X.c;
+  };
+  T A1[4], A2[4], E1[4], E2[4];
+  rtr(o1, A1);
+  rtr(o2, A2);
+  rtr(e1, E1);
+  rtr(e2, E2);
+  // dV / d var (rows: V's components, columns: the tangent)
+  const T dV1[3][3] = {{-A1[0], -A1[1], T(0)}, {-A1[2], -A1[3], T(0)}, {T(0), T(0), T(-1)}};
+  const T dV2[3][3] = {{A2[0], A2[1], vy}, {A2[2], A2[3], -vx}, {T(0), T(0), T(1)}};
+  // d(px, py) / d var
+  const T P2[2][3] = {{T(-1), T(0), py}, {T(0), T(-1), -px}};
+  const T PE[2][3] = {{E2[0], E2[1], T(0)}, {E2[2], E2[3], T(0)}};
+  // dVp / d var (third row zero)
+  const T dVp2[2][3] = {{T(0), T(0), uy}, {T(0), T(0), -ux}};
+  const T dVpE1[2][3] = {{-E1[0], -E1[1], T(0)}, {-E1[2], -E1[3], T(0)}};
+  T* J1 = J;
+  T* J2 = J + jstep;
+  T* J3 = J + 2 * jstep;
+  T* J4 = J + 3 * jstep;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    // (dD/d var[d]) V: rows (-dpy V2, dpx V2, -dpy V0 + dpx V1)
+    const T dv2[3] = {-P2[1][d] * V[2], P2[0][d] * V[2], -P2[1][d] * V[0] + P2[0][d] * V[1]};
+    const T dve[3] = {-PE[1][d] * V[2], PE[0][d] * V[2], -PE[1][d] * V[0] + PE[0][d] * V[1]};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const T DdV1 = D[i][0] * dV1[0][d] + D[i][1] * dV1[1][d] + D[i][2] * dV1[2][d];
+      const T DdV2 = D[i][0] * dV2[0][d] + D[i][1] * dV2[1][d] + D[i][2] * dV2[2][d];
+      const T vp2 = i < 2 ? dVp2[i][d] : T(0);
+      const T vpe1 = i < 2 ? dVpE1[i][d] : T(0);
+      const T vpe2 = i < 2 ? PE[i][d] : T(0);
+      J1[3 * i + d] = DdV1 * w[i];
+      J2[3 * i + d] = ((dv2[i] + DdV2) - vp2) * w[i];
+      J3[3 * i + d] = -vpe1 * w[i];
+      J4[3 * i + d] = (dve[i] - vpe2) * w[i];
+    }
+  }
+}
+
+// measurement.local(between(between(frame1, pose1), between(frame2, pose2))) with the reference's Jacobians (the chain of the
+// three betweens, moving_frame_between.py:46-64): blocks in the cost's variable order frame1, frame2, pose1, pose2
+template <typename T>
+__device__ __forceinline__ void mfb_term(const thx_push2_term& tm, const SE2<T>& f1, const SE2<T>& f2, const SE2<T>& p1,
+                                         const SE2<T>& p2, int b, const Eps2<T>& eps, T* __restrict__ e, T* __restrict__ J,
+                                         int64_t jstep) {
+  const SE2<T> meas = aux_pose<T>(tm, 0, b);
+  T w[3];
+  row_weights<T>(tm, 1, b, w);
+  const bool want = J != nullptr;
+  SE2<T> p1f, p2f, vd, mi, E;
+  T JB1[9], JB2[9], JO1[9];
+  between_j0(f1, p1, p1f, JB1, want);
+  between_j0(f2, p2, p2f, JB2, want);
+  between_j0(p1f, p2f, vd, JO1, want);
+  se2_inv(meas, mi);
+  se2_mul(mi, vd, E);
+  T xi[3], unused[9];
+  se2_log_jlog(E, eps, xi, unused, false);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) e[i] = xi[i] * w[i];
+  if (!want) return;
+  T Jf1[9];
+  mat3_mul(JO1, JB1, Jf1);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      J[3 * i + d] = Jf1[3 * i + d] * w[i];
+      J[jstep + 3 * i + d] = JB2[3 * i + d] * w[i];
+      J[2 * jstep + 3 * i + d] = JO1[3 * i + d] * w[i];
+      J[3 * jstep + 3 * i + d] = (i == d ? w[i] : T(0));
+    }
+}
+
+// |d(eff's xy in the object's frame) - r|: weighted error (1) and the two weighted 1 x 3 blocks (obj, eff)
+template <typename T>
+__device__ __forceinline__ T contact_term(const thx_push2_term& tm, const SE2<T>& obj, const SE2<T>& eff, int b,
+                                          T* __restrict__ J, int64_t jstep) {
+  const T* sdf = static_cast<const T*>(tm.aux[0]) + (int64_t)b * tm.aux_bstride[0];
+  const T ox = paux<T>(tm, 1, b, 0), oy = paux<T>(tm, 1, b, 1);
+  const T cell = paux<T>(tm, 2, b), rad = paux<T>(tm, 3, b), w = paux<T>(tm, 4, b);
+  const int R = tm.rows, C = tm.cols;
+  T px, py;
+  unrotate(obj.c, obj.s, eff.x - obj.x, eff.y - obj.y, px, py);   // se2.py:399-415
+  // signed_distance_field.py:179-187
+  const bool oob = (px < ox) || (px > (ox + (T)(C - 1.0) * cell)) || (py < oy) || (py > (oy + (T)(R - 1.0) * cell));
+  const T col = (px - ox) / cell, row = (py - oy) / cell;
+  // :198-205 (the clamp is applied before the conversion: the same indices, and no out-of-range conversion)
+  const T lr = floor(row), lc = floor(col), hr = lr + (T)1, hc = lc + (T)1;
+  auto idx = [](T v, int hi) {
+    if (!(v > (T)0)) return 0;   // (also NaN)
+    return v < (T)hi ? (int)v : hi;
+  };
+  const int lri = idx(lr, R - 1), lci = idx(lc, C - 1), hri = idx(hr, R - 1), hci = idx(hc, C - 1);
+  const T sll = sdf[(int64_t)lri * C + lci], shl = sdf[(int64_t)hri * C + lci];
+  const T slh = sdf[(int64_t)lri * C + hci], shh = sdf[(int64_t)hri * C + hci];
+  const T hrd = hr - row, hcd = hc - col, lrd = row - lr, lcd = col - lc;
+  T dist = hrd * hcd * sll + lrd * hcd * shl + hrd * lcd * slh + lrd * lcd * shh;   // :215-220
+  T j1 = (hrd * (slh - sll) + lrd * (shh - shl)) / cell;                             // :231-238
+  T j2 = (hcd * (shl - sll) + lcd * (shh - slh)) / cell;
+  if (oob) dist = (T)0, j1 = (T)0, j2 = (T)0;   // sdf_boundary_value = 0
+  const T diff = dist - rad;
+  if (J) {
+    const T sgn = dist < rad ? (T)-1 : (T)1;   // eff_obj_contact.py: both Jacobians negated where d < r
+    // d(px, py) / d obj = [[-1, 0, py], [0, -1, -px]];  d / d eff = R(obj)^T [R(eff) | 0]
+    const T g0[3] = {(T)-1, (T)0, py}, g1[3] = {(T)0, (T)-1, -px};
+    const T q00 = obj.c * eff.c + obj.s * eff.s, q01 = obj.c * -eff.s + obj.s * eff.c;
+    const T q10 = -obj.s * eff.c + obj.c * eff.s, q11 = -obj.s * -eff.s + obj.c * eff.c;
+    const T h0[3] = {q00, q01, (T)0}, h1[3] = {q10, q11, (T)0};
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      J[d] = (j1 * g0[d] + j2 * g1[d]) * sgn * w;
+      J[jstep + d] = (j1 * h0[d] + j2 * h1[d]) * sgn * w;
+    }
+  }
+  return (diff < (T)0 ? -diff : diff) * w;
+}
+
+template <typename T>
+__device__ __forceinline__ void prior_term(const thx_push2_term& tm, const SE2<T>& var, int b, const Eps2<T>& eps,
+                                           T* __restrict__ e, T* __restrict__ J) {
+  const SE2<T> target = aux_pose<T>(tm, 0, b);
+  T w[3];
+  row_weights<T>(tm, 1, b, w);
+  T Jl[9];
+  local_eval2(target, var, w, eps, e, Jl, J != nullptr);
+  if (J) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) J[i] = Jl[i];
+  }
+}
+
+__device__ __forceinline__ int push_dim(int kind) { return kind == THX_PUSH2_CONTACT ? 1 : 3; }
+__device__ __forceinline__ int push_vars(int kind) { return kind == THX_PUSH2_CONTACT ? 2 : (kind == THX_PUSH2_PRIOR ? 1 : 4); }
+
+// the kind is one of the four, every pose a term reads lies inside the state, its weight width is 1 or 3
+__device__ __forceinline__ bool push_reads_ok(const thx_push2_term& tm, int V) {
+  if (tm.kind < THX_PUSH2_QSP || tm.kind > THX_PUSH2_PRIOR) return false;
+  const int nv = push_vars(tm.kind);
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+    if (s < nv && (tm.pose[s] < 0 || tm.pose[s] >= V)) return false;
+  if (tm.kind == THX_PUSH2_CONTACT) return tm.rows >= 1 && tm.cols >= 1;
+  return tm.wdim == 1 || tm.wdim == 3;
+}
+
+// weighted error of term tm for problem b into ev (dim values); Jb != nullptr: also the weighted blocks, block s at Jb + s * jstep
+template <typename T>
+__device__ __forceinline__ void push_term(const thx_push2_term& tm, const T* __restrict__ x, int B, int b, const Eps2<T>& eps,
+                                          T* __restrict__ ev, T* __restrict__ Jb, int64_t jstep) {
+  const SE2<T> a = load_pose(x, (int64_t)tm.pose[0] * B + b);
+  if (tm.kind == THX_PUSH2_PRIOR) {
+    prior_term<T>(tm, a, b, eps, ev, Jb);
+    return;
+  }
+  const SE2<T> c = load_pose(x, (int64_t)tm.pose[1] * B + b);
+  if (tm.kind == THX_PUSH2_CONTACT) {
+    ev[0] = contact_term<T>(tm, a, c, b, Jb, jstep);
+    return;
+  }
+  const SE2<T> d = load_pose(x, (int64_t)tm.pose[2] * B + b);
+  const SE2<T> f = load_pose(x, (int64_t)tm.pose[3] * B + b);
+  if (tm.kind == THX_PUSH2_QSP)
+    qsp_term<T>(tm, a, c, d, f, b, ev, Jb, jstep);
+  else
+    mfb_term<T>(tm, a, c, d, f, b, eps, ev, Jb, jstep);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+push2_eval_kernel(const thx_push2_term* __restrict__ terms, int n_terms, const T* __restrict__ x, int V, T* __restrict__ J,
+                  int64_t j_total, T* __restrict__ e, int64_t lde, int m, int B, Eps2<T> eps) {
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (int64_t)n_terms * B) return;
+  const int t = (int)(gid / B), b = (int)(gid % B);
+  const thx_push2_term& tm = terms[t];   // (read in place: a private copy of the 128 bytes would live in scratch)
+  if (!push_reads_ok(tm, V)) return;
+  const int dim = push_dim(tm.kind), nv = push_vars(tm.kind);
+  if (tm.row0 < 0 || tm.row0 + dim > m || tm.j_off < 0 || tm.j_off + (int64_t)3 * dim * nv > j_total) return;
+  T* eb = e + (int64_t)b * lde + tm.row0;
+  T* Jb = J + tm.j_off * B + (int64_t)3 * dim * b;
+  T ev[3];
+  push_term<T>(tm, x, B, b, eps, ev, Jb, (int64_t)3 * dim * B);
+  eb[0] = ev[0];
+  if (dim == 3) eb[1] = ev[1], eb[2] = ev[2];
+}
+
+template <typename T>
+__global__ void __launch_bounds__(kPushErrThreads)
+push2_error_kernel(const thx_push2_term* __restrict__ terms, int n_terms, const T* __restrict__ x, int V, T* __restrict__ err,
+                   int B, Eps2<T> eps) {
+  __shared__ double part[kPushErrThreads];
+  const int b = blockIdx.x;
+  double acc = 0.0;
+  for (int t = threadIdx.x; t < n_terms; t += kPushErrThreads) {
+    const thx_push2_term& tm = terms[t];   // (read in place: a private copy of the 128 bytes would live in scratch)
+    if (!push_reads_ok(tm, V)) continue;
+    T ev[3] = {T(0), T(0), T(0)};
+    push_term<T>(tm, x, B, b, eps, ev, nullptr, 0);
+    acc += (double)ev[0] * (double)ev[0];
+    if (push_dim(tm.kind) == 3) acc += (double)ev[1] * (double)ev[1] + (double)ev[2] * (double)ev[2];
+  }
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = kPushErrThreads / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) err[b] = (T)(0.5 * part[0]);
+}
+
+// what both exports check on the host before any launch
+inline int push2_check(const char* who, const void* terms, int32_t n_terms, const void* x, int32_t V, int32_t B, int dtype,
+                       const thx_se2_eps* eps) {
+  if (!terms || !x || !eps) return fail(who, ": null pointer");
+  if (dtype != THX_F32 && dtype != THX_F64) return fail(who, ": bad dtype");
+  if (n_terms < 1) return fail(who, ": n_terms < 1");
+  if (B < 1) return fail(who, ": empty batch");
+  if (V < 1) return fail(who, ": V < 1");
+  const uintptr_t el = dtype == THX_F32 ? 4 : 8;
+  // (the state is read one 4-element record per load)
+  if (reinterpret_cast<uintptr_t>(terms) % 8 || reinterpret_cast<uintptr_t>(x) % (4 * el)) return fail(who, ": pointer not aligned");
+  return 0;
+}
+
+template <typename T>
+inline Eps2<T> make_eps2(const thx_se2_eps* e) {
+  return Eps2<T>{(T)e->near_zero, (T)e->d_near_zero};
+}
+
+}  // namespace thx
+
+using namespace thx;
+
+extern "C" int thx_push2_eval(const thx_push2_term* terms, int32_t n_terms, const void* x, int32_t V, void* J, int64_t j_total,
+                              void* e, int64_t lde, int32_t m, int32_t B, int dtype, const thx_se2_eps* eps, void* stream) {
+  const char* who = "thx_push2_eval";
+  if (!J || !e) return fail(who, ": null pointer");
+  if (int rc = push2_check(who, terms, n_terms, x, V, B, dtype, eps)) return rc;
+  if (m < 1 || lde < m) return fail(who, ": lde < m");
+  if (j_total < 3) return fail(who, ": j_total < 3");
+  const uintptr_t el = dtype == THX_F32 ? 4 : 8;
+  if (reinterpret_cast<uintptr_t>(J) % el || reinterpret_cast<uintptr_t>(e) % el) return fail(who, ": pointer not aligned");
+  const int64_t total = (int64_t)n_terms * B;
+  if ((total + 255) / 256 > (int64_t)INT32_MAX) return fail(who, ": grid limit exceeded (n_terms * B)");
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  THX_DISPATCH(dtype,
+               hipLaunchKernelGGL(push2_eval_kernel<float>, grid, block, 0, as_stream(stream), terms, n_terms, (const float*)x, V,
+                                  (float*)J, j_total, (float*)e, lde, m, B, make_eps2<float>(eps)),
+               hipLaunchKernelGGL(push2_eval_kernel<double>, grid, block, 0, as_stream(stream), terms, n_terms, (const double*)x, V,
+                                  (double*)J, j_total, (double*)e, lde, m, B, make_eps2<double>(eps)));
+  return check_launch(who);
+}
+
+extern "C" int thx_push2_error(const thx_push2_term* terms, int32_t n_terms, const void* x, int32_t V, void* err, int32_t B,
+                               int dtype, const thx_se2_eps* eps, void* stream) {
+  const char* who = "thx_push2_error";
+  if (!err) return fail(who, ": null pointer");
+  if (int rc = push2_check(who, terms, n_terms, x, V, B, dtype, eps)) return rc;
+  if (reinterpret_cast<uintptr_t>(err) % (dtype == THX_F32 ? 4 : 8)) return fail(who, ": pointer not aligned");
+  const dim3 grid((unsigned)B), block(kPushErrThreads);   // (B <= INT32_MAX: within the grid limit of the x dimension)
+  THX_DISPATCH(dtype,
+               hipLaunchKernelGGL(push2_error_kernel<float>, grid, block, 0, as_stream(stream), terms, n_terms, (const float*)x, V,
+                                  (float*)err, B, make_eps2<float>(eps)),
+               hipLaunchKernelGGL(push2_error_kernel<double>, grid, block, 0, as_stream(stream), terms, n_terms, (const double*)x,
+                                  V, (double*)err, B, make_eps2<double>(eps)));
+  return check_launch(who);
+}

@@ -265,6 +265,186 @@ class GPMotionModel(DoubleIntegrator):
 
 
 # --------------------------------------------------------------------------------------------------------------------------------
+# planar pushing on SE2 (examples/tactile_pose_estimation.py): torch restatements on theseus_amd/se2_torch.py of
+#   QuasiStaticPushingPlanar     theseus/embodied/motionmodel/quasi_static_pushing_planar.py
+#   MovingFrameBetween           theseus/embodied/measurements/moving_frame_between.py (SE2 only)
+#   EffectorObjectContactPlanar  theseus/embodied/collision/eff_obj_contact.py
+# They run on CPU and on the device and autograd goes through them; an objective made only of them and of Difference priors on
+# SE2 is evaluated by the fused kernels of csrc/push_kernels.hip (theseus_amd/pushing.py: PackedPlanarPushing), for which these
+# classes are the differentiable twin.
+# --------------------------------------------------------------------------------------------------------------------------------
+def _require_se2(owner, *variables):
+    for v in variables:
+        if "SE2" not in _names(v):
+            raise ValueError(f"{owner}: the poses must be SE2 on this back end; got {type(v).__name__} ({v.name}).")
+
+
+class QuasiStaticPushingPlanar(CostFunction):
+    """error = D V - Vp of the velocity-only quasi-static model (Zhou et al. 2017, Eqs. 3-7): V the object's velocity in its own
+    frame [R2^T (t_obj2 - t_obj1); angle(obj1^-1 obj2)], Vp the contact point's [R2^T (t_eff2 - t_eff1); 0], D built from the
+    contact point (eff2's xy) in obj2's frame and ``c_square``."""
+
+    def __init__(self, obj1, obj2, eff1, eff2, c_square, cost_weight: CostWeight, name: Optional[str] = None):
+        super().__init__(cost_weight, name)
+        _require_se2("QuasiStaticPushingPlanar", obj1, obj2, eff1, eff2)
+        self.obj1, self.obj2, self.eff1, self.eff2 = obj1, obj2, eff1, eff2
+        if not isinstance(c_square, (Variable, torch.Tensor)):   # (a number: on the poses' device)
+            c_square = torch.tensor(float(c_square), dtype=obj1.dtype, device=obj1.device)
+        c_square = _as_variable(c_square, dtype=obj1.dtype, name=f"csquare_{self.name}")
+        if c_square.tensor.squeeze().ndim > 1:
+            raise ValueError("c_square must be a 0-D or 1-D tensor.")
+        if c_square.tensor.ndim != 2:   # (a new Variable on a (B, 1) view: the caller's object is left as it is)
+            c_square = Variable(c_square.tensor.view(-1, 1), name=c_square.name)
+        self.c_square = c_square
+
+    def optim_vars(self):
+        return [self.obj1, self.obj2, self.eff1, self.eff2]
+
+    def aux_vars(self):
+        return [self.c_square] + self.weight.aux_vars()
+
+    def dim(self) -> int:
+        return 3
+
+    def _evaluate(self, jac: bool):
+        from . import se2_torch as S
+        o1, o2, e1, e2 = torch.broadcast_tensors(self.obj1.tensor, self.obj2.tensor, self.eff1.tensor, self.eff2.tensor)
+        R2 = o2[:, 2:]
+        cp2, J_cp2_e2 = S.xy(e2, jac=True)
+        cpo, (J_cpo_o2, J_cpo_cp2) = S.transform_to(o2, cp2, jac=True)
+        px, py = cpo[:, 0], cpo[:, 1]
+        one, zero = torch.ones_like(px), torch.zeros_like(px)
+        D = S._mat([[one, zero, -py], [zero, one, px], [-py, px, -self.c_square.tensor.view(-1).expand_as(px)]])
+        o1xy, J_o1xy = S.xy(o1, jac=True)
+        o2xy, J_o2xy = S.xy(o2, jac=True)
+        voo, (J_voo_ang, J_voo_vw) = S.unrotate(R2, o2xy - o1xy, jac=True)
+        od, (J_od_o1, J_od_o2) = S.between(o1, o2, jac=True)
+        omega, J_om = S.theta(od, jac=True)
+        V = torch.cat([voo, omega], dim=1)
+        e1xy, J_e1xy = S.xy(e1, jac=True)
+        vco, (J_vco_ang, J_vco_vcw) = S.unrotate(R2, cp2 - e1xy, jac=True)
+        Vp = torch.cat([vco, zero.unsqueeze(1)], dim=1)
+        err = (D @ V.unsqueeze(2)).squeeze(2) - Vp
+        if not jac:
+            return None, err
+        _, J_ang_o2 = S.theta(o2, jac=True)
+
+        def dD_times_V(J_cpo_var):   # (B, 2, 3) -> (B, 3, 3): column d = (dD / d var_d) V
+            dpx, dpy = J_cpo_var[:, 0], J_cpo_var[:, 1]
+            return torch.stack([-dpy * V[:, 2:3], dpx * V[:, 2:3], -dpy * V[:, 0:1] + dpx * V[:, 1:2]], dim=1)
+
+        def pad(J2):                 # (B, 2, 3) -> (B, 3, 3) with a zero third row
+            return torch.cat([J2, torch.zeros_like(J2[:, :1])], dim=1)
+        dV_o1 = torch.cat([J_voo_vw @ -J_o1xy, J_om @ J_od_o1], dim=1)
+        dV_o2 = torch.cat([J_voo_ang @ J_ang_o2 + J_voo_vw @ J_o2xy, J_om @ J_od_o2], dim=1)
+        J_cpo_e2 = J_cpo_cp2 @ J_cp2_e2
+        J_o1 = D @ dV_o1
+        J_o2 = dD_times_V(J_cpo_o2) + D @ dV_o2 - pad(J_vco_ang @ J_ang_o2)
+        J_e1 = -pad(J_vco_vcw @ -J_e1xy)
+        J_e2 = dD_times_V(J_cpo_e2) - pad(J_vco_vcw @ J_cp2_e2)
+        return [J_o1, J_o2, J_e1, J_e2], err
+
+    def error(self) -> torch.Tensor:
+        return self._evaluate(False)[1]
+
+    def jacobians(self):
+        return self._evaluate(True)
+
+
+class MovingFrameBetween(CostFunction):
+    """error = measurement.local(between(between(frame1, pose1), between(frame2, pose2))) on SE2.  NB the optimisation variables
+    are ordered frame1, frame2, pose1, pose2, and the Jacobians are the reference's: the chain of the three ``between``s
+    (moving_frame_between.py:46-64)."""
+
+    def __init__(self, frame1, frame2, pose1, pose2, measurement, cost_weight: CostWeight, name: Optional[str] = None):
+        if len({type(x).__name__ for x in (frame1, frame2, pose1, pose2, measurement)}) > 1:
+            raise ValueError("Inconsistent types between input variables.")
+        super().__init__(cost_weight, name)
+        _require_se2("MovingFrameBetween", frame1, frame2, pose1, pose2, measurement)
+        self.frame1, self.frame2, self.pose1, self.pose2, self.measurement = frame1, frame2, pose1, pose2, measurement
+
+    def optim_vars(self):
+        return [self.frame1, self.frame2, self.pose1, self.pose2]
+
+    def aux_vars(self):
+        return [self.measurement] + self.weight.aux_vars()
+
+    def dim(self) -> int:
+        return 3
+
+    def error(self) -> torch.Tensor:
+        from . import se2_torch as S
+        p1f = S.between(self.frame1.tensor, self.pose1.tensor)
+        p2f = S.between(self.frame2.tensor, self.pose2.tensor)
+        return S.local(self.measurement.tensor, S.between(p1f, p2f))
+
+    def jacobians(self):
+        from . import se2_torch as S
+        p1f, (JB1_f1, JB1_p1) = S.between(self.frame1.tensor, self.pose1.tensor, jac=True)
+        p2f, (JB2_f2, JB2_p2) = S.between(self.frame2.tensor, self.pose2.tensor, jac=True)
+        diff, (JO_1, JO_2) = S.between(p1f, p2f, jac=True)
+        err = S.local(self.measurement.tensor, diff)
+        return [JO_1 @ JB1_f1, JO_2 @ JB2_f2, JO_1 @ JB1_p1, JO_2 @ JB2_p2], err
+
+
+class EffectorObjectContactPlanar(CostFunction):
+    """error = |d - eff_radius|, d the signed distance of the effector's xy in the object's frame; both Jacobians are negated
+    where d < eff_radius (eff_obj_contact.py)."""
+
+    def __init__(self, obj, eff, sdf_origin, sdf_data, sdf_cell_size, eff_radius, cost_weight: CostWeight,
+                 name: Optional[str] = None, use_huber_loss: bool = False):
+        super().__init__(cost_weight, name)
+        _require_se2("EffectorObjectContactPlanar", obj, eff)
+        self.obj, self.eff = obj, eff
+        self.sdf_origin = SignedDistanceField2D.convert_origin(sdf_origin)
+        self.sdf_data = SignedDistanceField2D.convert_sdf_data(sdf_data)
+        self.sdf_cell_size = SignedDistanceField2D.convert_cell_size(sdf_cell_size)
+        if not isinstance(eff_radius, (Variable, torch.Tensor)):   # (a number: on the poses' device)
+            eff_radius = torch.tensor(float(eff_radius), dtype=obj.dtype, device=obj.device)
+        self.eff_radius = _as_variable(eff_radius, dtype=obj.dtype)
+        if self.eff_radius.tensor.squeeze().ndim > 1:
+            raise ValueError("eff_radius must be a 0-D or 1-D tensor.")
+        if self.eff_radius.tensor.ndim != 2:   # (a new Variable on a (B, 1) view: the caller's object is left as it is)
+            self.eff_radius = Variable(self.eff_radius.tensor.view(-1, 1), name=self.eff_radius.name)
+        self.sdf = SignedDistanceField2D(self.sdf_origin, self.sdf_cell_size, self.sdf_data)
+        if use_huber_loss:
+            raise NotImplementedError("Jacobians for huber loss are not yet implemented.")
+
+    _AUX = ("sdf_origin", "sdf_data", "sdf_cell_size", "eff_radius")
+
+    def optim_vars(self):
+        return [self.obj, self.eff]
+
+    def aux_vars(self):
+        return [getattr(self, k) for k in self._AUX] + self.weight.aux_vars()
+
+    def set_aux_var_at(self, index: int, variable: Variable):
+        """Replace the ``index``-th auxiliary variable (sdf_origin, sdf_data, sdf_cell_size, eff_radius); the SDF container
+        follows."""
+        setattr(self, self._AUX[index], variable)
+        self.sdf.update_data(self.sdf_origin, self.sdf_data, self.sdf_cell_size)
+
+    def dim(self) -> int:
+        return 1
+
+    def _distances(self):
+        from . import se2_torch as S
+        cp, J_xy = S.xy(self.eff.tensor, jac=True)
+        eo, (J_obj, J_pnt) = S.transform_to(self.obj.tensor, cp, jac=True)
+        dist, J_dist = self.sdf.signed_distance(eo.view(-1, 2, 1))
+        return dist, (J_dist @ J_obj, J_dist @ (J_pnt @ J_xy))
+
+    def error(self) -> torch.Tensor:
+        return (self._distances()[0] - self.eff_radius.tensor).abs()
+
+    def jacobians(self):
+        dist, (J_obj, J_eff) = self._distances()
+        r = self.eff_radius.tensor
+        sign = torch.where(dist < r, -torch.ones_like(dist), torch.ones_like(dist)).unsqueeze(2)
+        return [J_obj * sign, J_eff * sign], (dist - r).abs()
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
 # the packed family: csrc/traj_kernels.hip
 # --------------------------------------------------------------------------------------------------------------------------------
 TRAJ2_TERM = np.dtype([("kind", "<i4"), ("row0", "<i4"), ("col", "<i4", (4,)), ("rows", "<i4"), ("cols", "<i4"), ("j_off", "<i8"),

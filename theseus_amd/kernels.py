@@ -677,6 +677,32 @@ class HipKernels:
         _lib.check(self.lib.thx_traj2_error(_lib.ptr(table), int(n_terms), ctypes.c_void_p(x.data_ptr()), x.stride(0), int(n),
                                             _lib.ptr(err), B, _lib.dtype_code(x.dtype), _lib.stream_ptr(x.device)), "thx_traj2_error")
 
+    # ---- planar pushing on SE2 (csrc/push_kernels.hip) -----------------------------------------------
+    def push2_eval(self, table, n_terms, x, J, j_total, e):
+        """table: uint8 device tensor of ``n_terms`` thx_push2_term; x (V, B, 4) pose-major SE2 state; J flat block buffer
+        (j_total * B); e (B, m)."""
+        if x.ndim != 3 or x.shape[2] != 4 or not x.is_contiguous():
+            raise ValueError("push2_eval: the state must be a contiguous (V, B, 4) tensor")
+        V, B = x.shape[:2]
+        if J.numel() < j_total * B or e.shape[0] != B or J.dtype != x.dtype or e.dtype != x.dtype:
+            raise ValueError("push2_eval: state / block buffers do not fit")
+        if not x.is_cuda:
+            raise RuntimeError(f"push2_eval: the state must live on a HIP device (got {x.device}); there is no CPU fallback")
+        _lib.check(self.lib.thx_push2_eval(_lib.ptr(table), int(n_terms), _lib.ptr(x), V, _lib.ptr(J), int(j_total), _lib.ptr(e),
+                                           e.stride(0), e.shape[1], B, _lib.dtype_code(x.dtype), se2_eps(x.dtype),
+                                           _lib.stream_ptr(x.device)), "thx_push2_eval")
+
+    def push2_error(self, table, n_terms, x, err):
+        if x.ndim != 3 or x.shape[2] != 4 or not x.is_contiguous():
+            raise ValueError("push2_error: the state must be a contiguous (V, B, 4) tensor")
+        V, B = x.shape[:2]
+        if err.shape != (B,) or err.dtype != x.dtype:
+            raise ValueError("push2_error: state / output do not fit")
+        if not x.is_cuda:
+            raise RuntimeError(f"push2_error: the state must live on a HIP device (got {x.device}); there is no CPU fallback")
+        _lib.check(self.lib.thx_push2_error(_lib.ptr(table), int(n_terms), _lib.ptr(x), V, _lib.ptr(err), B,
+                                            _lib.dtype_code(x.dtype), se2_eps(x.dtype), _lib.stream_ptr(x.device)), "thx_push2_error")
+
     # ---- implicit backward ----------------------------------------------------------------------
     def _retract_vjp(self, grp: PGGroup, poses, delta, step, grad_out, grad_delta):
         P, B = poses.shape[:2]

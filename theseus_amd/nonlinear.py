@@ -250,9 +250,11 @@ class NonlinearLeastSquares(abc.ABC):
         unrolled = (backward_mode in (BackwardMode.UNROLL, BackwardMode.TRUNCATED) and outer_grad
                     and (self._needs_grad() or init_tensors is not None))
         if unrolled and not hasattr(packed, "unrolled_step"):
+            family = getattr(packed, "family", None)   # (a packed class that names its objective family: theseus_amd/pushing.py)
             raise NotImplementedError(
                 f"Differentiating through the iterations (backward_mode='{backward_mode.name.lower()}') needs a packer with "
-                f"unrolled_step() (generic, pose-graph and bundle-adjustment objectives have one; got {type(packed).__name__}).  "
+                f"unrolled_step() (generic, pose-graph and bundle-adjustment objectives have one; got {type(packed).__name__}"
+                + (f", the {family} objective family" if family else "") + ").  "
                 "Use backward_mode='implicit', or call under torch.no_grad().")
         if unrolled and isinstance(self, TrustRegion):
             raise NotImplementedError("differentiable iterations (backward_mode='unroll' / 'truncated' with gradients): Gauss-Newton / "
@@ -675,7 +677,9 @@ class NonlinearLeastSquares(abc.ABC):
             from .ba import ba_implicit_step
             with torch.set_grad_enabled(outer_grad):
                 return ba_implicit_step(self, packed, float(step), kwargs)
-        if packed.group == "Euclidean":   # generic objectives: theseus_amd/euclidean.py (torch forms g, cached-factor solve)
+        # generic objectives: theseus_amd/euclidean.py (torch forms g, cached-factor solve); a packed class of another group that
+        # brings its own ``implicit_step`` says so (theseus_amd/pushing.py)
+        if packed.group == "Euclidean" or getattr(packed, "own_implicit_step", False):
             with torch.set_grad_enabled(outer_grad):
                 return packed.implicit_step(self, float(step), kwargs)
         with torch.set_grad_enabled(outer_grad):

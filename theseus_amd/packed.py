@@ -695,13 +695,15 @@ class PackedPoseGraph:
 
 def packed_for(objective: Objective, kernels=None, order=None):
     """Get (or build) the packed representation attached to an objective (``order``: variable names in column order): the fused
-    pose-graph one, the fused 2D motion-planning one (theseus_amd/embodied.py: PackedTrajectory2D), or -- Euclidean variables with
+    pose-graph one, the fused planar-pushing one (theseus_amd/pushing.py: PackedPlanarPushing), the fused 2D motion-planning one
+    (theseus_amd/embodied.py: PackedTrajectory2D), or -- Euclidean variables with
     cost functions that hand over their Jacobian blocks -- the generic one of theseus_amd/euclidean.py."""
     from .embodied import PackedTrajectory2D
     from .euclidean import PackedEuclidean
+    from .pushing import PackedPlanarPushing
     p = getattr(objective, "_packed", None)
     order = tuple(order) if order is not None else tuple(objective.optim_vars.keys())
-    if (p is None or not isinstance(p, (PackedPoseGraph, PackedEuclidean)) or p.version != objective.current_version
+    if (p is None or not isinstance(p, (PackedPoseGraph, PackedEuclidean, PackedPlanarPushing)) or p.version != objective.current_version
             or (kernels is not None and p.K is not kernels) or p.order != order):
         try:
             p = PackedPoseGraph(objective, kernels, order)
@@ -710,9 +712,12 @@ def packed_for(objective: Objective, kernels=None, order=None):
                 raise
             try:
                 try:
-                    p = PackedTrajectory2D(objective, kernels, order)
+                    p = PackedPlanarPushing(objective, kernels, order)
                 except UnsupportedObjective:
-                    p = PackedEuclidean(objective, kernels, order)
+                    try:
+                        p = PackedTrajectory2D(objective, kernels, order)
+                    except UnsupportedObjective:
+                        p = PackedEuclidean(objective, kernels, order)
             except UnsupportedObjective:
                 raise fused_error from None
         objective._packed = p
