@@ -241,6 +241,21 @@ typedef struct {
                             * columns [32 c, +32) of tril(L) can be non-zero (thx_hblock_fill_mask).  The fp32 column-by-column
                             * dense-frame factorisation skips the K-loop block products whose operand sub-block is zero there
                             * (thx_chol_schedule.skip_zero_blocks); every other schedule ignores it.  NULL = no skipping. */
+  /* ROW GROUPS of the fp32 column pairs (thx_chol_schedule.regroup_rows; theseus_amd/compiler.py:RowGroups), all NULL / 0 = none.
+   * Row r of the natural-order factor is zero left of first[r], the first non-zero column of row r of H.  The rows below column pair
+   * (j, j + 1), j even, j + 2 < ntiles, are sorted by first[r] (stable: a variable's rows stay adjacent) and cut into GROUPS of
+   * THX_TILE rows; one workgroup produces a group's rows of block columns j, j + 1 and starts its K-loop at the group's first
+   * non-zero 32-column chunk.  A pair whose groups would all start at chunk 0 (j = 0 always) has no groups and keeps natural tiles. */
+  const int32_t* rg_group_ptr_host; /* HOST (npairs + 1), npairs = (ntiles - 1) / 2: the groups of pair j / 2 are
+                                     * [rg_group_ptr_host[j / 2], rg_group_ptr_host[j / 2 + 1]) (empty: natural tiles) */
+  const int32_t* rg_rows;           /* DEVICE (groups, THX_TILE): the matrix row of every slot of a group, -1 = no row (behind the last) */
+  const int32_t* rg_k0;             /* DEVICE (groups): first k-chunk of the group's K-loop, min(min first / 32, 4 j) */
+  const int32_t* rg_tile_ptr;       /* DEVICE (2 groups + 1): the pieces of (group g, block column j + s), s = 0 / 1, are */
+  const int32_t* rg_piece_blk;      /*   [rg_tile_ptr[2 g + s], rg_tile_ptr[2 g + s + 1]) of rg_piece_blk / rg_piece_rc -- as */
+  const int32_t* rg_piece_rc;       /*   piece_blk / piece_rc, the row relative to the group's slot 0 (a variable whose rows straddle
+                                     *   two groups is listed in both and clipped) */
+  int32_t rg_max_tile_pieces;       /* the largest piece count of one (group, block column): above thx_chol_schedule.
+                                     * hb_scatter_max_pieces a layout whose tiles are added by the matrix cores is not regrouped */
 } thx_hblock_layout;
 /*      thx_hblock_fill_mask: HOST-ONLY (no device is touched) -- the table behind thx_hblock_layout.l_mask.  blocks: host (nblocks, 2)
  *      int32 pairs (row variable p, column variable q), q <= p, the non-zero bd x bd blocks of tril(H) in any order.  Runs the
@@ -424,7 +439,12 @@ int thx_se3_retract(const void* poses, const void* delta, int64_t ldd, double st
  *          pattern, not right-looking) whose layout carries l_mask leave out the K-loop MFMAs of every 32 x 32 output block whose row
  *          or column operand sub-block of L is structurally zero at that k-chunk (the column-pair kernel, chol_offdiag2_f32_kernel).
  *          The skipped products are exact zeros: the factor is the same (up to the sign of a zero).  1 on, 0 off, < 0: the default
- *          (on). */
+ *          (on).
+ *        regroup_rows: where skip_zero_blocks is in effect and the layout carries row groups (thx_hblock_layout.rg_*), the column-pair
+ *          kernel takes the rows below a pair group by group instead of tile by tile and leaves out every k-chunk in front of the
+ *          group's first non-zero one -- loads, staging and barriers included.  Each output element receives the same products in
+ *          the same order: the factor is the same (up to the sign of a zero).  1 on, 0 off, < 0: the default (on);
+ *          skip_zero_blocks = 0 turns it off too. */
 typedef struct {
   int32_t split_diag_min_batch;
   int32_t column_pairs;
@@ -435,14 +455,15 @@ typedef struct {
   int32_t column_pairs_min_batch;
   int32_t right_looking_mode;
   int32_t skip_zero_blocks;
+  int32_t regroup_rows;
 } thx_chol_schedule;
 
 /* ---- thx_chol_plan: HOST-ONLY query (no device is touched, no GPU needed) -- the schedule a DENSE-frame factorisation
  *      (thx_chol_factor, thx_chol_factor_forward with has_rhs != 0, thx_chol_factor_hblocks with layout != NULL and no tile pattern)
  *      with these arguments takes: the same decision function the factorisation runs.  has_damping: a damping vector is given;
  *      ldv: row stride of rhs / y (with has_rhs; y assumed 16-byte aligned, as every torch allocation is); layout: only its host
- *      fields are read (bd, max_tile_pieces, whether diag_blk is set).  For tests and tools that must know which kernels a call
- *      reaches. */
+ *      fields are read (bd, max_tile_pieces, rg_max_tile_pieces, whether diag_blk / l_mask / the rg_ tables are set).  For tests
+ *      and tools that must know which kernels a call reaches. */
 typedef struct {
   int32_t right_looking;       /* 1: the right-looking schedule */
   int32_t right_looking_mode;  /* its launch arrangement (thx_chol_schedule.right_looking_mode), -1 when left-looking */
@@ -452,6 +473,7 @@ typedef struct {
   int32_t f64_half_cols;       /* fp64: block columns whose off-diagonal tiles come from chol_offdiag_f64h_kernel */
   int32_t f64_wide_cols;       /* fp64: ... from chol_offdiag_f64w8_kernel */
   int32_t forward_fused;       /* has_rhs: 1 the forward substitution rides in the factorisation's kernels, 0 a kernel of its own */
+  int32_t regroup_rows;        /* 1: the column pairs that have row groups take them (thx_chol_schedule.regroup_rows) */
 } thx_chol_plan_info;
 int thx_chol_plan(int32_t n, int64_t ld, int32_t B, int dtype, int has_damping, int has_rhs, int64_t ldv,
                   const thx_hblock_layout* layout, const thx_chol_schedule* schedule, thx_chol_plan_info* out);

@@ -182,6 +182,7 @@ class HessianBlocks:
         self.bstride = (self.elems + 3) // 4 * 4     # elements per problem (16-byte aligned in fp32)
         self._dev = {}
         self._l_mask = None
+        self._row_groups = None
 
     def l_mask(self) -> np.ndarray:
         """(ntiles, 4 * ntiles) int32: bit s of [t, c] set when the 32x32 sub-block (rows 128 t + 32 s, columns 32 c) of the
@@ -189,6 +190,13 @@ class HessianBlocks:
         if self._l_mask is None:
             self._l_mask = _lib.hblock_fill_mask(self.blocks, self.nvars, self.bd)
         return self._l_mask
+
+    def row_groups(self) -> Optional["RowGroups"]:
+        """The regrouped rows of the fp32 column pairs (thx_hblock_layout.rg_*), None when no pair would start a K-loop late."""
+        if self._row_groups is None:
+            rg = RowGroups(self)
+            self._row_groups = rg if rg.ngroups > 0 else False
+        return self._row_groups or None
 
     def on(self, device) -> "DeviceHessianBlocks":
         key = str(device)
@@ -223,6 +231,141 @@ class HessianBlocks:
         return H
 
 
+class RowGroups:
+    """Rows below every fp32 column pair regrouped by their first non-zero column (thx_hblock_layout.rg_*).
+
+    Row r of the natural-order factor is zero left of ``first[r]``, the first non-zero column of row r of H (L fills inside the
+    envelope of H only).  In the column-pair kernel every row of L is independent, so the rows below pair (j, j + 1) -- j even,
+    j + 2 < ntiles -- need not be dealt to workgroups tile by tile: they are sorted by ``first`` (stable: a variable's rows stay
+    adjacent and in order), cut into groups of 128, and a group's K-loop starts at chunk ``k0 = min(min first // 32, 4 j)``.
+    The rows of a variable that the pair's lower edge cuts (128 is no multiple of 6) move up to slot 0 of their group -- or of
+    the nearest group before it whose slot 0 no straddling variable holds -- so that the missing part of its blocks falls in
+    front of slot 0 and is clipped like any straddling piece.  A pair whose groups all start at chunk 0 keeps its natural tiles
+    (no groups).
+
+    group_ptr  (npairs + 1)      groups of pair j / 2: [group_ptr[j / 2], group_ptr[j / 2 + 1])
+    rows       (ngroups, 128)    matrix row of every slot, -1 behind the last row
+    k0         (ngroups)         first 32-column chunk of the group's K-loop
+    tile_ptr   (2 ngroups + 1)   pieces of (group g, column tile j + s): [tile_ptr[2 g + s], tile_ptr[2 g + s + 1])
+    piece_blk, piece_rc          as HessianBlocks', the row relative to the group's slot 0
+    """
+
+    def __init__(self, hb: "HessianBlocks"):
+        d, P, nt = hb.bd, hb.nvars, hb.ntiles
+        n = d * P
+        firstp = np.arange(P)
+        by_row = [[] for _ in range(P)]
+        for k, (a, b) in enumerate(hb.blocks.tolist()):
+            firstp[a] = min(firstp[a], b)
+            by_row[a].append((b, k))
+        self.first = np.repeat(d * firstp, d)           # (n) first non-zero column of every row of H (and of L)
+        self.npairs = max(0, (nt - 1) // 2)
+        group_ptr, rows, k0s, tile_ptr, pblk, prc = [0], [], [], [0], [], []
+        self.max_tile_pieces = 0
+        for jp in range(self.npairs):
+            j = 2 * jp
+            r0 = (j + 2) * TILE
+            rr = np.arange(r0, n)
+            srows = rr[np.argsort(self.first[rr], kind="stable")]
+            if r0 % d:   # the variable cut by the pair's lower edge: nothing may sit in the slots in front of its rows
+                head = srows // d == r0 // d
+                g = int(np.argmax(head)) // TILE
+                while g > 0 and not head[TILE * g] and srows[TILE * g] % d:   # (a variable straddling into group g has its slot 0)
+                    g -= 1
+                rest = srows[~head]
+                cut = int((~head[:TILE * g]).sum())
+                srows = np.concatenate([rest[:cut], srows[head], rest[cut:]])
+            assert self._slots_ok(srows, d)
+            ng = (srows.size + TILE - 1) // TILE
+            k0 = [min(int(self.first[srows[TILE * g:TILE * g + TILE]].min()) // 32, 4 * j) for g in range(ng)]
+            if max(k0) == 0:
+                group_ptr.append(group_ptr[-1])
+                continue
+            for g in range(ng):
+                slots = srows[TILE * g:TILE * g + TILE]
+                rows.append(np.concatenate([slots, np.full(TILE - slots.size, -1)]))
+                k0s.append(k0[g])
+                pose = slots // d
+                starts = [s for s in range(slots.size) if s == 0 or pose[s] != pose[s - 1]]
+                for tj in (j, j + 1):
+                    cnt = 0
+                    for s in starts:
+                        s0 = s - int(slots[s]) % d       # slot of the variable's row 0 (negative: it starts in the group before)
+                        for q, k in by_row[int(pose[s])]:
+                            c0 = d * q - TILE * tj
+                            if c0 + d > 0 and c0 < TILE:
+                                pblk.append(k)
+                                prc.append(((s0 & 0xFFFF) << 16) | (c0 & 0xFFFF))
+                                cnt += 1
+                    tile_ptr.append(tile_ptr[-1] + cnt)
+                    self.max_tile_pieces = max(self.max_tile_pieces, cnt)
+            group_ptr.append(group_ptr[-1] + ng)
+        self.ngroups = group_ptr[-1]
+        self.group_ptr = np.array(group_ptr, dtype=np.int32)
+        self.rows = np.array(rows, dtype=np.int32).reshape(-1, TILE)
+        self.k0 = np.array(k0s, dtype=np.int32)
+        self.tile_ptr = np.array(tile_ptr, dtype=np.int32)
+        self.piece_blk = np.array(pblk, dtype=np.int32)
+        self.piece_rc = np.array(prc, dtype=np.int64).astype(np.uint32).view(np.int32)
+        self._hb = hb
+
+    @staticmethod
+    def _slots_ok(srows: np.ndarray, d: int) -> bool:
+        """A piece lands all d rows of its block on consecutive slots: a run of a variable's rows may begin behind the variable's
+        row 0 only at slot 0 of a group and end before its last row only at a group's last slot (what falls outside is clipped)."""
+        r = srows.tolist()
+        for s in range(len(r)):
+            begins = s == 0 or s % TILE == 0 or r[s - 1] != r[s] - 1 or r[s] % d == 0
+            ends = s == len(r) - 1 or s % TILE == TILE - 1 or r[s + 1] != r[s] + 1 or r[s] % d == d - 1
+            if (begins and r[s] % d and s % TILE) or (ends and r[s] % d != d - 1 and s % TILE != TILE - 1 and s != len(r) - 1):
+                return False
+        return True
+
+    def expand(self, Hc: np.ndarray, ld: int) -> np.ndarray:
+        """(B, bstride) -> dense (B, ld, ld), the way the regrouped column-pair workgroups gather it: rows [128 (j + 2), n) of
+        column tiles j, j + 1 of every regrouped pair, group by group, piece by piece (everything else stays zero)."""
+        B, d = Hc.shape[0], self._hb.bd
+        H = np.zeros((B, ld, ld), dtype=Hc.dtype)
+        for jp in range(self.npairs):
+            for g in range(self.group_ptr[jp], self.group_ptr[jp + 1]):
+                for s in range(2):
+                    tj = 2 * jp + s
+                    for pc in range(self.tile_ptr[2 * g + s], self.tile_ptr[2 * g + s + 1]):
+                        rc = int(self.piece_rc[pc]) & 0xFFFFFFFF
+                        r0 = int(np.array(rc >> 16, dtype=np.uint16).view(np.int16))
+                        c0 = int(np.array(rc & 0xFFFF, dtype=np.uint16).view(np.int16))
+                        blk = Hc[:, self.piece_blk[pc] * d * d:(self.piece_blk[pc] + 1) * d * d].reshape(B, d, d)
+                        for e in range(d * d):
+                            r, c = r0 + e // d, c0 + e % d
+                            if 0 <= r < TILE and 0 <= c < TILE and self.rows[g, r] >= 0:
+                                H[:, self.rows[g, r], TILE * tj + c] = blk[:, e // d, e % d]
+        return H
+
+    def skipped_fraction(self, l_mask: np.ndarray):
+        """Model: the share of the pair K-loops' 32x32 block products (chol_offdiag2_f32_kernel: per row tile and k-chunk four waves
+        times the four + four sub-blocks of tiles j, j + 1) that the regrouped schedule leaves out -- the chunks in front of a
+        group's k0 and, behind it, the column-side zero sub-blocks of ``l_mask``.  Pairs without groups count with the
+        natural-tile skip (row-side and column-side masks).  Returns ({j: fraction}, fraction over all pairs)."""
+        nt = l_mask.shape[0]
+        pop = lambda m: bin(int(m) & 15).count("1")   # noqa: E731
+        per, tot_all, tot_run = {}, 0, 0
+        for jp in range(self.npairs):
+            j = 2 * jp
+            cols = [pop(l_mask[j, kc]) + pop(l_mask[j + 1, kc]) for kc in range(4 * j)]
+            allp = (nt - 2 - j) * 4 * j * 32
+            run = 0
+            if self.group_ptr[jp + 1] > self.group_ptr[jp]:
+                for g in range(self.group_ptr[jp], self.group_ptr[jp + 1]):
+                    run += sum(4 * cols[kc] for kc in range(int(self.k0[g]), 4 * j))
+            else:
+                for i in range(j + 2, nt):
+                    run += sum(pop(l_mask[i, kc]) * cols[kc] for kc in range(4 * j))
+            per[j] = 1.0 - run / allp if allp else 0.0
+            tot_all += allp
+            tot_run += run
+        return per, (1.0 - tot_run / tot_all if tot_all else 0.0)
+
+
 class DeviceHessianBlocks:
     _FIELDS = ["diag_blk", "inc_blk", "tile_ptr", "piece_blk", "piece_rc"]
 
@@ -242,4 +385,13 @@ class DeviceHessianBlocks:
         # the structurally non-zero 32x32 sub-blocks of the natural-order factor (thx_hblock_layout.l_mask), once per layout and device
         self.t["l_mask"] = torch.from_numpy(hb.l_mask()).to(device)
         c.l_mask = self.t["l_mask"].data_ptr()
+        # the row groups of the fp32 column pairs (thx_hblock_layout.rg_*); none: the fields stay NULL
+        rg = hb.row_groups()
+        if rg is not None:
+            self.rg_group_ptr_host = np.ascontiguousarray(rg.group_ptr)   # (host table: kept alive here)
+            c.rg_group_ptr_host = self.rg_group_ptr_host.ctypes.data
+            for f in ("rows", "k0", "tile_ptr", "piece_blk", "piece_rc"):
+                self.t["rg_" + f] = torch.from_numpy(np.ascontiguousarray(getattr(rg, f))).to(device)
+                setattr(c, "rg_" + f, self.t["rg_" + f].data_ptr())
+            c.rg_max_tile_pieces = rg.max_tile_pieces
         self.c = c

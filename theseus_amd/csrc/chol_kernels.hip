@@ -142,6 +142,7 @@ struct FactorPlan {
   bool rl_fwd_fused;     // ... with the forward substitution riding on it (else FACTOR_NEEDS_FORWARD)
   bool colpair;          // (left-looking) the column-pair schedule (fp32)
   bool zskip;            // the off-diagonal K-loops skip structurally zero 32x32 sub-blocks (HBlk.l_mask; fp32 left-looking dense frame)
+  bool regroup;          // ... and the column pairs that have row groups take them (HBlk.rg_*, thx_chol_schedule.regroup_rows)
   int hbm;               // the off-diagonal kernels' HB template argument: 0 dense H, HB_MODE_SCATTER, HB_MODE_ROUNDS
   int f64_wide_max, f64_half_max;
 };
@@ -187,6 +188,11 @@ static FactorPlan plan_factor(bool f64, int n, int64_t ld, int B, bool has_dampi
   p.schedule = Schedule::LeftLooking;
   p.colpair = column_pairs != 0 && !f64 && !tp && !packed && B >= pair_min_batch;
   p.zskip = !f64 && !tp && !packed && use_hb && hbp->l_mask != nullptr && (!sched || sched->skip_zero_blocks != 0);
+  // row groups: the pair kernel only, a layout that carries all the tables, every group's pieces within what the matrix-core
+  // scatter is allowed per tile, and row offsets anywhere in the frame that fit the buffer loads' 32-bit offsets
+  p.regroup = p.zskip && p.colpair && (!sched || sched->regroup_rows != 0) && hbp->rg_group_ptr_host && hbp->rg_rows && hbp->rg_k0 &&
+              hbp->rg_tile_ptr && hbp->rg_piece_blk && hbp->rg_piece_rc &&
+              (p.hbm != HB_MODE_SCATTER || hbp->rg_max_tile_pieces <= hb_scatter_max) && (int64_t)n * ld * 4 < ((int64_t)1 << 31);
   return p;
 }
 
@@ -252,6 +258,16 @@ struct FactorLaunch {
       with_hb_mode(P.hbm, [&](auto mode) {
         launch_lds<chol_offdiag2_f32_kernel<decltype(mode)::value>>(dev, dim3((h.nb + 7) / 8 * 8 * nrt), dim3(256), OFF2_SMEM, h.s, H_of(h),
                                                                     L_of(h), panel_of(h), n, ld, j, P.ntiles, i_first, nrt, h.nb, hb_of(h));
+      });
+  }
+  // ... of the row groups [g_first, g_first + ng) of pair j (P.regroup)
+  void pair_groups(const Half& h, int j, int g_first, int ng) const {
+    if constexpr (sizeof(T) == 4)
+      with_hb_mode(P.hbm, [&](auto mode) {
+        constexpr int M = decltype(mode)::value;
+        if constexpr (M != 0)
+          launch_lds<chol_offdiag2_f32_kernel<M, true>>(dev, dim3((h.nb + 7) / 8 * 8 * ng), dim3(256), OFF2_SMEM, h.s, H_of(h), L_of(h),
+                                                        panel_of(h), n, ld, j, P.ntiles, g_first, ng, h.nb, hb_of(h));
       });
   }
 
@@ -545,7 +561,10 @@ static int run_left_looking(const FactorLaunch<T>& c) {
       if (pair) {
         c.off(h, j, j + 1, 1);
         c.diag(h, j + 1);
-        c.pair(h, j, j + 2, ntiles - 2 - j);
+        const int32_t* gp = c.P.regroup ? c.hb.rg_group_ptr_host : nullptr;
+        const int g0 = gp ? gp[j / 2] : 0, ng = gp ? gp[j / 2 + 1] - g0 : 0;
+        if (ng > 0) c.pair_groups(h, j, g0, ng);
+        else c.pair(h, j, j + 2, ntiles - 2 - j);
         continue;
       }
       const int nrt = tp ? tp->col_count_host[j] : ntiles - 1 - j;   // (tile-sparse: the column's non-zero row tiles)
@@ -596,6 +615,7 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
                   packed ? tp->nslots : 0, lpt, ls ? ls->ent_col : nullptr, ls ? ls->tile_valid : nullptr};
   HBlk hb = use_hb ? *hbp : HBlk{};
   if (!P.zskip) hb.l_mask = nullptr;
+  if (!P.regroup) hb.rg_rows = hb.rg_k0 = hb.rg_tile_ptr = hb.rg_piece_blk = hb.rg_piece_rc = nullptr;
   std::lock_guard<std::mutex> guard(g_launch_mutex);
   const int dev = current_device();
   const FactorLaunch<T> c{H, ld, n, B, damping, ellipsoidal, eps, L, panel, info, rhs, y, ldv, st, tp, ls, P, pat, use_hb, hb, packed,
@@ -727,7 +747,8 @@ static int check_rhs(const void* rhs, const void* y, int64_t ldv, int n, const c
 // the kernels' view of a block-compact Hessian: the layout's tables and the value buffer (B, bstride)
 static HBlk hblk_from(const thx_hblock_layout* layout, const void* Hc, int64_t bstride) {
   return HBlk{Hc, bstride, layout->bd, layout->tile_ptr, layout->piece_blk, layout->piece_rc, layout->diag_blk, layout->max_tile_pieces,
-              layout->l_mask};
+              layout->l_mask, layout->rg_rows, layout->rg_k0, layout->rg_tile_ptr, layout->rg_piece_blk, layout->rg_piece_rc,
+              layout->rg_group_ptr_host, layout->rg_max_tile_pieces};
 }
 
 int thx_chol_factor(const void* H, int64_t ld, int32_t n, int32_t B, const void* damping, int ellipsoidal,
@@ -813,8 +834,7 @@ int thx_chol_plan(int32_t n, int64_t ld, int32_t B, int dtype, int has_damping, 
   if (has_rhs && ldv < n) return fail("thx_chol_plan: ldv < n");
   if (dtype != THX_F32 && dtype != THX_F64) return fail("bad dtype");
   if (layout && layout->ntiles != (n + TILE - 1) / TILE) return fail("thx_chol_plan: the block layout is not this matrix's");
-  HBlk hb = layout ? hblk_from(layout, nullptr, 0) : HBlk{};   // (no data pointers: the plan reads bd, diag_blk, max_tile_pieces)
-  hb.l_mask = nullptr;                                         // (skipping zero sub-blocks is not part of the report)
+  HBlk hb = layout ? hblk_from(layout, nullptr, 0) : HBlk{};   // (no data pointers: the plan reads bd, the piece maxima, which tables are set)
   const FactorPlan p = plan_factor(dtype == THX_F64, n, ld, B, has_damping != 0, has_rhs != 0, ldv, true, nullptr,
                                    layout ? &hb : nullptr, nullptr, schedule);
   const bool rl = p.schedule == Schedule::RightLooking;
@@ -831,6 +851,7 @@ int thx_chol_plan(int32_t n, int64_t ld, int32_t B, int dtype, int has_damping, 
   out->f64_half_cols = half;
   out->f64_wide_cols = f64_lanes ? std::max(0, std::min(p.f64_wide_max, cols) - half) : 0;
   out->forward_fused = has_rhs && (!rl || p.rl_fwd_fused);
+  out->regroup_rows = p.regroup;
   return 0;
 }
 

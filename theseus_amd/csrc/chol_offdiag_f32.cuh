@@ -261,6 +261,12 @@ chol_offdiag_f32_kernel(const float* __restrict__ H, float* __restrict__ L, cons
 // Needs diag(j), tile (j + 1, j) and diag(j + 1) before it: the host launches column j's head tile alone (factor_impl).
 // LDS 76 KB (two workgroups per CU): [0, 54 KB) three staging buffers | [36 KB, 76 KB) the panel copy of the substitution in
 // progress (lands there straight from global memory after the K-loop; overlaps the third staging buffer only).
+// RG (FactorPlan.regroup, HBlk.rg_*): the workgroup's 128 rows are a ROW GROUP instead of row tile i -- the rows below the pair
+// sorted by their first non-zero column, so that the K-loop starts at the group's first non-zero chunk k0 (every row of the
+// group is zero left of it: exact zeros left out, as with the sub-block masks, but for the whole workgroup -- no loads, staging
+// stores or barriers for those chunks).  Every row of L is independent here and keeps its own products in their order: L is
+// bit-identical (up to the sign of a zero).  The group's rows come from a table (operand B's row offsets, the rows stored to),
+// its pieces of H from tables keyed by (group, block column); the row-side sub-block mask has no meaning for a group and is gone.
 // ------------------------------------------------------------------------------------------------
 constexpr int OFF2_PANEL_OFF = 2 * 128 * 36;              // floats: right behind staging buffers 0 and 1
 constexpr int OFF2_SMEM = (OFF2_PANEL_OFF + 10 * 1024) * 4;   // 76 KB
@@ -268,7 +274,7 @@ static_assert(64 * 132 <= OFF2_PANEL_OFF, "the H gather (half a tile) must not t
 static_assert(2 * 128 * 36 <= OFF2_PANEL_OFF, "staging buffers 0 and 1 must not touch the panel copy");
 static_assert(OFF2_SMEM >= 3 * 128 * 36 * 4 && 2 * OFF2_SMEM <= 160 * 1024, "three staging buffers; two workgroups per CU");
 
-template <int HB>   // (as chol_offdiag_f32_kernel)
+template <int HB, bool RG = false>   // (HB as chol_offdiag_f32_kernel; RG: i_first is the pair's first GROUP, nrow_tiles its group count)
 __global__ void __launch_bounds__(256, 2)
 chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, const float* __restrict__ panel, int n,
                          int64_t ld, int j, int ntiles, int i_first, int nrow_tiles, int B, HBlk hb) {
@@ -277,18 +283,27 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
   const int bid = blockIdx.x;
   const int xcd = bid & 7, slot = bid >> 3;
   const int b = (slot / nrow_tiles) * 8 + xcd;   // problem-major: all row tiles of a problem on ONE XCD (panel rows j, j + 1 in its L2)
-  const int i = i_first + slot % nrow_tiles;
+  const int i = i_first + slot % nrow_tiles;     // (RG: the group)
   if (b >= B) return;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t mat = (int64_t)b * ld * ld;
   const int col0 = j * TILE, row0 = i * TILE;
   const int validB = min(TILE, n - row0);
+  static_assert(!RG || HB != 0, "row groups come with a block-compact H");
+  HBlk hq = hb;   // where the workgroup's pieces of H are listed
+  if constexpr (RG) {
+    hq.tile_ptr = hb.rg_tile_ptr;
+    hq.piece_blk = hb.rg_piece_blk;
+    hq.piece_rc = hb.rg_piece_rc;
+  }
   float* sA0 = smem;
   float* sA1 = smem + 128 * 36;
   float* sB = smem + 2 * 128 * 36;
   float* Pc = smem + OFF2_PANEL_OFF;
   const int r = 32 * wave + (lane & 31), g = lane >> 5, rl = lane & 31;
-  const bool rvalid = r < validB;
+  int srow = row0 + r;   // the matrix row of this lane's row of the workgroup
+  if constexpr (RG) srow = hb.rg_rows[i * TILE + r];
+  const bool rvalid = RG ? srow >= 0 : r < validB;
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
   HBPre2<float, HB ? 2 * HB_NPRE_OFF : 1> hb2;
@@ -297,13 +312,25 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
   unsigned voff[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) voff[u] = (unsigned)(((lrow + 32 * u) * (int)ld + lc * 4) * 4);
+  // operand B's rows: RG -- the group's rows anywhere in the frame (the host checked n * ld * 4 < 2^31); a slot without a row is
+  // out of the buffer's range and reads zeros, as the rows behind the matrix do
+  unsigned voffB[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    voffB[u] = voff[u];
+    if constexpr (RG) {
+      const int rw = hb.rg_rows[i * TILE + lrow + 32 * u];
+      voffB[u] = rw < 0 ? 0x80000000u : (unsigned)((rw * (int)ld + lc * 4) * 4);
+    }
+  }
   const float* Lb = L + mat;
   const __amdgpu_buffer_rsrc_t rsA0 =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Lb + (int64_t)col0 * ld), 0, (int)(TILE * ld * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsA1 =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Lb + (int64_t)(col0 + TILE) * ld), 0, (int)(TILE * ld * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsB =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Lb + (int64_t)row0 * ld), 0, (int)(validB * ld * 4), 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Lb + (RG ? (int64_t)0 : (int64_t)row0 * ld)), 0,
+                                        (int)((RG ? n : validB) * ld * 4), 0x00020000);
   uint4 q0[4], q1[4], qb[4];
   auto gload3 = [&](int kc) __attribute__((always_inline)) {
     const int so = kc * 32 * 4;
@@ -311,7 +338,7 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
     for (int u = 0; u < 4; ++u) {
       const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(rsA0, voff[u], so, 0);
       const u32x4 c = __builtin_amdgcn_raw_buffer_load_b128(rsA1, voff[u], so, 0);
-      const u32x4 d = __builtin_amdgcn_raw_buffer_load_b128(rsB, voff[u], so, 0);
+      const u32x4 d = __builtin_amdgcn_raw_buffer_load_b128(rsB, voffB[u], so, 0);
       q0[u] = make_uint4(a.x, a.y, a.z, a.w);
       q1[u] = make_uint4(c.x, c.y, c.z, c.w);
       qb[u] = make_uint4(d.x, d.y, d.z, d.w);
@@ -329,8 +356,11 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
   Engine<float>::zero(P0);
   Engine<float>::zero(P1);
   const int nk = 4 * j;
-  if (nk > 0) gload3(0);
-  if constexpr (HB) hb2.load(hb, b, i, j, tid);
+  int k0 = 0;   // first chunk of the K-loop
+  if constexpr (RG) k0 = __builtin_amdgcn_readfirstlane(hb.rg_k0[i]);
+  if (nk > k0) gload3(k0);
+  if constexpr (RG) hb2.load_run(hq, b, 2 * i, tid);
+  else if constexpr (HB) hb2.load(hb, b, i, j, tid);
   const float* sBw = sB + 32 * wave * 36;
   // Structurally zero 32x32 sub-blocks of L (HBlk.l_mask, nullptr: none): per k-chunk the 4-bit masks of tiles j, j + 1 (the
   // column side: operand A sub-block cb, the same for the four waves) and of row tile i (the row side: this wave's operand B
@@ -346,11 +376,11 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
     if (lm) {
       nm0 = lm[j * nch + kc];
       nm1 = lm[(j + 1) * nch + kc];
-      nmi = lm[i * nch + kc];
+      if constexpr (!RG) nmi = lm[i * nch + kc];
     }
   };
-  if (nk > 0) lmask_load(0);
-  for (int kc = 0; kc < nk; ++kc) {
+  if (nk > k0) lmask_load(k0);
+  for (int kc = k0; kc < nk; ++kc) {
     const int m0 = nm0, m1 = nm1, mi = nmi;
     __syncthreads();
 #pragma unroll
@@ -365,7 +395,8 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
       gload3(kc + 1);
       lmask_load(kc + 1);
     }
-    if (!((mi >> wv) & 1)) continue;   // this wave's rows of L_i are zero at the chunk: nothing to add
+    if constexpr (!RG)
+      if (!((mi >> wv) & 1)) continue;   // this wave's rows of L_i are zero at the chunk: nothing to add
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const float4 fb = *reinterpret_cast<const float4*>(sBw + rl * 36 + 8 * ks + 4 * g);
@@ -429,7 +460,7 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
         // buffer 1): no second copy, no second barrier
         const int n0 = hb2.p1 - hb2.p0, ntot = hb2.cnt / (hb.bd * hb.bd);
         static_assert(256 * 2 * HB_NPRE_OFF + 64 * 36 <= 128 * 36, "list + overflow chunk inside staging buffer 0");
-        hb_add<float, Engine<float>::Acc, decltype(hb2), 256 * 2 * HB_NPRE_OFF>(P, hb2, hb, b, smem, sel == 0 ? 0 : n0, sel == 0 ? n0 : ntot,
+        hb_add<float, Engine<float>::Acc, decltype(hb2), 256 * 2 * HB_NPRE_OFF>(P, hb2, hq, b, smem, sel == 0 ? 0 : n0, sel == 0 ? n0 : ntot,
                                                                                sel == 0, tid);
       } else {
       __syncthreads();   // whatever read the staging buffers last is done
@@ -437,7 +468,7 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
       for (int half = 0; half < 2; ++half) {
         for (int k = tid; k < 64 * LDH / 4; k += 256) reinterpret_cast<float4*>(smem)[k] = make_float4(0.f, 0.f, 0.f, 0.f);
         __syncthreads();
-        hb2.foreach(hb, b, tid, sel, [&](int rr, int cc, float v) __attribute__((always_inline)) {
+        hb2.foreach(hq, b, tid, sel, [&](int rr, int cc, float v) __attribute__((always_inline)) {
           if ((rr >> 6) == half) smem[(rr & 63) * LDH + cc] = v;
         });
         __syncthreads();
@@ -486,7 +517,7 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
       sub_mma_sw<sb, sb>(Pc, P, X, lane);    // X_s  = W_ss P_s
     });
     if (rvalid) {
-      float* Lrow = L + mat + (int64_t)(row0 + r) * ld + jj * TILE + 4 * g;
+      float* Lrow = L + mat + (int64_t)srow * ld + jj * TILE + 4 * g;
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb)
 #pragma unroll

@@ -105,6 +105,15 @@ struct HBlk {
   // thx_hblock_layout.l_mask: (ntiles, 4 * ntiles) 4-bit masks of the structurally non-zero 32-row sub-blocks of tile t at 32-column
   // chunk c -- set by factor_impl only for the fp32 column-by-column dense-frame schedule (FactorPlan.zskip), nullptr otherwise
   const int32_t* l_mask;
+  // thx_hblock_layout.rg_*: the row groups of the fp32 column pairs (chol_offdiag2_f32_kernel<HB, true>) -- set by factor_impl only
+  // with FactorPlan.regroup, nullptr otherwise
+  const int32_t* rg_rows;
+  const int32_t* rg_k0;
+  const int32_t* rg_tile_ptr;
+  const int32_t* rg_piece_blk;
+  const int32_t* rg_piece_rc;
+  const int32_t* rg_group_ptr_host;   // (HOST table: run_left_looking sizes the launches by it; no kernel reads it)
+  int rg_max_tile_pieces;
 };
 
 // The pieces of lower tile (ti, tj) of problem b -- f(r, c, value), (r, c) relative to the tile origin and inside the tile; the
@@ -241,7 +250,11 @@ struct HBPre2 {
   }
   int tw[NPRE], tblk[NPRE], tpc[NPRE];   // (HBPre: the two phases)
   __device__ __forceinline__ void load_tables(const HBlk& hb, int ti, int tj, int tid) {
-    const int bd = hb.bd, bb = bd * bd, t = ti * (ti + 1) / 2 + tj;
+    load_tables_run(hb, ti * (ti + 1) / 2 + tj, tid);
+  }
+  // (the runs t, t + 1 of whatever tile_ptr / piece_* tables ``hb`` carries: the row groups' tables are keyed by group)
+  __device__ __forceinline__ void load_tables_run(const HBlk& hb, int t, int tid) {
+    const int bd = hb.bd, bb = bd * bd;
     p0 = hb.tile_ptr[t];
     p1 = hb.tile_ptr[t + 1];
     cnt = (hb.tile_ptr[t + 2] - p0) * bb;
@@ -281,6 +294,10 @@ struct HBPre2 {
   }
   __device__ __forceinline__ void load(const HBlk& hb, int b, int ti, int tj, int tid) {
     load_tables(hb, ti, tj, tid);
+    load_values(hb, b, tid);
+  }
+  __device__ __forceinline__ void load_run(const HBlk& hb, int b, int t, int tid) {
+    load_tables_run(hb, t, tid);
     load_values(hb, b, tid);
   }
   // f(r, c, value) for the pieces of tile ``sel`` (0 / 1)
