@@ -6,8 +6,9 @@ import pytest
 import torch
 
 from tests.helpers import load_golden
-from tests.test_traj2_host import _lm, assert_blocks_close, check_implicit_gradients, check_iterates
-from tests.traj2_common import FIXTURES, build, random_problem
+from tests.test_traj2_host import (_lm, assert_blocks_close, check_implicit_gradients, check_iterates,
+                                   run_implicit_with_nothing_to_differentiate)
+from tests.traj2_common import FIXTURES, build, random_problem, slice_aux
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -62,6 +63,26 @@ def test_kernels_match_the_torch_classes_on_a_larger_random_problem(dtype):
     compare_with_torch_classes(packed, REL[dtype])
 
 
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["f64", "f32"])
+def test_kernels_read_sliced_auxiliaries_through_their_batch_stride(dtype):
+    """B = 3, N = 4; cost_eps, the start target and sdf_data are views into larger tensors (tests/traj2_common.py: slice_aux): the
+    kernels index them by a batch stride that is not their width -- 3, 5 and 2 R C elements.  CPU twin:
+    tests/test_traj2_host.py::test_sliced_auxiliaries_are_read_in_place."""
+    import theseus_amd as th
+    g = load_golden(FIXTURES[1])
+    obj, _, _ = build(th, g, device=DEV, dtype=dtype, N=4)
+    parents = slice_aux(obj, g, device=DEV, dtype=dtype)
+    _, packed = _packed(th, obj)
+    compare_with_torch_classes(packed, REL[dtype])
+    table = packed._table
+    assert packed._aux_key is not None
+    with torch.no_grad():
+        parents["cost_eps"][:, 1] += 0.3
+        parents["sdf_data"][:, 0] *= 0.8
+    compare_with_torch_classes(packed, REL[dtype])
+    assert packed._table is table
+
+
 @pytest.mark.parametrize("fixture", FIXTURES)
 def test_fused_assemble_matches_the_reference(fixture):
     import theseus_amd as th
@@ -91,6 +112,14 @@ def test_implicit_gradients_reproduce_the_reference(fixture):
     _, opt, leaves, sol, _ = _lm(th, g, None, device=DEV, backward_mode="implicit")
     assert type(opt.linear_solver.linearization.packed).__name__ == "PackedTrajectory2D"
     check_implicit_gradients(g, leaves, sol, g["var_order"].tolist())
+
+
+def test_implicit_mode_under_no_grad_stays_fused(monkeypatch):
+    """the implicit last step with nothing to differentiate: thx_traj2_eval + the gradient thx_block_assemble formed, no torch class"""
+    import theseus_amd as th
+    g = load_golden(FIXTURES[1])
+    _, final = run_implicit_with_nothing_to_differentiate(th, g, None, "no_grad", monkeypatch, device=DEV)
+    np.testing.assert_allclose(final.cpu().numpy(), g["implicit_final"], rtol=1e-8, atol=1e-10)
 
 
 def test_the_fused_path_is_really_taken(monkeypatch):

@@ -14,7 +14,7 @@ import torch
 from tests.conftest import ROOT
 from tests.helpers import load_golden
 from tests.test_cabi_and_host import declared_symbols, lib_path  # noqa: F401  (lib_path: the session fixture that builds)
-from tests.traj2_common import ALL_CASES, FIXTURES, LM_DAMPING, LM_KW, build, classify, state_of
+from tests.traj2_common import ALL_CASES, FIXTURES, LM_DAMPING, LM_KW, build, classify, slice_aux, state_of
 
 NAMES = ("thx_traj2_eval", "thx_traj2_error")
 
@@ -234,3 +234,85 @@ def test_argument_checks_under_the_host_sanitizers(tmp_path):
                     os.path.join(b.CSRC, "traj_kernels.hip"), "-o", exe], check=True)
     run = subprocess.run([exe], capture_output=True, text=True)
     assert run.returncode == 0 and "ALL REFUSED" in run.stdout, run.stdout + run.stderr
+
+
+def assert_blocks_equal_the_torch_classes(packed, rel):
+    """the fused evaluation's blocks and errors <-> the torch classes at the same state, each to ``rel`` of its largest magnitude"""
+    Jv, ev = packed._eval()
+    for c, cost in enumerate(packed.costs):
+        jac, err = cost.weighted_jacobians_error()
+        for k, (got, want) in enumerate([(ev[c], err)] + list(zip(Jv[c], jac))):
+            assert_blocks_close(got.numpy(), want.expand_as(got).numpy(), rel, f"{cost.name} {'error' if k == 0 else f'block {k - 1}'}")
+
+
+def test_sliced_auxiliaries_are_read_in_place():
+    """Slices of larger batched tensors (dense per problem, non-contiguous as a whole) go into the term table with their own batch
+    stride: no private copy, so the table is built once and an in-place edit of the parent tensor is seen.  An auxiliary whose
+    per-problem values are NOT dense still gets its private copy, and the table is then looked at again at every call."""
+    import theseus_amd as th
+    from tests.traj2_oracle_kernels import Traj2OracleKernels
+    g = load_golden(FIXTURES[1])
+    obj, _, _ = build(th, g)
+    parents = slice_aux(obj, g)
+    lin = th.HipLinearization(obj, kernels=Traj2OracleKernels())
+    lin.linearize()
+    packed = lin.packed
+    assert type(packed).__name__ == "PackedTrajectory2D"
+    table, key = packed._table, packed._aux_key
+    assert key is not None
+    assert_blocks_equal_the_torch_classes(packed, 1e-12)
+    assert_blocks_close(lin.Atb.squeeze(2).numpy(), g["Atb"], 1e-12, "Atb")   # (the same values as the fixture's own tensors)
+    obj.error_metric()
+    packed.sync(deep=True)
+    assert packed._table is table
+    with torch.no_grad():
+        parents["cost_eps"][:, 1] += 0.3
+        parents["sdf_data"][:, 0] *= 0.8
+        parents["start"][:, 2:4] -= 0.05
+    before = lin.Atb.clone()
+    lin.linearize()
+    assert packed._table is table and float((lin.Atb - before).abs().max()) > 1e-3
+    assert_blocks_equal_the_torch_classes(packed, 1e-12)
+    # every second column of a (B, 4) tensor: one problem's two values are not adjacent
+    wide = torch.full((3, 4), -7.0, dtype=torch.float64)
+    wide[:, ::2] = torch.from_numpy(g["goal"]) + 0.1
+    obj.get_variable("goal").tensor = wide[:, ::2]
+    assert not wide[:, ::2][0].is_contiguous()
+    lin.linearize()
+    assert packed._aux_key is None and packed._table is not table
+    assert_blocks_equal_the_torch_classes(packed, 1e-12)
+    with torch.no_grad():
+        wide[:, ::2] += 0.2
+    before = lin.Atb.clone()
+    lin.linearize()   # (the copy is made again)
+    assert float((lin.Atb - before).abs().max()) > 1e-3
+    assert_blocks_equal_the_torch_classes(packed, 1e-12)
+
+
+def run_implicit_with_nothing_to_differentiate(th, g, kernels, how, monkeypatch, device="cpu"):
+    """``backward_mode="implicit"`` under no_grad (``how`` = "no_grad") or with no leaf requiring grad ("no_leaf"); every torch
+    evaluation of a cost function is refused -> (optimizer, the final state (B, n))"""
+    def refuse(*a, **kw):
+        raise AssertionError("a cost function was evaluated by torch although nothing is differentiated")
+    for cls in (th.eb.Collision2D, th.eb.DoubleIntegrator, th.Difference):
+        for method in ("error", "jacobians"):
+            monkeypatch.setattr(cls, method, refuse)
+    obj, _, _ = build(th, g, device=device)
+    opt = th.LevenbergMarquardt(obj, linearization_kwargs=dict(kernels=kernels) if kernels is not None else {}, **LM_KW)
+    with torch.set_grad_enabled(how == "no_leaf"):
+        sol, _ = th.TheseusLayer(opt).forward(None, optimizer_kwargs=dict(damping=LM_DAMPING, backward_mode="implicit"))
+    assert type(opt.linear_solver.linearization.packed).__name__ == "PackedTrajectory2D"
+    return opt, state_of(sol, g["var_order"].tolist())
+
+
+@pytest.mark.parametrize("how", ["no_grad", "no_leaf"])
+def test_implicit_mode_with_nothing_to_differentiate_stays_fused(how, monkeypatch):
+    """The implicit last step linearizes with ``graph=True``; with nothing to differentiate it is one more thx_traj2_eval, and the
+    result is the reference's state after its implicit run (check_implicit_gradients' tolerance for that state)."""
+    import theseus_amd as th
+    from tests.traj2_oracle_kernels import Traj2OracleKernels
+    g = load_golden(FIXTURES[1])
+    K = Traj2OracleKernels()
+    _, final = run_implicit_with_nothing_to_differentiate(th, g, K, how, monkeypatch)
+    assert K.calls["traj2_eval"] >= 2 and not final.requires_grad
+    np.testing.assert_allclose(final.numpy(), g["implicit_final"], rtol=1e-8, atol=1e-10)

@@ -43,6 +43,25 @@ def build(th, f, device="cpu", dtype=torch.float64, grad=False, N=N, prefix=""):
     return obj, leaves, list(obj.cost_functions.keys())
 
 
+def slice_aux(obj, f, device="cpu", dtype=torch.float64):
+    """Replace three auxiliaries of ``obj`` (built from ``f``) by views into larger tensors: one problem's values are dense, the
+    batch stride is not their width -- cost_eps a (B, 1) column of a (B, 3) tensor, the start target a (B, 2) column range of a
+    (B, 5) tensor, sdf_data ``big[:, 0]`` of a (B, 2, R, C) tensor; the rest of the parents holds values no cost should ever see.
+    -> {name: parent tensor}"""
+    B = f["poses0"].shape[0]
+
+    def parent(key, shape, index):
+        big = torch.full(shape, -7.0, dtype=dtype, device=device)
+        big[index] = torch.from_numpy(np.asarray(f[key])).to(dtype).to(device)   # (a shared (1, ...) value is broadcast)
+        obj.get_variable(key).tensor = big[index]
+        assert obj.get_variable(key).tensor.shape[0] == B and not big[index].is_contiguous() and big[index][0].is_contiguous()
+        return big
+    R, C = f["sdf_data"].shape[1:]
+    s = slice(None)
+    return {"cost_eps": parent("cost_eps", (B, 3), (s, slice(1, 2))), "start": parent("start", (B, 5), (s, slice(2, 4))),
+            "sdf_data": parent("sdf_data", (B, 2, R, C), (s, 0))}
+
+
 def state_of(values, names):
     """{variable name: (B, 2)} -> (B, n) in ``names`` order"""
     return torch.cat([values[k] for k in names], dim=1)

@@ -15,17 +15,10 @@
 // reference's operation order wherever a branch is decided (grid bounds, floor, d < r, Taylor switches, atan2 arguments), so a kink
 // lands where the torch classes of theseus_amd/embodied.py put it.  Registers only; LDS: the reduction of thx_push2_error.
 #pragma clang fp contract(off)
-#include "common.cuh"
+#include "term_family.cuh"
 #include "lie_se2.cuh"
 
 namespace thx {
-
-constexpr int kPushErrThreads = 256;
-
-template <typename T>
-__device__ __forceinline__ T paux(const thx_push2_term& tm, int k, int b, int i = 0) {
-  return static_cast<const T*>(tm.aux[k])[(int64_t)b * tm.aux_bstride[k] + i];
-}
 
 // one pose record as ONE vector load (the record is 4 * sizeof(T) aligned: checked on the host)
 __device__ __forceinline__ SE2<float> load_pose(const float* __restrict__ x, int64_t rec) {
@@ -46,9 +39,9 @@ __device__ __forceinline__ SE2<T> aux_pose(const thx_push2_term& tm, int k, int 
 // the 1 | 3 row weights of a Scale / DiagonalCostWeight at aux slot k
 template <typename T>
 __device__ __forceinline__ void row_weights(const thx_push2_term& tm, int k, int b, T* w) {
-  w[0] = paux<T>(tm, k, b, 0);
-  w[1] = tm.wdim == 3 ? paux<T>(tm, k, b, 1) : w[0];
-  w[2] = tm.wdim == 3 ? paux<T>(tm, k, b, 2) : w[0];
+  w[0] = aux_at<T>(tm, k, b, 0);
+  w[1] = tm.wdim == 3 ? aux_at<T>(tm, k, b, 1) : w[0];
+  w[2] = tm.wdim == 3 ? aux_at<T>(tm, k, b, 2) : w[0];
 }
 
 // R^T p (so2.py: unrotate = rotate with (cos, -sin))
@@ -80,7 +73,7 @@ __device__ __forceinline__ void between_j0(const SE2<T>& A, const SE2<T>& B, SE2
 template <typename T>
 __device__ __forceinline__ void qsp_term(const thx_push2_term& tm, const SE2<T>& o1, const SE2<T>& o2, const SE2<T>& e1,
                                          const SE2<T>& e2, int b, T* __restrict__ e, T* __restrict__ J, int64_t jstep) {
-  const T c2 = paux<T>(tm, 0, b);
+  const T c2 = aux_at<T>(tm, 0, b);
   T w[3];
   row_weights<T>(tm, 1, b, w);
   // contact point (eff2's xy) in the object's frame: se2.py transform_to
@@ -187,28 +180,10 @@ template <typename T>
 __device__ __forceinline__ T contact_term(const thx_push2_term& tm, const SE2<T>& obj, const SE2<T>& eff, int b,
                                           T* __restrict__ J, int64_t jstep) {
   const T* sdf = static_cast<const T*>(tm.aux[0]) + (int64_t)b * tm.aux_bstride[0];
-  const T ox = paux<T>(tm, 1, b, 0), oy = paux<T>(tm, 1, b, 1);
-  const T cell = paux<T>(tm, 2, b), rad = paux<T>(tm, 3, b), w = paux<T>(tm, 4, b);
-  const int R = tm.rows, C = tm.cols;
-  T px, py;
+  const T rad = aux_at<T>(tm, 3, b), w = aux_at<T>(tm, 4, b);
+  T px, py, dist, j1, j2;
   unrotate(obj.c, obj.s, eff.x - obj.x, eff.y - obj.y, px, py);   // se2.py:399-415
-  // signed_distance_field.py:179-187
-  const bool oob = (px < ox) || (px > (ox + (T)(C - 1.0) * cell)) || (py < oy) || (py > (oy + (T)(R - 1.0) * cell));
-  const T col = (px - ox) / cell, row = (py - oy) / cell;
-  // :198-205 (the clamp is applied before the conversion: the same indices, and no out-of-range conversion)
-  const T lr = floor(row), lc = floor(col), hr = lr + (T)1, hc = lc + (T)1;
-  auto idx = [](T v, int hi) {
-    if (!(v > (T)0)) return 0;   // (also NaN)
-    return v < (T)hi ? (int)v : hi;
-  };
-  const int lri = idx(lr, R - 1), lci = idx(lc, C - 1), hri = idx(hr, R - 1), hci = idx(hc, C - 1);
-  const T sll = sdf[(int64_t)lri * C + lci], shl = sdf[(int64_t)hri * C + lci];
-  const T slh = sdf[(int64_t)lri * C + hci], shh = sdf[(int64_t)hri * C + hci];
-  const T hrd = hr - row, hcd = hc - col, lrd = row - lr, lcd = col - lc;
-  T dist = hrd * hcd * sll + lrd * hcd * shl + hrd * lcd * slh + lrd * lcd * shh;   // :215-220
-  T j1 = (hrd * (slh - sll) + lrd * (shh - shl)) / cell;                             // :231-238
-  T j2 = (hcd * (shl - sll) + lcd * (shh - slh)) / cell;
-  if (oob) dist = (T)0, j1 = (T)0, j2 = (T)0;   // sdf_boundary_value = 0
+  sdf_bilinear<T>(sdf, tm.rows, tm.cols, aux_at<T>(tm, 1, b, 0), aux_at<T>(tm, 1, b, 1), aux_at<T>(tm, 2, b), px, py, dist, j1, j2);
   const T diff = dist - rad;
   if (J) {
     const T sgn = dist < rad ? (T)-1 : (T)1;   // eff_obj_contact.py: both Jacobians negated where d < r
@@ -296,13 +271,12 @@ push2_eval_kernel(const thx_push2_term* __restrict__ terms, int n_terms, const T
 }
 
 template <typename T>
-__global__ void __launch_bounds__(kPushErrThreads)
+__global__ void __launch_bounds__(kErrThreads)
 push2_error_kernel(const thx_push2_term* __restrict__ terms, int n_terms, const T* __restrict__ x, int V, T* __restrict__ err,
                    int B, Eps2<T> eps) {
-  __shared__ double part[kPushErrThreads];
   const int b = blockIdx.x;
   double acc = 0.0;
-  for (int t = threadIdx.x; t < n_terms; t += kPushErrThreads) {
+  for (int t = threadIdx.x; t < n_terms; t += kErrThreads) {
     const thx_push2_term& tm = terms[t];   // (read in place: a private copy of the 128 bytes would live in scratch)
     if (!push_reads_ok(tm, V)) continue;
     T ev[3] = {T(0), T(0), T(0)};
@@ -310,27 +284,7 @@ push2_error_kernel(const thx_push2_term* __restrict__ terms, int n_terms, const 
     acc += (double)ev[0] * (double)ev[0];
     if (push_dim(tm.kind) == 3) acc += (double)ev[1] * (double)ev[1] + (double)ev[2] * (double)ev[2];
   }
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = kPushErrThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) err[b] = (T)(0.5 * part[0]);
-}
-
-// what both exports check on the host before any launch
-inline int push2_check(const char* who, const void* terms, int32_t n_terms, const void* x, int32_t V, int32_t B, int dtype,
-                       const thx_se2_eps* eps) {
-  if (!terms || !x || !eps) return fail(who, ": null pointer");
-  if (dtype != THX_F32 && dtype != THX_F64) return fail(who, ": bad dtype");
-  if (n_terms < 1) return fail(who, ": n_terms < 1");
-  if (B < 1) return fail(who, ": empty batch");
-  if (V < 1) return fail(who, ": V < 1");
-  const uintptr_t el = dtype == THX_F32 ? 4 : 8;
-  // (the state is read one 4-element record per load)
-  if (reinterpret_cast<uintptr_t>(terms) % 8 || reinterpret_cast<uintptr_t>(x) % (4 * el)) return fail(who, ": pointer not aligned");
-  return 0;
+  store_half_sum(acc, err + b);
 }
 
 template <typename T>
@@ -345,15 +299,11 @@ using namespace thx;
 extern "C" int thx_push2_eval(const thx_push2_term* terms, int32_t n_terms, const void* x, int32_t V, void* J, int64_t j_total,
                               void* e, int64_t lde, int32_t m, int32_t B, int dtype, const thx_se2_eps* eps, void* stream) {
   const char* who = "thx_push2_eval";
-  if (!J || !e) return fail(who, ": null pointer");
-  if (int rc = push2_check(who, terms, n_terms, x, V, B, dtype, eps)) return rc;
-  if (m < 1 || lde < m) return fail(who, ": lde < m");
-  if (j_total < 3) return fail(who, ": j_total < 3");
-  const uintptr_t el = dtype == THX_F32 ? 4 : 8;
-  if (reinterpret_cast<uintptr_t>(J) % el || reinterpret_cast<uintptr_t>(e) % el) return fail(who, ": pointer not aligned");
-  const int64_t total = (int64_t)n_terms * B;
-  if ((total + 255) / 256 > (int64_t)INT32_MAX) return fail(who, ": grid limit exceeded (n_terms * B)");
-  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  unsigned blocks = 0;
+  // (the state is read one 4-element record per load)
+  if (int rc = family_check(who, !J || !e || !eps, terms, n_terms, x, 4, B, dtype, V < 1 ? ": V < 1" : nullptr)) return rc;
+  if (int rc = family_check_eval(who, J, j_total < 3 ? ": j_total < 3" : nullptr, e, lde, m, n_terms, B, dtype, &blocks)) return rc;
+  const dim3 grid(blocks), block(256);
   THX_DISPATCH(dtype,
                hipLaunchKernelGGL(push2_eval_kernel<float>, grid, block, 0, as_stream(stream), terms, n_terms, (const float*)x, V,
                                   (float*)J, j_total, (float*)e, lde, m, B, make_eps2<float>(eps)),
@@ -365,10 +315,9 @@ extern "C" int thx_push2_eval(const thx_push2_term* terms, int32_t n_terms, cons
 extern "C" int thx_push2_error(const thx_push2_term* terms, int32_t n_terms, const void* x, int32_t V, void* err, int32_t B,
                                int dtype, const thx_se2_eps* eps, void* stream) {
   const char* who = "thx_push2_error";
-  if (!err) return fail(who, ": null pointer");
-  if (int rc = push2_check(who, terms, n_terms, x, V, B, dtype, eps)) return rc;
+  if (int rc = family_check(who, !err || !eps, terms, n_terms, x, 4, B, dtype, V < 1 ? ": V < 1" : nullptr)) return rc;
   if (reinterpret_cast<uintptr_t>(err) % (dtype == THX_F32 ? 4 : 8)) return fail(who, ": pointer not aligned");
-  const dim3 grid((unsigned)B), block(kPushErrThreads);   // (B <= INT32_MAX: within the grid limit of the x dimension)
+  const dim3 grid((unsigned)B), block(kErrThreads);   // (B <= INT32_MAX: within the grid limit of the x dimension)
   THX_DISPATCH(dtype,
                hipLaunchKernelGGL(push2_error_kernel<float>, grid, block, 0, as_stream(stream), terms, n_terms, (const float*)x, V,
                                   (float*)err, B, make_eps2<float>(eps)),

@@ -12,43 +12,19 @@
 //
 // The geometric part (cell coordinates, bounds test, bilinear value, distance > eps test) runs in the run's dtype with
 // contraction off and in the reference's operation order, so a kink lands where the torch classes put it.
-#include "common.cuh"
+#include "term_family.cuh"
 
 namespace thx {
-
-constexpr int kTrajErrThreads = 256;
-
-template <typename T>
-__device__ inline T aux_at(const thx_traj2_term& tm, int k, int b, int i = 0) {
-  return static_cast<const T*>(tm.aux[k])[(int64_t)b * tm.aux_bstride[k] + i];
-}
 
 // Collision2D: weighted error (1) and, when J != nullptr, the weighted 1 x 2 block.
 template <typename T>
 __device__ inline T collision_term(const thx_traj2_term& tm, const T* __restrict__ x, int b, T* __restrict__ J) {
 #pragma clang fp contract(off)
-  const T px = x[tm.col[0]], py = x[tm.col[0] + 1];
   const T* sdf = static_cast<const T*>(tm.aux[0]) + (int64_t)b * tm.aux_bstride[0];
-  const T ox = aux_at<T>(tm, 1, b, 0), oy = aux_at<T>(tm, 1, b, 1);
-  const T cell = aux_at<T>(tm, 2, b), eps = aux_at<T>(tm, 3, b), w = aux_at<T>(tm, 4, b);
-  const int R = tm.rows, C = tm.cols;
-  // signed_distance_field.py:179-187
-  const bool oob = (px < ox) || (px > (ox + (T)(C - 1.0) * cell)) || (py < oy) || (py > (oy + (T)(R - 1.0) * cell));
-  const T col = (px - ox) / cell, row = (py - oy) / cell;
-  // :198-205 (the clamp is applied before the conversion: the same indices, and no out-of-range conversion)
-  const T lr = floor(row), lc = floor(col), hr = lr + (T)1, hc = lc + (T)1;
-  auto idx = [](T v, int hi) {
-    if (!(v > (T)0)) return 0;   // (also NaN)
-    return v < (T)hi ? (int)v : hi;
-  };
-  const int lri = idx(lr, R - 1), lci = idx(lc, C - 1), hri = idx(hr, R - 1), hci = idx(hc, C - 1);
-  const T sll = sdf[(int64_t)lri * C + lci], shl = sdf[(int64_t)hri * C + lci];
-  const T slh = sdf[(int64_t)lri * C + hci], shh = sdf[(int64_t)hri * C + hci];
-  const T hrd = hr - row, hcd = hc - col, lrd = row - lr, lcd = col - lc;
-  T dist = hrd * hcd * sll + lrd * hcd * shl + hrd * lcd * slh + lrd * lcd * shh;   // :215-220
-  T j1 = (hrd * (slh - sll) + lrd * (shh - shl)) / cell;                             // :231-238
-  T j2 = (hcd * (shl - sll) + lcd * (shh - slh)) / cell;
-  if (oob) dist = (T)0, j1 = (T)0, j2 = (T)0;   // sdf_boundary_value = 0 (collision.py:40-42)
+  const T eps = aux_at<T>(tm, 3, b), w = aux_at<T>(tm, 4, b);
+  T dist, j1, j2;
+  sdf_bilinear<T>(sdf, tm.rows, tm.cols, aux_at<T>(tm, 1, b, 0), aux_at<T>(tm, 1, b, 1), aux_at<T>(tm, 2, b), x[tm.col[0]],
+                  x[tm.col[0] + 1], dist, j1, j2);   // (outside the grid: sdf_boundary_value = 0, collision.py:40-42)
   T err = eps - dist;                           // collision.py:61-62
   if (err < (T)0) err = (T)0;
   if (dist > eps) j1 = (T)0, j2 = (T)0;         // :71-73
@@ -145,14 +121,13 @@ traj2_eval_kernel(const thx_traj2_term* __restrict__ terms, int n_terms, const T
 }
 
 template <typename T>
-__global__ void __launch_bounds__(kTrajErrThreads)
+__global__ void __launch_bounds__(kErrThreads)
 traj2_error_kernel(const thx_traj2_term* __restrict__ terms, int n_terms, const T* __restrict__ x, int64_t ldx, int n,
                    T* __restrict__ err) {
-  __shared__ double part[kTrajErrThreads];
   const int b = blockIdx.x;
   const T* xb = x + (int64_t)b * ldx;
   double acc = 0.0;
-  for (int t = threadIdx.x; t < n_terms; t += kTrajErrThreads) {
+  for (int t = threadIdx.x; t < n_terms; t += kErrThreads) {
     const thx_traj2_term tm = terms[t];
     if (!term_reads_ok(tm, n)) continue;
     if (tm.kind == THX_TRAJ2_COLLISION) {
@@ -168,27 +143,11 @@ traj2_error_kernel(const thx_traj2_term* __restrict__ terms, int n_terms, const 
       acc += (double)ev[0] * (double)ev[0] + (double)ev[1] * (double)ev[1];
     }
   }
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = kTrajErrThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) err[b] = (T)(0.5 * part[0]);
+  store_half_sum(acc, err + b);
 }
 
-// what both exports check on the host before any launch
-inline int traj2_check(const char* who, const void* terms, int32_t n_terms, const void* x, int64_t ldx, int32_t n, int32_t B, int dtype) {
-  if (!terms || !x) return fail(who, ": null pointer");
-  if (dtype != THX_F32 && dtype != THX_F64) return fail(who, ": bad dtype");
-  if (n_terms < 1) return fail(who, ": n_terms < 1");
-  if (B < 1) return fail(who, ": empty batch");
-  if (n < 2) return fail(who, ": n < 2");
-  if (ldx < n) return fail(who, ": ldx < n");
-  const uintptr_t el = dtype == THX_F32 ? 4 : 8;
-  if (reinterpret_cast<uintptr_t>(terms) % 8 || reinterpret_cast<uintptr_t>(x) % el) return fail(who, ": pointer not aligned");
-  return 0;
-}
+// the family's own size checks: the message of the first that fails
+inline const char* traj2_bad_size(int64_t ldx, int32_t n) { return n < 2 ? ": n < 2" : (ldx < n ? ": ldx < n" : nullptr); }
 
 }  // namespace thx
 
@@ -197,15 +156,10 @@ using namespace thx;
 extern "C" int thx_traj2_eval(const thx_traj2_term* terms, int32_t n_terms, const void* x, int64_t ldx, int32_t n, void* J,
                               int64_t j_total, void* e, int64_t lde, int32_t m, int32_t B, int dtype, void* stream) {
   const char* who = "thx_traj2_eval";
-  if (!J || !e) return fail(who, ": null pointer");
-  if (int rc = traj2_check(who, terms, n_terms, x, ldx, n, B, dtype)) return rc;
-  if (m < 1 || lde < m) return fail(who, ": lde < m");
-  if (j_total < 2) return fail(who, ": j_total < 2");
-  const uintptr_t el = dtype == THX_F32 ? 4 : 8;
-  if (reinterpret_cast<uintptr_t>(J) % el || reinterpret_cast<uintptr_t>(e) % el) return fail(who, ": pointer not aligned");
-  const int64_t total = (int64_t)n_terms * B;
-  if ((total + 255) / 256 > (int64_t)INT32_MAX) return fail(who, ": grid limit exceeded (n_terms * B)");
-  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  unsigned blocks = 0;
+  if (int rc = family_check(who, !J || !e, terms, n_terms, x, 1, B, dtype, traj2_bad_size(ldx, n))) return rc;
+  if (int rc = family_check_eval(who, J, j_total < 2 ? ": j_total < 2" : nullptr, e, lde, m, n_terms, B, dtype, &blocks)) return rc;
+  const dim3 grid(blocks), block(256);
   THX_DISPATCH(dtype,
                hipLaunchKernelGGL(traj2_eval_kernel<float>, grid, block, 0, as_stream(stream), terms, n_terms, (const float*)x,
                                   ldx, n, (float*)J, j_total, (float*)e, lde, m, B),
@@ -217,10 +171,9 @@ extern "C" int thx_traj2_eval(const thx_traj2_term* terms, int32_t n_terms, cons
 extern "C" int thx_traj2_error(const thx_traj2_term* terms, int32_t n_terms, const void* x, int64_t ldx, int32_t n, void* err,
                                int32_t B, int dtype, void* stream) {
   const char* who = "thx_traj2_error";
-  if (!err) return fail(who, ": null pointer");
-  if (int rc = traj2_check(who, terms, n_terms, x, ldx, n, B, dtype)) return rc;
+  if (int rc = family_check(who, !err, terms, n_terms, x, 1, B, dtype, traj2_bad_size(ldx, n))) return rc;
   if (reinterpret_cast<uintptr_t>(err) % (dtype == THX_F32 ? 4 : 8)) return fail(who, ": pointer not aligned");
-  const dim3 grid((unsigned)B), block(kTrajErrThreads);   // (B <= INT32_MAX: within the grid limit of the x dimension)
+  const dim3 grid((unsigned)B), block(kErrThreads);   // (B <= INT32_MAX: within the grid limit of the x dimension)
   THX_DISPATCH(dtype,
                hipLaunchKernelGGL(traj2_error_kernel<float>, grid, block, 0, as_stream(stream), terms, n_terms, (const float*)x,
                                   ldx, n, (float*)err),

@@ -11,12 +11,13 @@ classes are the fallback and the differentiable twin.
 """
 from typing import List, Optional, Union
 
-import numpy as np
 import torch
 
 from . import _lib
 from .core import CostFunction, CostWeight, Point2, Variable, Vector
 from .euclidean import PackedEuclidean, _is_euclidean
+from .generic import _names
+from .term_table import TermKind, TermTable, term_dtype, weight_var
 
 
 def _as_variable(x, dtype=None, name=None) -> Variable:
@@ -25,10 +26,6 @@ def _as_variable(x, dtype=None, name=None) -> Variable:
     if not isinstance(x, torch.Tensor):
         x = torch.tensor(float(x), dtype=dtype or torch.get_default_dtype())
     return Variable(x, name=name)
-
-
-def _names(obj):
-    return {c.__name__ for c in type(obj).__mro__}
 
 
 class SignedDistanceField2D:
@@ -447,9 +444,7 @@ class EffectorObjectContactPlanar(CostFunction):
 # --------------------------------------------------------------------------------------------------------------------------------
 # the packed family: csrc/traj_kernels.hip
 # --------------------------------------------------------------------------------------------------------------------------------
-TRAJ2_TERM = np.dtype([("kind", "<i4"), ("row0", "<i4"), ("col", "<i4", (4,)), ("rows", "<i4"), ("cols", "<i4"), ("j_off", "<i8"),
-                       ("aux", "<u8", (5,)), ("aux_bstride", "<i8", (5,)), ("wdim", "<i4"), ("pad", "<i4")])
-assert TRAJ2_TERM.itemsize == 128
+TRAJ2_TERM = term_dtype("col")
 
 
 def _traj2_kind(c):
@@ -464,13 +459,19 @@ def _traj2_kind(c):
     return None
 
 
-class PackedTrajectory2D(PackedEuclidean):
-    """PackedEuclidean whose NON-differentiated evaluation is fused: ``assemble(graph=False)`` = thx_traj2_eval into persistent
-    block buffers + thx_block_assemble on them, ``error_metric`` = thx_traj2_error.  The term table holds device pointers of the
-    auxiliary tensors themselves (an SDF grid shared by every collision cost is one tensor, stored once); it is rebuilt when
-    somebody replaces one of them.  Everything differentiated (``assemble(graph=True)``, ``unrolled_step``) is the parent's."""
+class PackedTrajectory2D(TermTable, PackedEuclidean):
+    """PackedEuclidean whose NON-differentiated evaluation is fused (theseus_amd/term_table.py): ``assemble(graph=False)`` =
+    thx_traj2_eval into persistent block buffers + thx_block_assemble on them, ``error_metric`` = thx_traj2_error.  Everything
+    differentiated (``assemble(graph=True)``, ``unrolled_step``) is the parent's."""
 
-    _DIMS = {_lib.TRAJ2_COLLISION: 1, _lib.TRAJ2_GP: 4, _lib.TRAJ2_PRIOR: 2}
+    _TERM, _TANGENT = TRAJ2_TERM, 2
+    _KINDS = {
+        _lib.TRAJ2_COLLISION: TermKind(lambda c: [(c.sdf_data, None), (c.sdf_origin, 2), (c.sdf_cell_size, 1), (c.cost_eps, 1),
+                                                  (c.weight.scale, 1)], grid=0),
+        _lib.TRAJ2_GP: TermKind(lambda c: [(c.dt, 1), (c.weight.dt, 1), (c.weight.Qc_inv, 4)]),
+        _lib.TRAJ2_PRIOR: TermKind(lambda c: [(c.target, 2), (weight_var(c), None)], weight=1),
+    }
+    _WEIGHT_WIDTHS = ((1, 2), "This cost needs a 2-dimensional DiagonalCostWeight.")
 
     def __init__(self, objective, kernels=None, order=None):
         from .kernels import default_kernels
@@ -478,121 +479,18 @@ class PackedTrajectory2D(PackedEuclidean):
         K = kernels or default_kernels()
         if not hasattr(K, "traj2_eval"):
             raise UnsupportedObjective("these kernels have no fused trajectory evaluation")
-        kinds = [_traj2_kind(c) for c in objective.cost_functions.values()]
-        if not kinds or any(k is None for k in kinds):
+        self.kinds = [_traj2_kind(c) for c in objective.cost_functions.values()]
+        if not self.kinds or any(k is None for k in self.kinds):
             raise UnsupportedObjective("HIP backend, fused 2D motion planning: every cost must be a Collision2D on a Point2 with a "
                                        "ScaleCostWeight, a GPMotionModel with dof 2 or a Difference on a 2-dof Euclidean variable "
                                        "with a Scale / DiagonalCostWeight.")
         super().__init__(objective, K, order)
-        self.kinds = kinds
-        rows, r, joff, j = [], 0, [], 0
-        for c, k in zip(self.costs, kinds):
-            rows.append(r)
-            joff.append(j)
-            r += c.dim()
-            j += 2 * c.dim() * len(self.cost_vars[len(rows) - 1])
-        self.rows, self.joff, self.j_total = rows, joff, j
-        self.term_order = sorted(range(len(self.costs)), key=lambda c: kinds[c])   # (stable: by kind, then the objective's order)
-        self._aux_refs = self._aux_key = self._table = None
-        self._aux_stamp = -1
-        self._J = self._e = self._Jv = self._ev = None
-        self._asm_cache = {}
 
-    # ---- the term table ------------------------------------------------------------------------------------------------------
-    def _term_aux(self, c, kind):
-        if kind == _lib.TRAJ2_COLLISION:
-            return [c.sdf_data, c.sdf_origin, c.sdf_cell_size, c.cost_eps, c.weight.scale]
-        if kind == _lib.TRAJ2_GP:
-            return [c.dt, c.weight.dt, c.weight.Qc_inv]
-        return [c.target, c.weight.scale if "ScaleCostWeight" in _names(c.weight) else c.weight.diagonal]
+    def _term_vars(self, c):
+        return [self.cols[k][0] for k in self.cost_vars[c]]   # (state columns)
 
-    def _sync_aux(self, deep: bool = False):
-        if self._table is not None and not deep and self._aux_stamp == Variable._global_updates:
-            return
-        dev, dt, B = self._state.device, self._state.dtype, self._state.shape[0]
-        tensors = [[a.tensor for a in self._term_aux(c, k)] for c, k in zip(self.costs, self.kinds)]
-        key = tuple((id(t), t.data_ptr(), t.shape[0]) for ts in tensors for t in ts) + (str(dev), B)
-        self._aux_stamp = Variable._global_updates
-        if self._table is not None and key == self._aux_key:
-            return
-        table = np.zeros(len(self.costs), TRAJ2_TERM)
-        refs = []
-        for slot, c in enumerate(self.term_order):
-            cost, kind, ts = self.costs[c], self.kinds[c], tensors[c]
-            row = table[slot]
-            row["kind"], row["row0"], row["j_off"] = kind, self.rows[c], self.joff[c]
-            cols = [self.cols[k][0] for k in self.cost_vars[c]]
-            row["col"] = cols + [-1] * (4 - len(cols))
-            expect = {_lib.TRAJ2_COLLISION: (None, 2, 1, 1, 1), _lib.TRAJ2_GP: (1, 1, 4), _lib.TRAJ2_PRIOR: (2, None)}[kind]
-            for k, (t, width) in enumerate(zip(ts, expect)):
-                per = t[0].numel()
-                if t.device != dev or t.dtype != dt:
-                    raise RuntimeError(f"{cost.name}: an auxiliary tensor lives on {t.device} / {t.dtype}, the state on {dev} / {dt}; "
-                                       "there is no CPU fallback")
-                if t.shape[0] not in (1, B) or (width is not None and per != width):
-                    raise ValueError(f"{cost.name}: auxiliary tensor of shape {tuple(t.shape)} does not fit batch {B}")
-                td = t.detach()
-                if not td.is_contiguous():
-                    td = td.contiguous()
-                    key = None   # (a private copy: look again at the next call)
-                refs.append(td)
-                row["aux"][k], row["aux_bstride"][k] = td.data_ptr(), per if t.shape[0] > 1 else 0
-            if kind == _lib.TRAJ2_COLLISION:
-                row["rows"], row["cols"] = ts[0].shape[1], ts[0].shape[2]
-            elif kind == _lib.TRAJ2_PRIOR:
-                wdim = ts[1][0].numel()
-                if wdim not in (1, 2):
-                    raise ValueError("This cost needs a 2-dimensional DiagonalCostWeight.")
-                row["wdim"] = wdim
-        self._table = torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).to(dev)
-        self._aux_refs, self._aux_key = (tensors, refs), key
-        if key is None:
-            self._aux_stamp = -1
+    def _launch_eval(self, state):
+        self.K.traj2_eval(self._table, len(self.costs), state, self.n, self._J, self.j_total, self._e)
 
-    def sync(self, force: bool = False, deep: bool = False):
-        super().sync(force, deep)
-        self._sync_aux(deep or force)
-
-    def _buffers(self):
-        B, dev, dt = self._state.shape[0], self._state.device, self._state.dtype
-        if self._J is None or self._e.shape[0] != B or self._e.device != dev or self._e.dtype != dt:
-            self._J = torch.zeros(self.j_total * B, dtype=dt, device=dev)
-            self._e = torch.zeros(B, self.m, dtype=dt, device=dev)
-            self._Jv, self._ev = [], []
-            for c, cost in enumerate(self.costs):
-                d, o = cost.dim(), self.joff[c]
-                self._Jv.append([self._J[(o + 2 * d * s) * B:(o + 2 * d * (s + 1)) * B].view(B, d, 2) for s in range(len(self.cost_vars[c]))])
-                self._ev.append(self._e[:, self.rows[c]:self.rows[c] + d])
-            self._asm_cache = {}
-
-    def _differentiated(self) -> bool:
-        return torch.is_grad_enabled() and any(v.tensor.requires_grad for v in self._tracked())
-
-    def _eval(self, state=None):
-        """thx_traj2_eval at ``state`` (default: the current one) -> (Jacobian block views, error views) of the persistent buffers"""
-        self.sync()
-        self._buffers()
-        self.K.traj2_eval(self._table, len(self.costs), self._state if state is None else state, self.n, self._J, self.j_total,
-                          self._e)
-        return self._Jv, self._ev
-
-    # ---- the overrides --------------------------------------------------------------------------------------------------------
-    def weighted_blocks(self):
-        if self._differentiated():
-            return super().weighted_blocks()
-        return self._eval()
-
-    def assemble(self, H: torch.Tensor, g: torch.Tensor, graph: bool = False):
-        if graph:
-            return super().assemble(H, g, graph=True)
-        Jv, ev = self._eval()
-        self.K.block_assemble_strided(self.asm, Jv, ev, H, g, self._asm_cache)
-        self._blocks = (Jv, ev)
-        return None
-
-    def error_metric(self, state=None, out: Optional[torch.Tensor] = None, poses=None):
-        self.sync()
-        x = state if state is not None else (poses if poses is not None else self._state)
-        err = out if out is not None else torch.empty(x.shape[0], dtype=x.dtype, device=x.device)
-        self.K.traj2_error(self._table, len(self.costs), x.detach(), self.n, err)
-        return err
+    def _launch_error(self, state, err):
+        self.K.traj2_error(self._table, len(self.costs), state, self.n, err)

@@ -700,10 +700,11 @@ def packed_for(objective: Objective, kernels=None, order=None):
     cost functions that hand over their Jacobian blocks -- the generic one of theseus_amd/euclidean.py."""
     from .embodied import PackedTrajectory2D
     from .euclidean import PackedEuclidean
+    from .generic import PackedState
     from .pushing import PackedPlanarPushing
     p = getattr(objective, "_packed", None)
     order = tuple(order) if order is not None else tuple(objective.optim_vars.keys())
-    if (p is None or not isinstance(p, (PackedPoseGraph, PackedEuclidean, PackedPlanarPushing)) or p.version != objective.current_version
+    if (p is None or not isinstance(p, (PackedPoseGraph, PackedState)) or p.version != objective.current_version
             or (kernels is not None and p.K is not kernels) or p.order != order):
         try:
             p = PackedPoseGraph(objective, kernels, order)

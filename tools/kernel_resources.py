@@ -1,4 +1,4 @@
-"""VGPRs / scratch / occupancy of every kernel of one .hip file (hipcc -Rpass-analysis=kernel-resource-usage), one line per kernel.
+"""VGPRs / SGPRs / scratch / occupancy of every kernel of one .hip file (hipcc -Rpass-analysis=kernel-resource-usage), one line per kernel.
 usage: python tools/kernel_resources.py theseus_amd/csrc/chol_kernels.hip [extra hipcc flags]"""
 import re
 import subprocess
@@ -23,5 +23,5 @@ names = subprocess.run(["c++filt"] + [r["name"] for r in rows], capture_output=T
 for r, n in zip(rows, names):
     n = re.sub(r"\(.*", "", n.replace("void thx::", ""))
     g = lambda k: r.get(k, "?")  # noqa: E731
-    print(f"{n:58s} VGPRs {g('VGPRs'):>4s} AGPRs {g('AGPRs'):>4s} scratch {g('ScratchSize [bytes/lane]'):>5s} "
+    print(f"{n:58s} VGPRs {g('VGPRs'):>4s} AGPRs {g('AGPRs'):>4s} SGPRs {g('TotalSGPRs'):>4s} scratch {g('ScratchSize [bytes/lane]'):>5s} "
           f"occupancy {g('Occupancy [waves/SIMD]')} LDS {g('LDS Size [bytes/block]')}")
