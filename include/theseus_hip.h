@@ -256,6 +256,21 @@ typedef struct {
                                      *   two groups is listed in both and clipped) */
   int32_t rg_max_tile_pieces;       /* the largest piece count of one (group, block column): above thx_chol_schedule.
                                      * hb_scatter_max_pieces a layout whose tiles are added by the matrix cores is not regrouped */
+  /* ZERO SOLVES (thx_chol_schedule.skip_zero_solves), all NULL / 0 = none.  A group's rows are dealt to the four waves of its
+   * workgroup in strips of 32 slots; a strip whose rows all begin at or behind column 32 zf is zero in the chunks before zf, so the
+   * wave leaves out those chunks of the K-loop, the sub-blocks of its two substitutions left of zf and the coupling products of
+   * those columns -- and a group whose four strips all begin behind the pair's columns only stores zeros. */
+  const int32_t* rg_zf;             /* DEVICE (groups, 4): per strip min first / 32, NOT capped; a strip without rows: >= 4 j + 8 */
+  /* PAIR 0 has no K-loop and no groups above; with these tables its rows (256 .. n - 1) are sorted and cut into groups the same
+   * way, so that the rows whose tiles (i, 0) / (i, 1) are structurally zero share strips and groups.  Groups 0 .. rg0_ngroups - 1,
+   * in ascending order of first; rg0_tile_ptr / rg0_piece_* keyed as rg_tile_ptr (group g, block column s). */
+  const int32_t* rg0_rows;          /* DEVICE (rg0_ngroups, THX_TILE) */
+  const int32_t* rg0_zf;            /* DEVICE (rg0_ngroups, 4) */
+  const int32_t* rg0_tile_ptr;      /* DEVICE (2 rg0_ngroups + 1) */
+  const int32_t* rg0_piece_blk;     /* DEVICE */
+  const int32_t* rg0_piece_rc;      /* DEVICE */
+  int32_t rg0_ngroups;              /* 0: pair 0 keeps its natural tiles */
+  int32_t rg0_max_tile_pieces;      /* as rg_max_tile_pieces: above the scatter limit pair 0 ALONE falls back to natural tiles */
 } thx_hblock_layout;
 /*      thx_hblock_fill_mask: HOST-ONLY (no device is touched) -- the table behind thx_hblock_layout.l_mask.  blocks: host (nblocks, 2)
  *      int32 pairs (row variable p, column variable q), q <= p, the non-zero bd x bd blocks of tril(H) in any order.  Runs the
@@ -444,7 +459,15 @@ int thx_se3_retract(const void* poses, const void* delta, int64_t ldd, double st
  *          kernel takes the rows below a pair group by group instead of tile by tile and leaves out every k-chunk in front of the
  *          group's first non-zero one -- loads, staging and barriers included.  Each output element receives the same products in
  *          the same order: the factor is the same (up to the sign of a zero).  1 on, 0 off, < 0: the default (on);
- *          skip_zero_blocks = 0 turns it off too. */
+ *          skip_zero_blocks = 0 turns it off too.
+ *        skip_zero_solves: where regroup_rows applies (skip_zero_blocks and regroup_rows not 0, column pairs, fp32, left-looking) and
+ *          the layout carries thx_hblock_layout.rg_zf / rg0_*: every wave of a row group's workgroup starts its K-loop at its OWN
+ *          strip's first non-zero chunk and leaves out the sub-blocks of the two substitutions and the coupling products whose
+ *          operand is structurally zero; a group that lies wholly behind the pair's columns stores zeros and does nothing else; and
+ *          pair 0 takes its rows group by group as well (rg0_*).  Each output element keeps the same products in the same order.
+ *          The identity holds for factorisations that succeed (info == 0): failure is reported through info by the diagonal
+ *          kernels, and where a panel is not finite a structurally zero entry of L, NaN without the skip, is 0 with it.
+ *          1 on, 0 off (exactly the launches of regroup_rows alone), < 0: the default (on). */
 typedef struct {
   int32_t split_diag_min_batch;
   int32_t column_pairs;
@@ -456,13 +479,14 @@ typedef struct {
   int32_t right_looking_mode;
   int32_t skip_zero_blocks;
   int32_t regroup_rows;
+  int32_t skip_zero_solves;
 } thx_chol_schedule;
 
 /* ---- thx_chol_plan: HOST-ONLY query (no device is touched, no GPU needed) -- the schedule a DENSE-frame factorisation
  *      (thx_chol_factor, thx_chol_factor_forward with has_rhs != 0, thx_chol_factor_hblocks with layout != NULL and no tile pattern)
  *      with these arguments takes: the same decision function the factorisation runs.  has_damping: a damping vector is given;
  *      ldv: row stride of rhs / y (with has_rhs; y assumed 16-byte aligned, as every torch allocation is); layout: only its host
- *      fields are read (bd, max_tile_pieces, rg_max_tile_pieces, whether diag_blk / l_mask / the rg_ tables are set).  For tests
+ *      fields are read (bd, max_tile_pieces, rg_max_tile_pieces, rg0_ngroups, rg0_max_tile_pieces, whether diag_blk / l_mask / the rg_ / rg0_ tables are set).  For tests
  *      and tools that must know which kernels a call reaches. */
 typedef struct {
   int32_t right_looking;       /* 1: the right-looking schedule */
@@ -474,6 +498,7 @@ typedef struct {
   int32_t f64_wide_cols;       /* fp64: ... from chol_offdiag_f64w8_kernel */
   int32_t forward_fused;       /* has_rhs: 1 the forward substitution rides in the factorisation's kernels, 0 a kernel of its own */
   int32_t regroup_rows;        /* 1: the column pairs that have row groups take them (thx_chol_schedule.regroup_rows) */
+  int32_t skip_zero_solves;    /* 1: the row groups' waves skip their zero solves and / or pair 0 runs on groups (thx_chol_schedule.skip_zero_solves) */
 } thx_chol_plan_info;
 int thx_chol_plan(int32_t n, int64_t ld, int32_t B, int dtype, int has_damping, int has_rhs, int64_t ldv,
                   const thx_hblock_layout* layout, const thx_chol_schedule* schedule, thx_chol_plan_info* out);

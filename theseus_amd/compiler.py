@@ -192,10 +192,11 @@ class HessianBlocks:
         return self._l_mask
 
     def row_groups(self) -> Optional["RowGroups"]:
-        """The regrouped rows of the fp32 column pairs (thx_hblock_layout.rg_*), None when no pair would start a K-loop late."""
+        """The regrouped rows of the fp32 column pairs (thx_hblock_layout.rg_*), None when no pair would start a K-loop late and
+        pair 0 has no strip of rows that begins behind column 32."""
         if self._row_groups is None:
             rg = RowGroups(self)
-            self._row_groups = rg if rg.ngroups > 0 else False
+            self._row_groups = rg if rg.ngroups > 0 or rg.ngroups0 > 0 else False
         return self._row_groups or None
 
     def on(self, device) -> "DeviceHessianBlocks":
@@ -248,6 +249,12 @@ class RowGroups:
     k0         (ngroups)         first 32-column chunk of the group's K-loop
     tile_ptr   (2 ngroups + 1)   pieces of (group g, column tile j + s): [tile_ptr[2 g + s], tile_ptr[2 g + s + 1])
     piece_blk, piece_rc          as HessianBlocks', the row relative to the group's slot 0
+    zf         (ngroups, 4)      per 32-slot strip (= wave of the workgroup) min first // 32, NOT capped (a strip without rows:
+                                 4 j + 8): what of the strip's substitutions and coupling is a product with zeros
+                                 (thx_chol_schedule.skip_zero_solves)
+
+    Pair 0 has no K-loop and keeps group_ptr[0:2] == 0; its rows, sorted and cut the same way, are in tables of their own --
+    ngroups0, rows0, zf0, tile_ptr0, piece_blk0, piece_rc0, max_tile_pieces0 -- present when some strip begins behind chunk 0.
     """
 
     def __init__(self, hb: "HessianBlocks"):
@@ -260,10 +267,10 @@ class RowGroups:
             by_row[a].append((b, k))
         self.first = np.repeat(d * firstp, d)           # (n) first non-zero column of every row of H (and of L)
         self.npairs = max(0, (nt - 1) // 2)
-        group_ptr, rows, k0s, tile_ptr, pblk, prc = [0], [], [], [0], [], []
+        group_ptr, rows, k0s, zfs, tile_ptr, pblk, prc = [0], [], [], [], [0], [], []
         self.max_tile_pieces = 0
-        for jp in range(self.npairs):
-            j = 2 * jp
+
+        def sorted_rows(j):
             r0 = (j + 2) * TILE
             rr = np.arange(r0, n)
             srows = rr[np.argsort(self.first[rr], kind="stable")]
@@ -276,6 +283,33 @@ class RowGroups:
                 cut = int((~head[:TILE * g]).sum())
                 srows = np.concatenate([rest[:cut], srows[head], rest[cut:]])
             assert self._slots_ok(srows, d)
+            return srows
+
+        def strip_chunks(slots, j):   # per 32-slot strip (= wave) min first // 32, uncapped; a strip without rows: behind the pair
+            return [int(self.first[slots[s:s + 32]].min()) // 32 if slots.size > s else 4 * j + 8 for s in range(0, TILE, 32)]
+
+        def add_group(slots, j, rows, tile_ptr, pblk, prc):   # -> the largest piece count of (this group, one block column)
+            rows.append(np.concatenate([slots, np.full(TILE - slots.size, -1)]))
+            pose = slots // d
+            starts = [s for s in range(slots.size) if s == 0 or pose[s] != pose[s - 1]]
+            most = 0
+            for tj in (j, j + 1):
+                cnt = 0
+                for s in starts:
+                    s0 = s - int(slots[s]) % d       # slot of the variable's row 0 (negative: it starts in the group before)
+                    for q, k in by_row[int(pose[s])]:
+                        c0 = d * q - TILE * tj
+                        if c0 + d > 0 and c0 < TILE:
+                            pblk.append(k)
+                            prc.append(((s0 & 0xFFFF) << 16) | (c0 & 0xFFFF))
+                            cnt += 1
+                tile_ptr.append(tile_ptr[-1] + cnt)
+                most = max(most, cnt)
+            return most
+
+        for jp in range(self.npairs):
+            j = 2 * jp
+            srows = sorted_rows(j)
             ng = (srows.size + TILE - 1) // TILE
             k0 = [min(int(self.first[srows[TILE * g:TILE * g + TILE]].min()) // 32, 4 * j) for g in range(ng)]
             if max(k0) == 0:
@@ -283,30 +317,35 @@ class RowGroups:
                 continue
             for g in range(ng):
                 slots = srows[TILE * g:TILE * g + TILE]
-                rows.append(np.concatenate([slots, np.full(TILE - slots.size, -1)]))
                 k0s.append(k0[g])
-                pose = slots // d
-                starts = [s for s in range(slots.size) if s == 0 or pose[s] != pose[s - 1]]
-                for tj in (j, j + 1):
-                    cnt = 0
-                    for s in starts:
-                        s0 = s - int(slots[s]) % d       # slot of the variable's row 0 (negative: it starts in the group before)
-                        for q, k in by_row[int(pose[s])]:
-                            c0 = d * q - TILE * tj
-                            if c0 + d > 0 and c0 < TILE:
-                                pblk.append(k)
-                                prc.append(((s0 & 0xFFFF) << 16) | (c0 & 0xFFFF))
-                                cnt += 1
-                    tile_ptr.append(tile_ptr[-1] + cnt)
-                    self.max_tile_pieces = max(self.max_tile_pieces, cnt)
+                zfs.append(strip_chunks(slots, j))
+                self.max_tile_pieces = max(self.max_tile_pieces, add_group(slots, j, rows, tile_ptr, pblk, prc))
             group_ptr.append(group_ptr[-1] + ng)
         self.ngroups = group_ptr[-1]
         self.group_ptr = np.array(group_ptr, dtype=np.int32)
         self.rows = np.array(rows, dtype=np.int32).reshape(-1, TILE)
         self.k0 = np.array(k0s, dtype=np.int32)
+        self.zf = np.array(zfs, dtype=np.int32).reshape(-1, 4)
         self.tile_ptr = np.array(tile_ptr, dtype=np.int32)
         self.piece_blk = np.array(pblk, dtype=np.int32)
         self.piece_rc = np.array(prc, dtype=np.int64).astype(np.uint32).view(np.int32)
+        # pair 0, in tables of its own (group_ptr keeps it empty): no K-loop to shorten, but sorted rows put the rows whose X0 / X1
+        # are structurally zero into the same strips and groups
+        rows0, zf0, tile_ptr0, pblk0, prc0 = [], [], [0], [], []
+        self.max_tile_pieces0 = 0
+        if self.npairs > 0:
+            srows = sorted_rows(0)
+            groups = [srows[TILE * g:TILE * g + TILE] for g in range((srows.size + TILE - 1) // TILE)]
+            if any(int(self.first[sl[s:s + 32]].min()) >= 32 for sl in groups for s in range(0, sl.size, 32)):   # (a strip starts late)
+                for slots in groups:
+                    zf0.append(strip_chunks(slots, 0))
+                    self.max_tile_pieces0 = max(self.max_tile_pieces0, add_group(slots, 0, rows0, tile_ptr0, pblk0, prc0))
+        self.ngroups0 = len(rows0)
+        self.rows0 = np.array(rows0, dtype=np.int32).reshape(-1, TILE)
+        self.zf0 = np.array(zf0, dtype=np.int32).reshape(-1, 4)
+        self.tile_ptr0 = np.array(tile_ptr0, dtype=np.int32)
+        self.piece_blk0 = np.array(pblk0, dtype=np.int32)
+        self.piece_rc0 = np.array(prc0, dtype=np.int64).astype(np.uint32).view(np.int32)
         self._hb = hb
 
     @staticmethod
@@ -324,22 +363,31 @@ class RowGroups:
     def expand(self, Hc: np.ndarray, ld: int) -> np.ndarray:
         """(B, bstride) -> dense (B, ld, ld), the way the regrouped column-pair workgroups gather it: rows [128 (j + 2), n) of
         column tiles j, j + 1 of every regrouped pair, group by group, piece by piece (everything else stays zero)."""
-        B, d = Hc.shape[0], self._hb.bd
-        H = np.zeros((B, ld, ld), dtype=Hc.dtype)
+        H = np.zeros((Hc.shape[0], ld, ld), dtype=Hc.dtype)
         for jp in range(self.npairs):
-            for g in range(self.group_ptr[jp], self.group_ptr[jp + 1]):
-                for s in range(2):
-                    tj = 2 * jp + s
-                    for pc in range(self.tile_ptr[2 * g + s], self.tile_ptr[2 * g + s + 1]):
-                        rc = int(self.piece_rc[pc]) & 0xFFFFFFFF
-                        r0 = int(np.array(rc >> 16, dtype=np.uint16).view(np.int16))
-                        c0 = int(np.array(rc & 0xFFFF, dtype=np.uint16).view(np.int16))
-                        blk = Hc[:, self.piece_blk[pc] * d * d:(self.piece_blk[pc] + 1) * d * d].reshape(B, d, d)
-                        for e in range(d * d):
-                            r, c = r0 + e // d, c0 + e % d
-                            if 0 <= r < TILE and 0 <= c < TILE and self.rows[g, r] >= 0:
-                                H[:, self.rows[g, r], TILE * tj + c] = blk[:, e // d, e % d]
+            self._expand_groups(H, Hc, 2 * jp, range(self.group_ptr[jp], self.group_ptr[jp + 1]), self.rows, self.tile_ptr,
+                                self.piece_blk, self.piece_rc)
         return H
+
+    def expand0(self, Hc: np.ndarray, ld: int) -> np.ndarray:
+        """``expand`` for pair 0's own tables: rows [256, n) of column tiles 0, 1."""
+        H = np.zeros((Hc.shape[0], ld, ld), dtype=Hc.dtype)
+        self._expand_groups(H, Hc, 0, range(self.ngroups0), self.rows0, self.tile_ptr0, self.piece_blk0, self.piece_rc0)
+        return H
+
+    def _expand_groups(self, H, Hc, j, groups, rows, tile_ptr, piece_blk, piece_rc):
+        B, d = Hc.shape[0], self._hb.bd
+        for g in groups:
+            for s in range(2):
+                for pc in range(tile_ptr[2 * g + s], tile_ptr[2 * g + s + 1]):
+                    rc = int(piece_rc[pc]) & 0xFFFFFFFF
+                    r0 = int(np.array(rc >> 16, dtype=np.uint16).view(np.int16))
+                    c0 = int(np.array(rc & 0xFFFF, dtype=np.uint16).view(np.int16))
+                    blk = Hc[:, piece_blk[pc] * d * d:(piece_blk[pc] + 1) * d * d].reshape(B, d, d)
+                    for e in range(d * d):
+                        r, c = r0 + e // d, c0 + e % d
+                        if 0 <= r < TILE and 0 <= c < TILE and rows[g, r] >= 0:
+                            H[:, rows[g, r], TILE * (j + s) + c] = blk[:, e // d, e % d]
 
     def skipped_fraction(self, l_mask: np.ndarray):
         """Model: the share of the pair K-loops' 32x32 block products (chol_offdiag2_f32_kernel: per row tile and k-chunk four waves
@@ -365,6 +413,35 @@ class RowGroups:
             tot_run += run
         return per, (1.0 - tot_run / tot_all if tot_all else 0.0)
 
+    def zero_solve_model(self, l_mask: np.ndarray):
+        """Model of thx_chol_schedule.skip_zero_solves in 32x32x32 block products, per pair j: a wave's two substitutions are
+        10 + 10 products and its coupling 16; with z0 / z1 leading zero sub-blocks of its strip in tiles (i, j) / (i, j + 1) they
+        are (4 - z0)(5 - z0) / 2 + (4 - z1)(5 - z1) / 2 and 4 (4 - z0).  The K-loop counts as in ``skipped_fraction``, a wave
+        starting at its own strip's first chunk.  Pairs without groups keep their natural tiles (nothing changes).  Returns
+        {j: dict(solve=(today, proposed), kloop=(today, proposed), z=[[z of the four waves] per group])}."""
+        nt = l_mask.shape[0]
+        pop = lambda m: bin(int(m) & 15).count("1")   # noqa: E731
+        tri = lambda m: m * (m + 1) // 2              # noqa: E731
+        out = {}
+        for jp in range(self.npairs):
+            j = 2 * jp
+            cols = [pop(l_mask[j, kc]) + pop(l_mask[j + 1, kc]) for kc in range(4 * j)]
+            g0, g1 = int(self.group_ptr[jp]), int(self.group_ptr[jp + 1])
+            zf = self.zf[g0:g1] if g1 > g0 else (self.zf0 if j == 0 else np.zeros((0, 4), np.int32))
+            solve_today = (nt - 2 - j) * 4 * 36
+            if zf.shape[0] == 0:   # natural tiles
+                k = sum(pop(l_mask[i, kc]) * cols[kc] for i in range(j + 2, nt) for kc in range(4 * j))
+                out[j] = dict(solve=(solve_today, solve_today), kloop=(k, k), z=[])
+                continue
+            z = np.clip(zf - 4 * j, 0, 8)
+            z0, z1 = np.minimum(z, 4), z - np.minimum(z, 4)
+            solve = int(sum(tri(4 - a) + 4 * (4 - a) + tri(4 - b) for a, b in zip(z0.reshape(-1).tolist(), z1.reshape(-1).tolist())))
+            k0 = np.minimum(zf.min(1), 4 * j)
+            k_today = sum(4 * cols[kc] for g in range(zf.shape[0]) for kc in range(int(k0[g]), 4 * j))
+            k_new = sum(cols[kc] for g in range(zf.shape[0]) for w in range(4) for kc in range(min(int(zf[g, w]), 4 * j), 4 * j))
+            out[j] = dict(solve=(solve_today, solve), kloop=(k_today, k_new), z=z.tolist())
+        return out
+
 
 class DeviceHessianBlocks:
     _FIELDS = ["diag_blk", "inc_blk", "tile_ptr", "piece_blk", "piece_rc"]
@@ -387,11 +464,16 @@ class DeviceHessianBlocks:
         c.l_mask = self.t["l_mask"].data_ptr()
         # the row groups of the fp32 column pairs (thx_hblock_layout.rg_*); none: the fields stay NULL
         rg = hb.row_groups()
-        if rg is not None:
+        if rg is not None and rg.ngroups > 0:
             self.rg_group_ptr_host = np.ascontiguousarray(rg.group_ptr)   # (host table: kept alive here)
             c.rg_group_ptr_host = self.rg_group_ptr_host.ctypes.data
-            for f in ("rows", "k0", "tile_ptr", "piece_blk", "piece_rc"):
+            for f in ("rows", "k0", "tile_ptr", "piece_blk", "piece_rc", "zf"):
                 self.t["rg_" + f] = torch.from_numpy(np.ascontiguousarray(getattr(rg, f))).to(device)
                 setattr(c, "rg_" + f, self.t["rg_" + f].data_ptr())
             c.rg_max_tile_pieces = rg.max_tile_pieces
+        if rg is not None and rg.ngroups0 > 0:   # pair 0's groups (thx_hblock_layout.rg0_*)
+            for f in ("rows", "zf", "tile_ptr", "piece_blk", "piece_rc"):
+                self.t["rg0_" + f] = torch.from_numpy(np.ascontiguousarray(getattr(rg, f + "0"))).to(device)
+                setattr(c, "rg0_" + f, self.t["rg0_" + f].data_ptr())
+            c.rg0_ngroups, c.rg0_max_tile_pieces = rg.ngroups0, rg.max_tile_pieces0
         self.c = c

@@ -143,6 +143,8 @@ struct FactorPlan {
   bool colpair;          // (left-looking) the column-pair schedule (fp32)
   bool zskip;            // the off-diagonal K-loops skip structurally zero 32x32 sub-blocks (HBlk.l_mask; fp32 left-looking dense frame)
   bool regroup;          // ... and the column pairs that have row groups take them (HBlk.rg_*, thx_chol_schedule.regroup_rows)
+  bool zsolve;           // ... their waves skip zero solves (HBlk.rg_zf) and / or pair 0 runs on groups (thx_chol_schedule.skip_zero_solves)
+  bool pair0;            // pair 0 takes its own row groups (HBlk.rg0_*; only with zsolve)
   int hbm;               // the off-diagonal kernels' HB template argument: 0 dense H, HB_MODE_SCATTER, HB_MODE_ROUNDS
   int f64_wide_max, f64_half_max;
 };
@@ -193,6 +195,13 @@ static FactorPlan plan_factor(bool f64, int n, int64_t ld, int B, bool has_dampi
   p.regroup = p.zskip && p.colpair && (!sched || sched->regroup_rows != 0) && hbp->rg_group_ptr_host && hbp->rg_rows && hbp->rg_k0 &&
               hbp->rg_tile_ptr && hbp->rg_piece_blk && hbp->rg_piece_rc &&
               (p.hbm != HB_MODE_SCATTER || hbp->rg_max_tile_pieces <= hb_scatter_max) && (int64_t)n * ld * 4 < ((int64_t)1 << 31);
+  // zero solves: wherever regrouping may apply -- the groups' per-wave first chunks, and pair 0 on groups of its own (a layout may have
+  // these without any group above: three block columns).  Pair 0 alone falls back to natural tiles over the scatter limit.
+  const bool zs = p.zskip && p.colpair && (!sched || (sched->regroup_rows != 0 && sched->skip_zero_solves != 0)) &&
+                  (int64_t)n * ld * 4 < ((int64_t)1 << 31);
+  p.pair0 = zs && p.ntiles > 2 && hbp->rg0_ngroups > 0 && hbp->rg0_rows && hbp->rg0_zf && hbp->rg0_tile_ptr && hbp->rg0_piece_blk &&
+            hbp->rg0_piece_rc && (p.hbm != HB_MODE_SCATTER || hbp->rg0_max_tile_pieces <= hb_scatter_max);
+  p.zsolve = (zs && p.regroup && hbp->rg_zf) || p.pair0;
   return p;
 }
 
@@ -261,14 +270,23 @@ struct FactorLaunch {
       });
   }
   // ... of the row groups [g_first, g_first + ng) of pair j (P.regroup)
-  void pair_groups(const Half& h, int j, int g_first, int ng) const {
+  void pair_groups(const Half& h, int j, int g_first, int ng) const { pair_groups(h, j, g_first, ng, hb_of(h)); }
+  void pair_groups(const Half& h, int j, int g_first, int ng, const HBlk& x) const {
     if constexpr (sizeof(T) == 4)
       with_hb_mode(P.hbm, [&](auto mode) {
         constexpr int M = decltype(mode)::value;
         if constexpr (M != 0)
           launch_lds<chol_offdiag2_f32_kernel<M, true>>(dev, dim3((h.nb + 7) / 8 * 8 * ng), dim3(256), OFF2_SMEM, h.s, H_of(h), L_of(h),
-                                                        panel_of(h), n, ld, j, P.ntiles, g_first, ng, h.nb, hb_of(h));
+                                                        panel_of(h), n, ld, j, P.ntiles, g_first, ng, h.nb, x);
       });
+  }
+
+  // ... of pair 0's own groups (P.pair0): the same kernel, the rg_ tables of this launch are pair 0's
+  void pair_groups0(const Half& h) const {
+    HBlk x = hb_of(h);
+    x.rg_rows = x.rg0_rows, x.rg_zf = x.rg0_zf, x.rg_tile_ptr = x.rg0_tile_ptr, x.rg_piece_blk = x.rg0_piece_blk, x.rg_piece_rc = x.rg0_piece_rc;
+    x.rg_k0 = nullptr;   // (no K-loop)
+    pair_groups(h, 0, 0, x.rg0_ngroups, x);
   }
 
   // the diagonal phase of block column j (nc > 1: the level schedule -- block columns [j, j + nc) in one launch, blockIdx.y the
@@ -564,6 +582,7 @@ static int run_left_looking(const FactorLaunch<T>& c) {
         const int32_t* gp = c.P.regroup ? c.hb.rg_group_ptr_host : nullptr;
         const int g0 = gp ? gp[j / 2] : 0, ng = gp ? gp[j / 2 + 1] - g0 : 0;
         if (ng > 0) c.pair_groups(h, j, g0, ng);
+        else if (j == 0 && c.P.pair0) c.pair_groups0(h);
         else c.pair(h, j, j + 2, ntiles - 2 - j);
         continue;
       }
@@ -616,6 +635,7 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
   HBlk hb = use_hb ? *hbp : HBlk{};
   if (!P.zskip) hb.l_mask = nullptr;
   if (!P.regroup) hb.rg_rows = hb.rg_k0 = hb.rg_tile_ptr = hb.rg_piece_blk = hb.rg_piece_rc = nullptr;
+  if (!P.zsolve || !P.regroup) hb.rg_zf = nullptr;
   std::lock_guard<std::mutex> guard(g_launch_mutex);
   const int dev = current_device();
   const FactorLaunch<T> c{H, ld, n, B, damping, ellipsoidal, eps, L, panel, info, rhs, y, ldv, st, tp, ls, P, pat, use_hb, hb, packed,
@@ -748,7 +768,8 @@ static int check_rhs(const void* rhs, const void* y, int64_t ldv, int n, const c
 static HBlk hblk_from(const thx_hblock_layout* layout, const void* Hc, int64_t bstride) {
   return HBlk{Hc, bstride, layout->bd, layout->tile_ptr, layout->piece_blk, layout->piece_rc, layout->diag_blk, layout->max_tile_pieces,
               layout->l_mask, layout->rg_rows, layout->rg_k0, layout->rg_tile_ptr, layout->rg_piece_blk, layout->rg_piece_rc,
-              layout->rg_group_ptr_host, layout->rg_max_tile_pieces};
+              layout->rg_group_ptr_host, layout->rg_max_tile_pieces, layout->rg_zf, layout->rg0_rows, layout->rg0_zf, layout->rg0_tile_ptr,
+              layout->rg0_piece_blk, layout->rg0_piece_rc, layout->rg0_ngroups, layout->rg0_max_tile_pieces};
 }
 
 int thx_chol_factor(const void* H, int64_t ld, int32_t n, int32_t B, const void* damping, int ellipsoidal,
@@ -852,6 +873,7 @@ int thx_chol_plan(int32_t n, int64_t ld, int32_t B, int dtype, int has_damping, 
   out->f64_wide_cols = f64_lanes ? std::max(0, std::min(p.f64_wide_max, cols) - half) : 0;
   out->forward_fused = has_rhs && (!rl || p.rl_fwd_fused);
   out->regroup_rows = p.regroup;
+  out->skip_zero_solves = p.zsolve;
   return 0;
 }
 

@@ -267,6 +267,12 @@ chol_offdiag_f32_kernel(const float* __restrict__ H, float* __restrict__ L, cons
 // stores or barriers for those chunks).  Every row of L is independent here and keeps its own products in their order: L is
 // bit-identical (up to the sign of a zero).  The group's rows come from a table (operand B's row offsets, the rows stored to),
 // its pieces of H from tables keyed by (group, block column); the row-side sub-block mask has no meaning for a group and is gone.
+// ZERO SOLVES (FactorPlan.zsolve, HBlk.rg_zf): each wave's 32 rows have a first non-zero chunk of their own, not capped at 4 j.  The
+// wave leaves out the k-chunks in front of it and, where its rows begin inside or behind the pair's columns, the sub-blocks of the
+// two substitutions and the coupling products whose operand is zero; a group that lies wholly behind block column j (or the
+// pair) stores zeros for that tile (both tiles) and skips the tile's loads, staging and barriers as a workgroup.  Pair 0 -- no
+// K-loop, so no groups of the kind above -- runs on groups of its own through the same instantiation (pair_groups0).  The same
+// products in the same order for every element that is computed; what is left out is a product with an exact zero.
 // ------------------------------------------------------------------------------------------------
 constexpr int OFF2_PANEL_OFF = 2 * 128 * 36;              // floats: right behind staging buffers 0 and 1
 constexpr int OFF2_SMEM = (OFF2_PANEL_OFF + 10 * 1024) * 4;   // 76 KB
@@ -305,6 +311,37 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
   if constexpr (RG) srow = hb.rg_rows[i * TILE + r];
   const bool rvalid = RG ? srow >= 0 : r < validB;
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  typedef const int32_t __attribute__((address_space(4))) * lmask_t;
+  const int wv = __builtin_amdgcn_readfirstlane(wave);
+  const int nk = 4 * j;
+  // ZERO SOLVES (HBlk.rg_zf, nullptr: none -- everything below is then 0): this wave's 32 rows are zero left of chunk zf.  z of the pair's
+  // eight 32-column sub-blocks are zero for the wave, z0 of them in tile (i, j), z1 in tile (i, j + 1); zall: the same for the
+  // wave of the group that begins first.  All of it in scalar registers: every branch on them is wave or workgroup uniform.
+  int zf = 0, zmin = 0;
+  if constexpr (RG) {
+    const lmask_t zt = (lmask_t)(uintptr_t)hb.rg_zf;
+    if (zt) {
+      zf = zt[4 * i + wv];
+      zmin = min(min(zt[4 * i], zt[4 * i + 1]), min(zt[4 * i + 2], zt[4 * i + 3]));
+    }
+  }
+  const int z = min(max(zf - nk, 0), 8), z0 = RG ? min(z, 4) : 0, z1 = RG ? z - z0 : 0;
+  const int zall = RG ? min(max(zmin - nk, 0), 8) : 0;
+  // rows of the group that are zero in ncb 32-column sub-blocks from column col0 on: the zeros are STORED (L may hold anything,
+  // and the SYRK / head-tile kernels and the solves read whole rows)
+  auto store_zeros = [&](int ncb) __attribute__((always_inline)) {
+    if (rvalid) {
+      float* Lrow = L + mat + (int64_t)srow * ld + col0 + 4 * g;
+      for (int cb = 0; cb < ncb; ++cb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) *reinterpret_cast<float4*>(Lrow + 32 * cb + 8 * q) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  if constexpr (RG)
+    if (zall == 8) {   // every row of the group begins behind the pair: both tiles are zeros, nothing to load
+      store_zeros(8);
+      return;
+    }
 
   HBPre2<float, HB ? 2 * HB_NPRE_OFF : 1> hb2;
   // ---- K-loop over block columns 0 .. j - 1: P0 += L_i L_j^T, P1 += L_i L_{j+1}^T ----
@@ -355,9 +392,9 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
   Engine<float>::Acc P0, P1;
   Engine<float>::zero(P0);
   Engine<float>::zero(P1);
-  const int nk = 4 * j;
   int k0 = 0;   // first chunk of the K-loop
-  if constexpr (RG) k0 = __builtin_amdgcn_readfirstlane(hb.rg_k0[i]);
+  if constexpr (RG)   // (with the strips' table min(zmin, nk) is rg_k0[i], min(min first / 32, 4 j); pair 0's tables have no rg_k0)
+    k0 = hb.rg_zf ? min(zmin, nk) : __builtin_amdgcn_readfirstlane(hb.rg_k0[i]);
   if (nk > k0) gload3(k0);
   if constexpr (RG) hb2.load_run(hq, b, 2 * i, tid);
   else if constexpr (HB) hb2.load(hb, b, i, j, tid);
@@ -367,10 +404,8 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
   // sub-block).  An MFMA of an all-zero operand adds exact zeros: its output block's products are left out (wave-uniform
   // branches), every accumulator still receives the others in the same order.  Scalar loads through the constant address space
   // (as kloop_f's K-list), one chunk ahead: issued with the chunk's operand prefetch, they complete under the MFMAs.
-  typedef const int32_t __attribute__((address_space(4))) * lmask_t;
   const lmask_t lm = (lmask_t)(uintptr_t)hb.l_mask;
   const int nch = 4 * ntiles;
-  const int wv = __builtin_amdgcn_readfirstlane(wave);
   int nm0 = 15, nm1 = 15, nmi = 15;   // the masks of the next chunk
   auto lmask_load = [&](int kc) __attribute__((always_inline)) {
     if (lm) {
@@ -397,6 +432,8 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
     }
     if constexpr (!RG)
       if (!((mi >> wv) & 1)) continue;   // this wave's rows of L_i are zero at the chunk: nothing to add
+    if constexpr (RG)
+      if (kc < zf) continue;             // ... the same, from the strip's first chunk
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const float4 fb = *reinterpret_cast<const float4*>(sBw + rl * 36 + 8 * ks + 4 * g);
@@ -445,7 +482,7 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
     });
   };
   // P <- H_(i, jj) - P  (block-compact H: the tile's pieces through the free staging buffers, 64 rows at a time; dense: loads)
-  auto h_minus = [&](Engine<float>::Acc& P, int sel, int jj) __attribute__((always_inline)) {
+  auto h_minus = [&](Engine<float>::Acc& P, int sel, int jj, bool first) __attribute__((always_inline)) {   // (first: no call before it)
     if constexpr (HB) {
       constexpr int LDH = 132;
       // P = -sum first, H's pieces are ADDED
@@ -457,11 +494,11 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
         // a few pieces per tile (pose graphs): added by the matrix cores, see hb_scatter.  Both tiles' values go to staging
         // buffer 0 as ONE list before tile (i, j)'s pieces are applied (the caller's barrier before panel_dma(j): the K-loop is
         // done with the buffers); nothing writes that buffer until tile (i, j + 1)'s turn (column j's share of it is staged in
-        // buffer 1): no second copy, no second barrier
+        // buffer 1): no second copy, no second barrier.  (Tile (i, j) left out: tile (i, j + 1)'s call is the first and stages the list.)
         const int n0 = hb2.p1 - hb2.p0, ntot = hb2.cnt / (hb.bd * hb.bd);
         static_assert(256 * 2 * HB_NPRE_OFF + 64 * 36 <= 128 * 36, "list + overflow chunk inside staging buffer 0");
         hb_add<float, Engine<float>::Acc, decltype(hb2), 256 * 2 * HB_NPRE_OFF>(P, hb2, hq, b, smem, sel == 0 ? 0 : n0, sel == 0 ? n0 : ntot,
-                                                                               sel == 0, tid);
+                                                                               first, tid);
       } else {
       __syncthreads();   // whatever read the staging buffers last is done
 #pragma unroll
@@ -505,16 +542,19 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
       }
     }
   };
-  // X = P L_jj^-T with the panel copy in LDS (chol_offdiag's substitution), X -> tile (i, jj) of L
-  auto substitute_store = [&](Engine<float>::Acc& P, Engine<float>::Acc& X, int jj) __attribute__((always_inline)) {
+  // X = P L_jj^-T with the panel copy in LDS (chol_offdiag's substitution), X -> tile (i, jj) of L.  zs: the wave's first zs
+  // sub-blocks of P are structurally zero -- X_t = 0 for t < zs, left as zeroed, and its products with them are left out
+  auto substitute_store = [&](Engine<float>::Acc& P, Engine<float>::Acc& X, int jj, int zs) __attribute__((always_inline)) {
     Engine<float>::zero(X);
     static_for<4>([&](auto is) __attribute__((always_inline)) {
       constexpr int sb = decltype(is)::value;
-      static_for<sb>([&](auto it) __attribute__((always_inline)) {
-        constexpr int tb = decltype(it)::value;
-        sub_mma_sw<sb, tb>(Pc, X, P, lane);  // P_s += (-L_st) X_t
-      });
-      sub_mma_sw<sb, sb>(Pc, P, X, lane);    // X_s  = W_ss P_s
+      if (sb >= zs) {
+        static_for<sb>([&](auto it) __attribute__((always_inline)) {
+          constexpr int tb = decltype(it)::value;
+          if (tb >= zs) sub_mma_sw<sb, tb>(Pc, X, P, lane);  // P_s += (-L_st) X_t
+        });
+        sub_mma_sw<sb, sb>(Pc, P, X, lane);    // X_s  = W_ss P_s
+      }
     });
     if (rvalid) {
       float* Lrow = L + mat + (int64_t)srow * ld + jj * TILE + 4 * g;
@@ -527,41 +567,53 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
     }
   };
 
-  // ---- tile (i, j) ----
-  __syncthreads();      // the K-loop's last chunk has been consumed: the panel copy overlaps staging buffer 2
-  panel_dma(j);
-  h_minus(P0, 0, j);
-  __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): this wave's pieces of the panel have landed
-  __syncthreads();
-  gload1(nk);           // first chunk of L_{j+1,j}: in flight under the substitution
   Engine<float>::Acc X0;
-  substitute_store(P0, X0, j);
-  // ---- block column j's share of tile (i, j + 1): P1 += X0 L_{j+1,j}^T, X0 from registers ----
-  static_for<4>([&](auto ic) __attribute__((always_inline)) {
-    constexpr int c = decltype(ic)::value;
-    __syncthreads();    // (c = 0: the substitution's reads of the panel copy are done as well)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) *reinterpret_cast<uint4*>(sA1 + (lrow + 32 * u) * 36 + 4 * lc) = q1[u];
+  bool first = true;   // (no h_minus call yet)
+  if (!RG || zall < 4) {
+    // ---- tile (i, j) ----
+    __syncthreads();      // the K-loop's last chunk has been consumed: the panel copy overlaps staging buffer 2
+    panel_dma(j);
+    h_minus(P0, 0, j, true);
+    first = false;
+    __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): this wave's pieces of the panel have landed
     __syncthreads();
-    if (c == 0) panel_dma(j + 1);   // lands under the four chunks' MFMAs
-    if (c < 3) gload1(nk + c + 1);
+    gload1(nk);           // first chunk of L_{j+1,j}: in flight under the substitution
+    substitute_store(P0, X0, j, z0);
+    // ---- block column j's share of tile (i, j + 1): P1 += X0 L_{j+1,j}^T, X0 from registers (chunk c of X0 zero: only the
+    //      wave's MFMAs are left out, the chunk is staged for the others) ----
+    static_for<4>([&](auto ic) __attribute__((always_inline)) {
+      constexpr int c = decltype(ic)::value;
+      __syncthreads();    // (c = 0: the substitution's reads of the panel copy are done as well)
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
+      for (int u = 0; u < 4; ++u) *reinterpret_cast<uint4*>(sA1 + (lrow + 32 * u) * 36 + 4 * lc) = q1[u];
+      __syncthreads();
+      if (c == 0) panel_dma(j + 1);   // lands under the four chunks' MFMAs
+      if (c < 3) gload1(nk + c + 1);
+      if (c >= z0) {
 #pragma unroll
-      for (int cb = 0; cb < 4; ++cb) {
-        const float4 fa = *reinterpret_cast<const float4*>(sA1 + (32 * cb + rl) * 36 + 8 * ks + 4 * g);
-        P1.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.x, X0.v[c][4 * ks + 0], P1.v[cb], 0, 0, 0);
-        P1.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.y, X0.v[c][4 * ks + 1], P1.v[cb], 0, 0, 0);
-        P1.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.z, X0.v[c][4 * ks + 2], P1.v[cb], 0, 0, 0);
-        P1.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.w, X0.v[c][4 * ks + 3], P1.v[cb], 0, 0, 0);
+        for (int ks = 0; ks < 4; ++ks) {
+#pragma unroll
+          for (int cb = 0; cb < 4; ++cb) {
+            const float4 fa = *reinterpret_cast<const float4*>(sA1 + (32 * cb + rl) * 36 + 8 * ks + 4 * g);
+            P1.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.x, X0.v[c][4 * ks + 0], P1.v[cb], 0, 0, 0);
+            P1.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.y, X0.v[c][4 * ks + 1], P1.v[cb], 0, 0, 0);
+            P1.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.z, X0.v[c][4 * ks + 2], P1.v[cb], 0, 0, 0);
+            P1.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.w, X0.v[c][4 * ks + 3], P1.v[cb], 0, 0, 0);
+          }
+        }
       }
-    }
-  });
+    });
+  } else {
+    // every row of the group begins behind block column j: tile (i, j) is zeros and adds nothing to tile (i, j + 1).  The K-loop
+    // had no iterations (k0 = 4 j): LDS is untouched so far
+    store_zeros(4);
+    panel_dma(j + 1);
+  }
   // ---- tile (i, j + 1) ----
-  h_minus(P1, 1, j + 1);
+  h_minus(P1, 1, j + 1, first);
   __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0)
   __syncthreads();
-  substitute_store(P1, X0, j + 1);
+  substitute_store(P1, X0, j + 1, z1);
 }
 
 // (A variant computing TWO row tiles per workgroup -- the column panel streamed once for both products, 3 staged operand

@@ -114,6 +114,17 @@ struct HBlk {
   const int32_t* rg_piece_rc;
   const int32_t* rg_group_ptr_host;   // (HOST table: run_left_looking sizes the launches by it; no kernel reads it)
   int rg_max_tile_pieces;
+  // thx_hblock_layout.rg_zf: per (group, wave) the first non-zero chunk of the wave's 32 rows -- set by factor_impl only with
+  // FactorPlan.zsolve, nullptr otherwise (pair_groups0 puts pair 0's table here)
+  const int32_t* rg_zf;
+  // thx_hblock_layout.rg0_*: pair 0's groups (HOST side only: pair_groups0 moves them into the rg_ fields of its launch)
+  const int32_t* rg0_rows;
+  const int32_t* rg0_zf;
+  const int32_t* rg0_tile_ptr;
+  const int32_t* rg0_piece_blk;
+  const int32_t* rg0_piece_rc;
+  int rg0_ngroups;
+  int rg0_max_tile_pieces;
 };
 
 // The pieces of lower tile (ti, tj) of problem b -- f(r, c, value), (r, c) relative to the tile origin and inside the tile; the

@@ -11,6 +11,21 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 
+def zero_solves(rg, m):
+    """thx_chol_schedule.skip_zero_solves (RowGroups.zero_solve_model): per pair the substitution + coupling products and the K-loop
+    products, today -> with every wave skipping what its strip's first chunk makes zero, and the leading zero sub-blocks per wave."""
+    model = rg.zero_solve_model(m)
+    print(f"{'pair':>5s} {'subst + coupling':>18s} {'K-loop':>14s}   leading zero 32-column sub-blocks per wave (of 8), group by group")
+    tot = [0, 0, 0, 0]
+    for j, r in model.items():
+        zs = " ".join("[" + ",".join(str(v) for v in g) + "]" for g in r["z"]) or "natural tiles"
+        print(f"j={j:<3d} {r['solve'][0]:>8d} -> {r['solve'][1]:<7d} {r['kloop'][0]:>6d} -> {r['kloop'][1]:<5d}   {zs}")
+        tot = [a + b for a, b in zip(tot, r["solve"] + r["kloop"])]
+    pct = lambda a, b: f"{100 * (b / a - 1):+.1f} %" if a else "-"   # noqa: E731
+    print(f"all   {tot[0]:>8d} -> {tot[1]:<7d} {tot[2]:>6d} -> {tot[3]:<5d}   ({pct(tot[0], tot[1])} substitution + coupling, {pct(tot[2], tot[3])} K-loop)")
+    return tot
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--poses", type=int, default=256)
@@ -23,6 +38,10 @@ def main():
     rg, m, nt = hb.row_groups(), hb.l_mask(), hb.ntiles
     if rg is None:
         print("no pair of this layout would start a K-loop late: no row groups")
+        return
+    zero_solves(rg, m)
+    if rg.ngroups == 0:
+        print("no pair of this layout would start a K-loop late: pair 0's groups only")
         return
     pop = lambda x: bin(int(x) & 15).count("1")   # noqa: E731
     per, total = rg.skipped_fraction(m)
