@@ -271,6 +271,9 @@ typedef struct {
   const int32_t* rg0_piece_rc;      /* DEVICE */
   int32_t rg0_ngroups;              /* 0: pair 0 keeps its natural tiles */
   int32_t rg0_max_tile_pieces;      /* as rg_max_tile_pieces: above the scatter limit pair 0 ALONE falls back to natural tiles */
+  const int32_t* row_first;         /* DEVICE (nvars * bd) or NULL: first[r], the first non-zero column of row r of H -- and of L, which
+                                     * fills inside the envelope of H only.  Set for every layout, with or without row groups; the
+                                     * factorisations do not read it, thx_chol_solve_env / thx_chol_solve_backward_env take it. */
 } thx_hblock_layout;
 /*      thx_hblock_fill_mask: HOST-ONLY (no device is touched) -- the table behind thx_hblock_layout.l_mask.  blocks: host (nblocks, 2)
  *      int32 pairs (row variable p, column variable q), q <= p, the non-zero bd x bd blocks of tril(H) in any order.  Runs the
@@ -603,7 +606,15 @@ int thx_vec_gather(const void* src, int64_t lds, void* dst, int64_t ldd, const i
  *        extra pass over L.
  *      thx_chol_solve_backward: x = L^-T y (second half; x may alias y).
  *      thx_chol_solve: x = (L L^T)^-1 rhs with a cached factor, any rhs -- the backward pass solves
- *        with it (cf. optimizer/autograd/baspacho_sparse_autograd.py:117-168); x may alias rhs. */
+ *        with it (cf. optimizer/autograd/baspacho_sparse_autograd.py:117-168); x may alias rhs.
+ *      thx_chol_solve_backward_env / thx_chol_solve_env: the same two solves reading only the ROW ENVELOPE of L.  row_first: DEVICE
+ *        (n) int32, a column at or left of which row r of L begins (thx_hblock_layout.row_first), or NULL = the plain solves
+ *        (which forward here with NULL).  PRECONDITION: L holds exact zeros left of row_first[r] in every row r -- the case for
+ *        every factor of a block layout, whatever the schedule.  The dense-frame kernels then fetch nothing that lies wholly left
+ *        of row_first[r] (a thread there re-reads the row's first needed 16-byte group and multiplies by zero); the sums keep
+ *        their order, so x is bit-identical to the plain solve's whenever info == 0.  (A failed factor may hold non-finite
+ *        values; 0 * inf is NaN on either path, in other places.)  Batches served by the block-row kernel read every tile as before.
+ *      All four copy only the ten 32 x 32 sub-blocks on and below the diagonal of a solve panel: the substitutions read no other. */
 int thx_chol_factor(const void* H, int64_t ld, int32_t n, int32_t B, const void* damping, int ellipsoidal,
                     double damping_eps, void* L, void* Winv, int32_t* info, int dtype, void* stream,
                     const thx_chol_schedule* schedule);
@@ -614,6 +625,10 @@ int thx_chol_solve_backward(const void* L, int64_t ld, int32_t n, int32_t B, con
                             void* x, int64_t ldv, int dtype, void* stream);
 int thx_chol_solve(const void* L, int64_t ld, int32_t n, int32_t B, const void* Winv, const void* rhs,
                    void* x, int64_t ldv, int dtype, void* stream);
+int thx_chol_solve_backward_env(const void* L, int64_t ld, int32_t n, int32_t B, const void* Winv, const void* y,
+                                void* x, int64_t ldv, const int32_t* row_first, int dtype, void* stream);
+int thx_chol_solve_env(const void* L, int64_t ld, int32_t n, int32_t B, const void* Winv, const void* rhs,
+                       void* x, int64_t ldv, const int32_t* row_first, int dtype, void* stream);
 /*      thx_chol_solve_multi: the same solves for a BLOCK of right-hand sides per problem -- what TheseusLayer.compute_samples
  *        (theseus/theseus_layer.py:99-135: delta + L^-T y for n_samples normal draws y, the sampling step of LEO,
  *        examples/state_estimation_2d.py:319) and marginal covariances (blocks of H^-1: solves against unit vectors) need from the

@@ -89,7 +89,7 @@ class HBlockLayout(Structure):  # thx_hblock_layout: block-compact Hessian (devi
         (k, c_void_p) for k in ("rg_group_ptr_host", "rg_rows", "rg_k0", "rg_tile_ptr", "rg_piece_blk", "rg_piece_rc")] + [
         ("rg_max_tile_pieces", c_int32)] + [
         (k, c_void_p) for k in ("rg_zf", "rg0_rows", "rg0_zf", "rg0_tile_ptr", "rg0_piece_blk", "rg0_piece_rc")] + [
-        ("rg0_ngroups", c_int32), ("rg0_max_tile_pieces", c_int32)]
+        ("rg0_ngroups", c_int32), ("rg0_max_tile_pieces", c_int32), ("row_first", c_void_p)]
 
 
 def hblock_fill_mask(blocks, nvars: int, bd: int):
@@ -239,6 +239,10 @@ _SIGNATURES = {
                        c_void_p],
     "thx_chol_solve_backward": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                 c_void_p],
+    "thx_chol_solve_env": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int,
+                           c_void_p],
+    "thx_chol_solve_backward_env": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int,
+                                    c_void_p],
     "thx_chol_solve_multi": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int, c_int,
                              c_void_p],
     "thx_lu_factor": [c_void_p, c_int64, c_int32, c_int32, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int,

@@ -180,6 +180,10 @@ class HessianBlocks:
         self.piece_rc = np.array([((x[1] & 0xFFFF) << 16) | (x[2] & 0xFFFF) for x in flat], dtype=np.int64).astype(np.uint32).view(np.int32)
         self.elems = self.nblocks * d * d
         self.bstride = (self.elems + 3) // 4 * 4     # elements per problem (16-byte aligned in fp32)
+        # (n) first non-zero column of every row of H -- and of L, which fills inside the envelope of H only (thx_hblock_layout.row_first)
+        firstp = np.arange(P)
+        np.minimum.at(firstp, p, q)
+        self.row_first = np.repeat(d * firstp, d).astype(np.int32)
         self._dev = {}
         self._l_mask = None
         self._row_groups = None
@@ -260,12 +264,10 @@ class RowGroups:
     def __init__(self, hb: "HessianBlocks"):
         d, P, nt = hb.bd, hb.nvars, hb.ntiles
         n = d * P
-        firstp = np.arange(P)
         by_row = [[] for _ in range(P)]
         for k, (a, b) in enumerate(hb.blocks.tolist()):
-            firstp[a] = min(firstp[a], b)
             by_row[a].append((b, k))
-        self.first = np.repeat(d * firstp, d)           # (n) first non-zero column of every row of H (and of L)
+        self.first = hb.row_first.astype(np.int64)      # (n) first non-zero column of every row of H (and of L)
         self.npairs = max(0, (nt - 1) // 2)
         group_ptr, rows, k0s, zfs, tile_ptr, pblk, prc = [0], [], [], [], [0], [], []
         self.max_tile_pieces = 0
@@ -462,6 +464,9 @@ class DeviceHessianBlocks:
         # the structurally non-zero 32x32 sub-blocks of the natural-order factor (thx_hblock_layout.l_mask), once per layout and device
         self.t["l_mask"] = torch.from_numpy(hb.l_mask()).to(device)
         c.l_mask = self.t["l_mask"].data_ptr()
+        # the row envelope of H and L for the dense-frame solves (thx_hblock_layout.row_first), with or without row groups
+        self.t["row_first"] = torch.from_numpy(hb.row_first).to(device)
+        c.row_first = self.t["row_first"].data_ptr()
         # the row groups of the fp32 column pairs (thx_hblock_layout.rg_*); none: the fields stay NULL
         rg = hb.row_groups()
         if rg is not None and rg.ngroups > 0:

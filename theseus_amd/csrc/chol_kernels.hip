@@ -652,10 +652,11 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
 template <typename T>
 static int solve_impl(const void* L, int64_t ld, int n, int B, const void* panel, const void* rhs, void* x,
                       int64_t ldv, bool forward, bool backward, hipStream_t st, const thx_tile_pattern* tp = nullptr,
-                      const thx_level_schedule* ls = nullptr) {
+                      const thx_level_schedule* ls = nullptr, const int32_t* row_first = nullptr) {
   const int ntiles = (n + TILE - 1) / TILE;
   const bool list = tp != nullptr;
-  const size_t sm = solve_smem<T>(list ? 0 : ntiles * TILE);
+  const bool env = row_first != nullptr && !list;   // the envelope path of the dense-frame kernels (thx_chol_solve_env)
+  const size_t sm = solve_smem<T>(list ? 0 : ntiles * TILE, env);
   if (sm > LDS_LIMIT) return fail("thx_chol_solve: n too large for the LDS plan (thx_chol_solve_sparse has no limit)");
   const bool packed = ld == 0;
   if (packed && (!list || !tp->row_slot || tp->nslots <= 0))
@@ -680,7 +681,7 @@ static int solve_impl(const void* L, int64_t ld, int n, int B, const void* panel
         const int nc = ls->level_col_host[l + 1] - rp.j0;
         if (nc > 0)
           launch_lds<chol_fwd_kernel<T, true>>(dev, dim3(B, nc), dim3(256), sm, st, (const T*)L, (const T*)panel, src, (T*)x, n, ld, ldv,
-                                               ntiles, rp);
+                                               ntiles, rp, nullptr);
       }
       src = (const T*)x;
     }
@@ -691,16 +692,20 @@ static int solve_impl(const void* L, int64_t ld, int n, int B, const void* panel
         const int nc = ls->level_col_host[l + 1] - rp.j0;
         if (nc > 0)
           launch_lds<chol_bwd_kernel<T, true>>(dev, dim3(B, nc), dim3(256), sm, st, (const T*)L, (const T*)panel, (const T*)x, (T*)x, n,
-                                               ld, ldv, ntiles, rp);
+                                               ld, ldv, ntiles, rp, nullptr);
       }
     }
     return check_launch("thx_chol_solve_levels");
   }
   if (forward) {
-    with_bool(list, [&](auto lk) {
-      launch_lds<chol_fwd_kernel<T, decltype(lk)::value>>(dev, dim3(B), dim3(256), sm, st, (const T*)L, (const T*)panel, src, (T*)x, n,
-                                                          ld, ldv, ntiles, rp);
-    });
+    if (env)
+      launch_lds<chol_fwd_kernel<T, false, true>>(dev, dim3(B), dim3(256), sm, st, (const T*)L, (const T*)panel, src, (T*)x, n, ld, ldv,
+                                                  ntiles, rp, row_first);
+    else
+      with_bool(list, [&](auto lk) {
+        launch_lds<chol_fwd_kernel<T, decltype(lk)::value>>(dev, dim3(B), dim3(256), sm, st, (const T*)L, (const T*)panel, src, (T*)x, n,
+                                                            ld, ldv, ntiles, rp, nullptr);
+      });
     src = (const T*)x;  // the backward pass then runs in place
   }
   // small batches, dense frame: one launch per block row (chol_bwd_rows_kernel; bit-identical to chol_bwd_kernel) -- up to
@@ -716,10 +721,13 @@ static int solve_impl(const void* L, int64_t ld, int n, int B, const void* panel
                                           ld, ldv, ntiles, jb);
     return check_launch("thx_chol_solve (block rows)");
   }
-  if (backward)
+  if (backward && env)
+    launch_lds<chol_bwd_kernel<T, false, true>>(dev, dim3(B), dim3(256), sm, st, (const T*)L, (const T*)panel, src, (T*)x, n, ld, ldv,
+                                                ntiles, rp, row_first);
+  else if (backward)
     with_bool(list, [&](auto lk) {
       launch_lds<chol_bwd_kernel<T, decltype(lk)::value>>(dev, dim3(B), dim3(256), sm, st, (const T*)L, (const T*)panel, src, (T*)x, n,
-                                                          ld, ldv, ntiles, rp);
+                                                          ld, ldv, ntiles, rp, nullptr);
     });
   return check_launch("thx_chol_solve");
 }
@@ -812,11 +820,12 @@ int thx_chol_factor_sparse(const void* H, int64_t ld, int32_t n, int32_t B, cons
 }
 
 static int solve_dispatch(const void* L, int64_t ld, int32_t n, int32_t B, const void* Winv, const void* rhs, void* x,
-                          int64_t ldv, bool fwd, bool bwd, int dtype, void* stream, const thx_tile_pattern* tp = nullptr) {
+                          int64_t ldv, bool fwd, bool bwd, int dtype, void* stream, const thx_tile_pattern* tp = nullptr,
+                          const int32_t* row_first = nullptr) {
   if (!L || !Winv || !rhs || !x) return fail("thx_chol_solve: null pointer");
   if (n <= 0 || B <= 0 || (ld != 0 && ld < n) || ldv < n) return fail("thx_chol_solve: bad sizes");
-  THX_DISPATCH(dtype, return solve_impl<float>(L, ld, n, B, Winv, rhs, x, ldv, fwd, bwd, as_stream(stream), tp),
-               return solve_impl<double>(L, ld, n, B, Winv, rhs, x, ldv, fwd, bwd, as_stream(stream), tp));
+  THX_DISPATCH(dtype, return solve_impl<float>(L, ld, n, B, Winv, rhs, x, ldv, fwd, bwd, as_stream(stream), tp, nullptr, row_first),
+               return solve_impl<double>(L, ld, n, B, Winv, rhs, x, ldv, fwd, bwd, as_stream(stream), tp, nullptr, row_first));
   return 0;
 }
 
@@ -982,14 +991,24 @@ int thx_vec_gather(const void* src, int64_t lds, void* dst, int64_t ldd, const i
   return check_launch("thx_vec_gather");
 }
 
+int thx_chol_solve_env(const void* L, int64_t ld, int32_t n, int32_t B, const void* Winv, const void* rhs, void* x,
+                       int64_t ldv, const int32_t* row_first, int dtype, void* stream) {
+  return solve_dispatch(L, ld, n, B, Winv, rhs, x, ldv, true, true, dtype, stream, nullptr, row_first);
+}
+
+int thx_chol_solve_backward_env(const void* L, int64_t ld, int32_t n, int32_t B, const void* Winv, const void* y, void* x,
+                                int64_t ldv, const int32_t* row_first, int dtype, void* stream) {
+  return solve_dispatch(L, ld, n, B, Winv, y, x, ldv, false, true, dtype, stream, nullptr, row_first);
+}
+
 int thx_chol_solve(const void* L, int64_t ld, int32_t n, int32_t B, const void* Winv, const void* rhs, void* x,
                    int64_t ldv, int dtype, void* stream) {
-  return solve_dispatch(L, ld, n, B, Winv, rhs, x, ldv, true, true, dtype, stream);
+  return thx_chol_solve_env(L, ld, n, B, Winv, rhs, x, ldv, nullptr, dtype, stream);
 }
 
 int thx_chol_solve_backward(const void* L, int64_t ld, int32_t n, int32_t B, const void* Winv, const void* y, void* x,
                             int64_t ldv, int dtype, void* stream) {
-  return solve_dispatch(L, ld, n, B, Winv, y, x, ldv, false, true, dtype, stream);
+  return thx_chol_solve_backward_env(L, ld, n, B, Winv, y, x, ldv, nullptr, dtype, stream);
 }
 
 int thx_diag(const void* H, int64_t ld, int32_t n, int32_t B, void* d, int64_t ldv, int dtype, void* stream) {

@@ -25,9 +25,41 @@ __device__ __forceinline__ void panel_g2l(const T* __restrict__ Pn, T* tile, int
     *reinterpret_cast<uint4*>(tile + rr * C::LDM + c) = *reinterpret_cast<const uint4*>(Pn + rr * TILE + c);
 }
 
+// The substitutions read the ten 32x32 sub-blocks on and below the panel's diagonal only (panel_forward: row block s, columns
+// [0, 32 s + 32); panel_backward: column block t, rows [32 t, 128)): this copy leaves the six upper ones out -- their part of the LDS
+// tile stays unwritten and unread, the layout is panel_g2l's.
+// Sub-block by sub-block, every thread one (fp64: two) 16-byte group of each: no predicate, so the ten (twenty) loads are independent
+// and in flight together, where panel_g2l's row loop goes to memory four times (eight) per panel.
 template <typename T>
-static size_t solve_smem(int npad) {
-  return (size_t)128 * CT<T>::LDM * sizeof(T) + (size_t)(npad + 128 + 32) * sizeof(T);
+__device__ __forceinline__ void panel_g2l_lower(const T* __restrict__ Pn, T* tile, int tid) {
+  using C = CT<T>;
+  constexpr int GPS = 32 / C::VEC, IPS = 32 * GPS / 256;   // 16-byte groups per sub-block row; groups per thread and sub-block
+  static_assert(IPS * 256 == 32 * GPS, "a sub-block is a whole number of rounds of the workgroup");
+  uint4 v[10 * IPS];
+#pragma unroll
+  for (int sb = 0; sb < 10; ++sb) {
+    const int sr = sb < 1 ? 0 : sb < 3 ? 1 : sb < 6 ? 2 : 3, sc = sb - sr * (sr + 1) / 2;   // (sub-block row, column), sc <= sr
+#pragma unroll
+    for (int i = 0; i < IPS; ++i) {
+      const int it = tid + 256 * i, r = 32 * sr + it / GPS, c = 32 * sc + (it % GPS) * C::VEC;
+      v[IPS * sb + i] = *reinterpret_cast<const uint4*>(Pn + r * TILE + c);
+    }
+  }
+#pragma unroll
+  for (int sb = 0; sb < 10; ++sb) {
+    const int sr = sb < 1 ? 0 : sb < 3 ? 1 : sb < 6 ? 2 : 3, sc = sb - sr * (sr + 1) / 2;
+#pragma unroll
+    for (int i = 0; i < IPS; ++i) {
+      const int it = tid + 256 * i, r = 32 * sr + it / GPS, c = 32 * sc + (it % GPS) * C::VEC;
+      *reinterpret_cast<uint4*>(tile + r * C::LDM + c) = v[IPS * sb + i];
+    }
+  }
+}
+
+// (env: the envelope path of the dense-frame kernels keeps the 128 first-column values of the current block row behind ubuf)
+template <typename T>
+static size_t solve_smem(int npad, bool env = false) {
+  return (size_t)128 * CT<T>::LDM * sizeof(T) + (size_t)(npad + 128 + 32) * sizeof(T) + (env ? 128 * sizeof(int32_t) : 0);
 }
 
 // Row-wise tile pattern of L for the list-driven solves (thx_chol_solve_sparse): for block row i the column tiles j < i with
@@ -46,10 +78,14 @@ struct RowPat {
 // L y = rhs (stand-alone; the LM iteration gets y from the factorisation).
 // LIST = false: the whole solution vector lives in LDS (n <= ~23 k fp32 / 3.4 k fp64) and every tile of a block row is streamed.
 // LIST = true : the tiles of the row's list only, and the vector stays in global memory (L2) -- no limit on n.
-template <typename T, bool LIST>
+// ENV (dense frame only): row r of L holds exact zeros left of row_first[r] (thx_chol_solve_env).  For a VEC group that lies wholly
+// left of it a lane re-reads the row's first needed group (no new bytes from HBM; unconditional loads, see chol_bwd_kernel) and adds
+// 0 instead of the group's dot product, which is a sum of exact zeros: each lane's partial sums keep their order and their bits.
+template <typename T, bool LIST, bool ENV = false>
 __global__ void __launch_bounds__(256)
 chol_fwd_kernel(const T* __restrict__ L, const T* __restrict__ panel, const T* __restrict__ rhs, T* __restrict__ y,
-                int n, int64_t ld, int64_t ldv, int ntiles, RowPat rp) {
+                int n, int64_t ld, int64_t ldv, int ntiles, RowPat rp, const int32_t* __restrict__ row_first) {
+  static_assert(!(LIST && ENV), "the envelope path is the dense frame's");
   using C = CT<T>;
   using V = typename C::V;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -71,12 +107,19 @@ chol_fwd_kernel(const T* __restrict__ L, const T* __restrict__ panel, const T* _
   const int jlo = (LIST && rp.j0 >= 0) ? rp.j0 + (int)blockIdx.y : 0, jhi = (LIST && rp.j0 >= 0) ? jlo + 1 : ntiles;
   for (int jb = jlo; jb < jhi; ++jb) {
     const int row0 = jb * TILE, valid = (LIST && rp.tile_valid) ? rp.tile_valid[jb] : min(TILE, n - row0);
-    panel_g2l<T>(panel + ((int64_t)b * ntiles + jb) * TILE * TILE, tile, tid);
+    if constexpr (LIST) panel_g2l<T>(panel + ((int64_t)b * ntiles + jb) * TILE * TILE, tile, tid);
+    else panel_g2l_lower<T>(panel + ((int64_t)b * ntiles + jb) * TILE * TILE, tile, tid);
     // t[r] = sum_{k < row0} L[row0 + r][k] y[k]: wave w takes rows r = w (mod 4), four rows in flight
     const int l0 = LIST ? rp.row_ptr[jb] : 0;
     const int items = LIST ? (rp.row_ptr[jb + 1] - l0) * QPT : row0 / C::VEC;
     for (int rr = wave; rr < TILE; rr += 16) {
       T s[4] = {T(0), T(0), T(0), T(0)};
+      int fr[4] = {0, 0, 0, 0};   // ENV: first 16-byte group of the wave's four rows, as chol_bwd_kernel's fb (wave uniform)
+      if constexpr (ENV) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          if (rr + 4 * u < valid) fr[u] = min(row_first[row0 + rr + 4 * u] / C::VEC * C::VEC, row0 - C::VEC);
+      }
       for (int it = lane; it < items; it += 64) {
         const int k = LIST ? rp.row_tile[l0 + it / QPT] * TILE + (it % QPT) * C::VEC : it * C::VEC;
         // the listed tile's rows: dense frame (row0 + r) * ld + k, or the packed tile's own 128 x 128 block
@@ -93,9 +136,12 @@ chol_fwd_kernel(const T* __restrict__ L, const T* __restrict__ panel, const T* _
         for (int u = 0; u < 4; ++u) {
           const int r = rr + 4 * u;
           if (r < valid) {
-            const V lv = *reinterpret_cast<const V*>(Lt_ + (int64_t)r * lds_);
-            if constexpr (sizeof(T) == 4) s[u] += lv.x * yk.x + lv.y * yk.y + lv.z * yk.z + lv.w * yk.w;
-            else s[u] += lv.x * yk.x + lv.y * yk.y;
+            const int out = ENV ? max(fr[u] - k, 0) : 0;   // > 0: left of the row's envelope -- re-read its first group, add 0
+            const V lv = *reinterpret_cast<const V*>(Lt_ + (int64_t)r * lds_ + out);
+            T d;
+            if constexpr (sizeof(T) == 4) d = lv.x * yk.x + lv.y * yk.y + lv.z * yk.z + lv.w * yk.w;
+            else d = lv.x * yk.x + lv.y * yk.y;
+            s[u] += out > 0 ? T(0) : d;
           }
         }
       }
@@ -127,10 +173,19 @@ chol_fwd_kernel(const T* __restrict__ L, const T* __restrict__ panel, const T* _
 }
 
 // L^T x = y : right-looking from the last block row; every (LIST: every structurally non-zero) tile of L is streamed once
-template <typename T, bool LIST>
+// ENV (dense frame only): row r of L holds exact zeros left of row_first[r] (thx_chol_solve_backward_env).  The push keeps its rows
+// (uniform across the workgroup, unrolled by 8) and the order of its fused multiply-adds.  A thread that owns columns k .. k + VEC - 1
+// needs row r only when k + VEC > row_first[r]; otherwise it re-reads the row's FIRST needed 16-byte group (which the thread that
+// owns it fetches anyway: no new bytes from HBM) and multiplies by 0 instead of x_r.  The loads stay unconditional on purpose: with
+// each of the eight loads under its own lane predicate the compiler waits for vmcnt(0) in front of every one of them, and the
+// kernel took 6.80 ms instead of 3.45 at the headline size.  What changes is a product with an exact zero turned into a product of
+// a finite number with zero, so x is bit-identical for info == 0.  A factor that failed (info != 0) may hold non-finite values, and
+// 0 * inf is NaN on either path, in other places: such a solution is garbage either way.
+template <typename T, bool LIST, bool ENV = false>
 __global__ void __launch_bounds__(256)
 chol_bwd_kernel(const T* __restrict__ L, const T* __restrict__ panel, const T* __restrict__ yin, T* __restrict__ x,
-                int n, int64_t ld, int64_t ldv, int ntiles, RowPat rp) {
+                int n, int64_t ld, int64_t ldv, int ntiles, RowPat rp, const int32_t* __restrict__ row_first) {
+  static_assert(!(LIST && ENV), "the envelope path is the dense frame's");
   using C = CT<T>;
   using V = typename C::V;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -139,6 +194,7 @@ chol_bwd_kernel(const T* __restrict__ L, const T* __restrict__ panel, const T* _
   T* z = tile + 128 * C::LDM;  // [npad]
   T* xb = z + npad;            // [128] current block
   T* ubuf = xb + 128;          // [32]
+  int32_t* fb = reinterpret_cast<int32_t*>(ubuf + 32);   // ENV: [128] first needed 16-byte group of the current block's rows
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const bool packed = LIST && rp.nslots > 0;
   const T* Lb = L + (int64_t)b * (packed ? (int64_t)rp.nslots * TILE * TILE : ld * ld);
@@ -156,8 +212,13 @@ chol_bwd_kernel(const T* __restrict__ L, const T* __restrict__ panel, const T* _
   const int jhi = (LIST && rp.j0 >= 0) ? rp.j0 + (int)blockIdx.y : ntiles - 1, jlo = (LIST && rp.j0 >= 0) ? jhi : 0;
   for (int jb = jhi; jb >= jlo; --jb) {
     const int row0 = jb * TILE, valid = (LIST && rp.tile_valid) ? rp.tile_valid[jb] : min(TILE, n - row0);
-    panel_g2l<T>(panel + ((int64_t)b * ntiles + jb) * TILE * TILE, tile, tid);
+    if constexpr (LIST) panel_g2l<T>(panel + ((int64_t)b * ntiles + jb) * TILE * TILE, tile, tid);
+    else panel_g2l_lower<T>(panel + ((int64_t)b * ntiles + jb) * TILE * TILE, tile, tid);
     if (tid < TILE) xb[tid] = LIST ? (tid < valid ? zg[row0 + tid] : T(0)) : z[row0 + tid];
+    if constexpr (ENV) {
+      // the row's first 16-byte group; a row that begins inside the diagonal tile keeps the last group in front of it (zeros)
+      if (tid < TILE) fb[tid] = tid < valid ? min(row_first[row0 + tid] / C::VEC * C::VEC, row0 - C::VEC) : 0;
+    }
     __syncthreads();
     if (wave == 0) panel_backward<T>(tile, xb, ubuf, lane);
     __syncthreads();
@@ -177,14 +238,19 @@ chol_bwd_kernel(const T* __restrict__ L, const T* __restrict__ panel, const T* _
       T s[4] = {T(0), T(0), T(0), T(0)};
       const T* Lk = packed ? Lb + (int64_t)rp.row_slot[l0 + it / QPT] * TILE * TILE + (it % QPT) * C::VEC : Lb + (int64_t)row0 * ld + k;
       const int64_t lds_ = packed ? (int64_t)TILE : ld;   // (row stride of the listed tile)
-      int rr = 0;
-      for (; rr + 8 <= valid; rr += 8) {
-        V lv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) lv[u] = *reinterpret_cast<const V*>(Lk + (int64_t)(rr + u) * lds_);
+      // eight rows r0 .. r0 + 7: the loads (out: ENV, how far left of the row's first 16-byte group the thread's columns lie; 0 =
+      // inside the envelope), and their multiply-adds in row order
+      auto load8 = [&](V (&lv)[8], int (&out)[8], int r0) {
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-          const T xv = xb[rr + u];
+          out[u] = ENV ? max(fb[r0 + u] - k, 0) : 0;
+          lv[u] = *reinterpret_cast<const V*>(Lk + (int64_t)(r0 + u) * lds_ + out[u]);
+        }
+      };
+      auto fma8 = [&](const V (&lv)[8], const int (&out)[8], int r0) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const T xv = out[u] > 0 ? T(0) : xb[r0 + u];
           // (explicit fused multiply-adds: -ffp-contract leaves the choice to the vectoriser, which mixes packed multiplies +
           //  adds into the chain -- the block-row kernel below must reproduce this sum bit for bit)
           if constexpr (sizeof(T) == 4) {
@@ -193,10 +259,45 @@ chol_bwd_kernel(const T* __restrict__ L, const T* __restrict__ panel, const T* _
             s[0] = fma_t(lv[u].x, xv, s[0]); s[1] = fma_t(lv[u].y, xv, s[1]);
           }
         }
+      };
+      int rr = 0;
+      V la[8];
+      int oa[8];
+      if constexpr (ENV) {
+        // Two groups of eight rows in flight: the lanes left of a row's envelope hold a load slot without bringing new bytes, so
+        // with one group in flight the kernel fell from the memory bound to the latency bound (15.05 GB in 3.16 ms = 4.8 TB/s
+        // where the plain kernel streams 6.2).  The next group's loads are issued before the current group's multiply-adds.
+        const int ng = valid / 8;
+        if (ng > 0) {
+          V lb[8];
+          int ob[8];
+          load8(la, oa, 0);
+          int g = 0;
+          for (; g + 2 < ng; g += 2) {
+            load8(lb, ob, 8 * (g + 1));
+            fma8(la, oa, 8 * g);
+            load8(la, oa, 8 * (g + 2));
+            fma8(lb, ob, 8 * (g + 1));
+          }
+          if (g + 1 < ng) {   // two groups left (la holds the first), or one
+            load8(lb, ob, 8 * (g + 1));
+            fma8(la, oa, 8 * g);
+            fma8(lb, ob, 8 * (g + 1));
+          } else {
+            fma8(la, oa, 8 * g);
+          }
+          rr = 8 * ng;
+        }
+      } else {
+        for (; rr + 8 <= valid; rr += 8) {
+          load8(la, oa, rr);
+          fma8(la, oa, rr);
+        }
       }
       for (; rr < valid; ++rr) {
-        const V lv = *reinterpret_cast<const V*>(Lk + (int64_t)rr * lds_);
-        const T xv = xb[rr];
+        const int out = ENV ? max(fb[rr] - k, 0) : 0;
+        const V lv = *reinterpret_cast<const V*>(Lk + (int64_t)rr * lds_ + out);
+        const T xv = out > 0 ? T(0) : xb[rr];
         if constexpr (sizeof(T) == 4) {
           s[0] = fma_t(lv.x, xv, s[0]); s[1] = fma_t(lv.y, xv, s[1]); s[2] = fma_t(lv.z, xv, s[2]); s[3] = fma_t(lv.w, xv, s[3]);
         } else {

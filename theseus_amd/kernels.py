@@ -827,11 +827,20 @@ class HipKernels:
         self.chol_schedule.f64_half_max_ktiles = int(max_ktiles)
         return prev
 
-    def chol_solve(self, L, n, panels, rhs, x):
+    @staticmethod
+    def _row_first_ptr(row_first, n):
+        """The (n) int32 device table of thx_chol_solve_env / thx_chol_solve_backward_env (None -> NULL: the plain solves)."""
+        if row_first is not None and (row_first.dtype != torch.int32 or row_first.numel() < n):
+            raise ValueError(f"row_first must hold {n} int32 values, got {row_first.dtype} x {row_first.numel()}")
+        return _lib.ptr(row_first, "row_first")
+
+    def chol_solve(self, L, n, panels, rhs, x, row_first=None):
+        """thx_chol_solve_env; ``row_first`` (a block layout's table): L holds exact zeros left of row_first[r] in every row, and the
+        solves read the row envelope only -- the same bits."""
         B, ld = L.shape[0], L.shape[-1]
-        _lib.check(self.lib.thx_chol_solve(_lib.ptr(L), ld, n, B, _lib.ptr(panels), _lib.ptr(rhs), _lib.ptr(x),
-                                           rhs.stride(0), _lib.dtype_code(L.dtype), _lib.stream_ptr(L.device)),
-                   "thx_chol_solve")
+        _lib.check(self.lib.thx_chol_solve_env(_lib.ptr(L), ld, n, B, _lib.ptr(panels), _lib.ptr(rhs), _lib.ptr(x), rhs.stride(0),
+                                               self._row_first_ptr(row_first, n), _lib.dtype_code(L.dtype),
+                                               _lib.stream_ptr(L.device)), "thx_chol_solve")
 
     def chol_solve_sparse(self, L, n, panels, rhs, x, pattern, backward_only=False):
         """thx_chol_solve_sparse: the triangular solves over the structurally non-zero tiles of L only (``pattern``: a
@@ -841,11 +850,12 @@ class HipKernels:
                                                   rhs.stride(0), int(bool(backward_only)), pattern.c_struct(L.device),
                                                   _lib.dtype_code(L.dtype), _lib.stream_ptr(L.device)), "thx_chol_solve_sparse")
 
-    def chol_solve_backward(self, L, n, panels, y, x):
+    def chol_solve_backward(self, L, n, panels, y, x, row_first=None):
+        """thx_chol_solve_backward_env (``row_first``: as ``chol_solve``)."""
         B, ld = L.shape[0], L.shape[-1]
-        _lib.check(self.lib.thx_chol_solve_backward(_lib.ptr(L), ld, n, B, _lib.ptr(panels), _lib.ptr(y), _lib.ptr(x),
-                                                    y.stride(0), _lib.dtype_code(L.dtype), _lib.stream_ptr(L.device)),
-                   "thx_chol_solve_backward")
+        _lib.check(self.lib.thx_chol_solve_backward_env(_lib.ptr(L), ld, n, B, _lib.ptr(panels), _lib.ptr(y), _lib.ptr(x), y.stride(0),
+                                                        self._row_first_ptr(row_first, n), _lib.dtype_code(L.dtype),
+                                                        _lib.stream_ptr(L.device)), "thx_chol_solve_backward")
 
     def chol_solve_multi(self, L, n, panels, rhs, x, which=0):
         """thx_chol_solve_multi: ``rhs`` / ``x`` (B, nrhs, n), one vector per row (unit stride along n, any row / batch strides

@@ -112,15 +112,26 @@ class HipCholeskyCore:
         L, panels = snapshot
         rhs = rhs.contiguous()
         x = torch.empty_like(rhs)
-        self.K.chol_solve(L, self.linearization.n, panels, rhs, x)
+        self.K.chol_solve(L, self.linearization.n, panels, rhs, x, **self._envelope())
         return x
 
+    solve_envelope = True   # False: the dense-frame solves read every tile of L in full (the same bits; tests compare the two)
+
+    def _envelope(self) -> Dict[str, torch.Tensor]:
+        """``row_first=`` of the dense-frame solves when the factor is a block layout's: every schedule of thx_chol_factor_hblocks
+        leaves exact zeros left of the first non-zero column of each row of H, and the solves read the row envelope only."""
+        lin = self.linearization
+        if self.solve_envelope and getattr(lin, "_compact", False) and lin.hblocks is not None:
+            return {"row_first": lin.hblocks.t["row_first"]}
+        return {}
+
     def _substitute(self, rhs, x, backward_only: bool):
-        """x = L^-T rhs (``backward_only``) or (L L^T)^-1 rhs with the current factor (dense frame: every tile of L)."""
+        """x = L^-T rhs (``backward_only``) or (L L^T)^-1 rhs with the current factor (dense frame: the row envelope of L when the
+        linearization is block-compact, else every tile)."""
         if backward_only:
-            self.K.chol_solve_backward(self.L, self.linearization.n, self.panels, rhs, x)
+            self.K.chol_solve_backward(self.L, self.linearization.n, self.panels, rhs, x, **self._envelope())
         else:
-            self.K.chol_solve(self.L, self.linearization.n, self.panels, rhs, x)
+            self.K.chol_solve(self.L, self.linearization.n, self.panels, rhs, x, **self._envelope())
 
     # ---- blocks of right-hand sides on the cached factor (thx_chol_solve_multi): posterior samples, marginal covariances ----------
     def _factor_owner(self) -> "HipCholeskyCore":
