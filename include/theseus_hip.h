@@ -394,6 +394,46 @@ int thx_push2_eval(const thx_push2_term* terms, int32_t n_terms, const void* x, 
 int thx_push2_error(const thx_push2_term* terms, int32_t n_terms, const void* x, int32_t V, void* err, int32_t B, int dtype,
                     const thx_se2_eps* eps, void* stream);
 
+/* ---- Homography image alignment, dense Lucas-Kanade (examples/homography_estimation.py): the cost family of the example's
+ *      objective.  terms[t] (DEVICE array built by the host, sorted by kind: the n_align alignment terms come first) is one cost
+ *      function on the (B, n) Euclidean state x; col[0] = first state column of its 8-dof variable h, H = [h0 .. h7, 1] row major:
+ *        THX_HOMOG_ALIGN  the masked mean squared difference between feat_src, warped by H, and feat_dst (the example's
+ *                         homography_error_fn over theseus/third_party/utils.py grid_sample, with G = adj(H) / det(H) and the
+ *                         plain division u = q_x / q_z), dim 1;  aux = feat_src, feat_dst (each chans x rows x cols, row major),
+ *                         weight (1);  rows, cols >= 2, chans >= 1
+ *        THX_HOMOG_PRIOR  Difference on an 8-dof Euclidean variable (theseus/embodied/misc/local_cost_fn.py:16-75), dim 8;
+ *                         aux = target (8), weight (wdim = 1: ScaleCostWeight, 8: DiagonalCostWeight)
+ *      aux[k] are device pointers of the run's dtype, aux_bstride[k] their element batch strides (0 = shared by all problems).
+ *      Both exports are two launches on `stream`.  (a) One 256-thread workgroup per (alignment term, problem, chunk of
+ *      THX_HOMOG_CHUNK destination pixels) samples feat_src at the four clamped corners of every pixel's source point, loops over
+ *      the channels and reduces sum m d^2, sum m and (eval only) the eight sums m d ds/dh in a fixed order into
+ *      scratch (n_align, B, chunks, THX_HOMOG_SUMS) doubles; `chunks` >= the largest ceil(rows * cols / THX_HOMOG_CHUNK) of the
+ *      alignment terms.  The per-pixel arithmetic runs in the run's dtype with contraction off, the sums in fp64; no atomics.
+ *      (b) thx_homog_eval: one thread per (term, problem) adds the chunks in index order and writes the WEIGHTED 1 x 8 block and
+ *      the weighted error exactly where thx_traj2_eval puts them (block width 8: block s of term t of problem b starts
+ *      (j_off + 8 * dim * s) * B + 8 * dim * b elements into J; e is (B, m) with row stride lde, the term's rows from row0), and
+ *      evaluates the prior terms.  thx_homog_error: err[b] = 0.5 * sum of the squared weighted errors, summed in fp64.
+ *      Terms whose rows, columns, blocks or sizes fall outside m / n / j_total / the limits above are skipped.  For non-finite
+ *      source coordinates the values are unspecified; no index leaves the image. */
+#define THX_HOMOG_ALIGN 0
+#define THX_HOMOG_PRIOR 1
+#define THX_HOMOG_CHUNK 1024 /* destination pixels per workgroup of stage (a) */
+#define THX_HOMOG_SUMS 10    /* doubles per (alignment term, problem, chunk) of the scratch */
+typedef struct {
+  int32_t kind, row0;
+  int32_t col[4]; /* col[0]: first state column of the 8-dof variable (the rest unused: -1) */
+  int32_t rows, cols; /* alignment: the feature maps' height and width */
+  int64_t j_off;
+  const void* aux[5];
+  int64_t aux_bstride[5];
+  int32_t wdim, chans; /* chans: alignment: the feature maps' channel count */
+} thx_homog_term;
+int thx_homog_eval(const thx_homog_term* terms, int32_t n_terms, int32_t n_align, const void* x, int64_t ldx, int32_t n,
+                   void* scratch, int32_t chunks, void* J, int64_t j_total, void* e, int64_t lde, int32_t m, int32_t B, int dtype,
+                   void* stream);
+int thx_homog_error(const thx_homog_term* terms, int32_t n_terms, int32_t n_align, const void* x, int64_t ldx, int32_t n,
+                    void* scratch, int32_t chunks, void* err, int32_t B, int dtype, void* stream);
+
 /* ---- Objective.error_metric(): 0.5 * ||weighted error||^2 per problem (core/objective.py:37-38,
  *      562-641).  `partials` is a (B, THX_ERR_CHUNKS) scratch; the reduction order is fixed
  *      (deterministic).  err is (B). */

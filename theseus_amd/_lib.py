@@ -21,6 +21,9 @@ THX_LU_MAX_N = 4096  # largest system of thx_lu_factor (include/theseus_hip.h)
 THX_BA_ERR_CHUNKS = 256
 TRAJ2_COLLISION, TRAJ2_GP, TRAJ2_PRIOR = 0, 1, 2  # THX_TRAJ2_* (kinds of a thx_traj2_term)
 PUSH2_QSP, PUSH2_MFB, PUSH2_CONTACT, PUSH2_PRIOR = 0, 1, 2, 3  # THX_PUSH2_* (kinds of a thx_push2_term)
+HOMOG_ALIGN, HOMOG_PRIOR = 0, 1  # THX_HOMOG_* (kinds of a thx_homog_term)
+THX_HOMOG_CHUNK = 1024  # destination pixels per workgroup of thx_homog_eval / thx_homog_error's first stage
+THX_HOMOG_SUMS = 10  # doubles per (alignment term, problem, chunk) of their scratch
 LOSS_NONE, LOSS_WELSCH, LOSS_HUBER, LOSS_HINGE = 0, 1, 2, 3  # THX_LOSS_* (theseus/core/robust_loss.py:33-62)
 LOSS_FLATTEN = 4  # THX_LOSS_FLATTEN: RobustCostFunction(flatten_dims=True), or-ed into a loss code
 LOSS_GEMAN_MCCLURE = 8  # THX_LOSS_GEMAN_MCCLURE (robust_loss.py:92-113; the radius entry carries log(mu * radius))
@@ -268,6 +271,9 @@ _SIGNATURES = {
     "thx_push2_eval": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int,
                        POINTER(SE2Eps), c_void_p],
     "thx_push2_error": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int, POINTER(SE2Eps), c_void_p],
+    "thx_homog_eval": [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64,
+                       c_int32, c_int32, c_int, c_void_p],
+    "thx_homog_error": [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int, c_void_p],
     "thx_diag": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_int, c_void_p],
     "thx_lm_accept": [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
                       c_void_p, c_int, c_double, c_double, c_double, c_void_p, c_int, c_void_p],

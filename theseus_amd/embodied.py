@@ -7,14 +7,15 @@
 They implement ``error`` / ``jacobians`` / ``weighted_jacobians_error``, so an objective made of them runs through the generic
 path (theseus_amd/euclidean.py: PackedEuclidean) with every backward mode; an objective made ONLY of Collision2D, GPMotionModel
 and 2-dof Difference priors is evaluated by the fused kernels of csrc/traj_kernels.hip (PackedTrajectory2D below), for which these
-classes are the fallback and the differentiable twin.
+classes are the fallback and the differentiable twin.  Further down: the planar-pushing costs on SE2 and HomographyAlignment, the
+dense image-alignment cost of examples/homography_estimation.py, with their own fused families.
 """
 from typing import List, Optional, Union
 
 import torch
 
 from . import _lib
-from .core import CostFunction, CostWeight, Point2, Variable, Vector
+from .core import CostFunction, CostWeight, Point2, ScaleCostWeight, Variable, Vector
 from .euclidean import PackedEuclidean, _is_euclidean
 from .generic import _names
 from .term_table import TermKind, TermTable, term_dtype, weight_var
@@ -439,6 +440,132 @@ class EffectorObjectContactPlanar(CostFunction):
         r = self.eff_radius.tensor
         sign = torch.where(dist < r, -torch.ones_like(dist), torch.ones_like(dist)).unsqueeze(2)
         return [J_obj * sign, J_eff * sign], (dist - r).abs()
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# homography image alignment, dense Lucas-Kanade (examples/homography_estimation.py): a torch restatement of the example's
+# homography_error_fn (:140-168) over theseus/third_party/utils.py grid_sample, with an analytic Jacobian.  An objective made only
+# of it and of Difference priors on the 8-dof variable is evaluated by the fused kernels of csrc/homog_kernels.hip
+# (theseus_amd/homography.py: PackedHomography), for which this class is the differentiable twin.
+# --------------------------------------------------------------------------------------------------------------------------------
+class HomographyAlignment(CostFunction):
+    """error = sum m (s - feat_dst)^2 / sum m over all C Hh Ww elements: s is ``feat_src`` sampled bilinearly where the homography
+    H = [h0 .. h7, 1] (row major, ``H8``'s tensor) sends each pixel of ``feat_dst``, m the mask "the four bilinear weights add up
+    to more than 0.9".  Both feature maps are (B|1, C, Hh, Ww).  In the reference's operation order:
+      pixel (i, j) -> x = 2 j / (Ww - 1) - 1, y = 2 i / (Hh - 1) - 1;  G = adj(H) / det(H) by the cofactor formula;
+      q = G (x, y, 1), u = q_x / q_z, v = q_y / q_z;  ix = ((u + 1) / 2) (Ww - 1), iy = ((v + 1) / 2) (Hh - 1);
+      the weights come from the UNCLAMPED corners floor(ix), floor(ix) + 1, ..., the four corner indices are clamped to the image.
+    Two deliberate differences from the example: the inverse is the explicit cofactor formula (torch.inverse's LU rounding cannot
+    be reproduced in a kernel, and a different last bit moves floor()), and u, v are plain divisions -- kornia's
+    convert_points_from_homogeneous guards that division with an eps of 1e-8, a variant that is not reproduced here.
+    ``jacobians()`` is the analytic 1 x 8 block with floor() and the mask held constant, written in torch operations that stay
+    differentiable w.r.t. both feature maps.  For non-finite source coordinates (q_z = 0) the result is unspecified."""
+
+    def __init__(self, H8: Vector, feat_src, feat_dst, cost_weight: Optional[CostWeight] = None, name: Optional[str] = None):
+        if cost_weight is None:   # (scale 1, where H8 lives)
+            cost_weight = ScaleCostWeight(torch.ones(1, 1, dtype=H8.dtype, device=H8.device))
+        super().__init__(cost_weight, name)
+        if not _is_euclidean(H8) or H8.dof() != 8:
+            raise ValueError(f"HomographyAlignment ({self.name}): H8 must be a Vector of dof 8.")
+        w = _names(self.weight)
+        if not ("ScaleCostWeight" in w or "DiagonalCostWeight" in w):
+            raise ValueError(f"HomographyAlignment ({self.name}): the weight must be a ScaleCostWeight or a DiagonalCostWeight of "
+                             "width 1.")
+        self.H8, self.feat_src, self.feat_dst = H8, _as_variable(feat_src), _as_variable(feat_dst)
+        self.check_shapes()
+
+    def check_shapes(self):
+        """the feature maps are 4-D, of one shape (up to the batch) and at least 2 x 2; the weight has width 1"""
+        s, d = self.feat_src.tensor, self.feat_dst.tensor
+        if s.ndim != 4 or d.ndim != 4 or s.shape[1:] != d.shape[1:] or s.shape[2] < 2 or s.shape[3] < 2:
+            raise ValueError(f"{self.name}: feat_src {tuple(s.shape)} and feat_dst {tuple(d.shape)} must be (B|1, C, Hh, Ww) feature "
+                             "maps of the same C, Hh, Ww with Hh, Ww >= 2.")
+        if "DiagonalCostWeight" in _names(self.weight) and self.weight.diagonal.tensor.shape[1] != 1:
+            raise ValueError(f"{self.name}: this cost needs a 1-dimensional DiagonalCostWeight.")
+
+    def optim_vars(self):
+        return [self.H8]
+
+    def aux_vars(self):
+        return [self.feat_src, self.feat_dst] + self.weight.aux_vars()
+
+    def dim(self) -> int:
+        return 1
+
+    @staticmethod
+    def _inverse(h: torch.Tensor):
+        """(B, 8) -> the nine entries of adj(H) / det(H), each (B, 1)"""
+        a, b, c, d, e, f, g, k = (h[:, n:n + 1] for n in range(8))
+        i = torch.ones_like(a)
+        A = [e * i - f * k, c * k - b * i, b * f - c * e,
+             f * g - d * i, a * i - c * g, c * d - a * f,
+             d * k - e * g, b * g - a * k, a * e - b * d]
+        det = (a * A[0] + b * A[3]) + c * A[6]
+        return [x / det for x in A]
+
+    def source_points(self):
+        """-> (ix, iy), each (B, Hh Ww): where every destination pixel lands in feat_src, in pixels (not clamped)"""
+        return self._geometry()[:2]
+
+    def _geometry(self):
+        h = self.H8.tensor
+        Hh, Ww = self.feat_src.tensor.shape[2:]
+        G = self._inverse(h)
+        jj = torch.arange(Ww, dtype=h.dtype, device=h.device)
+        ii = torch.arange(Hh, dtype=h.dtype, device=h.device)
+        x = ((2 * jj) / (Ww - 1) - 1).repeat(Hh).unsqueeze(0)                 # (1, P), pixel = i Ww + j
+        y = ((2 * ii) / (Hh - 1) - 1).repeat_interleave(Ww).unsqueeze(0)
+        q = [(G[3 * r] * x + G[3 * r + 1] * y) + G[3 * r + 2] for r in range(3)]
+        u, v = q[0] / q[2], q[1] / q[2]
+        ix, iy = ((u + 1) / 2) * (Ww - 1), ((v + 1) / 2) * (Hh - 1)
+        return ix, iy, G, q, u, v
+
+    def _evaluate(self, jac: bool):
+        src, dst = self.feat_src.tensor, self.feat_dst.tensor
+        C, Hh, Ww = src.shape[1:]
+        P = Hh * Ww
+        ix, iy, G, q, u, v = self._geometry()
+        B = max(ix.shape[0], src.shape[0], dst.shape[0])
+        with torch.no_grad():
+            x0, y0 = torch.floor(ix), torch.floor(iy)
+            x1, y1 = x0 + 1, y0 + 1
+
+            def index(t, hi):   # (clamped before the conversion, NaN -> 0: what the kernel's homog_idx does)
+                return torch.where(t > 0, t, torch.zeros_like(t)).clamp(max=hi).long()
+            xi0, xi1, yi0, yi1 = index(x0, Ww - 1), index(x1, Ww - 1), index(y0, Hh - 1), index(y1, Hh - 1)
+        wx1, wx0, wy1, wy0 = x1 - ix, ix - x0, y1 - iy, iy - y0
+        nw, ne, sw, se = wx1 * wy1, wx0 * wy1, wx1 * wy0, wx0 * wy0
+        with torch.no_grad():
+            m = ((((nw + ne) + sw) + se) > 0.9).to(ix.dtype).expand(B, P)
+        flat = src.reshape(src.shape[0], C, P).expand(B, C, P)
+
+        def at(r, c):
+            return flat.gather(2, (r * Ww + c).expand(B, P).unsqueeze(1).expand(B, C, P))
+        vnw, vne, vsw, vse = at(yi0, xi0), at(yi0, xi1), at(yi1, xi0), at(yi1, xi1)
+        nw_, ne_, sw_, se_ = (t.unsqueeze(1) for t in (nw, ne, sw, se))
+        s = ((vnw * nw_ + vne * ne_) + vsw * sw_) + vse * se_
+        d = s - dst.reshape(dst.shape[0], C, P)
+        count = m.sum(dim=1, keepdim=True) * C   # (the mask has the feature maps' shape: every channel counts)
+        err = ((d * d).sum(dim=1) * m).sum(dim=1, keepdim=True) / count
+        if not jac:
+            return None, err
+        dsx = (vne - vnw) * wy1.unsqueeze(1) + (vse - vsw) * wy0.unsqueeze(1)
+        dsy = (vsw - vnw) * wx1.unsqueeze(1) + (vse - vne) * wx0.unsqueeze(1)
+        gu = ((d * dsx).sum(dim=1) * m) * ((Ww - 1) / 2)
+        gv = ((d * dsy).sum(dim=1) * m) * ((Hh - 1) / 2)
+        # d s / d h_(3k+l) = -(G^T r)_k q_l with r = d s / d q, from d q / d H_kl = -G[:, k] q_l
+        r = [gu / q[2], gv / q[2], -(gu * u + gv * v) / q[2]]
+        cols = []
+        for k in range(3):
+            tk = (G[k] * r[0] + G[3 + k] * r[1]) + G[6 + k] * r[2]
+            cols += [-(2 * (tk * q[l]).sum(dim=1, keepdim=True) / count) for l in range(3) if 3 * k + l < 8]
+        return [torch.cat(cols, dim=1).unsqueeze(1)], err
+
+    def error(self) -> torch.Tensor:
+        return self._evaluate(False)[1]
+
+    def jacobians(self):
+        return self._evaluate(True)
 
 
 # --------------------------------------------------------------------------------------------------------------------------------

@@ -677,6 +677,35 @@ class HipKernels:
         _lib.check(self.lib.thx_traj2_error(_lib.ptr(table), int(n_terms), ctypes.c_void_p(x.data_ptr()), x.stride(0), int(n),
                                             _lib.ptr(err), B, _lib.dtype_code(x.dtype), _lib.stream_ptr(x.device)), "thx_traj2_error")
 
+    # ---- homography image alignment (csrc/homog_kernels.hip) -------------------------------------------
+    def _homog_args(self, what, table, n_terms, n_align, x, n, scratch, chunks):
+        """the leading arguments thx_homog_eval and thx_homog_error share"""
+        B = x.shape[0]
+        if x.stride(1) != 1 or scratch.dtype != torch.float64 or scratch.numel() < n_align * B * chunks * _lib.THX_HOMOG_SUMS:
+            raise ValueError(f"{what}: state / scratch do not fit")
+        if not x.is_cuda:
+            raise RuntimeError(f"{what}: the state must live on a HIP device (got {x.device}); there is no CPU fallback")
+        return (_lib.ptr(table), int(n_terms), int(n_align), ctypes.c_void_p(x.data_ptr()), x.stride(0), int(n), _lib.ptr(scratch),
+                int(chunks))
+
+    def homog_eval(self, table, n_terms, n_align, x, n, scratch, chunks, J, j_total, e):
+        """table: uint8 device tensor of ``n_terms`` thx_homog_term, the ``n_align`` alignment terms first; x (B, >= n) state; scratch
+        fp64 (n_align, B, chunks, THX_HOMOG_SUMS); J flat block buffer (j_total * B); e (B, m)."""
+        B = x.shape[0]
+        if J.numel() < j_total * B or e.shape[0] != B or J.dtype != x.dtype or e.dtype != x.dtype:
+            raise ValueError("homog_eval: state / block buffers do not fit")
+        args = self._homog_args("homog_eval", table, n_terms, n_align, x, n, scratch, chunks)
+        _lib.check(self.lib.thx_homog_eval(*args, _lib.ptr(J), int(j_total), _lib.ptr(e), e.stride(0), e.shape[1], B,
+                                           _lib.dtype_code(x.dtype), _lib.stream_ptr(x.device)), "thx_homog_eval")
+
+    def homog_error(self, table, n_terms, n_align, x, n, scratch, chunks, err):
+        B = x.shape[0]
+        if err.shape != (B,) or err.dtype != x.dtype:
+            raise ValueError("homog_error: state / output do not fit")
+        args = self._homog_args("homog_error", table, n_terms, n_align, x, n, scratch, chunks)
+        _lib.check(self.lib.thx_homog_error(*args, _lib.ptr(err), B, _lib.dtype_code(x.dtype), _lib.stream_ptr(x.device)),
+                   "thx_homog_error")
+
     # ---- planar pushing on SE2 (csrc/push_kernels.hip) -----------------------------------------------
     def push2_eval(self, table, n_terms, x, J, j_total, e):
         """table: uint8 device tensor of ``n_terms`` thx_push2_term; x (V, B, 4) pose-major SE2 state; J flat block buffer

@@ -696,11 +696,13 @@ class PackedPoseGraph:
 def packed_for(objective: Objective, kernels=None, order=None):
     """Get (or build) the packed representation attached to an objective (``order``: variable names in column order): the fused
     pose-graph one, the fused planar-pushing one (theseus_amd/pushing.py: PackedPlanarPushing), the fused 2D motion-planning one
-    (theseus_amd/embodied.py: PackedTrajectory2D), or -- Euclidean variables with
+    (theseus_amd/embodied.py: PackedTrajectory2D), the fused homography-alignment one (theseus_amd/homography.py:
+    PackedHomography), or -- Euclidean variables with
     cost functions that hand over their Jacobian blocks -- the generic one of theseus_amd/euclidean.py."""
     from .embodied import PackedTrajectory2D
     from .euclidean import PackedEuclidean
     from .generic import PackedState
+    from .homography import PackedHomography
     from .pushing import PackedPlanarPushing
     p = getattr(objective, "_packed", None)
     order = tuple(order) if order is not None else tuple(objective.optim_vars.keys())
@@ -718,7 +720,10 @@ def packed_for(objective: Objective, kernels=None, order=None):
                     try:
                         p = PackedTrajectory2D(objective, kernels, order)
                     except UnsupportedObjective:
-                        p = PackedEuclidean(objective, kernels, order)
+                        try:
+                            p = PackedHomography(objective, kernels, order)
+                        except UnsupportedObjective:
+                            p = PackedEuclidean(objective, kernels, order)
             except UnsupportedObjective:
                 raise fused_error from None
         objective._packed = p

@@ -1,5 +1,6 @@
 """The term table of the fused cost families (csrc/term_family.cuh; the families: theseus_amd/embodied.py PackedTrajectory2D on
-csrc/traj_kernels.hip, theseus_amd/pushing.py PackedPlanarPushing on csrc/push_kernels.hip): one 128-byte record per cost function,
+csrc/traj_kernels.hip, theseus_amd/pushing.py PackedPlanarPushing on csrc/push_kernels.hip, theseus_amd/homography.py
+PackedHomography on csrc/homog_kernels.hip): one 128-byte record per cost function,
 sorted by kind, holding where the cost's rows and Jacobian blocks go, which variables it reads and the device pointers of its
 auxiliary tensors themselves (an SDF grid shared by every cost is one tensor, stored once).  ``TermTable`` is a mixin for a packed
 class (``PackedState`` of theseus_amd/generic.py) whose NON-differentiated evaluation is such a kernel: ``assemble(graph=False)`` =
@@ -37,7 +38,8 @@ def weight_var(c):
 
 class TermKind(NamedTuple):
     aux: Callable                  # cost -> [(variable, elements per problem | None)] in the aux slot order of include/theseus_hip.h
-    grid: Optional[int] = None     # the aux slot of a (B|1, rows, cols) grid: its shape goes into ``rows`` / ``cols``
+    grid: Optional[int] = None     # the aux slot of a (B|1, rows, cols) grid: its shape goes into ``rows`` / ``cols``; of a
+                                   # (B|1, channels, rows, cols) one: the channel count also goes into ``pad`` (thx_homog_term.chans)
     wdim: int = 0                  # the record's ``wdim`` ...
     weight: Optional[int] = None   # ... or the aux slot of a Scale / Diagonal weight whose width it is
 
@@ -107,9 +109,11 @@ class TermTable:
             row["wdim"] = kind.wdim
             if kind.grid is not None:
                 grid = ts[kind.grid]
-                if grid.ndim != 3:
+                if grid.ndim not in (3, 4):
                     raise ValueError(f"{cost.name}: sdf_data of shape {tuple(grid.shape)} is not a batch of grids")
-                row["rows"], row["cols"] = grid.shape[1], grid.shape[2]
+                row["rows"], row["cols"] = grid.shape[-2], grid.shape[-1]
+                if grid.ndim == 4:
+                    row["pad"] = grid.shape[1]
             if kind.weight is not None:
                 allowed, message = self._WEIGHT_WIDTHS
                 row["wdim"] = wdim = ts[kind.weight][0].numel()
