@@ -271,6 +271,18 @@ typedef struct {
   const int32_t* rg0_piece_rc;      /* DEVICE */
   int32_t rg0_ngroups;              /* 0: pair 0 keeps its natural tiles */
   int32_t rg0_max_tile_pieces;      /* as rg_max_tile_pieces: above the scatter limit pair 0 ALONE falls back to natural tiles */
+  /* SORTED COLUMNS of the fp32 column pairs (thx_chol_schedule.sort_pair_columns; theseus_amd/compiler.py:PairColumns), all NULL =
+   * none.  The K-loop of pair (j, j + 1) needs the product of a row r below the pair and a row c of tiles j, j + 1 at column k only
+   * for k >= max(first[r], first[c]).  The row groups sort the r side; these tables sort the c side: the pair's 256 rows, stably
+   * sorted by first (a variable's rows stay adjacent), cut into eight BLOCKS of 32 sorted slots.  A block is zero at a k-chunk as
+   * long as its first slot has not begun; the kernel leaves out its loads, staging stores and products there and moves the
+   * accumulators back to natural column order behind the K-loop.  Pairs j >= 2 that have row groups only; a pair whose eight
+   * blocks all start at chunk 0 has no table and runs as without the switch. */
+  const int32_t* sc_pair_host;      /* HOST (npairs): 1 when pair j / 2 has tables, else 0 */
+  const int32_t* sc_perm;           /* DEVICE (npairs, 256): sorted slot -> row of the pair, 0 .. 255 (row 128 j + value of L); a
+                                     * bijection per pair that has tables */
+  const int32_t* sc_mask;           /* DEVICE (npairs, 4 * ntiles): bit u of sc_mask[(j / 2) * 4 * ntiles + kc], kc < 4 j, is set when
+                                     * block u (sorted slots [32 u, 32 u + 32)) is active at k-chunk kc, i.e. kc >= min first / 32 */
   const int32_t* row_first;         /* DEVICE (nvars * bd) or NULL: first[r], the first non-zero column of row r of H -- and of L, which
                                      * fills inside the envelope of H only.  Set for every layout, with or without row groups; the
                                      * factorisations do not read it, thx_chol_solve_env / thx_chol_solve_backward_env take it. */
@@ -510,7 +522,13 @@ int thx_se3_retract(const void* poses, const void* delta, int64_t ldd, double st
  *          pair 0 takes its rows group by group as well (rg0_*).  Each output element keeps the same products in the same order.
  *          The identity holds for factorisations that succeed (info == 0): failure is reported through info by the diagonal
  *          kernels, and where a panel is not finite a structurally zero entry of L, NaN without the skip, is 0 with it.
- *          1 on, 0 off (exactly the launches of regroup_rows alone), < 0: the default (on). */
+ *          1 on, 0 off (exactly the launches of regroup_rows alone), < 0: the default (on).
+ *        sort_pair_columns: where regroup_rows applies and the layout carries thx_hblock_layout.sc_*: a pair that has row groups and
+ *          sorted-column tables stages operand A of its K-loop -- the rows of tiles j, j + 1 -- in ascending order of their first
+ *          non-zero column and leaves out, per k-chunk, the blocks of 32 sorted rows that have not begun (loads, staging stores and
+ *          products), then moves the accumulators to natural column order.  Each output element keeps the same products in the
+ *          same order; like skip_zero_blocks the identity holds for info == 0.  1 on, 0 off (exactly the launches without it),
+ *          < 0: the default (on). */
 typedef struct {
   int32_t split_diag_min_batch;
   int32_t column_pairs;
@@ -523,6 +541,7 @@ typedef struct {
   int32_t skip_zero_blocks;
   int32_t regroup_rows;
   int32_t skip_zero_solves;
+  int32_t sort_pair_columns;
 } thx_chol_schedule;
 
 /* ---- thx_chol_plan: HOST-ONLY query (no device is touched, no GPU needed) -- the schedule a DENSE-frame factorisation
@@ -542,6 +561,7 @@ typedef struct {
   int32_t forward_fused;       /* has_rhs: 1 the forward substitution rides in the factorisation's kernels, 0 a kernel of its own */
   int32_t regroup_rows;        /* 1: the column pairs that have row groups take them (thx_chol_schedule.regroup_rows) */
   int32_t skip_zero_solves;    /* 1: the row groups' waves skip their zero solves and / or pair 0 runs on groups (thx_chol_schedule.skip_zero_solves) */
+  int32_t sort_pair_columns;   /* 1: the pairs that have row groups and sorted-column tables take them (thx_chol_schedule.sort_pair_columns) */
 } thx_chol_plan_info;
 int thx_chol_plan(int32_t n, int64_t ld, int32_t B, int dtype, int has_damping, int has_rhs, int64_t ldv,
                   const thx_hblock_layout* layout, const thx_chol_schedule* schedule, thx_chol_plan_info* out);

@@ -187,6 +187,7 @@ class HessianBlocks:
         self._dev = {}
         self._l_mask = None
         self._row_groups = None
+        self._pair_columns = None
 
     def l_mask(self) -> np.ndarray:
         """(ntiles, 4 * ntiles) int32: bit s of [t, c] set when the 32x32 sub-block (rows 128 t + 32 s, columns 32 c) of the
@@ -202,6 +203,13 @@ class HessianBlocks:
             rg = RowGroups(self)
             self._row_groups = rg if rg.ngroups > 0 or rg.ngroups0 > 0 else False
         return self._row_groups or None
+
+    def pair_columns(self) -> Optional["PairColumns"]:
+        """The sorted columns of the fp32 column pairs (thx_hblock_layout.sc_*), None when no pair has a table."""
+        if self._pair_columns is None:
+            pc = PairColumns(self, self.row_groups())
+            self._pair_columns = pc if pc.npairs_sorted > 0 else False
+        return self._pair_columns or None
 
     def on(self, device) -> "DeviceHessianBlocks":
         key = str(device)
@@ -445,6 +453,70 @@ class RowGroups:
         return out
 
 
+class PairColumns:
+    """The 256 columns of every fp32 column pair sorted by their first non-zero column (thx_hblock_layout.sc_*).
+
+    The K-loop of pair (j, j + 1) multiplies row r below the pair with row c of tiles j, j + 1 over the columns k < 128 j; the
+    product is structurally zero for k < max(first[r], first[c]).  ``RowGroups`` sorts the r side.  Here the c side: the pair's 256
+    matrix rows 128 j ... 128 j + 255, stably sorted by ``first`` (a variable's rows stay adjacent), are cut into eight blocks of 32
+    sorted slots; block u is zero in every k-chunk before ``first_chunk[u] = min first // 32`` (a value >= 4 j: never active in
+    this pair).  Pairs j >= 2 that have row groups (the kernel variant is the row groups'); a pair whose eight blocks all start at
+    chunk 0 has no table.
+
+    has          (npairs)              1: the pair has tables
+    perm         (npairs, 256)         sorted slot -> column of the pair, 0 ... 255 (matrix row 128 j + value); identity without tables
+    first_chunk  (npairs, 8)           per block min first // 32
+    mask         (npairs, 4 ntiles)    per k-chunk kc < 4 j: bit u set when block u is active (kc >= first_chunk[u]); 255 elsewhere
+    """
+
+    def __init__(self, hb: "HessianBlocks", rg: Optional[RowGroups]):
+        nt = hb.ntiles
+        first = hb.row_first.astype(np.int64)
+        self.npairs = max(0, (nt - 1) // 2)
+        self.has = np.zeros(self.npairs, dtype=np.int32)
+        self.perm = np.tile(np.arange(2 * TILE, dtype=np.int32), (self.npairs, 1))
+        self.first_chunk = np.zeros((self.npairs, 8), dtype=np.int32)
+        self.mask = np.full((self.npairs, 4 * nt), 255, dtype=np.int32)
+        for jp in range(1, self.npairs):
+            if rg is None or rg.group_ptr[jp + 1] == rg.group_ptr[jp]:
+                continue
+            j = 2 * jp
+            f = first[TILE * j:TILE * j + 2 * TILE]
+            order = np.argsort(f, kind="stable")
+            fc = f[order].reshape(8, 32).min(1) // 32
+            if fc.max() == 0:
+                continue
+            self.has[jp] = 1
+            self.perm[jp] = order
+            self.first_chunk[jp] = fc
+            for kc in range(4 * j):
+                self.mask[jp, kc] = sum(1 << u for u in range(8) if kc >= fc[u])
+        self.npairs_sorted = int(self.has.sum())
+
+    def executed_fraction(self, rg: RowGroups):
+        """Model in 32x32x32 block products, per pair j: the K-loop's products executed with the row groups and the natural-order
+        column masks (``l_mask``; what ``RowGroups.skipped_fraction`` counts) against the row groups and the sorted blocks, both as
+        shares of the dense count.  Returns ({j: (today, sorted)}, (today, sorted) over all pairs with a K-loop)."""
+        hb = rg._hb
+        l_mask, nt = hb.l_mask(), hb.ntiles
+        pop = lambda m: bin(int(m)).count("1")   # noqa: E731
+        per, tot, run_a, run_b = {}, 0, 0, 0
+        for jp in range(1, self.npairs):
+            j = 2 * jp
+            allp = (nt - 2 - j) * 4 * j * 32
+            g0, g1 = int(rg.group_ptr[jp]), int(rg.group_ptr[jp + 1])
+            nat = [pop(l_mask[j, kc] & 15) + pop(l_mask[j + 1, kc] & 15) for kc in range(4 * j)]
+            srt = [pop(self.mask[jp, kc] & 255) for kc in range(4 * j)] if self.has[jp] else nat
+            if g1 > g0:
+                a = sum(4 * nat[kc] for g in range(g0, g1) for kc in range(int(rg.k0[g]), 4 * j))
+                b = sum(4 * srt[kc] for g in range(g0, g1) for kc in range(int(rg.k0[g]), 4 * j))
+            else:
+                a = b = sum(pop(l_mask[i, kc] & 15) * nat[kc] for i in range(j + 2, nt) for kc in range(4 * j))
+            per[j] = (a / allp, b / allp)
+            tot, run_a, run_b = tot + allp, run_a + a, run_b + b
+        return per, ((run_a / tot, run_b / tot) if tot else (0.0, 0.0))
+
+
 class DeviceHessianBlocks:
     _FIELDS = ["diag_blk", "inc_blk", "tile_ptr", "piece_blk", "piece_rc"]
 
@@ -481,4 +553,11 @@ class DeviceHessianBlocks:
                 self.t["rg0_" + f] = torch.from_numpy(np.ascontiguousarray(getattr(rg, f + "0"))).to(device)
                 setattr(c, "rg0_" + f, self.t["rg0_" + f].data_ptr())
             c.rg0_ngroups, c.rg0_max_tile_pieces = rg.ngroups0, rg.max_tile_pieces0
+        pc = hb.pair_columns()   # the sorted columns of the pairs that have row groups (thx_hblock_layout.sc_*); none: NULL
+        if pc is not None:
+            self.sc_pair_host = np.ascontiguousarray(pc.has)   # (host table: kept alive here)
+            c.sc_pair_host = self.sc_pair_host.ctypes.data
+            for f in ("perm", "mask"):
+                self.t["sc_" + f] = torch.from_numpy(np.ascontiguousarray(getattr(pc, f))).to(device)
+                setattr(c, "sc_" + f, self.t["sc_" + f].data_ptr())
         self.c = c

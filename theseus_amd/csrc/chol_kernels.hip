@@ -145,6 +145,7 @@ struct FactorPlan {
   bool regroup;          // ... and the column pairs that have row groups take them (HBlk.rg_*, thx_chol_schedule.regroup_rows)
   bool zsolve;           // ... their waves skip zero solves (HBlk.rg_zf) and / or pair 0 runs on groups (thx_chol_schedule.skip_zero_solves)
   bool pair0;            // pair 0 takes its own row groups (HBlk.rg0_*; only with zsolve)
+  bool sortcols;         // the pairs with row groups and sorted-column tables take those too (HBlk.sc_*, thx_chol_schedule.sort_pair_columns)
   int hbm;               // the off-diagonal kernels' HB template argument: 0 dense H, HB_MODE_SCATTER, HB_MODE_ROUNDS
   int f64_wide_max, f64_half_max;
 };
@@ -202,6 +203,7 @@ static FactorPlan plan_factor(bool f64, int n, int64_t ld, int B, bool has_dampi
   p.pair0 = zs && p.ntiles > 2 && hbp->rg0_ngroups > 0 && hbp->rg0_rows && hbp->rg0_zf && hbp->rg0_tile_ptr && hbp->rg0_piece_blk &&
             hbp->rg0_piece_rc && (p.hbm != HB_MODE_SCATTER || hbp->rg0_max_tile_pieces <= hb_scatter_max);
   p.zsolve = (zs && p.regroup && hbp->rg_zf) || p.pair0;
+  p.sortcols = p.regroup && (!sched || sched->sort_pair_columns != 0) && hbp->sc_pair_host && hbp->sc_perm && hbp->sc_mask;
   return p;
 }
 
@@ -275,9 +277,18 @@ struct FactorLaunch {
     if constexpr (sizeof(T) == 4)
       with_hb_mode(P.hbm, [&](auto mode) {
         constexpr int M = decltype(mode)::value;
-        if constexpr (M != 0)
+        if constexpr (M != 0) {
+          if (P.sortcols && j >= 2 && x.sc_pair_host[j / 2]) {   // this pair's sorted columns
+            HBlk xs = x;
+            xs.sc_perm = x.sc_perm + (int64_t)(j / 2) * 2 * TILE;
+            xs.sc_mask = x.sc_mask + (int64_t)(j / 2) * 4 * P.ntiles;
+            launch_lds<chol_offdiag2_f32_kernel<M, true, true>>(dev, dim3((h.nb + 7) / 8 * 8 * ng), dim3(256), OFF2_SMEM, h.s, H_of(h),
+                                                                L_of(h), panel_of(h), n, ld, j, P.ntiles, g_first, ng, h.nb, xs);
+            return;
+          }
           launch_lds<chol_offdiag2_f32_kernel<M, true>>(dev, dim3((h.nb + 7) / 8 * 8 * ng), dim3(256), OFF2_SMEM, h.s, H_of(h), L_of(h),
                                                         panel_of(h), n, ld, j, P.ntiles, g_first, ng, h.nb, x);
+        }
       });
   }
 
@@ -636,6 +647,7 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
   if (!P.zskip) hb.l_mask = nullptr;
   if (!P.regroup) hb.rg_rows = hb.rg_k0 = hb.rg_tile_ptr = hb.rg_piece_blk = hb.rg_piece_rc = nullptr;
   if (!P.zsolve || !P.regroup) hb.rg_zf = nullptr;
+  if (!P.sortcols) hb.sc_perm = hb.sc_mask = hb.sc_pair_host = nullptr;
   std::lock_guard<std::mutex> guard(g_launch_mutex);
   const int dev = current_device();
   const FactorLaunch<T> c{H, ld, n, B, damping, ellipsoidal, eps, L, panel, info, rhs, y, ldv, st, tp, ls, P, pat, use_hb, hb, packed,
@@ -777,7 +789,8 @@ static HBlk hblk_from(const thx_hblock_layout* layout, const void* Hc, int64_t b
   return HBlk{Hc, bstride, layout->bd, layout->tile_ptr, layout->piece_blk, layout->piece_rc, layout->diag_blk, layout->max_tile_pieces,
               layout->l_mask, layout->rg_rows, layout->rg_k0, layout->rg_tile_ptr, layout->rg_piece_blk, layout->rg_piece_rc,
               layout->rg_group_ptr_host, layout->rg_max_tile_pieces, layout->rg_zf, layout->rg0_rows, layout->rg0_zf, layout->rg0_tile_ptr,
-              layout->rg0_piece_blk, layout->rg0_piece_rc, layout->rg0_ngroups, layout->rg0_max_tile_pieces};
+              layout->rg0_piece_blk, layout->rg0_piece_rc, layout->rg0_ngroups, layout->rg0_max_tile_pieces, layout->sc_perm,
+              layout->sc_mask, layout->sc_pair_host};
 }
 
 int thx_chol_factor(const void* H, int64_t ld, int32_t n, int32_t B, const void* damping, int ellipsoidal,
@@ -883,6 +896,7 @@ int thx_chol_plan(int32_t n, int64_t ld, int32_t B, int dtype, int has_damping, 
   out->forward_fused = has_rhs && (!rl || p.rl_fwd_fused);
   out->regroup_rows = p.regroup;
   out->skip_zero_solves = p.zsolve;
+  out->sort_pair_columns = p.sortcols;
   return 0;
 }
 

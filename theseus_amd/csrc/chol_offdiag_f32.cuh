@@ -280,7 +280,17 @@ static_assert(64 * 132 <= OFF2_PANEL_OFF, "the H gather (half a tile) must not t
 static_assert(2 * 128 * 36 <= OFF2_PANEL_OFF, "staging buffers 0 and 1 must not touch the panel copy");
 static_assert(OFF2_SMEM >= 3 * 128 * 36 * 4 && 2 * OFF2_SMEM <= 160 * 1024, "three staging buffers; two workgroups per CU");
 
-template <int HB, bool RG = false>   // (HB as chol_offdiag_f32_kernel; RG: i_first is the pair's first GROUP, nrow_tiles its group count)
+// SORTED COLUMNS (SC; FactorPlan.sortcols, HBlk.sc_perm / sc_mask of THIS pair): the column side of the K-loop gets what the row
+// groups gave the row side.  The pair's 256 columns c -- the rows of tiles j, j + 1, operand A -- are staged in ascending order of
+// their first non-zero column: staged block u of sA0 / sA1 (32 rows) holds sorted slots 32 u .. / 128 + 32 u ..., and is all zero at
+// a chunk as long as its FIRST row has not begun.  sc_mask[kc] names the eight blocks' active ones: for the others the loads, the
+// staging stores and the MFMAs are left out (workgroup-uniform, as the m0 / m1 branch).  Every column accumulates independently
+// of the others and keeps its products in their order; P0 / P1 hold sorted slots until the K-loop ends and are then moved to natural
+// column order through LDS, 128 columns at a time, each wave its own 32 rows.  Everything behind runs on natural P0 / P1.
+constexpr int OFF2_UNPERM_LD = 129;   // row stride of the un-permute buffer: 128 columns + one that takes the other half's values
+static_assert(4 * 32 * OFF2_UNPERM_LD * 4 <= OFF2_SMEM, "the four waves' un-permute buffers fit in the kernel's LDS");
+
+template <int HB, bool RG = false, bool SC = false>   // (HB as chol_offdiag_f32_kernel; RG: i_first is the pair's first GROUP, nrow_tiles its group count)
 __global__ void __launch_bounds__(256, 2)
 chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, const float* __restrict__ panel, int n,
                          int64_t ld, int j, int ntiles, int i_first, int nrow_tiles, int B, HBlk hb) {
@@ -345,10 +355,24 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
 
   HBPre2<float, HB ? 2 * HB_NPRE_OFF : 1> hb2;
   // ---- K-loop over block columns 0 .. j - 1: P0 += L_i L_j^T, P1 += L_i L_{j+1}^T ----
+  static_assert(!SC || RG, "sorted columns come with row groups");
   const int lrow = tid >> 3, lc = tid & 7;
   unsigned voff[4];
+  auto natural_voff = [&]() __attribute__((always_inline)) {
 #pragma unroll
-  for (int u = 0; u < 4; ++u) voff[u] = (unsigned)(((lrow + 32 * u) * (int)ld + lc * 4) * 4);
+    for (int u = 0; u < 4; ++u) voff[u] = (unsigned)(((lrow + 32 * u) * (int)ld + lc * 4) * 4);
+  };
+  if constexpr (!SC) natural_voff();   // (SC: the K-loop has offsets of its own, these are made behind it for gload1)
+  // SC: operand A's staged row lrow + 32 u of sA0 / sA1 is the pair's sorted slot 32 u + lrow / 128 + 32 u + lrow -- row sc_perm[slot]
+  // of the 256 rows from col0 on
+  unsigned voffA0[4], voffA1[4];
+  if constexpr (SC) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      voffA0[u] = (unsigned)((hb.sc_perm[lrow + 32 * u] * (int)ld + lc * 4) * 4);
+      voffA1[u] = (unsigned)((hb.sc_perm[128 + lrow + 32 * u] * (int)ld + lc * 4) * 4);
+    }
+  }
   // operand B's rows: RG -- the group's rows anywhere in the frame (the host checked n * ld * 4 < 2^31); a slot without a row is
   // out of the buffer's range and reads zeros, as the rows behind the matrix do
   unsigned voffB[4];
@@ -368,16 +392,30 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
   const __amdgpu_buffer_rsrc_t rsB =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Lb + (RG ? (int64_t)0 : (int64_t)row0 * ld)), 0,
                                         (int)((RG ? n : validB) * ld * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsA =   // (SC: the rows of both tiles, sorted slots point anywhere in them)
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Lb + (int64_t)col0 * ld), 0, (int)(2 * TILE * ld * 4), 0x00020000);
   uint4 q0[4], q1[4], qb[4];
-  auto gload3 = [&](int kc) __attribute__((always_inline)) {
+  // (SC: am, the chunk's 8-bit mask of active sorted blocks -- block u of sA0 is bit u, of sA1 bit 4 + u; an inactive block is not loaded)
+  auto gload3 = [&](int kc, int am) __attribute__((always_inline)) {
     const int so = kc * 32 * 4;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(rsA0, voff[u], so, 0);
-      const u32x4 c = __builtin_amdgcn_raw_buffer_load_b128(rsA1, voff[u], so, 0);
+      if constexpr (SC) {
+        if ((am >> u) & 1) {
+          const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(rsA, voffA0[u], so, 0);
+          q0[u] = make_uint4(a.x, a.y, a.z, a.w);
+        }
+        if ((am >> (4 + u)) & 1) {
+          const u32x4 c = __builtin_amdgcn_raw_buffer_load_b128(rsA, voffA1[u], so, 0);
+          q1[u] = make_uint4(c.x, c.y, c.z, c.w);
+        }
+      } else {
+        const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(rsA0, voff[u], so, 0);
+        const u32x4 c = __builtin_amdgcn_raw_buffer_load_b128(rsA1, voff[u], so, 0);
+        q0[u] = make_uint4(a.x, a.y, a.z, a.w);
+        q1[u] = make_uint4(c.x, c.y, c.z, c.w);
+      }
       const u32x4 d = __builtin_amdgcn_raw_buffer_load_b128(rsB, voffB[u], so, 0);
-      q0[u] = make_uint4(a.x, a.y, a.z, a.w);
-      q1[u] = make_uint4(c.x, c.y, c.z, c.w);
       qb[u] = make_uint4(d.x, d.y, d.z, d.w);
     }
   };
@@ -395,7 +433,17 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
   int k0 = 0;   // first chunk of the K-loop
   if constexpr (RG)   // (with the strips' table min(zmin, nk) is rg_k0[i], min(min first / 32, 4 j); pair 0's tables have no rg_k0)
     k0 = hb.rg_zf ? min(zmin, nk) : __builtin_amdgcn_readfirstlane(hb.rg_k0[i]);
-  if (nk > k0) gload3(k0);
+  // SC: the masks come two chunks ahead of the MFMAs -- the next chunk's loads branch on theirs (scm1), and a scalar load issued with
+  // those loads (scm2) has completed under a whole chunk's MFMAs by the time it is needed
+  const lmask_t scm = (lmask_t)(uintptr_t)hb.sc_mask;
+  int scm1 = 255, scm2 = 255;
+  if constexpr (SC) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) q0[u] = q1[u] = make_uint4(0u, 0u, 0u, 0u);
+    if (nk > k0) scm1 = scm[k0];
+    if (nk > k0 + 1) scm2 = scm[k0 + 1];
+  }
+  if (nk > k0) gload3(k0, scm1);
   if constexpr (RG) hb2.load_run(hq, b, 2 * i, tid);
   else if constexpr (HB) hb2.load(hb, b, i, j, tid);
   const float* sBw = sB + 32 * wave * 36;
@@ -404,7 +452,7 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
   // sub-block).  An MFMA of an all-zero operand adds exact zeros: its output block's products are left out (wave-uniform
   // branches), every accumulator still receives the others in the same order.  Scalar loads through the constant address space
   // (as kloop_f's K-list), one chunk ahead: issued with the chunk's operand prefetch, they complete under the MFMAs.
-  const lmask_t lm = (lmask_t)(uintptr_t)hb.l_mask;
+  const lmask_t lm = (lmask_t)(uintptr_t)(SC ? nullptr : hb.l_mask);   // (SC: the natural-order masks say nothing about sorted blocks)
   const int nch = 4 * ntiles;
   int nm0 = 15, nm1 = 15, nmi = 15;   // the masks of the next chunk
   auto lmask_load = [&](int kc) __attribute__((always_inline)) {
@@ -416,18 +464,22 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
   };
   if (nk > k0) lmask_load(k0);
   for (int kc = k0; kc < nk; ++kc) {
-    const int m0 = nm0, m1 = nm1, mi = nmi;
+    const int m0 = SC ? (scm1 & 15) : nm0, m1 = SC ? (scm1 >> 4) : nm1, mi = nmi;
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int row = lrow + 32 * u;
-      *reinterpret_cast<uint4*>(sA0 + row * 36 + 4 * lc) = q0[u];
-      *reinterpret_cast<uint4*>(sA1 + row * 36 + 4 * lc) = q1[u];
+      if (!SC || ((m0 >> u) & 1)) *reinterpret_cast<uint4*>(sA0 + row * 36 + 4 * lc) = q0[u];
+      if (!SC || ((m1 >> u) & 1)) *reinterpret_cast<uint4*>(sA1 + row * 36 + 4 * lc) = q1[u];
       *reinterpret_cast<uint4*>(sB + row * 36 + 4 * lc) = qb[u];
     }
     __syncthreads();
-    if (kc + 1 < nk) {
-      gload3(kc + 1);
+    if constexpr (SC) {
+      scm1 = scm2;
+      if (kc + 1 < nk) gload3(kc + 1, scm1);
+      if (kc + 2 < nk) scm2 = scm[kc + 2];
+    } else if (kc + 1 < nk) {
+      gload3(kc + 1, 255);
       lmask_load(kc + 1);
     }
     if constexpr (!RG)
@@ -566,6 +618,45 @@ chol_offdiag2_f32_kernel(const float* __restrict__ H, float* __restrict__ L, con
               make_float4(X.v[cb][4 * q], X.v[cb][4 * q + 1], X.v[cb][4 * q + 2], X.v[cb][4 * q + 3]);
     }
   };
+
+  if constexpr (SC) {
+    natural_voff();
+    // ---- un-permute: P0 / P1 hold the pair's columns in sorted order, lane (rl, g) those of row 32 wave + rl at sorted slots
+    //      32 cb + 8 q + 4 g + s.  Two rounds of 128 natural columns (tile j -> P0, tile j + 1 -> P1): the lane writes all of its 256
+    //      values to row rl of the wave's buffer, a value of the other tile to the row's spare column 128, and reads its natural
+    //      columns back.  Round 0's values wait in T until round 1 has read P0 / P1 for the last time.  A wave's LDS operations
+    //      execute in order and only its own lanes touch its buffer; the barrier in front separates them from the K-loop's last
+    //      chunk, the one behind (tile (i, j)'s, below) from the panel copy, which lands on top of these buffers.
+    if (nk > k0) {   // (else P0 = P1 = 0; zall < 4 then: the branch below opens with the barrier behind)
+      __syncthreads();
+      if (zf < nk) {   // (else this wave ran no chunk)
+        float* ub = smem + wave * (32 * OFF2_UNPERM_LD) + rl * OFF2_UNPERM_LD;
+        Engine<float>::Acc T;
+        auto round = [&](int t, Engine<float>::Acc& D) __attribute__((always_inline)) {
+#pragma unroll
+          for (int cb = 0; cb < 8; ++cb)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              const int4 pv = *reinterpret_cast<const int4*>(hb.sc_perm + 32 * cb + 8 * q + 4 * g);
+              const Engine<float>::Acc& S = cb < 4 ? P0 : P1;
+              ub[min((unsigned)(pv.x - 128 * t), 128u)] = S.v[cb & 3][4 * q + 0];
+              ub[min((unsigned)(pv.y - 128 * t), 128u)] = S.v[cb & 3][4 * q + 1];
+              ub[min((unsigned)(pv.z - 128 * t), 128u)] = S.v[cb & 3][4 * q + 2];
+              ub[min((unsigned)(pv.w - 128 * t), 128u)] = S.v[cb & 3][4 * q + 3];
+            }
+          __builtin_amdgcn_wave_barrier();
+#pragma unroll
+          for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) D.v[cb][q] = ub[32 * cb + 8 * (q >> 2) + 4 * g + (q & 3)];
+          __builtin_amdgcn_wave_barrier();
+        };
+        round(0, T);
+        round(1, P1);
+        P0 = T;
+      }
+    }
+  }
 
   Engine<float>::Acc X0;
   bool first = true;   // (no h_minus call yet)

@@ -125,6 +125,12 @@ struct HBlk {
   const int32_t* rg0_piece_rc;
   int rg0_ngroups;
   int rg0_max_tile_pieces;
+  // thx_hblock_layout.sc_*: the sorted columns of the fp32 column pairs (chol_offdiag2_f32_kernel<HB, true, true>, the only kernel
+  // that reads them) -- set by factor_impl only with FactorPlan.sortcols, nullptr otherwise; pair_groups points sc_perm / sc_mask
+  // at the tables of the launch's OWN pair
+  const int32_t* sc_perm;        // (256) sorted slot -> column of the pair, 0 .. 255
+  const int32_t* sc_mask;        // (4 ntiles) per k-chunk the 8-bit mask of the active sorted blocks
+  const int32_t* sc_pair_host;   // (HOST table, npairs: the pair has tables; no kernel reads it)
 };
 
 // The pieces of lower tile (ti, tj) of problem b -- f(r, c, value), (r, c) relative to the tile origin and inside the tile; the

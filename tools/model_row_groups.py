@@ -68,6 +68,18 @@ def main():
     print(f"K-loops of the factor: {kloops} tile products, {pair_k:.0f} of them in the pair kernel; left out {pair_k * total:.1f} "
           f"regrouped, {pair_k * (1 - today / all_p):.1f} by the masks alone: {kloops - pair_k * (1 - today / all_p):.1f} -> "
           f"{kloops - pair_k * total:.1f} executed ({100 * pair_k * (total - (1 - today / all_p)) / (kloops - pair_k * (1 - today / all_p)):.1f} % fewer)")
+    # thx_chol_schedule.sort_pair_columns (PairColumns, thx_hblock_layout.sc_*): the pair's 256 columns sorted by first, 8 blocks of 32
+    pc = hb.pair_columns()
+    if pc is None:
+        print("sorted pair columns: no pair has a table")
+        return
+    pcper, (ex_a, ex_b) = pc.executed_fraction(rg)
+    print(f"{'pair':>5s} {'executed, regrouped':>20s} {'with sorted columns':>20s}   first chunks of the 8 sorted blocks")
+    for j, (xa, xb) in pcper.items():
+        fc = pc.first_chunk[j // 2].tolist() if pc.has[j // 2] else "no table"
+        print(f"j={j:<3d} {xa:20.3f} {xb:20.3f}   {fc}")
+    print(f"all pair K-loops: {ex_a:.3f} -> {ex_b:.3f} executed; {pair_k * (ex_a - ex_b):.1f} of the factor's {kloops - pair_k * total:.1f} "
+          f"executed tile products left out")
 
 if __name__ == "__main__":
     main()
