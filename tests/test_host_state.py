@@ -245,7 +245,7 @@ def test_update_skips_the_variable_walk_only_when_batch_and_device_are_unchanged
 
 def test_one_repointing_per_forward_and_the_inputs_are_never_written():
     """The optimizer's first sync packs the caller's tensors into a PRIVATE state buffer and leaves the variables on the tensors they
-    hold; they are re-pointed ONCE, to views of the final state, when the loop is done (PackedPoseGraph.sync, ``_defer_repoint``) --
+    hold; they are re-pointed ONCE, to views of the final state, when the loop is done (TrackedVariables._finish_sync, ``_defer_repoint``) --
     re-pointing them to the packed copy first was 5 ms of host time per forward at 4096 poses.  The caller's tensors keep their
     values; an end_iter_callback still sees the current iterate (the loop flushes before anybody can look)."""
     th, g, obj, opt, layer = _layer(iters=3)

@@ -16,21 +16,16 @@ import numpy as np
 import torch
 
 from . import _lib
-from .core import Objective, Variable
+from .core import Objective
 from .compiler import PoseGraphStructure
-from .kernels import PGTensors, default_kernels, fast_approx_local_jacobians, round_up
+from .kernels import PGTensors, fast_approx_local_jacobians, round_up
 from .linear_solver import DenseCholeskyOnly, LinearSolver
 from .linearization import Linearization, VariableOrdering
-from .packed import (UnsupportedObjective, _AuxDeepStamp, _aux_vars, _kind, _opt_deep_stamp, _radius_vars, _unwrap_robust,
-                     _views_deep_stamp, _weight_diag)
+from .packed import UnsupportedObjective, _aux_vars, _kind, _radius_vars, _unwrap_robust, _weight_diag
+from .packer_base import TrackedVariables
 
 ERR_CHUNKS = _lib.THX_BA_ERR_CHUNKS
 
-
-import operator
-
-_GET_TENSOR = {True: operator.attrgetter("_tensor"), False: operator.attrgetter("tensor")}   # own Variable: skip the property
-_DATA_PTR, _VERSION, _NUM_UPDATES = operator.methodcaller("data_ptr"), operator.attrgetter("_version"), operator.attrgetter("_num_updates")
 
 def _csr(owner: np.ndarray, n: int, secondary: Optional[np.ndarray] = None):
     """ids grouped by owner (stable / sorted by ``secondary``) -> (ptr (n+1), ids)."""
@@ -169,14 +164,16 @@ class BATensors:
         return d
 
 
-class PackedBA:
+class PackedBA(TrackedVariables):
     """Packed device representation of a bundle-adjustment objective (the PackedPoseGraph of this problem class)."""
 
     group = "BA"
+    # the optimizer's first sync re-points the variables at the packed copy of its inputs, the end of the loop at the final state:
+    # two re-pointings per forward().  Deferring the first one changes when the callers' tensors are replaced.
+    defers_repoint = False
 
     def __init__(self, objective: Objective, kernels=None):
-        self.objective = objective
-        self.K = kernels or default_kernels()
+        super().__init__(objective, kernels)
         self.cam_vars, self.pt_vars = [], []
         for v in objective.optim_vars.values():
             k = _kind(v)
@@ -243,20 +240,7 @@ class PackedBA:
         self._cost_rows_dev: Dict[str, Any] = {}
         self.version = objective.current_version
         self.tensors: Optional[BATensors] = None
-        seen, self._tracked_list = set(), []          # shared calibration / weights / radius appear once
-        for v in self._walk_tracked():
-            if id(v) not in seen:
-                seen.add(id(v))
-                self._tracked_list.append(v)
-        self._own_variables = all(isinstance(v, Variable) for v in self._tracked_list)
-        self._stamp = None
-        self._deep_stamp = None
-        self._aux_stamp = _AuxDeepStamp()
-        self._keep_graph_tensors = False   # (see PackedPoseGraph)
-        self._global_stamp = -1
-        self._vars_stale = False
-        self._state_exposed = False
-        self._scratch = {}
+        self._start_tracking()
 
     def _refuse_fast_approx(self, exc=NotImplementedError):
         """See PackedPoseGraph._refuse_fast_approx (the SE3 camera priors would silently get their exact Jacobian)."""
@@ -265,12 +249,6 @@ class PackedBA:
                       "kernels (camera Difference/Local costs); there is no CPU/eager fallback.")
 
     # ---- packing ------------------------------------------------------------------------------------------
-    def _tracked(self):
-        return self._tracked_list
-
-    def tracked_list(self):
-        return self._tracked_list
-
     def _walk_tracked(self):
         yield from self.cam_vars
         yield from self.pt_vars
@@ -288,30 +266,8 @@ class PackedBA:
             yield c.measurement
             yield from _aux_vars(c.weight)
 
-    def _counters_unchanged(self) -> bool:
-        return self._own_variables and self._stamp is not None and Variable._global_updates == self._global_stamp
-
-    def _current_stamp(self, deep: bool = False, count: Optional[int] = None):
-        # the objective is frozen once an optimizer holds it (Optimizer.optimize checks its version): the walk over the cost
-        # functions is done once, later stamps are one pass over the cached list (7 k variables at the headline size)
-        tracked = self.__dict__.get("_tracked_list")
-        if tracked is None:
-            tracked = self._tracked_list = list(self._tracked())
-        if count is not None:
-            tracked = tracked[:count]
-        if deep:
-            # (optimisation part, auxiliary part): see PackedPoseGraph._current_stamp / packed._AuxDeepStamp
-            ts = list(map(_GET_TENSOR[self._own_variables], tracked))
-            n_opt = min(len(self.cam_vars) + len(self.pt_vars), len(ts))
-            opt = _opt_deep_stamp(ts[:n_opt])
-            return opt if count is not None else (opt, self._aux_stamp.stamp(ts[n_opt:]))
-        return tuple(map(_NUM_UPDATES, tracked))
-
-    @staticmethod
-    def _stack(ts, B):
-        if all(t.shape[0] == ts[0].shape[0] for t in ts):
-            return torch.stack(ts, dim=0).contiguous()
-        return torch.stack([t.expand(B, *t.shape[1:]) for t in ts], dim=0).contiguous()
+    def _state_groups(self):
+        return [(self.cam_vars, self.tensors.cams), (self.pt_vars, self.tensors.points)]
 
     @contextlib.contextmanager
     def pinned(self, tensors, cc_tensors=None):
@@ -325,21 +281,13 @@ class PackedBA:
             self.tensors, self.cc_tensors, self._pinned = live, live_cc, was
 
     def sync(self, force: bool = False, deep: bool = False):
+        """Re-pack EVERYTHING when any variable changed (TrackedVariables._changed)."""
         if self.__dict__.get("_pinned", False):
             return
-        deep = deep or not self._own_variables   # see PackedPoseGraph.sync
-        if (not force and not deep and self.tensors is not None
-                and Variable._global_updates == self._global_stamp):
+        look = self._changed(force, deep)
+        if look is None:
             return
-        # (nobody called Variable.update() / to() since the last look: the update counters -- the shallow stamp -- are what they
-        #  were; a pass over 42 k variables of a bundle-adjustment objective is ~10 ms of host time per optimize())
-        shallow = self._own_variables or self._stamp is None    # (reference Variables: the deep stamp alone, see PackedPoseGraph.sync)
-        stamp = self._stamp if (self._counters_unchanged() or not shallow) else self._current_stamp()
-        dstamp = self._current_stamp(deep=True) if deep else None
-        if (not force and self.tensors is not None and stamp == self._stamp and (not deep or dstamp == self._deep_stamp)):
-            self._global_stamp = Variable._global_updates
-            return
-        self._deep_stamp = dstamp if dstamp is not None else self._current_stamp(deep=True)
+        _, _, stamp, dstamp = look
         self.flush_variables()
         obj = self.objective
         obj._resolve_batch_size()
@@ -380,59 +328,14 @@ class PackedBA:
             self.cc_tensors = PGTensors(poses=cams, meas=self._stack([c.measurement.tensor for c in self.cc_costs], B),
                                         w_between=self._stack([_weight_diag(c.weight, 6) for c in self.cc_costs], B),
                                         prior_target=empty(0, 1, 3, 4), w_prior=empty(0, 1, 6))
-        if (not (cams.requires_grad or pts.requires_grad) and (self._keep_graph_tensors or not self._own_variables)
-                and any(v.tensor.requires_grad for v in self.cam_vars + self.pt_vars)):
-            # (packed under no_grad from tensors that carry autograd history: see PackedPoseGraph.sync -- the variables keep them)
-            self._stamp = self._current_stamp() if not self._counters_unchanged() else self._stamp
-            self._global_stamp = Variable._global_updates
-            self._vars_stale = False
-            self._state_exposed = False
-        else:
-            self._repoint_variables()
-
-    def _repoint_variables(self):
-        # (after the implicit last step the state carries an autograd graph: the per-variable views stay attached to it)
-        with torch.set_grad_enabled(self.tensors.cams.requires_grad or self.tensors.points.requires_grad):
-            attr = "_tensor" if self._own_variables else "tensor"   # (own Variable: no update count for a re-pointing, core.py)
-            for v, t in zip(self.cam_vars, self.tensors.cams.unbind(0)):  # one call builds all the views
-                setattr(v, attr, t)
-            for v, t in zip(self.pt_vars, self.tensors.points.unbind(0)):
-                setattr(v, attr, t)
-        if not self._counters_unchanged():
-            self._stamp = self._current_stamp()
-        # deep stamp: only the optimisation variables were re-pointed here -- the auxiliary variables' entries (the bulk: 1 k
-        # measurements of a pose graph, 33 k features of a bundle-adjustment problem) are still the ones sync() looked at
-        n_opt = len(self.cam_vars) + len(self.pt_vars)
-        old = self._deep_stamp
-        if old is not None:
-            self._deep_stamp = (_views_deep_stamp((self.tensors.cams, self.tensors.points)), old[1])
-        else:
-            self._deep_stamp = self._current_stamp(deep=True)
-        self._global_stamp = Variable._global_updates
-        self._vars_stale = False
-        self._state_exposed = True
-
-    def privatize_state(self):
-        """See PackedPoseGraph.privatize_state: never recycle a state buffer the variables' tensors view."""
-        if self._state_exposed:
-            with torch.no_grad():
-                self.tensors.cams = self.tensors.cams.detach().clone()
-                self.tensors.points = self.tensors.points.detach().clone()
-            self._state_exposed = False
-            self._vars_stale = True
-
-    def flush_variables(self):
-        if self._vars_stale and self.tensors is not None:
-            self._repoint_variables()
+        self._finish_sync(stamp, dstamp)
 
     # ---- optimisation state = (cams, points) ------------------------------------------------------------------
-    @property
-    def state(self):
+    def _get_state(self):
         return (self.tensors.cams, self.tensors.points)
 
-    @property
-    def device(self):
-        return self.tensors.cams.device
+    def _set_state(self, new):
+        self.tensors.cams, self.tensors.points = new
 
     @property
     def batch(self):
@@ -445,21 +348,6 @@ class PackedBA:
     @property
     def dstruct(self):
         return self.structure.on(self.tensors.cams.device)
-
-    def alloc_state(self):
-        return (torch.empty_like(self.tensors.cams), torch.empty_like(self.tensors.points))
-
-    def clone_state(self):
-        return (self.tensors.cams.clone(), self.tensors.points.clone())
-
-    def swap_state(self, new, repoint: bool = False):
-        old = self.state
-        self.tensors.cams, self.tensors.points = new
-        if repoint:
-            self._repoint_variables()
-        else:
-            self._vars_stale = True
-        return old
 
     # ---- BackwardMode.UNROLL / TRUNCATED (theseus_amd/nonlinear.py: the differentiable tail loop) ------------------------------
     def prepare_unroll(self):
@@ -506,14 +394,6 @@ class PackedBA:
         return out
 
     # ---- fused operations ----------------------------------------------------------------------------------------
-    def _buf(self, key, shape, dtype=None):
-        t = self._scratch.get(key)
-        dt = dtype or self.objective.dtype
-        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dt or t.device != self.device:
-            t = torch.empty(*shape, dtype=dt, device=self.device)
-            self._scratch[key] = t
-        return t
-
     def error_metric(self, state=None, out: Optional[torch.Tensor] = None, poses=None):
         self.sync()
         B = self.batch
@@ -534,9 +414,7 @@ class PackedBA:
 
     def retract(self, delta: torch.Tensor, step: float, ignore_mask: Optional[torch.Tensor], out):
         self.sync()
-        m = None
-        if ignore_mask is not None:
-            m = ignore_mask if ignore_mask.dtype == torch.uint8 else ignore_mask.to(torch.uint8)
+        m = self._mask_u8(ignore_mask)
         self.K.se3_retract(self.tensors.cams, delta, step, m, out[0])   # columns [0, 6C)
         self.K.vec_retract(self.tensors.points, delta, self.nc, step, m, out[1])
         return out

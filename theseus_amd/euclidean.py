@@ -50,7 +50,7 @@ class PackedEuclidean(PackedState):
         parts = [v.tensor if v.tensor.shape[0] == B else v.tensor.expand(B, -1) for v in self.vars]
         with torch.no_grad():
             self._state = torch.cat(parts, dim=1).contiguous()
-        self._repoint()
+        self._repoint_variables()
 
     def _var_view(self, state, k):
         c0, d = self.cols[k]

@@ -15,7 +15,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .kernels import default_kernels, round_up
+from .kernels import round_up
+from .packer_base import StateOwner
 
 H_TARGET = np.dtype([("row0", "<i4"), ("col0", "<i4"), ("dof_a", "<i4"), ("dof_b", "<i4"), ("term_begin", "<i4"),
                      ("term_end", "<i4"), ("elem_begin", "<i4"), ("pad", "<i4")])
@@ -126,7 +127,7 @@ class BlockAssembler:
         K.block_assemble(self, jacobians, errors, H if hessian else None, g if gradient else None)
 
 
-class PackedState:
+class PackedState(StateOwner):
     """The packed-state interface of the optimiser loop (theseus_amd/packed.py: PackedPoseGraph) for objectives whose cost functions
     hand over their weighted Jacobian blocks: the state the loop moves around is ONE tensor, the variables' tensors are views of it,
     the cost functions are evaluated by torch at such views and H, g come from the blocks through ``BlockAssembler``.  A subclass
@@ -134,8 +135,7 @@ class PackedState:
     ``solution_dict`` / ``history_dict`` and ``_implicit_retract`` (theseus_amd/euclidean.py: (B, n); theseus_amd/pushing.py: (V, B, 4))."""
 
     def __init__(self, objective, kernels=None, order=None):
-        self.objective = objective
-        self.K = kernels or default_kernels()
+        super().__init__(objective, kernels)
         self.order = tuple(order) if order is not None else tuple(objective.optim_vars.keys())
         if sorted(self.order) != sorted(objective.optim_vars.keys()):
             raise ValueError("the variable ordering must hold every optimisation variable of the objective exactly once")
@@ -154,10 +154,6 @@ class PackedState:
         self.version = objective.current_version
         self._state: Optional[torch.Tensor] = None
         self._views = None          # what the variables' tensors are when they view the state
-        self._vars_stale = False
-        self._state_exposed = False
-        self._keep_graph_tensors = False
-        self._defer_repoint = False
         self._blocks = None         # weighted blocks of the last assemble(): the launch reads these tensors
 
     # ---- state <-> variables -----------------------------------------------------------------------------------------
@@ -171,7 +167,16 @@ class PackedState:
                     seen.add(id(a))
                     yield a
 
-    def _repoint(self):
+    def tracked_list(self):
+        return list(self._tracked())
+
+    def _get_state(self):
+        return self._state
+
+    def _set_state(self, new):
+        self._state = new
+
+    def _repoint_variables(self):
         with torch.set_grad_enabled(self._state.requires_grad):
             self._views = [self._var_view(self._state, k) for k in range(len(self.vars))]
         for v, t in zip(self.vars, self._views):
@@ -194,43 +199,9 @@ class PackedState:
         self.objective._resolve_batch_size()
         return self.objective.batch_size
 
-    def privatize_state(self):
-        if self._state_exposed:
-            with torch.no_grad():
-                self._state = self._state.detach().clone()
-            self._state_exposed = False
-            self._vars_stale = True
-
-    def flush_variables(self):
-        if self._vars_stale and self._state is not None:
-            self._repoint()
-
-    @property
-    def state(self):
-        return self._state
-
-    @property
-    def device(self):
-        return self._state.device
-
     @property
     def optim_variables(self):
         return self.vars
-
-    def alloc_state(self):
-        return torch.empty_like(self._state)
-
-    def clone_state(self):
-        return self._state.clone()
-
-    def swap_state(self, new, repoint: bool = False):
-        old = self._state
-        self._state = new
-        if repoint:
-            self._repoint()
-        else:
-            self._vars_stale = True
-        return old
 
     # ---- evaluation (torch: the cost functions are user code) ----------------------------------------------------------
     class _at:
@@ -327,10 +298,6 @@ class PackedState:
             b[:, r:r + d] = -e
             r += d
         return A, b
-
-    @staticmethod
-    def _mask_u8(ignore_mask):
-        return ignore_mask if ignore_mask is None or ignore_mask.dtype == torch.uint8 else ignore_mask.to(torch.uint8)
 
     # ---- BackwardMode.IMPLICIT ----------------------------------------------------------------------------------------------
     def implicit_step(self, opt, step: float, kwargs):

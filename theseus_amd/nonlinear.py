@@ -262,7 +262,7 @@ class NonlinearLeastSquares(abc.ABC):
         # (only THEN may a no_grad re-pack leave the variables on their own graph-carrying tensors instead of views of the packed state)
         packed._keep_graph_tensors = init_tensors is not None
         with torch.no_grad():
-            packed._defer_repoint = True   # (PackedPoseGraph.sync: the variables are re-pointed once, when the loop is done)
+            packed._defer_repoint = True   # (TrackedVariables._finish_sync: the variables are re-pointed once, when the loop is done)
             try:
                 packed.sync(deep=True)   # once per optimize(): also catches in-place edits of the variables' tensors
             finally:
@@ -665,7 +665,7 @@ class NonlinearLeastSquares(abc.ABC):
         return info
 
     def _needs_grad(self):
-        return any(v.tensor.requires_grad for v in self.linear_solver.linearization.packed._tracked())
+        return any(v.tensor.requires_grad for v in self.linear_solver.linearization.packed.tracked_list())
 
     def _implicit_last_step(self, packed, outer_grad: bool, kwargs):
         """X_new = X exp(delta), delta = H^-1 g(theta): H is built outside autograd (i.e. detached, as

@@ -14,80 +14,11 @@ import numpy as np
 import torch
 
 from .compiler import PoseGraphStructure
-from .core import Objective, Variable
-from .kernels import PGTensors, default_kernels, fast_approx_local_jacobians, round_up, _lib
+from .core import Objective
+from .kernels import PGTensors, fast_approx_local_jacobians, round_up, _lib
+from .packer_base import _DATA_PTR, TrackedVariables
 
 ERR_CHUNKS = _lib.THX_ERR_CHUNKS
-
-
-import operator
-
-_GET_TENSOR = {True: operator.attrgetter("_tensor"), False: operator.attrgetter("tensor")}   # own Variable: skip the property
-_DATA_PTR, _VERSION, _NUM_UPDATES = operator.methodcaller("data_ptr"), operator.attrgetter("_version"), operator.attrgetter("_num_updates")
-
-# one C++ loop over a list of tensors instead of 33 k method calls (torch's cudagraph trees check their static inputs with it)
-_PTRS_EQUAL = getattr(torch._C, "_tensors_data_ptrs_at_indices_equal", None)
-
-
-class _AuxDeepStamp:
-    """Deep stamp of the AUXILIARY variables' tensors (measurements, weights, ... -- 33 k of them in a bundle-adjustment objective):
-    has anybody replaced a tensor object, swapped the storage under one (``var.tensor.data = other`` / ``set_()``: object and
-    version counter stay), or edited one in place (``var.tensor.mul_()``: only the autograd version counter moves)?  The reference
-    re-reads ``var.tensor`` at every evaluation (core/objective.py:813-830) and sees all three.
-
-    Three flat comparisons instead of a 3-tuple per tensor (12 ms at 33 k tensors):
-      * the tuple of object ids (0.9 ms; the tensors are kept referenced here, so an id cannot be recycled);
-      * the storage pointers, in one C++ call against the cached list (2 ms; a Python pass of ``data_ptr()`` calls: 4.3 ms);
-      * the version counters of one REPRESENTATIVE per group of tensors that share one: views share their base's counter
-        (``feat[:, k]`` for 32768 observations is one counter), so an in-place edit through ANY of them moves the representative's.
-        A tensor's ``_base`` is fixed at creation: the grouping holds for as long as the ids do."""
-
-    def __init__(self):
-        self.refs = self.ids = self.ptrs = self.ptrs_t = self.reps = self.idx = None
-
-    def stamp(self, ts):
-        ids = tuple(map(id, ts))
-        if ids != self.ids:
-            self.refs, self.ids = ts, ids
-            self.ptrs = list(map(_DATA_PTR, ts))
-            self.ptrs_t = tuple(self.ptrs)
-            self.idx = list(range(len(ts)))
-            groups = {}
-            for t in ts:
-                base = t._base
-                groups.setdefault(id(base) if base is not None else id(t), t)
-            self.reps = list(groups.values())
-        else:
-            same = None
-            if _PTRS_EQUAL is not None and ts:
-                try:
-                    same = _PTRS_EQUAL(ts, self.ptrs, self.idx)
-                except TypeError:      # (a private torch symbol: another signature in another release -> the Python pass)
-                    same = None
-            if same is None:
-                same = list(map(_DATA_PTR, ts)) == self.ptrs
-            if not same:
-                self.ptrs = list(map(_DATA_PTR, ts))
-                self.ptrs_t = tuple(self.ptrs)
-        return ids, self.ptrs_t, tuple(map(_VERSION, self.reps))
-
-
-def _opt_deep_stamp(ts):
-    """Deep stamp of the optimisation variables' tensors: storage pointer + version counter (they are views of the packed state:
-    holding the objects would pin a state buffer), as two flat tuples."""
-    return tuple(map(_DATA_PTR, ts)), tuple(map(_VERSION, ts))
-
-
-def _views_deep_stamp(buffers):
-    """``_opt_deep_stamp`` of variables that were JUST re-pointed at ``buf.unbind(0)`` of these buffers, without touching the 8.7 k
-    view objects: view k starts ``k * stride(0)`` elements into its buffer and shares the buffer's version counter."""
-    ptrs, vers = (), ()
-    for buf in buffers:
-        n, step = buf.shape[0], buf.stride(0) * buf.element_size()
-        base = buf.data_ptr()
-        ptrs += tuple(range(base, base + n * step, step)) if step else (base,) * n
-        vers += (buf._version,) * n
-    return ptrs, vers
 
 
 class UnsupportedObjective(NotImplementedError):
@@ -177,12 +108,11 @@ def _aux_vars(x):
     return list(a() if callable(a) else a)
 
 
-class PackedPoseGraph:
+class PackedPoseGraph(TrackedVariables):
     def __init__(self, objective: Objective, kernels=None, order=None):
         """``order``: names of the optimisation variables in COLUMN order (a VariableOrdering -- e.g. the fill-reducing one of
         theseus_amd/sparse.py); default = insertion order (theseus/optimizer/variable_ordering.py:19-27)."""
-        self.objective = objective
-        self.K = kernels or default_kernels()
+        super().__init__(objective, kernels)
         self.pose_vars = []
         self.group = None
         self.order = tuple(order) if order is not None else tuple(objective.optim_vars.keys())
@@ -234,18 +164,8 @@ class PackedPoseGraph:
         self.ld = round_up(self.n, 32)
         self.version = objective.current_version
         self.tensors: Optional[PGTensors] = None
-        # the O(1) "nothing changed" test relies on theseus_amd.core.Variable's global update counter
-        self._own_variables = all(isinstance(v, Variable) for v in self.tracked_list())
-        self._stamp = None
-        self._deep_stamp = None
-        self._aux_stamp = _AuxDeepStamp()
-        self._keep_graph_tensors = False   # set by the optimizer around an optimize() that differentiates from the initial tensors
-        self._defer_repoint = False        # set by the optimizer around its first sync (see sync)
-        self._global_stamp = -1
-        self._vars_stale = False
-        self._state_exposed = False
         self._known = []
-        self._scratch = {}
+        self._start_tracking()
 
     def _refuse_fast_approx(self, exc=NotImplementedError):
         """``fast_approx_local_jacobians`` (theseus/embodied/misc/local_cost_fn.py:43-57: identity Jacobians for Local /
@@ -259,9 +179,8 @@ class PackedPoseGraph:
                       "through theseus_amd.plugin (generic block path).")
 
     # ---- packing ----------------------------------------------------------------------------
-    def _tracked(self):
-        for v in self.pose_vars:
-            yield v
+    def _walk_tracked(self):
+        yield from self.pose_vars
         for c in self.edge_costs:
             yield c.measurement
             yield from _aux_vars(c.weight)
@@ -271,74 +190,17 @@ class PackedPoseGraph:
         for r in self.edge_radius + self.prior_radius:
             yield from _radius_vars(r)
 
-    def tracked_list(self):
-        """Every variable the packed buffers are built from, each ONCE (a cost weight shared by 1024 edges is one entry), the
-        optimisation variables (poses) first.  The objective is frozen once an optimizer holds it (Optimizer.optimize checks its
-        version): the walk over the cost functions is done once."""
-        tracked = self.__dict__.get("_tracked_list")
-        if tracked is None:
-            seen, tracked = set(), []
-            for v in self._tracked():
-                if id(v) not in seen:
-                    seen.add(id(v))
-                    tracked.append(v)
-            self._tracked_list = tracked
-        return tracked
-
-    def _counters_unchanged(self) -> bool:
-        return self._own_variables and self._stamp is not None and Variable._global_updates == self._global_stamp
-
-    def _current_stamp(self, deep: bool = False, count: Optional[int] = None):
-        # the objective is frozen once an optimizer holds it (Optimizer.optimize checks its version): the walk over the cost
-        # functions is done once, later stamps are one pass over the cached list (7 k variables at the headline size)
-        tracked = self.tracked_list()
-        if count is not None:
-            tracked = tracked[:count]
-        if deep:
-            # (optimisation part, auxiliary part): catches IN-PLACE edits of a variable's tensor that never go through
-            # Variable.update() (an nn.Parameter stepped by a torch optimizer, ``var.tensor.mul_()``), ``var.tensor = other`` and
-            # ``var.tensor.data = other`` -- see _AuxDeepStamp.  ``count``: the optimisation part alone.
-            ts = list(map(_GET_TENSOR[self._own_variables], tracked))
-            n_opt = min(len(self.pose_vars), len(ts))
-            opt = _opt_deep_stamp(ts[:n_opt])
-            return opt if count is not None else (opt, self._aux_stamp.stamp(ts[n_opt:]))
-        return tuple(map(_NUM_UPDATES, tracked))
-
-    @staticmethod
-    def _stack(ts, B):
-        """list of (b_k, ...) with b_k in {1,B} -> (len, 1|B, ...) contiguous."""
-        if not ts:
-            return None
-        if all(t.shape[0] == ts[0].shape[0] for t in ts):
-            return torch.stack(ts, dim=0).contiguous()
-        return torch.stack([t.expand(B, *t.shape[1:]) for t in ts], dim=0).contiguous()
+    def _state_groups(self):
+        return [(self.pose_vars, self.tensors.poses)]
 
     def sync(self, force: bool = False, deep: bool = False):
-        """(Re)pack the variable tensors into the device buffers if any variable changed.  ``deep`` also looks for in-place
-        edits of the variables' tensors (storage pointer + version counter): the optimizers ask for it once per
-        ``optimize()``, the inner-loop calls keep the O(1) test; with the reference's own Variable class (theseus_amd/
-        plugin.py) every call is deep -- there is no global update counter to lean on.  Poses and auxiliary tensors are
-        re-packed independently (the reference's loop replaces the pose tensors every iteration, the measurements never)."""
-        deep = deep or not self._own_variables
-        if (not force and not deep and self.tensors is not None
-                and Variable._global_updates == self._global_stamp):
-            return  # nobody called Variable.update()/to() since the last look: O(1) fast path
-        # (nobody called Variable.update() / to() since the last look: the update counters -- the shallow stamp -- are what they
-        #  were; a pass over 42 k variables of a bundle-adjustment objective is ~10 ms of host time per optimize())
-        # (the reference's Variable: the deep stamp -- storage + version of every tensor -- is the only one looked at: a
-        #  Variable.update() that changes neither is not a change.  One pass per call instead of two.)
-        shallow = self._own_variables or self._stamp is None
-        stamp = self._stamp if (self._counters_unchanged() or not shallow) else self._current_stamp()
-        dstamp = self._current_stamp(deep=True) if deep else None
-        nP = len(self.pose_vars)
-        if force or self.tensors is None:
-            poses_changed = aux_changed = True
-        else:
-            poses_changed = (shallow and stamp[:nP] != self._stamp[:nP]) or (deep and dstamp[0] != self._deep_stamp[0])
-            aux_changed = (shallow and stamp[nP:] != self._stamp[nP:]) or (deep and dstamp[1] != self._deep_stamp[1])
-        if not (poses_changed or aux_changed):
-            self._global_stamp = Variable._global_updates
+        """(Re)pack the variable tensors into the device buffers if any variable changed (TrackedVariables._changed).  Poses and
+        auxiliary tensors are re-packed independently (the reference's loop replaces the pose tensors every iteration, the
+        measurements never)."""
+        look = self._changed(force, deep)
+        if look is None:
             return
+        poses_changed, aux_changed, stamp, dstamp = look
         self.flush_variables()
         obj = self.objective
         if not (self._own_variables and obj._batch_size_is_current()):   # (Objective.update just walked the variables)
@@ -373,36 +235,7 @@ class PackedPoseGraph:
                                      loss_between=table(self.loss_between), loss_prior=table(self.loss_prior))
         else:
             self.tensors.poses = poses
-        # (the auxiliary entries of the deep stamp: what this call saw -- _repoint_variables patches the poses' entries)
-        self._deep_stamp = dstamp if dstamp is not None else self._current_stamp(deep=True)
-        if adopted:   # the variables hold these very views already: only the stamps move
-            self._stamp = stamp
-            self._global_stamp = Variable._global_updates
-            self._vars_stale = False
-            self._state_exposed = True
-        elif (not poses.requires_grad and (self._keep_graph_tensors or not self._own_variables)
-              and any(v.tensor.requires_grad for v in self.pose_vars)):
-            # packed under no_grad from tensors that carry autograd history (the values the caller passed in, about to be
-            # differentiated through: backward_mode="unroll"): re-pointing the variables to views of this graph-less copy would cut
-            # them off -- they keep their tensors (same values), the copy is private.  Only where that is needed: theseus_amd's
-            # own loop says so for the optimize() calls that captured the initial tensors (``_keep_graph_tensors``: everywhere
-            # else the variables view the packed state, also inside callbacks and after an exception); under the reference's
-            # loop (its Variable class), which re-assigns every variable every iteration anyway.
-            self._stamp = stamp
-            self._global_stamp = Variable._global_updates
-            self._vars_stale = False
-            self._state_exposed = False
-        elif self._defer_repoint and self._own_variables:
-            # the optimizer's sync at the start of optimize(): the loop is about to continue on a PRIVATE state buffer and re-points
-            # the variables when it is done (or before anybody can look: callbacks, exceptions -- flush_variables) -- re-pointing
-            # them to views of THIS buffer first was 5 ms of host time per optimize() at 4096 poses in front of the first kernel,
-            # for views nobody ever read.  The variables keep the tensors they hold (the same values) until then.
-            self._stamp = stamp
-            self._global_stamp = Variable._global_updates
-            self._vars_stale = True
-            self._state_exposed = False
-        else:
-            self._repoint_variables()
+        self._finish_sync(stamp, dstamp, adopted)
 
     # ---- buffers whose per-pose views are known (so that a list of variable tensors can be recognised as one buffer) ----
     def remember_views(self, buf: torch.Tensor, views):
@@ -424,56 +257,6 @@ class PackedPoseGraph:
             if ids == vids and list(map(_DATA_PTR, tensors)) == ptrs and tensors[0].shape == buf.shape[1:]:
                 return buf
         return None
-
-    def _repoint_variables(self):
-        """Make every optimisation variable's tensor a view of the packed pose buffer."""
-        poses = self.tensors.poses
-        # the optimiser calls this under no_grad; after the implicit last step the pose buffer carries a graph
-        # and the per-variable views must stay attached to it
-        with torch.set_grad_enabled(poses.requires_grad):
-            views = poses.unbind(0)  # one call builds all the views
-            attr = "_tensor" if self._own_variables else "tensor"   # (own Variable: no update count for a re-pointing, core.py)
-            for v, t in zip(self.pose_vars, views):
-                setattr(v, attr, t)
-        self.remember_views(poses, views)
-        if not self._counters_unchanged():
-            self._stamp = self._current_stamp()
-        # deep stamp: only the optimisation variables were re-pointed here -- the auxiliary variables' entries (the bulk: 1 k
-        # measurements of a pose graph, 33 k features of a bundle-adjustment problem) are still the ones sync() looked at
-        n_opt = len(self.pose_vars)
-        old = self._deep_stamp
-        if old is not None:
-            self._deep_stamp = (_views_deep_stamp((poses,)), old[1])
-        else:
-            self._deep_stamp = self._current_stamp(deep=True)
-        self._global_stamp = Variable._global_updates
-        self._vars_stale = False
-        self._state_exposed = True   # the variables (and whoever holds their tensors) now view the state buffer
-
-    def privatize_state(self):
-        """Called at the start of ``optimize()``: if the state buffer is the one the variables' tensors view (i.e. what the
-        previous ``optimize()`` / ``forward()`` handed to the user, possibly carrying an autograd graph), continue on a
-        private copy -- the loop recycles its two state buffers through raw-pointer kernels and must never write into a
-        tensor somebody else holds."""
-        if self._state_exposed:
-            with torch.no_grad():
-                self.tensors.poses = self.tensors.poses.detach().clone()
-            self._state_exposed = False
-            self._vars_stale = True
-
-    def set_poses(self, poses: torch.Tensor, repoint: bool = True):
-        """Adopt a new packed pose buffer (after an accepted LM step).  ``repoint=False`` defers the
-        O(#variables) Python re-pointing of the Variable objects (the optimiser loop flushes before anybody
-        can look: callbacks, loop exit)."""
-        self.tensors.poses = poses
-        if repoint:
-            self._repoint_variables()
-        else:
-            self._vars_stale = True
-
-    def flush_variables(self):
-        if self._vars_stale and self.tensors is not None:
-            self._repoint_variables()
 
     # ---- BackwardMode.UNROLL / TRUNCATED (theseus_amd/autograd.py:PGUnrolledIteration) ---------------------------------------
     def prepare_unroll(self):
@@ -501,7 +284,7 @@ class PackedPoseGraph:
     def unroll_incidence(self, device) -> torch.Tensor:
         """(P, Dmax) rows of [grad_pose_i (E) ; grad_pose_j (E) ; grad_pose_prior (K) ; zero row] that belong to each pose."""
         key = ("unroll_inc", str(device))
-        if key not in self._scratch:
+        if key not in self._bufs:
             s = self.structure
             E, Kp = s.num_edges, s.num_priors
             rows = [[] for _ in range(s.num_poses)]
@@ -512,33 +295,19 @@ class PackedPoseGraph:
                 rows[int(s.prior_pose[k])].append(2 * E + k)
             dmax = max(1, max(len(r) for r in rows))
             pad = 2 * E + Kp
-            self._scratch[key] = torch.tensor([r + [pad] * (dmax - len(r)) for r in rows], dtype=torch.long, device=device)
-        return self._scratch[key]
+            self._bufs[key] = torch.tensor([r + [pad] * (dmax - len(r)) for r in rows], dtype=torch.long, device=device)
+        return self._bufs[key]
 
     # ---- optimisation state: what the LM loop moves around (here: the packed pose buffer) --------------
-    @property
-    def state(self):
+    def _get_state(self):
         return self.tensors.poses
 
-    @property
-    def device(self):
-        return self.tensors.poses.device
+    def _set_state(self, poses: torch.Tensor):
+        self.tensors.poses = poses
 
     @property
     def optim_variables(self):
         return self.pose_vars
-
-    def alloc_state(self):
-        return torch.empty_like(self.tensors.poses)
-
-    def clone_state(self):
-        return self.tensors.poses.clone()
-
-    def swap_state(self, new, repoint: bool = False):
-        """Adopt ``new`` as the current state; returns the previous buffer for re-use."""
-        old = self.tensors.poses
-        self.set_poses(new, repoint=repoint)
-        return old
 
     def keep_where(self, mask: torch.Tensor, out):
         """out <- current state where mask (B,), else out."""
@@ -557,16 +326,6 @@ class PackedPoseGraph:
         (nonlinear_optimizer.py:150-163): name -> (B, ..., K + 1) on the host."""
         h = hist.to(dtype).cpu()
         return {v.name: h[:, k].movedim(0, -1).contiguous() for k, v in enumerate(self.pose_vars)}
-
-    # ---- scratch ------------------------------------------------------------------------------
-    def _buf(self, key, shape, dtype=None):
-        t = self._scratch.get(key)
-        dt = dtype or self.objective.dtype
-        dev = self.tensors.poses.device
-        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dt or t.device != dev:
-            t = torch.empty(*shape, dtype=dt, device=dev)
-            self._scratch[key] = t
-        return t
 
     @property
     def batch(self):
@@ -602,10 +361,7 @@ class PackedPoseGraph:
 
     def retract(self, delta: torch.Tensor, step: float, ignore_mask: Optional[torch.Tensor], out: torch.Tensor):
         self.sync()
-        m = None
-        if ignore_mask is not None:
-            m = ignore_mask if ignore_mask.dtype == torch.uint8 else ignore_mask.to(torch.uint8)
-        self.K.retract(self.tensors.poses, delta, step, m, out)
+        self.K.retract(self.tensors.poses, delta, step, self._mask_u8(ignore_mask), out)
         return out
 
     def jacobian_blocks(self, robust: bool = True, jacobians: bool = True):
@@ -713,18 +469,13 @@ def packed_for(objective: Objective, kernels=None, order=None):
         except UnsupportedObjective as fused_error:
             if not isinstance(objective, Objective):   # the reference's own Objective: theseus_amd/plugin.py has its generic path
                 raise
-            try:
+            for cls in (PackedPlanarPushing, PackedTrajectory2D, PackedHomography, PackedEuclidean):
                 try:
-                    p = PackedPlanarPushing(objective, kernels, order)
+                    p = cls(objective, kernels, order)
+                    break
                 except UnsupportedObjective:
-                    try:
-                        p = PackedTrajectory2D(objective, kernels, order)
-                    except UnsupportedObjective:
-                        try:
-                            p = PackedHomography(objective, kernels, order)
-                        except UnsupportedObjective:
-                            p = PackedEuclidean(objective, kernels, order)
-            except UnsupportedObjective:
+                    pass
+            else:
                 raise fused_error from None
         objective._packed = p
     return p

@@ -78,7 +78,7 @@ class PackedPlanarPushing(TermTable, PackedState):
         with torch.no_grad():
             self._state = torch.stack([v.tensor if v.tensor.shape[0] == B else v.tensor.expand(B, -1) for v in self.vars],
                                       dim=0).contiguous()
-        self._repoint()
+        self._repoint_variables()
 
     def _var_view(self, state, k):
         return state[k]
