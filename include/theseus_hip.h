@@ -261,6 +261,31 @@ typedef struct {
    * wave leaves out those chunks of the K-loop, the sub-blocks of its two substitutions left of zf and the coupling products of
    * those columns -- and a group whose four strips all begin behind the pair's columns only stores zeros. */
   const int32_t* rg_zf;             /* DEVICE (groups, 4): per strip min first / 32, NOT capped; a strip without rows: >= 4 j + 8 */
+  /* SORTED ROWS of the diagonal tiles (thx_chol_schedule.sort_tile_rows; theseus_amd/compiler.py:TileRows), all NULL = none.  The
+   * SYRK of diagonal tile j needs the product of its rows r and c at column k only for k >= max(first[r], first[c]).  The tile's 128
+   * rows, stably sorted by first (a variable's rows stay adjacent; rows at or behind n last), are cut into eight RANK blocks of 16;
+   * rank block q is staged at block row PLACE[q] of the kernel's 8 x 8 block grid, PLACE = (1, 2, 3, 7, 6, 5, 4, 0), which evens
+   * out the active blocks of the four waves (wave g owns block rows 4 + g and 3 - g).  The placement is the host's: the kernel
+   * sees the permutation and the masks only.  Layouts that carry row groups only; a tile whose blocks all begin at chunk 0 has no
+   * table and runs as without the switch. */
+  const int32_t* tr_tile_host;      /* HOST (ntiles): 1 when tile j has tables, else 0 (tile 0 never has) */
+  const int32_t* tr_perm16;         /* DEVICE (ntiles, 128): staged slot -> row of the tile, 0 .. 127 (row 128 j + value of L); a
+                                     * bijection per tile that has tables */
+  const int32_t* tr_mask16;         /* DEVICE (ntiles, 4 * ntiles): bit u of tr_mask16[j * 4 * ntiles + kc], kc < 4 j, is set when
+                                     * staged block row u (slots [16 u, 16 u + 16)) is active at k-chunk kc, i.e. kc >= min first / 32 */
+  /* ... and the HEAD TILES (j + 1, j) of the column pairs, j even, 2 <= j, j + 1 < ntiles (the same switch), all NULL = none: tile j's
+   * rows -- the head tile's columns -- in the plain stable sort by first, four blocks of 32 (tr_perm16 cannot serve: its placement puts
+   * the earliest and the latest rank into the same 32 rows).  A block's loads, staging stores and products are left out by the whole
+   * workgroup while it has not begun, the K-loop starts at th_k0h, and the accumulators return to natural column order behind it. */
+  const int32_t* th_tile_host;      /* HOST (ntiles): 1 when head tile (j + 1, j) has tables, else 0 */
+  const int32_t* th_perm32;         /* DEVICE (ntiles, 128): sorted slot -> row of tile j, 0 .. 127 */
+  const int32_t* th_mask32;         /* DEVICE (ntiles, 4 * ntiles): bit u of th_mask32[j * 4 * ntiles + kc], kc < 4 j, is set when block u
+                                     * (sorted slots [32 u, 32 u + 32)) is active at k-chunk kc */
+  const int32_t* th_k0h;            /* DEVICE (ntiles): first k-chunk at which a row of tile j + 1 and a block of tile j have both begun,
+                                     * capped at 4 j */
+  /* (LAYOUT NOTE: tr_* and th_* stand here, in front of the rg0_* fields, and thx_chol_schedule.sort_tile_rows stands behind regroup_rows
+   *  -- not at the structs' ends: the offsets of every field behind them differ from earlier versions of this header, and a caller
+   *  built against one, or one that initialises these structs positionally, must be rebuilt / updated.) */
   /* PAIR 0 has no K-loop and no groups above; with these tables its rows (256 .. n - 1) are sorted and cut into groups the same
    * way, so that the rows whose tiles (i, 0) / (i, 1) are structurally zero share strips and groups.  Groups 0 .. rg0_ngroups - 1,
    * in ascending order of first; rg0_tile_ptr / rg0_piece_* keyed as rg_tile_ptr (group g, block column s). */
@@ -528,7 +553,16 @@ int thx_se3_retract(const void* poses, const void* delta, int64_t ldd, double st
  *          non-zero column and leaves out, per k-chunk, the blocks of 32 sorted rows that have not begun (loads, staging stores and
  *          products), then moves the accumulators to natural column order.  Each output element keeps the same products in the
  *          same order; like skip_zero_blocks the identity holds for info == 0.  1 on, 0 off (exactly the launches without it),
- *          < 0: the default (on). */
+ *          < 0: the default (on).
+ *        sort_tile_rows (stands behind regroup_rows in the struct, see the layout note in thx_hblock_layout): where regroup_rows applies.
+ *          With thx_hblock_layout.th_*: the head tile (j + 1, j) of a column pair whose tile j has tables stages its operand A in sorted
+ *          order, leaves out the blocks of 32 that have not begun, starts its K-loop at th_k0h and un-permutes its accumulators.
+ *          Where also the diagonal phase is split (split_diag_min_batch) and the layout carries
+ *          thx_hblock_layout.tr_*: the SYRK of a diagonal tile that has sorted-row tables stages the tile's rows in ascending order of
+ *          their first non-zero column and leaves out, per k-chunk, the block rows of 16 that have not begun (loads, staging stores,
+ *          products and their share of the fused forward substitution), then moves the accumulators back to natural order.  Each
+ *          output element keeps the same products in the same order; the identity holds for info == 0.  1 on, 0 off (exactly
+ *          the launches without it), < 0: the default (on). */
 typedef struct {
   int32_t split_diag_min_batch;
   int32_t column_pairs;
@@ -540,6 +574,7 @@ typedef struct {
   int32_t right_looking_mode;
   int32_t skip_zero_blocks;
   int32_t regroup_rows;
+  int32_t sort_tile_rows;
   int32_t skip_zero_solves;
   int32_t sort_pair_columns;
 } thx_chol_schedule;
@@ -562,6 +597,7 @@ typedef struct {
   int32_t regroup_rows;        /* 1: the column pairs that have row groups take them (thx_chol_schedule.regroup_rows) */
   int32_t skip_zero_solves;    /* 1: the row groups' waves skip their zero solves and / or pair 0 runs on groups (thx_chol_schedule.skip_zero_solves) */
   int32_t sort_pair_columns;   /* 1: the pairs that have row groups and sorted-column tables take them (thx_chol_schedule.sort_pair_columns) */
+  int32_t sort_tile_rows;      /* 1: the head tiles and / or the split SYRKs that have sorted-row tables take them (thx_chol_schedule.sort_tile_rows) */
 } thx_chol_plan_info;
 int thx_chol_plan(int32_t n, int64_t ld, int32_t B, int dtype, int has_damping, int has_rhs, int64_t ldv,
                   const thx_hblock_layout* layout, const thx_chol_schedule* schedule, thx_chol_plan_info* out);

@@ -72,14 +72,14 @@ class CholSchedule(Structure):  # thx_chol_schedule: per-call schedule of the fa
     _fields_ = [("split_diag_min_batch", c_int32), ("column_pairs", c_int32), ("right_looking_max_batch", c_int32),
                 ("hb_scatter_max_pieces", c_int32), ("f64_wide_max_ktiles", c_int32),
                 ("f64_half_max_ktiles", c_int32), ("column_pairs_min_batch", c_int32), ("right_looking_mode", c_int32),
-                ("skip_zero_blocks", c_int32), ("regroup_rows", c_int32), ("skip_zero_solves", c_int32),
-                ("sort_pair_columns", c_int32)]
+                ("skip_zero_blocks", c_int32), ("regroup_rows", c_int32), ("sort_tile_rows", c_int32),
+                ("skip_zero_solves", c_int32), ("sort_pair_columns", c_int32)]
 
 
 class CholPlanInfo(Structure):  # thx_chol_plan_info: the schedule a dense-frame factorisation takes (thx_chol_plan, host only)
     _fields_ = [(k, c_int32) for k in ("right_looking", "right_looking_mode", "split_diag", "nparts", "column_pairs",
                                        "f64_half_cols", "f64_wide_cols", "forward_fused", "regroup_rows",
-                                       "skip_zero_solves", "sort_pair_columns")]
+                                       "skip_zero_solves", "sort_pair_columns", "sort_tile_rows")]
 
 
 class LevelSchedule(Structure):  # thx_level_schedule: elimination-tree levels of a tile pattern (2 host + 2 device int32 tables)
@@ -92,7 +92,8 @@ class HBlockLayout(Structure):  # thx_hblock_layout: block-compact Hessian (devi
                                                                                                ("l_mask", c_void_p)] + [
         (k, c_void_p) for k in ("rg_group_ptr_host", "rg_rows", "rg_k0", "rg_tile_ptr", "rg_piece_blk", "rg_piece_rc")] + [
         ("rg_max_tile_pieces", c_int32)] + [
-        (k, c_void_p) for k in ("rg_zf", "rg0_rows", "rg0_zf", "rg0_tile_ptr", "rg0_piece_blk", "rg0_piece_rc")] + [
+        (k, c_void_p) for k in ("rg_zf", "tr_tile_host", "tr_perm16", "tr_mask16", "th_tile_host", "th_perm32", "th_mask32", "th_k0h",
+                                "rg0_rows", "rg0_zf", "rg0_tile_ptr", "rg0_piece_blk", "rg0_piece_rc")] + [
         ("rg0_ngroups", c_int32), ("rg0_max_tile_pieces", c_int32)] + [
         (k, c_void_p) for k in ("sc_pair_host", "sc_perm", "sc_mask", "row_first")]
 

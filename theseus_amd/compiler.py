@@ -188,6 +188,7 @@ class HessianBlocks:
         self._l_mask = None
         self._row_groups = None
         self._pair_columns = None
+        self._tile_rows = None
 
     def l_mask(self) -> np.ndarray:
         """(ntiles, 4 * ntiles) int32: bit s of [t, c] set when the 32x32 sub-block (rows 128 t + 32 s, columns 32 c) of the
@@ -210,6 +211,15 @@ class HessianBlocks:
             pc = PairColumns(self, self.row_groups())
             self._pair_columns = pc if pc.npairs_sorted > 0 else False
         return self._pair_columns or None
+
+    def tile_rows(self) -> Optional["TileRows"]:
+        """The sorted rows of the diagonal tiles (thx_hblock_layout.tr_*), None when the layout has no row groups above a pair
+        (regroup_rows cannot apply) or no tile has a table."""
+        if self._tile_rows is None:
+            rg = self.row_groups()
+            tr = TileRows(self) if rg is not None and rg.ngroups > 0 else None
+            self._tile_rows = tr if tr is not None and tr.ntables > 0 else False
+        return self._tile_rows or None
 
     def on(self, device) -> "DeviceHessianBlocks":
         key = str(device)
@@ -517,6 +527,95 @@ class PairColumns:
         return per, ((run_a / tot, run_b / tot) if tot else (0.0, 0.0))
 
 
+class TileRows:
+    """The 128 rows of every diagonal tile sorted by their first non-zero column (thx_hblock_layout.tr_*).
+
+    The SYRK of diagonal tile j multiplies rows r and c of the tile over the columns k < 128 j; the product is structurally zero for
+    k < max(first[r], first[c]).  The tile's rows, stably sorted by ``first`` (a variable's rows stay adjacent; rows at or behind n
+    are never active and go last), are cut into eight rank blocks of 16.  The kernel's four waves meet at two barriers per
+    k-chunk, wave g owning block rows 4 + g and 3 - g of the 8 x 8 block grid, so a chunk costs what its busiest wave executes:
+    rank block q is staged at block row ``PLACE[q]``, the fixed placement with the lowest such cost on the headline graph (0.738
+    of dense against 0.847 for the identity; ``model``).  Block row u is zero in every k-chunk before ``first_chunk[u]``; a value
+    >= 4 j: never active.  A tile whose blocks all begin at chunk 0 (tile 0 always) has no table.
+
+    has          (ntiles)              1: the tile has tables
+    perm         (ntiles, 128)         staged slot -> row of the tile, 0 ... 127 (matrix row 128 j + value); identity without tables
+    first_chunk  (ntiles, 8)           per staged block row min first // 32
+    mask         (ntiles, 4 ntiles)    per k-chunk kc < 4 j: bit u set when block row u is active (kc >= first_chunk[u]); 255 elsewhere
+    """
+
+    PLACE = (1, 2, 3, 7, 6, 5, 4, 0)
+    NEVER = 1 << 30   # ``first`` of a row at or behind n
+
+    def __init__(self, hb: "HessianBlocks", place=PLACE):
+        nt, n = hb.ntiles, hb.bd * hb.nvars
+        first = np.full(nt * TILE, self.NEVER, dtype=np.int64)
+        first[:n] = hb.row_first
+        self.place = tuple(place)
+        self.has = np.zeros(nt, dtype=np.int32)
+        self.perm = np.tile(np.arange(TILE, dtype=np.int32), (nt, 1))
+        self.first_chunk = np.zeros((nt, 8), dtype=np.int32)
+        self.mask = np.full((nt, 4 * nt), 255, dtype=np.int32)
+        for j in range(1, nt):
+            f = first[TILE * j:TILE * j + TILE]
+            order = np.argsort(f, kind="stable")
+            fc_rank = np.minimum(f[order].reshape(8, 16).min(1) // 32, 4 * nt)
+            if fc_rank.max() == 0:
+                continue
+            self.has[j] = 1
+            for q in range(8):
+                u = self.place[q]
+                self.perm[j, 16 * u:16 * u + 16] = order[16 * q:16 * q + 16]
+                self.first_chunk[j, u] = fc_rank[q]
+            for kc in range(4 * j):
+                self.mask[j, kc] = sum(1 << u for u in range(8) if kc >= self.first_chunk[j, u])
+        # the head tiles (j + 1, j) of the column pairs: tile j's rows in the plain stable sort, four blocks of 32
+        self.has32 = np.zeros(nt, dtype=np.int32)
+        self.perm32 = np.tile(np.arange(TILE, dtype=np.int32), (nt, 1))
+        self.first_chunk32 = np.zeros((nt, 4), dtype=np.int32)
+        self.mask32 = np.full((nt, 4 * nt), 15, dtype=np.int32)
+        self.k0h = np.zeros(nt, dtype=np.int32)
+        for j in range(2, nt - 1, 2):
+            f = first[TILE * j:TILE * j + TILE]
+            order = np.argsort(f, kind="stable")
+            fc = np.minimum(f[order].reshape(4, 32).min(1) // 32, 4 * nt)
+            k0 = min(max(int(first[TILE * (j + 1):TILE * (j + 2)].min()) // 32, int(fc.min())), 4 * j)
+            if fc.max() == 0 and k0 == 0:
+                continue
+            self.has32[j], self.perm32[j], self.first_chunk32[j], self.k0h[j] = 1, order, fc, k0
+            for kc in range(4 * j):
+                self.mask32[j, kc] = sum(1 << u for u in range(4) if kc >= fc[u])
+        self.ntables = int(self.has.sum()) + int(self.has32.sum())
+
+    @staticmethod
+    def wave_blocks(m: int):
+        """Per wave g the 16x16 block products of chunk mask ``m`` in Engine<float>::syrk36: block (u, v), v <= u, of block rows
+        u = 4 + g and 3 - g, executed when bits u and v are both set."""
+        bit = lambda u: (m >> u) & 1   # noqa: E731
+        return [sum(bit(u) & bit(v) for u in (4 + g, 3 - g) for v in range(u + 1)) for g in range(4)]
+
+    def model(self):
+        """Model in 16x16 block products per 32-column k-chunk, per tile j >= 1: ({j: (executed, slowest wave)}, (executed, slowest
+        wave) over all tiles), as shares of the dense count (36 products, 9 per wave and chunk).  Tiles without tables count dense."""
+        per, tot, ex, slow = {}, 0, 0, 0
+        for j in range(1, self.has.size):
+            w = [self.wave_blocks(int(self.mask[j, kc]) if self.has[j] else 255) for kc in range(4 * j)]
+            e, sl = sum(sum(x) for x in w), sum(max(x) for x in w)
+            per[j] = (e / (36 * 4 * j), sl / (9 * 4 * j))
+            tot, ex, slow = tot + 4 * j, ex + e, slow + sl
+        return per, ((ex / (36 * tot), slow / (9 * tot)) if tot else (1.0, 1.0))
+
+    def head_model(self):
+        """Model of the head tiles (j + 1, j), j even >= 2, in 32x32 block products per k-chunk (16 dense: four waves times four
+        blocks), skipped by the whole workgroup: ({j: executed}, executed over all of them), as shares of dense."""
+        per, tot, ex = {}, 0, 0
+        for j in range(2, self.has32.size - 1, 2):
+            e = sum(4 * bin(int(self.mask32[j, kc]) & 15).count("1") for kc in range(int(self.k0h[j]), 4 * j))
+            per[j] = e / (64 * j)
+            tot, ex = tot + 64 * j, ex + e
+        return per, (ex / tot if tot else 1.0)
+
+
 class DeviceHessianBlocks:
     _FIELDS = ["diag_blk", "inc_blk", "tile_ptr", "piece_blk", "piece_rc"]
 
@@ -560,4 +659,16 @@ class DeviceHessianBlocks:
             for f in ("perm", "mask"):
                 self.t["sc_" + f] = torch.from_numpy(np.ascontiguousarray(getattr(pc, f))).to(device)
                 setattr(c, "sc_" + f, self.t["sc_" + f].data_ptr())
+        tr = hb.tile_rows()      # the sorted rows of the diagonal tiles (thx_hblock_layout.tr_*); none: NULL
+        if tr is not None:
+            self.tr_tile_host = np.ascontiguousarray(tr.has)   # (host table: kept alive here)
+            c.tr_tile_host = self.tr_tile_host.ctypes.data
+            for f in ("perm", "mask"):
+                self.t["tr_" + f + "16"] = torch.from_numpy(np.ascontiguousarray(getattr(tr, f))).to(device)
+                setattr(c, "tr_" + f + "16", self.t["tr_" + f + "16"].data_ptr())
+            self.th_tile_host = np.ascontiguousarray(tr.has32)   # (host table: kept alive here)
+            c.th_tile_host = self.th_tile_host.ctypes.data
+            for f in ("perm32", "mask32", "k0h"):
+                self.t["th_" + f] = torch.from_numpy(np.ascontiguousarray(getattr(tr, f))).to(device)
+                setattr(c, "th_" + f, self.t["th_" + f].data_ptr())
         self.c = c

@@ -223,8 +223,20 @@ constexpr int SYRK32_WAVES = 3;
 // off the headline factorisation (87.9 / 88.0 -> 87.2 / 87.3 ms: its short K-loops want a third workgroup per CU); 4 (128 VGPRs,
 // 168 B of scratch) costs 2.7 ms (profiles/r6/ag_)
 constexpr int SYRK64_WAVES = 3;
-template <typename T, bool HB>
-__global__ void __launch_bounds__(256, sizeof(T) == 4 ? (HB ? SYRK32_WAVES : 3) : (HB ? SYRK64_WAVES : 2))
+// SORTED ROWS (SR; FactorPlan.sortrows, HBlk.tr_perm16 / tr_mask16; fp32, block-compact H, dense frame, left-looking): the tile's 128
+// rows are staged in the order tr_perm16[j] -- sorted by their first non-zero column, sixteen to a block row -- and tr_mask16[j][kc]
+// names the block rows that have begun at k-chunk kc.  For the others the loads, the staging stores and every product with them
+// are left out; each element keeps its products in their order.  Behind the K-loop the staged lower triangle goes back to
+// natural order through LDS (SYRK_SR_TRI floats, over the staging buffer and y), and everything else runs as without it.
+constexpr int SYRK_SR_TRI = TILE * (TILE + 1) / 2;
+// workgroups per CU the SR instantiation is compiled for.  The natural-order fp32 block-compact instance needs 128 VGPRs under
+// SYRK32_WAVES, so FOUR of its workgroups fit a CU; SR is held to the same 128 (no scratch).  Left at SYRK32_WAVES and with a
+// straight-line path for fully active chunks it took 145 VGPRs, three per CU, and the factor 35.19 - 35.23 ms instead of
+// 34.83 - 34.97 (profiles/tile_sorted_rows/variant_three_per_cu.txt, bench_first_set.txt).
+constexpr int SYRK32_SR_WAVES = 4;
+static_assert(SYRK32_SR_WAVES >= SYRK32_WAVES, "never fewer workgroups per CU than the natural-order instance is compiled for");
+template <typename T, bool HB, bool SR = false>
+__global__ void __launch_bounds__(256, sizeof(T) == 4 ? (HB ? (SR ? SYRK32_SR_WAVES : SYRK32_WAVES) : 3) : (HB ? SYRK64_WAVES : 2))
 chol_syrk_kernel(const T* __restrict__ H, T* __restrict__ L, const T* __restrict__ damping, int ellipsoidal, T damping_eps,
                  int n, int64_t ld, int j0, const T* __restrict__ rhs, T* __restrict__ yout, int64_t ldv, TilePat pat, HBlk hb) {
   using E = Engine<T>;
@@ -276,6 +288,102 @@ chol_syrk_kernel(const T* __restrict__ H, T* __restrict__ L, const T* __restrict
       hbp.load(hb, b, j, j, tid);
     }
   };
+  [[maybe_unused]] int srow = tid >> 1;   // the tile's row whose forward-substitution sum this thread pair holds
+  if constexpr (SR) {
+    static_assert(sizeof(T) == 4 && HB, "sorted rows: fp32, block-compact H");
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    typedef const int32_t __attribute__((address_space(4))) * cmask_t;
+    const int32_t* perm = hb.tr_perm16 + j * TILE;
+    const cmask_t pm = (cmask_t)(uintptr_t)(hb.tr_mask16 + (int64_t)j * 4 * ((n + TILE - 1) / TILE));
+    // staged row lrow + 32 u of pass u lies in block row 2 u + hi: wave uniform
+    const int lrow = tid >> 3, lc = tid & 7, hi = __builtin_amdgcn_readfirstlane(wave >> 1);
+    unsigned voff[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) voff[u] = (unsigned)((perm[lrow + 32 * u] * (int)ld + lc * 4) * 4);
+    // (rows behind the matrix: outside the buffer's extent, read as zeros)
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(L + lmat + (int64_t)row0 * ld), 0,
+                                                                          (int)((int64_t)valid * ld * 4), 0x00020000);
+    const int nk = Kspan / 32;
+    uint4 ra[2][4];   // (a piece is loaded and staged under the same mask bit)
+    auto gload = [&](uint4 (&x)[4], int kc, int m) __attribute__((always_inline)) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if ((m >> (2 * u + hi)) & 1) {
+          const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff[u], kc * 128, 0);
+          x[u] = make_uint4(v.x, v.y, v.z, v.w);
+        }
+    };
+    // the masks of chunks kc .. kc + 3: the prefetch two chunks ahead branches on m2, and m3 was asked for a chunk before that
+    int m0 = pm[0], m1 = nk > 1 ? pm[1] : 0, m2 = nk > 2 ? pm[2] : 0, m3 = nk > 3 ? pm[3] : 0;
+    gload(ra[0], 0, m0);
+    if (nk > 1) gload(ra[1], 1, m1);
+    prologue();
+    T gsum = T(0);
+    auto step = [&](uint4 (&x)[4], int kc) __attribute__((always_inline)) {
+      const int mc = m0;
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if ((mc >> (2 * u + hi)) & 1) *reinterpret_cast<uint4*>(stage + (lrow + 32 * u) * E::SYRK_LDT + 4 * lc) = x[u];
+      __syncthreads();
+      if (kc + 2 < nk) gload(x, kc + 2, m2);
+      m0 = m1, m1 = m2, m2 = m3;
+      m3 = kc + 4 < nk ? pm[kc + 4] : 0;
+      if (fwd && ((mc >> (tid >> 5)) & 1)) {   // staged slot tid >> 1 lies in block row tid >> 5
+        const float4* rp = reinterpret_cast<const float4*>(stage + (tid >> 1) * E::SYRK_LDT + (tid & 1) * 16);
+        const float4* yp = reinterpret_cast<const float4*>(ybuf + kc * 32 + (tid & 1) * 16);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float4 a = rp[i], yv = yp[i];
+          gsum += a.x * yv.x; gsum += a.y * yv.y; gsum += a.z * yv.z; gsum += a.w * yv.w;
+        }
+      }
+      if (wave == 0) E::template syrk36_masked<0>(stage, acc, lane, mc);
+      else if (wave == 1) E::template syrk36_masked<1>(stage, acc, lane, mc);
+      else if (wave == 2) E::template syrk36_masked<2>(stage, acc, lane, mc);
+      else E::template syrk36_masked<3>(stage, acc, lane, mc);
+    };
+    for (int kc = 0; kc < nk; kc += 2) {
+      step(ra[0], kc);
+      if (kc + 1 < nk) step(ra[1], kc + 1);
+    }
+    tpart = gsum;
+    srow = perm[tid >> 1];
+    // staged element (s, t) -> natural element (max, min) of (perm[s], perm[t]) of the packed lower triangle in LDS; of a diagonal
+    // block's two equal halves only s >= t is written; then every lane reads its natural fragments back (an element above the
+    // diagonal as its mirror image, which is what the natural-order accumulators hold there)
+    __syncthreads();   // the staging buffer and y are free
+    T* tri = stage;
+    auto put = [&](int u, int v, const f32x4& a) __attribute__((always_inline)) {
+      const int s = 16 * u + (lane & 15), t0 = 16 * v + 4 * (lane >> 4);
+      const int ps = perm[s];
+      const int4 pt = *reinterpret_cast<const int4*>(perm + t0);
+      const int ptk[4] = {pt.x, pt.y, pt.z, pt.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int hi_ = max(ps, ptk[k]), lo_ = min(ps, ptk[k]);
+        if (u != v || s >= t0 + k) tri[hi_ * (hi_ + 1) / 2 + lo_] = a[k];
+      }
+    };
+    auto get = [&](int u, int v, f32x4& a) __attribute__((always_inline)) {
+      const int r = 16 * u + (lane & 15), c0 = 16 * v + 4 * (lane >> 4);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int hi_ = max(r, c0 + k), lo_ = min(r, c0 + k);
+        a[k] = tri[hi_ * (hi_ + 1) / 2 + lo_];
+      }
+    };
+    const int UH = 4 + wave, UL = 3 - wave;
+#pragma unroll
+    for (int i = 0; i < 9; ++i)
+      if (i <= UH) put(UH, i, acc[i]);
+      else put(UL, i - UH - 1, acc[i]);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 9; ++i)
+      if (i <= UH) get(UH, i, acc[i]);
+      else get(UL, i - UH - 1, acc[i]);
+  } else {
   kloop_f<T, true, true, E::SYRK_LDT, (sizeof(T) == 8 && CT<T>::KB == 32)>(
       L + lmat + (lf.packed ? 0 : (int64_t)row0 * ld), valid, nullptr, 0, ldt, Kspan, stage, nullptr, tid,
       fwd ? ybuf : nullptr, &tpart, [&]() __attribute__((always_inline)) {
@@ -284,6 +392,7 @@ chol_syrk_kernel(const T* __restrict__ H, T* __restrict__ L, const T* __restrict
     else if (wave == 2) E::template syrk36<2>(stage, acc, lane);
     else E::template syrk36<3>(stage, acc, lane);
   }, prologue, klist, lf.packed ? pat.diag_s + pat.diag_kptr[j] : nullptr, nullptr, lf.pstride, ycompact);
+  }
 
   {
     const bool damp = damping != nullptr;
@@ -308,7 +417,7 @@ chol_syrk_kernel(const T* __restrict__ H, T* __restrict__ L, const T* __restrict
   }
   if (fwd) {  // g_j - L_j,0:j y -> y_j's place (chol_potrf_kernel finishes it): thread pair (2r, 2r+1) holds the halves of row r
     const T tsum = tpart + __shfl_xor(tpart, 1);
-    const int r = tid >> 1;
+    const int r = SR ? srow : tid >> 1;   // (SR: the pair holds a staged slot's sum)
     if ((tid & 1) == 0 && r < valid) yout[(int64_t)b * ldv + row0 + r] = rhs[(int64_t)b * ldv + row0 + r] - tsum;
   }
 }

@@ -78,6 +78,50 @@ struct Engine<float> {
       }
     }
   }
+  // syrk36 on SORTED staged rows (chol_syrk_kernel<float, true, true>): ``m`` names the chunk's active block rows (wave uniform); block
+  // (u, v) runs only when both its block rows are active, with the same MFMA sequence as above, and the fragments of an inactive
+  // block row are not read (its LDS rows hold stale data).
+  template <int G>
+  static __device__ __forceinline__ void syrk36_masked(const float* sA, f32x4* acc, int lane, int m) {
+    constexpr int UH = 4 + G, UL = 3 - G;
+    const bool hh = (m >> UH) & 1, hl = (m >> UL) & 1;
+    if (!hh && !hl) return;
+    const int o = (lane & 15) * 40 + 4 * (lane >> 4);
+    float fbh[8], fbl[8];   // (read only where loaded)
+    if (hh) {
+      const float4 a = *reinterpret_cast<const float4*>(sA + 16 * UH * 40 + o), b = *reinterpret_cast<const float4*>(sA + 16 * UH * 40 + o + 16);
+      fbh[0] = a.x; fbh[1] = a.y; fbh[2] = a.z; fbh[3] = a.w; fbh[4] = b.x; fbh[5] = b.y; fbh[6] = b.z; fbh[7] = b.w;
+    }
+    if (hl) {
+      const float4 c = *reinterpret_cast<const float4*>(sA + 16 * UL * 40 + o), d = *reinterpret_cast<const float4*>(sA + 16 * UL * 40 + o + 16);
+      fbl[0] = c.x; fbl[1] = c.y; fbl[2] = c.z; fbl[3] = c.w; fbl[4] = d.x; fbl[5] = d.y; fbl[6] = d.z; fbl[7] = d.w;
+    }
+#pragma unroll
+    for (int v = 0; v <= UH; ++v) {
+      if (!((m >> v) & 1)) continue;
+      const bool lo = v <= UL && hl;
+      if (!hh && !lo) continue;
+      float fa[8];
+      if (v == UH) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) fa[q] = fbh[q];
+      } else if (v == UL) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) fa[q] = fbl[q];
+      } else {
+        const float4 a = *reinterpret_cast<const float4*>(sA + 16 * v * 40 + o), b = *reinterpret_cast<const float4*>(sA + 16 * v * 40 + o + 16);
+        fa[0] = a.x; fa[1] = a.y; fa[2] = a.z; fa[3] = a.w; fa[4] = b.x; fa[5] = b.y; fa[6] = b.z; fa[7] = b.w;
+      }
+      if (hh) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc[v] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[q], fbh[q], acc[v], 0, 0, 0);
+      }
+      if (lo) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc[UH + 1 + v] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[q], fbl[q], acc[UH + 1 + v], 0, 0, 0);
+      }
+    }
+  }
   // The same nine blocks of H_jj, global -> registers BEFORE the K-loop (row index clamped into the matrix: the caller
   // masks by value), so that the H tile costs no exposed round trips after it.
   template <int G>

@@ -146,6 +146,8 @@ struct FactorPlan {
   bool zsolve;           // ... their waves skip zero solves (HBlk.rg_zf) and / or pair 0 runs on groups (thx_chol_schedule.skip_zero_solves)
   bool pair0;            // pair 0 takes its own row groups (HBlk.rg0_*; only with zsolve)
   bool sortcols;         // the pairs with row groups and sorted-column tables take those too (HBlk.sc_*, thx_chol_schedule.sort_pair_columns)
+  bool sorthead;         // the pairs' head tiles (j + 1, j) whose tile j has sorted-column tables take them (HBlk.th_*, thx_chol_schedule.sort_tile_rows)
+  bool sortrows;         // the split diagonal phase's SYRK stages the tiles that have sorted-row tables by them (HBlk.tr_*, thx_chol_schedule.sort_tile_rows)
   int hbm;               // the off-diagonal kernels' HB template argument: 0 dense H, HB_MODE_SCATTER, HB_MODE_ROUNDS
   int f64_wide_max, f64_half_max;
 };
@@ -204,6 +206,9 @@ static FactorPlan plan_factor(bool f64, int n, int64_t ld, int B, bool has_dampi
             hbp->rg0_piece_rc && (p.hbm != HB_MODE_SCATTER || hbp->rg0_max_tile_pieces <= hb_scatter_max);
   p.zsolve = (zs && p.regroup && hbp->rg_zf) || p.pair0;
   p.sortcols = p.regroup && (!sched || sched->sort_pair_columns != 0) && hbp->sc_pair_host && hbp->sc_perm && hbp->sc_mask;
+  p.sorthead = p.regroup && p.hbm != 0 && (!sched || sched->sort_tile_rows != 0) && hbp->th_tile_host && hbp->th_perm32 && hbp->th_mask32 &&
+               hbp->th_k0h;
+  p.sortrows = p.regroup && !p.fused_diag && (!sched || sched->sort_tile_rows != 0) && hbp->tr_tile_host && hbp->tr_perm16 && hbp->tr_mask16;
   return p;
 }
 
@@ -263,6 +268,22 @@ struct FactorLaunch {
     });
   }
 
+  // the head tile (j + 1, j) of column pair j: with sorted columns where tile j has a table (P.sorthead), else as any tile of column j
+  void head(const Half& h, int j) const {
+    if constexpr (sizeof(T) == 4) {
+      if (P.sorthead && hb.th_tile_host[j]) {
+        with_hb_mode(P.hbm, [&](auto mode) {
+          constexpr int M = decltype(mode)::value;
+          if constexpr (M != 0)
+            launch_lds<chol_offdiag_f32_kernel<M, true>>(dev, dim3((h.nb + 7) / 8 * 8), dim3(256), OFF32_SMEM, h.s, H_of(h), L_of(h), panel_of(h),
+                                                         n, ld, j, P.ntiles, j + 1, 1, h.nb, pat, hb_of(h));
+        });
+        return;
+      }
+    }
+    off(h, j, j + 1, 1);
+  }
+
   // tiles (i, j) and (i, j + 1) of row tiles [i_first, i_first + nrt) in one workgroup each (chol_offdiag2_f32_kernel)
   void pair(const Half& h, int j, int i_first, int nrt) const {
     if constexpr (sizeof(T) == 4)
@@ -312,9 +333,17 @@ struct FactorLaunch {
       if (fused)
         launch_lds<chol_diag_kernel<T, HB>>(dev, dim3(h.nb, nc), dim3(256), smem, h.s, H_of(h), L_of(h), panel_of(h), dh, ellipsoidal, (T)eps,
                                             info + h.b0, n, ld, j, ntiles, rh, yh, ldv, pat, hb_of(h));
-      else
+      else {
+        if constexpr (sizeof(T) == 4 && HB) {
+          if (P.sortrows && nc == 1 && hb.tr_tile_host[j]) {   // this tile's sorted rows; the un-permute buffer lies over staging + y
+            launch_lds<chol_syrk_kernel<T, HB, true>>(dev, dim3(h.nb, 1), dim3(256), std::max(smem, (size_t)SYRK_SR_TRI * sizeof(T)), h.s,
+                                                      H_of(h), L_of(h), dh, ellipsoidal, (T)eps, n, ld, j, rh, yh, ldv, pat, hb_of(h));
+            return;
+          }
+        }
         launch_lds<chol_syrk_kernel<T, HB>>(dev, dim3(h.nb, nc), dim3(256), smem, h.s, H_of(h), L_of(h), dh, ellipsoidal, (T)eps, n, ld, j, rh,
                                             yh, ldv, pat, hb_of(h));
+      }
     });
     if (!fused) {
       const int64_t tile_off = packed ? (int64_t)j * TILE * TILE : (int64_t)j * TILE * ld + (int64_t)j * TILE;
@@ -588,7 +617,7 @@ static int run_left_looking(const FactorLaunch<T>& c) {
       c.diag(h, j);
       if (split && k == 0 && j == 0) hipEventRecord(ds.ev_lag, h.s);
       if (pair) {
-        c.off(h, j, j + 1, 1);
+        c.head(h, j);
         c.diag(h, j + 1);
         const int32_t* gp = c.P.regroup ? c.hb.rg_group_ptr_host : nullptr;
         const int g0 = gp ? gp[j / 2] : 0, ng = gp ? gp[j / 2 + 1] - g0 : 0;
@@ -598,7 +627,9 @@ static int run_left_looking(const FactorLaunch<T>& c) {
         continue;
       }
       const int nrt = tp ? tp->col_count_host[j] : ntiles - 1 - j;   // (tile-sparse: the column's non-zero row tiles)
-      if (nrt > 0) c.off(h, j, tp ? 0 : j + 1, nrt);
+      // (an even last-but-one column of the pair schedule is a head tile without a pair behind it)
+      if (nrt == 1 && !tp && c.P.colpair && j % 2 == 0) c.head(h, j);
+      else if (nrt > 0) c.off(h, j, tp ? 0 : j + 1, nrt);
     }
     j += pair ? 2 : 1;
   }
@@ -648,6 +679,8 @@ static int factor_impl(const void* H, int64_t ld, int n, int B, const void* damp
   if (!P.regroup) hb.rg_rows = hb.rg_k0 = hb.rg_tile_ptr = hb.rg_piece_blk = hb.rg_piece_rc = nullptr;
   if (!P.zsolve || !P.regroup) hb.rg_zf = nullptr;
   if (!P.sortcols) hb.sc_perm = hb.sc_mask = hb.sc_pair_host = nullptr;
+  if (!P.sortrows) hb.tr_perm16 = hb.tr_mask16 = hb.tr_tile_host = nullptr;
+  if (!P.sorthead) hb.th_perm32 = hb.th_mask32 = hb.th_k0h = hb.th_tile_host = nullptr;
   std::lock_guard<std::mutex> guard(g_launch_mutex);
   const int dev = current_device();
   const FactorLaunch<T> c{H, ld, n, B, damping, ellipsoidal, eps, L, panel, info, rhs, y, ldv, st, tp, ls, P, pat, use_hb, hb, packed,
@@ -790,7 +823,8 @@ static HBlk hblk_from(const thx_hblock_layout* layout, const void* Hc, int64_t b
               layout->l_mask, layout->rg_rows, layout->rg_k0, layout->rg_tile_ptr, layout->rg_piece_blk, layout->rg_piece_rc,
               layout->rg_group_ptr_host, layout->rg_max_tile_pieces, layout->rg_zf, layout->rg0_rows, layout->rg0_zf, layout->rg0_tile_ptr,
               layout->rg0_piece_blk, layout->rg0_piece_rc, layout->rg0_ngroups, layout->rg0_max_tile_pieces, layout->sc_perm,
-              layout->sc_mask, layout->sc_pair_host};
+              layout->sc_mask, layout->sc_pair_host, layout->tr_perm16, layout->tr_mask16, layout->tr_tile_host,
+              layout->th_perm32, layout->th_mask32, layout->th_k0h, layout->th_tile_host};
 }
 
 int thx_chol_factor(const void* H, int64_t ld, int32_t n, int32_t B, const void* damping, int ellipsoidal,
@@ -897,6 +931,7 @@ int thx_chol_plan(int32_t n, int64_t ld, int32_t B, int dtype, int has_damping, 
   out->regroup_rows = p.regroup;
   out->skip_zero_solves = p.zsolve;
   out->sort_pair_columns = p.sortcols;
+  out->sort_tile_rows = p.sortrows || p.sorthead;
   return 0;
 }
 

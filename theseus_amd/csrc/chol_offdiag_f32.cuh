@@ -40,7 +40,17 @@ __device__ __forceinline__ void sub_mma_sw(const float* Pc, const Engine<float>:
   }
 }
 
-template <int HB>   // 0: dense H; HB_MODE_SCATTER / HB_MODE_ROUNDS: block-compact H, how a tile's pieces reach the accumulators
+// SORTED COLUMNS of a HEAD tile (SC; FactorPlan.sorthead, HBlk.th_*; launched only for tile (j + 1, j) of the column-pair schedule
+// when tile j has a table): the one-tile version of chol_offdiag2_f32_kernel<HB, true, true>.  Operand A -- the 128 rows of tile
+// j -- is staged in the order th_perm32[j], four blocks of 32 sorted by first non-zero column; th_mask32[j][kc] names the blocks
+// that have begun, the loads, staging stores and MFMAs of the others are left out (workgroup uniform), and the K-loop starts at
+// th_k0h[j].  Every column accumulates independently and keeps its products in their order.  Behind the K-loop each wave moves its
+// own 32 rows back to natural column order through its quarter of the staging buffers (the panel copy is already in LDS behind
+// them): two rounds of 64 natural columns, row stride 65, the values of the other half going to the spare column.
+constexpr int OFF32_UNPERM_LD = 65;
+static_assert(4 * 32 * OFF32_UNPERM_LD <= OFF32_STAGE_FLOATS, "the four waves' un-permute buffers fit in the staging buffers");
+
+template <int HB, bool SC = false>   // HB 0: dense H; HB_MODE_SCATTER / HB_MODE_ROUNDS: block-compact H, how a tile's pieces reach the accumulators
 __global__ void __launch_bounds__(256, 2)
 chol_offdiag_f32_kernel(const float* __restrict__ H, float* __restrict__ L, const float* __restrict__ panel, int n,
                         int64_t ld, int jarg, int ntiles, int i_first, int nrow_tiles, int B, TilePat pat, HBlk hb) {
@@ -137,7 +147,107 @@ chol_offdiag_f32_kernel(const float* __restrict__ H, float* __restrict__ L, cons
   const float* Ap = L + lmat + (lf.packed ? 0 : (int64_t)col0 * ld) + kcol0;   // rows of block row j (operand A) / i (operand B)
   const float* Bp = L + lmat + (lf.packed ? 0 : (int64_t)row0 * ld) + kcol0;
   const int validA = upd ? tile_rows(pat, n, j) : TILE;   // (update: tile column k may be the LAST block row)
+  if constexpr (SC) {
+    static_assert(HB != 0, "sorted head-tile columns come with a block-compact H");
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    typedef const int32_t __attribute__((address_space(4))) * cmask_t;
+    const int32_t* perm = hb.th_perm32 + jarg * TILE;
+    const cmask_t pm = (cmask_t)(uintptr_t)(hb.th_mask32 + (int64_t)jarg * 4 * ntiles);
+    const cmask_t pk = (cmask_t)(uintptr_t)hb.th_k0h;
+    const int nk = Kspan / 32, k0 = min(pk[jarg], nk);
+    const int lrow = tid >> 3, lc = tid & 7;
+    unsigned voffA[4], voffB[4];   // pass u: staged row lrow + 32 u -- of operand A sorted slot 32 u + lrow, block u
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      voffA[u] = (unsigned)((perm[lrow + 32 * u] * (int)ld + lc * 4) * 4);
+      voffB[u] = (unsigned)(((lrow + 32 * u) * (int)ld + lc * 4) * 4);
+    }
+    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Ap), 0, (int)(TILE * ld * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Bp), 0, (int)((int64_t)validB * ld * 4), 0x00020000);
+    uint4 ra[2][4], rb[2][4];   // (a piece of A is loaded and staged under the same mask bit)
+    auto gload = [&](uint4 (&xa)[4], uint4 (&xb)[4], int kc, int m) __attribute__((always_inline)) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if ((m >> u) & 1) {
+          const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(rsA, voffA[u], kc * 128, 0);
+          xa[u] = make_uint4(a.x, a.y, a.z, a.w);
+        }
+        const u32x4 d = __builtin_amdgcn_raw_buffer_load_b128(rsB, voffB[u], kc * 128, 0);
+        xb[u] = make_uint4(d.x, d.y, d.z, d.w);
+      }
+    };
+    // the masks of chunks kc .. kc + 3: the prefetch two chunks ahead branches on m2
+    int m0 = k0 < nk ? pm[k0] : 0, m1 = k0 + 1 < nk ? pm[k0 + 1] : 0, m2 = k0 + 2 < nk ? pm[k0 + 2] : 0, m3 = k0 + 3 < nk ? pm[k0 + 3] : 0;
+    if (k0 < nk) gload(ra[0], rb[0], k0, m0);
+    if (k0 + 1 < nk) gload(ra[1], rb[1], k0 + 1, m1);
+    prologue();
+    const float* sBw = sB + 32 * wave * 36;
+    const int rl = lane & 31;
+    auto step = [&](uint4 (&xa)[4], uint4 (&xb)[4], int kc) __attribute__((always_inline)) {
+      const int mc = m0;
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if ((mc >> u) & 1) *reinterpret_cast<uint4*>(sA + (lrow + 32 * u) * 36 + 4 * lc) = xa[u];
+        *reinterpret_cast<uint4*>(sB + (lrow + 32 * u) * 36 + 4 * lc) = xb[u];
+      }
+      __syncthreads();
+      if (kc + 2 < nk) gload(xa, xb, kc + 2, m2);
+      m0 = m1, m1 = m2, m2 = m3;
+      m3 = kc + 4 < nk ? pm[kc + 4] : 0;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {   // (Engine<float>::chunk, block cb only where it is active)
+        const float4 fb = *reinterpret_cast<const float4*>(sBw + rl * 36 + 8 * ks + 4 * g);
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) {
+          if (!((mc >> cb) & 1)) continue;
+          const float4 fa = *reinterpret_cast<const float4*>(sA + (32 * cb + rl) * 36 + 8 * ks + 4 * g);
+          P.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.x, fb.x, P.v[cb], 0, 0, 0);
+          P.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.y, fb.y, P.v[cb], 0, 0, 0);
+          P.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.z, fb.z, P.v[cb], 0, 0, 0);
+          P.v[cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.w, fb.w, P.v[cb], 0, 0, 0);
+        }
+      }
+    };
+    for (int kc = k0; kc < nk; kc += 2) {
+      step(ra[0], rb[0], kc);
+      if (kc + 1 < nk) step(ra[1], rb[1], kc + 1);
+    }
+    if (k0 < nk) {   // (workgroup uniform; no chunk ran: P is zero in any order)
+      __syncthreads();   // the last chunk has been consumed: the staging buffers are free
+      float* ub = smem + wave * 32 * OFF32_UNPERM_LD + rl * OFF32_UNPERM_LD;   // this lane's row of the wave's buffer
+      int pcol[4][16];   // natural column of this lane's staged columns 32 cb + 8 q + 4 g + k
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int4 pv = *reinterpret_cast<const int4*>(perm + 32 * cb + 8 * q + 4 * g);
+          pcol[cb][4 * q] = pv.x, pcol[cb][4 * q + 1] = pv.y, pcol[cb][4 * q + 2] = pv.z, pcol[cb][4 * q + 3] = pv.w;
+        }
+      Engine<float>::Acc N;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int c = pcol[cb][i] - 64 * h;
+            ub[(c >= 0 && c < 64) ? c : 64] = P.v[cb][i];
+          }
+        wave_lds_fence();
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) N.v[2 * h + cb][4 * q + k] = ub[32 * cb + 8 * q + 4 * g + k];
+        wave_lds_fence();
+      }
+      P = N;
+    }
+  } else {
   kloop<float, false>(Ap, validA, Bp, validB, ldt, Kspan, sA, sB, P, tid, nullptr, nullptr, prologue, klist, ksa, ksb, lf.pstride);
+  }
   if constexpr (HB) {
     // block-compact H: the tile's pieces are gathered into the (now free) staging buffers, 64 rows at a time, and read back in
     // the accumulator layout -- a few hundred elements instead of a 64 KB tile of zeros from HBM

@@ -131,6 +131,17 @@ struct HBlk {
   const int32_t* sc_perm;        // (256) sorted slot -> column of the pair, 0 .. 255
   const int32_t* sc_mask;        // (4 ntiles) per k-chunk the 8-bit mask of the active sorted blocks
   const int32_t* sc_pair_host;   // (HOST table, npairs: the pair has tables; no kernel reads it)
+  // thx_hblock_layout.tr_*: the sorted rows of the diagonal tiles (chol_syrk_kernel<float, true, true>, the only kernel that reads
+  // them) -- set by factor_impl only with FactorPlan.sortrows, nullptr otherwise
+  const int32_t* tr_perm16;      // (ntiles, 128) staged slot -> row of tile j, 0 .. 127
+  const int32_t* tr_mask16;      // (ntiles, 4 ntiles) per k-chunk the 8-bit mask of the active staged block rows of 16
+  const int32_t* tr_tile_host;   // (HOST table, ntiles: the tile has tables; no kernel reads it)
+  // thx_hblock_layout.th_*: the sorted columns of the head tiles (j + 1, j) (chol_offdiag_f32_kernel<HB, true>, the only kernel that
+  // reads them) -- set by factor_impl only with FactorPlan.sorthead, nullptr otherwise
+  const int32_t* th_perm32;      // (ntiles, 128) sorted slot -> row of tile j, 0 .. 127
+  const int32_t* th_mask32;      // (ntiles, 4 ntiles) per k-chunk the 4-bit mask of the active sorted blocks of 32
+  const int32_t* th_k0h;         // (ntiles) first k-chunk of the head tile's K-loop
+  const int32_t* th_tile_host;   // (HOST table, ntiles: tile j's head tile has tables; no kernel reads it)
 };
 
 // The pieces of lower tile (ti, tj) of problem b -- f(r, c, value), (r, c) relative to the tile origin and inside the tile; the

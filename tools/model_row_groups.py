@@ -80,6 +80,55 @@ def main():
         print(f"j={j:<3d} {xa:20.3f} {xb:20.3f}   {fc}")
     print(f"all pair K-loops: {ex_a:.3f} -> {ex_b:.3f} executed; {pair_k * (ex_a - ex_b):.1f} of the factor's {kloops - pair_k * total:.1f} "
           f"executed tile products left out")
+    tile_rows(hb, m)
+
+
+def tile_rows(hb, m):
+    """thx_chol_schedule.sort_tile_rows (TileRows, thx_hblock_layout.tr_*): the SYRK of diagonal tile j in 16x16 block products per
+    k-chunk (36 dense, nine per wave) -- executed, and what the busiest of the four waves executes (they meet at two barriers per
+    chunk) under the placement and under the identity.  Then the head tiles (j + 1, j), j even (thx_hblock_layout.th_*),
+    in 32x32 block products (16 dense per chunk) with the natural sub-block masks, and with tile j's rows sorted into four blocks of
+    32 that are skipped by the whole workgroup, the K-loop starting where both operands have begun."""
+    from theseus_amd.compiler import TileRows
+    tr = hb.tile_rows()
+    if tr is None:
+        print("sorted tile rows: no tile has a table")
+        return
+    nt = hb.ntiles
+    per, (ex, slow) = tr.model()
+    per_id, (_, slow_id) = TileRows(hb, place=range(8)).model()
+    nat = {}
+    ff = np.full(nt * 128, TileRows.NEVER, dtype=np.int64)
+    ff[:hb.row_first.size] = hb.row_first
+    for j in range(1, nt):   # natural order: block row u begins with the first of its own sixteen rows
+        fcn = ff[128 * j:128 * j + 128].reshape(8, 16).min(1) // 32
+        w = [TileRows.wave_blocks(sum(int(kc >= fcn[u]) << u for u in range(8))) for kc in range(4 * j)]
+        nat[j] = sum(sum(x) for x in w)
+    print(f"SYRK, sorted tile rows, placement {list(tr.place)}: executed / busiest wave, shares of dense")
+    print(f"{'tile':>5s} {'executed':>9s} {'busiest wave':>13s} {'identity placement':>19s} {'natural masks':>14s}   first chunks of the 8 block rows")
+    for j in range(1, nt):
+        fc = tr.first_chunk[j].tolist() if tr.has[j] else "no table"
+        print(f"j={j:<3d} {per[j][0]:9.2f} {per[j][1]:13.2f} {per_id[j][1]:19.2f} {nat[j] / (36 * 4 * j):14.2f}   {fc}")
+    tot = sum(4 * j for j in range(1, nt))
+    print(f"all SYRKs: executed {ex:.3f}, busiest wave {slow:.3f} (identity placement {slow_id:.3f}); natural-order masks would execute "
+          f"{sum(nat.values()) / (36 * tot):.3f}")
+    first = hb.row_first.astype(np.int64)
+    n = first.size
+    pop = lambda x: bin(int(x) & 15).count("1")   # noqa: E731
+    dense = natural = srt = 0
+    for j in range(2, nt - 1, 2):
+        f = np.full(128, TileRows.NEVER, dtype=np.int64)
+        rows = np.arange(128 * j, min(128 * j + 128, n))
+        f[:rows.size] = first[rows]
+        fc = np.sort(f, kind="stable").reshape(4, 32).min(1) // 32
+        k0h = max(int(first[128 * (j + 1):128 * (j + 2)].min()) // 32, int(fc.min()))
+        dense += 16 * 4 * j
+        natural += sum(pop(m[j + 1, kc]) * pop(m[j, kc]) for kc in range(4 * j))
+        srt += sum(4 * int((fc <= kc).sum()) for kc in range(min(k0h, 4 * j), 4 * j))
+    if dense:
+        print(f"head tiles (j + 1, j), j = 2 .. {nt - 2 - nt % 2}: natural masks execute {natural / dense:.3f}, tile j's rows sorted "
+              f"in four blocks of 32 and skipped by the workgroup {srt / dense:.3f}")
+
 
 if __name__ == "__main__":
     main()
