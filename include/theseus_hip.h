@@ -318,6 +318,25 @@ typedef struct {
  *      O(|L|)) and writes mask (host int32, ntiles x 4 * ntiles, ntiles = ceil(nvars * bd / THX_TILE)) in the layout of l_mask:
  *      a sub-block is marked when any variable block of L's fill overlaps it (sub-blocks wholly outside the matrix stay 0). */
 int thx_hblock_fill_mask(int32_t nvars, int32_t bd, int32_t nblocks, const int32_t* blocks, int32_t* mask);
+/*      thx_hblock_order: HOST-ONLY -- an order of the variables that shrinks the row envelope of tril(H), and with it the envelope
+ *      of L that the fp32 column-pair, SYRK and head-tile kernels and the envelope solves leave out (l_mask, rg_*, sc_*, tr_*, th_*,
+ *      row_first are all built from it).  blocks: as for thx_hblock_fill_mask.  Candidates: the insertion order, Cuthill-McKee from
+ *      both ends of a pseudo-diameter and their reverses, the greedy minimum-front-growth order (King) from those ends, the first and
+ *      the last variable and the four variables of lowest degree, forwards and reversed.  Each is scored by the sum over the scalar
+ *      rows r of P H P^T of (r - first[r])^2; the lowest score wins, the insertion order keeps every tie (a chain comes back as the
+ *      identity).  Deterministic.  perm_out (host, nvars): perm_out[k] = the variable at position k.  score_out (host, 2 values, may
+ *      be NULL): the score of the order returned and of the insertion order.
+ *      thx_hblocks_permute: dst[b][k] = block (map[k] >> 1) of src[b], transposed when map[k] & 1, for k < nblocks (map: device int32;
+ *      lists of bd x bd blocks, problem strides sstride / dstride in elements) -- the linearization's block list in the block order
+ *      of a layout built on another variable order: a block whose two variables swap sides of the diagonal arrives transposed. */
+int thx_hblock_order(int32_t nvars, int32_t bd, int32_t nblocks, const int32_t* blocks, int32_t* perm_out, int64_t* score_out);
+int thx_hblocks_permute(const void* src, int64_t sstride, void* dst, int64_t dstride, const int32_t* map, int32_t nblocks, int32_t bd,
+                        int32_t B, int dtype, void* stream);
+/*      thx_frame_permute: the same move for a DENSE frame -- Hp[b][i][j] = H[b][max(idx[i], idx[j])][min(idx[i], idx[j])] for
+ *      j <= i < n: the lower triangle of P H P^T from the lower triangle of H (idx: device int32, the column of H at every column of
+ *      the permuted order; frames (B, ld, ld) / (B, ldp, ldp); nothing above the diagonal or beyond n is written). */
+int thx_frame_permute(const void* H, int64_t ld, void* Hp, int64_t ldp, const int32_t* idx, int32_t n, int32_t B, int dtype,
+                      void* stream);
 int thx_pg_assemble_blocks(const thx_pg_structure* s, const thx_pg_data* d, const thx_hblock_layout* layout, void* Hc,
                            int64_t bstride, void* g, int dtype, const thx_lie_eps* eps, void* stream);
 int thx_hblocks_expand(const thx_hblock_layout* layout, const void* Hc, int64_t bstride, int32_t B, void* H, int64_t ld,

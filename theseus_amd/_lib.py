@@ -109,6 +109,18 @@ def hblock_fill_mask(blocks, nvars: int, bd: int):
     return mask
 
 
+def hblock_order(blocks, nvars: int, bd: int):
+    """thx_hblock_order (host only): (perm, score, natural score) -- ``perm[k]`` = the variable at position k of the order that
+    shrinks the row envelope of the lower block pattern ``blocks`` most among the candidates (the identity when none beats the
+    insertion order), and the envelope scores sum (r - first[r])^2 of that order and of the insertion order."""
+    import numpy as np
+    b = np.ascontiguousarray(np.asarray(blocks, dtype=np.int32).reshape(-1, 2))
+    perm = np.zeros(nvars, dtype=np.int32)
+    score = np.zeros(2, dtype=np.int64)
+    check(load().thx_hblock_order(nvars, bd, b.shape[0], b.ctypes.data, perm.ctypes.data, score.ctypes.data), "thx_hblock_order")
+    return perm, int(score[0]), int(score[1])
+
+
 def max_offdiag_tile_pieces(tile_ptr, ntiles: int) -> int:
     """thx_hblock_layout.max_tile_pieces: the largest piece count of a lower tile t = i (i + 1) / 2 + j with i > j (0: none)."""
     import numpy as np
@@ -233,6 +245,9 @@ _SIGNATURES = {
                                 c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, POINTER(TilePattern), c_int, c_void_p,
                                 POINTER(CholSchedule)],
     "thx_hblock_fill_mask": [c_int32, c_int32, c_int32, c_void_p, c_void_p],
+    "thx_hblock_order": [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p],
+    "thx_hblocks_permute": [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int, c_void_p],
+    "thx_frame_permute": [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int, c_void_p],
     "thx_chol_plan": [c_int32, c_int64, c_int32, c_int, c_int, c_int, c_int64, POINTER(HBlockLayout), POINTER(CholSchedule),
                       POINTER(CholPlanInfo)],
     "thx_chol_factor_levels": [POINTER(HBlockLayout), c_void_p, c_int64, c_int32, c_void_p, c_int, c_double, c_void_p, c_void_p,

@@ -672,3 +672,65 @@ class DeviceHessianBlocks:
                 self.t["th_" + f] = torch.from_numpy(np.ascontiguousarray(getattr(tr, f))).to(device)
                 setattr(c, "th_" + f, self.t["th_" + f].data_ptr())
         self.c = c
+
+
+class _OrderedPattern:
+    """What HessianBlocks reads of a structure, for a block pattern given directly (no cost tables: the layout is never assembled
+    into, its blocks arrive by thx_hblocks_permute)."""
+
+    def __init__(self, dof: int, nvars: int, pattern: np.ndarray):
+        self.dof, self.num_poses, self._pattern = dof, nvars, pattern
+        self.inc_ptr = np.zeros(nvars + 1, dtype=np.int32)
+        self.inc_other = np.zeros(0, dtype=np.int32)
+
+    def lower_block_pattern(self) -> np.ndarray:
+        return self._pattern
+
+
+class OrderedHessianBlocks:
+    """A block layout of the SAME matrix under another order of its variables (thx_hblock_order): ``perm[k]`` = the variable of
+    ``hb`` at position k.  ``layout`` is a HessianBlocks of P H P^T in its own right -- every table of it (pieces, l_mask, row
+    groups, sorted columns and rows, row_first) is built from the permuted positions by the code that builds the natural one.
+
+    block_map (layout.nblocks) int32: (block of ``hb`` << 1) | transposed -- block k of the layout is that block of the
+                                      linearization's list, transposed when its two variables swap sides of the diagonal
+    to_perm   (n) int32: column of the linearization at every column of the permuted order (g -> P g by thx_vec_gather)
+    from_perm (n) int32: the inverse (x of the permuted order -> delta)"""
+
+    def __init__(self, hb: HessianBlocks, perm: np.ndarray):
+        d, P = hb.bd, hb.nvars
+        perm = np.asarray(perm, dtype=np.int64)
+        if perm.shape != (P,) or not np.array_equal(np.sort(perm), np.arange(P)):
+            raise ValueError("OrderedHessianBlocks: perm is not a permutation of the layout's variables")
+        pos = np.empty(P, dtype=np.int64)
+        pos[perm] = np.arange(P)
+        a, b = pos[hb.blocks[:, 0]], pos[hb.blocks[:, 1]]
+        swapped = a < b
+        pat = np.stack([np.maximum(a, b), np.minimum(a, b)], axis=1)
+        self.base, self.perm, self.pos = hb, perm.astype(np.int32), pos.astype(np.int32)
+        self.layout = HessianBlocks(_OrderedPattern(d, P, pat[np.lexsort((pat[:, 1], pat[:, 0]))]))
+        ident = {(int(p), int(q)): k for k, (p, q) in enumerate(self.layout.blocks.tolist())}
+        self.block_map = np.zeros(hb.nblocks, dtype=np.int32)
+        for k, ((p, q), t) in enumerate(zip(pat.tolist(), swapped.tolist())):
+            self.block_map[ident[(p, q)]] = (k << 1) | int(t)
+        self.nswapped = int(swapped.sum())
+        self.to_perm = (d * perm[:, None] + np.arange(d)[None, :]).reshape(-1).astype(np.int32)
+        self.from_perm = (d * pos[:, None] + np.arange(d)[None, :]).reshape(-1).astype(np.int32)
+        self._dev = {}
+
+    def on(self, device):
+        """(DeviceHessianBlocks of the layout, {block_map, to_perm, from_perm} on the device)."""
+        key = str(device)
+        if key not in self._dev:
+            maps = {f: torch.from_numpy(getattr(self, f)).to(device) for f in ("block_map", "to_perm", "from_perm")}
+            self._dev[key] = (self.layout.on(device), maps)
+        return self._dev[key]
+
+
+def ordered_hessian_blocks(hb: HessianBlocks) -> Optional[OrderedHessianBlocks]:
+    """The layout of ``hb``'s matrix under thx_hblock_order's order, None when that is the insertion order (built once per layout)."""
+    cached = getattr(hb, "_ordered", None)
+    if cached is None:
+        perm, score, natural = _lib.hblock_order(hb.blocks, hb.nvars, hb.bd)
+        cached = hb._ordered = OrderedHessianBlocks(hb, perm) if score < natural else False
+    return cached or None

@@ -460,6 +460,22 @@ class HipKernels:
         _lib.check(self.lib.thx_hblocks_diag(hb.c, _lib.ptr(Hc), Hc.stride(0), Hc.shape[0], _lib.ptr(d), d.stride(0),
                                              _lib.dtype_code(Hc.dtype), _lib.stream_ptr(Hc.device)), "thx_hblocks_diag")
 
+    def hblocks_permute(self, src, dst, block_map, bd):
+        """thx_hblocks_permute: dst[b, k] = block (block_map[k] >> 1) of src[b], transposed when block_map[k] & 1."""
+        if src.dim() != 2 or dst.dim() != 2 or src.shape[0] != dst.shape[0] or src.dtype != dst.dtype or block_map.dtype != torch.int32:
+            raise ValueError(f"hblocks_permute: src {tuple(src.shape)} {src.dtype} / dst {tuple(dst.shape)} {dst.dtype} / map "
+                             f"{block_map.dtype} do not fit")
+        _lib.check(self.lib.thx_hblocks_permute(_lib.ptr(src), src.stride(0), _lib.ptr(dst), dst.stride(0), _lib.ptr(block_map),
+                                                block_map.numel(), bd, src.shape[0], _lib.dtype_code(src.dtype),
+                                                _lib.stream_ptr(src.device)), "thx_hblocks_permute")
+
+    def frame_permute(self, H, Hp, idx, n):
+        """thx_frame_permute: the lower triangle of P H P^T (``Hp``) from the lower triangle of the dense frame ``H``."""
+        if H.dim() != 3 or Hp.dim() != 3 or H.shape[0] != Hp.shape[0] or H.dtype != Hp.dtype or idx.dtype != torch.int32 or idx.numel() < n:
+            raise ValueError(f"frame_permute: H {tuple(H.shape)} {H.dtype} / Hp {tuple(Hp.shape)} {Hp.dtype} / idx {idx.dtype} do not fit")
+        _lib.check(self.lib.thx_frame_permute(_lib.ptr(H), H.shape[-1], _lib.ptr(Hp), Hp.shape[-1], _lib.ptr(idx), n, H.shape[0],
+                                              _lib.dtype_code(H.dtype), _lib.stream_ptr(H.device)), "thx_frame_permute")
+
     def chol_factor_hblocks(self, hb, Hc, n, damping, ellipsoidal, damping_eps, L, panels, info, pattern=None, rhs=None, y=None):
         """thx_chol_factor_forward / thx_chol_factor_sparse (``pattern``) with H read from the block list.  ``L`` (B, ld, ld): the
         dense frame; (B, nslots, 128, 128): the TILE-PACKED factor of ``pattern`` (ld = 0 in the C ABI)."""

@@ -34,25 +34,94 @@ class LinearSolver(abc.ABC):
         pass
 
 
+class _FactorSnapshot(tuple):
+    """(L, panels) of ``factor_snapshot`` with the order the factor was made in (``ordered``: HipCholeskyCore._factor_ord)."""
+    ordered = None
+
+
 class HipCholeskyCore:
     """Back-end half of the solver (buffers, factor, solves), shared by theseus_amd's mirror class below and
     the adapter for the real ``theseus`` (theseus_amd/plugin.py)."""
 
+    # "auto": a block-compact linearization is factorised in the order of thx_hblock_order -- the columns of H, L, g and x inside
+    # the solver follow the permutation, everything a caller hands in or gets back stays in the linearization's order;
+    # "natural": the linearization's own order
+    ordering = "auto"
+
     def _core_init(self):
         self.K = self.linearization.K
-        self.L = self.panels = self.info = self._y = None
+        self._L = self._panels = self.info = self._y = None
         self._lam = None
         self.factor_version = 0  # bumped by every factorisation (the implicit backward checks its factor is current)
+        self._factor_ord = None  # (layout, maps) of compiler.OrderedHessianBlocks the CURRENT factor was made in, None: natural order
+        self._Hp = self._gp = self._xp = None
+        self._natural_frame = None
+        self._force_natural = False
+
+    # ---- the factor frame as callers see it ---------------------------------------------------------------------------------------
+    @property
+    def L(self):
+        """The factor frame in the LINEARIZATION's order (tests / inspection; the solver itself works on ``_L``).  After a
+        factorisation in the solver's own order that is a second factorisation of the same system -- the linearization as it
+        stands, the damping of the last ``factorize`` -- in the natural order, made on first use and kept until the next one."""
+        return self._L if self._factor_ord is None else self._natural_factor()[0]
+
+    @L.setter
+    def L(self, value):
+        self._L = value
+
+    @property
+    def panels(self):
+        return self._panels if self._factor_ord is None else self._natural_factor()[1]
+
+    @panels.setter
+    def panels(self, value):
+        self._panels = value
+
+    def _natural_factor(self):
+        if self._natural_frame is None or self._natural_frame[0] != self.factor_version:
+            lin = self.linearization
+            L, panels = torch.zeros_like(self._L), torch.empty_like(self._panels)
+            has_lam, ellipsoidal, eps = self._factored_with
+            if getattr(lin, "_compact", False):
+                self.K.chol_factor_hblocks(lin.hblocks, lin.Hc, lin.n, self._lam if has_lam else None, ellipsoidal, eps, L, panels,
+                                           torch.zeros_like(self.info))
+            else:
+                self.K.chol_factor(lin.H, lin.n, self._lam if has_lam else None, ellipsoidal, eps, L, panels, torch.zeros_like(self.info))
+            self._natural_frame = (self.factor_version, L, panels)
+        return self._natural_frame[1:]
+
+    def _ordered(self):
+        """(DeviceHessianBlocks, device maps) of the layout the next factorisation runs in, None: the linearization's order."""
+        lin = self.linearization
+        if self.ordering == "natural" or self._force_natural:
+            return None
+        if self.ordering != "auto":
+            raise ValueError(f"ordering must be 'auto' or 'natural', got {self.ordering!r}")
+        # a block-compact linearization -- or one that could be and was asked to keep the dense frame (block_hessian=False): the
+        # same order, so that both storages compute the same bits
+        packed = getattr(lin, "packed", None)
+        if getattr(lin, "_compact", False) and lin.hblocks is not None:
+            host, dev = lin.hblocks.host, lin.Hc.device
+        elif (not getattr(lin, "_compact", False) and getattr(packed, "supports_block_hessian", lambda: False)()
+              and getattr(lin, "full_matrix", None) is None and lin.H is not None):
+            host, dev = packed.structure.hessian_blocks(), lin.H.device
+        else:
+            return None
+        from .compiler import ordered_hessian_blocks
+        oh = ordered_hessian_blocks(host)
+        return None if oh is None else oh.on(dev)
 
     def _ensure_buffers(self):
         lin = self.linearization
         g = lin.g     # (B, n): shape / dtype / device of the system (lin.H may be block-compact: never touched here)
         shape = (g.shape[0], lin.ld, lin.ld)
-        if self.L is None or tuple(self.L.shape) != shape or self.L.device != g.device or self.L.dtype != g.dtype:
+        if self._L is None or tuple(self._L.shape) != shape or self._L.device != g.device or self._L.dtype != g.dtype:
             B = g.shape[0]
             nt = (lin.n + _lib.THX_TILE - 1) // _lib.THX_TILE
-            self.L = torch.zeros(shape, dtype=g.dtype, device=g.device)
-            self.panels = torch.empty(B, nt, _lib.THX_TILE, _lib.THX_TILE, dtype=g.dtype, device=g.device)
+            self._L = torch.zeros(shape, dtype=g.dtype, device=g.device)
+            self._panels = torch.empty(B, nt, _lib.THX_TILE, _lib.THX_TILE, dtype=g.dtype, device=g.device)
+            self._Hp = self._gp = self._xp = self._natural_frame = None
             self._y = torch.empty(B, lin.n, dtype=g.dtype, device=g.device)
             self.info = torch.zeros(B, dtype=torch.int32, device=g.device)
             self._lam = torch.empty(B, dtype=g.dtype, device=g.device)
@@ -65,14 +134,38 @@ class HipCholeskyCore:
     def _factor_call(self, lam, ellipsoidal_damping, damping_eps, rhs, y, pattern=None):
         """One factorisation launch sequence: H from the block list when the linearization keeps it compact."""
         lin = self.linearization
-        if getattr(lin, "_compact", False):
-            self.K.chol_factor_hblocks(lin.hblocks, lin.Hc, lin.n, lam, ellipsoidal_damping, damping_eps, self.L, self.panels,
+        self._factor_ord = self._natural_frame = None
+        ordered = self._ordered() if pattern is None else None
+        if ordered is not None:
+            # the solver's own order: the block list moves into the permuted layout's block order (a block whose variables swap
+            # sides of the diagonal transposed), g is gathered; ``y`` comes out in the permuted order and stays there -- the
+            # backward substitution recognises it (_substitute)
+            layout, maps = ordered
+            compact = getattr(lin, "_compact", False)
+            shape = (lin.Hc.shape[0], layout.host.bstride) if compact else tuple(lin.H.shape)
+            if self._Hp is None or tuple(self._Hp.shape) != shape:
+                self._Hp = torch.zeros(shape, dtype=self._L.dtype, device=self._L.device)
+                self._gp, self._xp = torch.empty_like(self._y), torch.empty_like(self._y)
+            if rhs is not None:
+                self.K.vec_gather(rhs.contiguous(), self._gp, maps["to_perm"])
+            rhs_p = self._gp if rhs is not None else None
+            if compact:
+                self.K.hblocks_permute(lin.Hc, self._Hp, maps["block_map"], layout.host.bd)
+                self.K.chol_factor_hblocks(layout, self._Hp, lin.n, lam, ellipsoidal_damping, damping_eps, self._L, self._panels,
+                                           self.info, rhs=rhs_p, y=y)
+            else:   # (the dense frame of a matrix that has a block layout: block_hessian=False)
+                self.K.frame_permute(lin.H, self._Hp, maps["to_perm"], lin.n)
+                self.K.chol_factor(self._Hp, lin.n, lam, ellipsoidal_damping, damping_eps, self._L, self._panels, self.info,
+                                   rhs=rhs_p, y=y)
+            self._factor_ord = ordered
+        elif getattr(lin, "_compact", False):
+            self.K.chol_factor_hblocks(lin.hblocks, lin.Hc, lin.n, lam, ellipsoidal_damping, damping_eps, self._L, self._panels,
                                        self.info, pattern=pattern, rhs=rhs, y=y)
         elif pattern is not None:
-            self.K.chol_factor_sparse(lin.H, lin.n, lam, ellipsoidal_damping, damping_eps, self.L, self.panels, self.info,
+            self.K.chol_factor_sparse(lin.H, lin.n, lam, ellipsoidal_damping, damping_eps, self._L, self._panels, self.info,
                                       pattern, rhs=rhs, y=y)
         else:
-            self.K.chol_factor(lin.H, lin.n, lam, ellipsoidal_damping, damping_eps, self.L, self.panels, self.info, rhs=rhs, y=y)
+            self.K.chol_factor(lin.H, lin.n, lam, ellipsoidal_damping, damping_eps, self._L, self._panels, self.info, rhs=rhs, y=y)
 
     def factorize(self, damping: Optional[Union[float, torch.Tensor]] = None, ellipsoidal_damping: bool = True,
                   damping_eps: float = 1e-8, rhs: Optional[torch.Tensor] = None):
@@ -105,33 +198,51 @@ class HipCholeskyCore:
     def factor_snapshot(self):
         """A private copy of the CURRENT factor, for a solve after the solver has factorised again (the differentiated iterations
         of BackwardMode.UNROLL / TRUNCATED: every iteration's backward solves with that iteration's factor)."""
-        return self.L.clone(), self.panels.clone()
+        snap = _FactorSnapshot((self._L.clone(), self._panels.clone()))
+        snap.ordered = self._factor_ord
+        return snap
 
     def solve_with_snapshot(self, snapshot, rhs: torch.Tensor) -> torch.Tensor:
-        """(L L^T)^-1 rhs with a factor kept by ``factor_snapshot`` (dense frame: thx_chol_solve)."""
+        """(L L^T)^-1 rhs with a factor kept by ``factor_snapshot`` (dense frame: thx_chol_solve), in the order it was made in."""
         L, panels = snapshot
         rhs = rhs.contiguous()
         x = torch.empty_like(rhs)
-        self.K.chol_solve(L, self.linearization.n, panels, rhs, x, **self._envelope())
+        self._solve_frame(L, panels, getattr(snapshot, "ordered", None), rhs, x, backward_only=False)
         return x
 
     solve_envelope = True   # False: the dense-frame solves read every tile of L in full (the same bits; tests compare the two)
 
-    def _envelope(self) -> Dict[str, torch.Tensor]:
+    def _envelope(self, ordered=None) -> Dict[str, torch.Tensor]:
         """``row_first=`` of the dense-frame solves when the factor is a block layout's: every schedule of thx_chol_factor_hblocks
-        leaves exact zeros left of the first non-zero column of each row of H, and the solves read the row envelope only."""
+        leaves exact zeros left of the first non-zero column of each row of H, and the solves read the row envelope only
+        (``ordered``: the factor was made in that layout -- its table)."""
         lin = self.linearization
         if self.solve_envelope and getattr(lin, "_compact", False) and lin.hblocks is not None:
-            return {"row_first": lin.hblocks.t["row_first"]}
+            return {"row_first": (lin.hblocks if ordered is None else ordered[0]).t["row_first"]}
         return {}
+
+    def _solve_frame(self, L, panels, ordered, rhs, x, backward_only: bool):
+        """The dense-frame solves on (L, panels) made in ``ordered`` (None: the linearization's order).  A factor of the solver's
+        own order takes rhs gathered into it (thx_vec_gather) -- unless rhs is the y its factorisation left, which is there
+        already -- and x is gathered back."""
+        n = self.linearization.n
+        solve = self.K.chol_solve_backward if backward_only else self.K.chol_solve
+        if ordered is None:
+            solve(L, n, panels, rhs, x, **self._envelope())
+            return
+        maps = ordered[1]
+        if rhs is self._y:
+            src = rhs
+        else:
+            self.K.vec_gather(rhs, self._gp, maps["to_perm"])
+            src = self._gp
+        solve(L, n, panels, src, self._xp, **self._envelope(ordered))
+        self.K.vec_gather(self._xp, x, maps["from_perm"])
 
     def _substitute(self, rhs, x, backward_only: bool):
         """x = L^-T rhs (``backward_only``) or (L L^T)^-1 rhs with the current factor (dense frame: the row envelope of L when the
         linearization is block-compact, else every tile)."""
-        if backward_only:
-            self.K.chol_solve_backward(self.L, self.linearization.n, self.panels, rhs, x, **self._envelope())
-        else:
-            self.K.chol_solve(self.L, self.linearization.n, self.panels, rhs, x, **self._envelope())
+        self._solve_frame(self._L, self._panels, self._factor_ord, rhs, x, backward_only)
 
     # ---- blocks of right-hand sides on the cached factor (thx_chol_solve_multi): posterior samples, marginal covariances ----------
     def _factor_owner(self) -> "HipCholeskyCore":
@@ -148,13 +259,21 @@ class HipCholeskyCore:
         """``rhs`` (B, k, n), one vector per row, against the CURRENT factor: which = 0: (L L^T)^-1 rhs, 1: L^-T rhs, 2: L^-1 rhs
         (the codes of thx_chol_solve_levels).  Every group of 32 vectors reads L once per substitution.  Returns a new tensor."""
         own = self._factor_owner()
-        if own is None or own.L is None or own.factor_version == 0:
+        if own is None or own._L is None or own.factor_version == 0:
             raise RuntimeError("solve_multi_with_factor: nothing has been factorised yet (solve() or factorize() first).")
         n = own.linearization.n
-        if rhs.dim() != 3 or rhs.shape[0] != own.L.shape[0] or rhs.shape[2] != n or rhs.shape[1] < 1:
-            raise ValueError(f"solve_multi_with_factor: rhs must be (B = {own.L.shape[0]}, k >= 1, n = {n}), got {tuple(rhs.shape)}")
-        x = rhs.detach().to(own.L.dtype).clone(memory_format=torch.contiguous_format)
-        own.K.chol_solve_multi(own.L, n, own.panels, x, x, which=which)
+        if rhs.dim() != 3 or rhs.shape[0] != own._L.shape[0] or rhs.shape[2] != n or rhs.shape[1] < 1:
+            raise ValueError(f"solve_multi_with_factor: rhs must be (B = {own._L.shape[0]}, k >= 1, n = {n}), got {tuple(rhs.shape)}")
+        x = rhs.detach().to(own._L.dtype)
+        maps = own._factor_ord[1] if own._factor_ord is not None else None
+        # (a factor of the solver's own order, P H P^T = L L^T: which = 0 is H^-1 whatever the order; L^-1 takes its vectors in the
+        #  linearization's order and L^-T returns them in it -- L^-T (L^-1 rhs) is H^-1 rhs)
+        if maps is not None and which != 1:
+            x = x.index_select(2, maps["to_perm"].long())
+        x = x.clone(memory_format=torch.contiguous_format)
+        own.K.chol_solve_multi(own._L, n, own._panels, x, x, which=which)
+        if maps is not None and which != 2:
+            x = x.index_select(2, maps["from_perm"].long())
         return x
 
     @torch.no_grad()
@@ -169,7 +288,13 @@ class HipCholeskyCore:
             raise ValueError(f"sample_deltas: temperature must be positive, got {temperature}")
         if int(n_samples) < 1:
             raise ValueError(f"sample_deltas: n_samples must be at least 1, got {n_samples}")
-        delta = self.solve()
+        # (the draw that a given ``noise`` stands for is defined through the factor of AtA in the linearization's order,
+        #  theseus_layer.py:113-123: this solve factorises in that order)
+        self._force_natural = True
+        try:
+            delta = self.solve()
+        finally:
+            self._force_natural = False
         own = self._factor_owner()
         B, n = delta.shape
         if noise is None:
@@ -181,7 +306,7 @@ class HipCholeskyCore:
         else:
             raise ValueError(f"sample_deltas: noise must be ({n}, {n_samples}) or ({B}, {n}, {n_samples}), got {tuple(noise.shape)}")
         y = y.to(device=delta.device, dtype=delta.dtype).clone(memory_format=torch.contiguous_format)
-        own.K.chol_solve_multi(own.L, n, own.panels, y, y, which=1)
+        own.K.chol_solve_multi(own._L, n, own._panels, y, y, which=1)
         y.mul_(math.sqrt(float(temperature))).add_(delta.unsqueeze(1))
         return y.transpose(1, 2)
 
@@ -204,11 +329,13 @@ class HipCholeskyCore:
         if not cols:
             raise ValueError("marginal_covariance: no variables named")
         own = self._factorize_undamped()
-        B, n, d = own.L.shape[0], own.linearization.n, len(cols)
-        idx = torch.tensor(cols, dtype=torch.long, device=own.L.device)
-        E = torch.zeros(B, d, n, dtype=own.L.dtype, device=own.L.device)
+        B, n, d = own._L.shape[0], own.linearization.n, len(cols)
+        idx = torch.tensor(cols, dtype=torch.long, device=own._L.device)
+        if own._factor_ord is not None:   # (the factor's own order: the same columns, where it keeps them)
+            idx = own._factor_ord[1]["from_perm"].long()[idx]
+        E = torch.zeros(B, d, n, dtype=own._L.dtype, device=own._L.device)
         E[:, torch.arange(d, device=idx.device), idx] = 1
-        own.K.chol_solve_multi(own.L, n, own.panels, E, E, which=0)
+        own.K.chol_solve_multi(own._L, n, own._panels, E, E, which=0)
         C = E[:, :, idx]
         return (C + C.transpose(1, 2)) / 2
 
@@ -289,7 +416,13 @@ class HipCholeskyCore:
 
 class HipCholeskySolver(HipCholeskyCore, LinearSolver):
     def __init__(self, objective: Objective, linearization_cls: Optional[Type[Linearization]] = None,
-                 linearization_kwargs: Optional[Dict[str, Any]] = None, check_singular: bool = False, **kwargs):
+                 linearization_kwargs: Optional[Dict[str, Any]] = None, check_singular: bool = False, ordering: str = "auto",
+                 **kwargs):
+        """``ordering``: "auto" (default) -- a block-compact linearization is factorised in the envelope-reducing order of
+        thx_hblock_order, inside the solver only; "natural" -- in the linearization's order."""
+        if ordering not in ("auto", "natural"):
+            raise ValueError(f"ordering must be 'auto' or 'natural', got {ordering!r}")
+        self.ordering = ordering
         linearization_cls = linearization_cls or HipLinearization
         if not (isinstance(linearization_cls, type) and issubclass(linearization_cls, HipLinearization)):
             raise RuntimeError("HipCholeskySolver only works with theseus_amd.HipLinearization, "
@@ -392,7 +525,10 @@ class HipLUCore(DenseCholeskyOnly, HipCholeskyCore):
 
 class HipLUSolver(HipLUCore, LinearSolver):
     def __init__(self, objective: Objective, linearization_cls: Optional[Type[Linearization]] = None,
-                 linearization_kwargs: Optional[Dict[str, Any]] = None, check_singular: bool = False, **kwargs):
+                 linearization_kwargs: Optional[Dict[str, Any]] = None, check_singular: bool = False, ordering: str = "auto",
+                 **kwargs):
+        """``ordering``: accepted for the constructor it shares with HipCholeskySolver; the pivoted LU chooses its own pivots and
+        factorises in the linearization's order."""
         linearization_cls = linearization_cls or HipLinearization
         if not (isinstance(linearization_cls, type) and issubclass(linearization_cls, HipLinearization)):
             raise RuntimeError("HipLUSolver only works with theseus_amd.HipLinearization, "

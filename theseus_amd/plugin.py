@@ -616,7 +616,10 @@ class HipCholeskySolver(HipCholeskyCore, _RefCholeskyDenseSolver):
 
     def __init__(self, objective: th.Objective, linearization_cls: Optional[Type[_RefLinearization]] = None,
                  linearization_kwargs: Optional[Dict[str, Any]] = None, check_singular: bool = False,
-                 lagged_failure_check: bool = False, **kwargs):
+                 lagged_failure_check: bool = False, ordering: str = "auto", **kwargs):
+        if ordering not in ("auto", "natural"):   # (theseus_amd/linear_solver.py: HipCholeskyCore.ordering)
+            raise ValueError(f"ordering must be 'auto' or 'natural', got {ordering!r}")
+        self.ordering = ordering
         linearization_cls = linearization_cls or HipLinearization
         if not (isinstance(linearization_cls, type) and issubclass(linearization_cls, HipLinearization)):
             raise RuntimeError("HipCholeskySolver only works with theseus_amd.plugin.HipLinearization, "

@@ -1,13 +1,16 @@
 """Model of the regrouped fp32 column pairs (thx_hblock_layout.rg_*) from the REAL host tables: per pair the share of
 the pair K-loop's 32x32 block products that the regrouped schedule leaves out, next to what the sub-block masks alone skip, and
 the factor's K-loops in 128^3 tile products.  No GPU.
-usage: python tools/model_row_groups.py [--poses 256] [--edges 1024] [--topology-seed 0]"""
+``--order``: the insertion order of the poses ("natural"), the dense solver's own order (thx_hblock_order, "auto"), or both with
+the shares side by side at the end.
+usage: python tools/model_row_groups.py [--poses 256] [--edges 1024] [--topology-seed 0] [--order natural|auto|both]"""
 import argparse
 import os
 import sys
 
 import numpy as np
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 
@@ -26,15 +29,56 @@ def zero_solves(rg, m):
     return tot
 
 
+def shares(hb):
+    """The figures the orders are compared by, as shares of dense: envelope non-zeros and sum (row length)^2 of tril(L); executed pair
+    K-loop products regrouped and with sorted columns; SYRK products executed / busiest wave; head-tile products; solve bytes (fp32)."""
+    from model_solve_bytes import solve_bytes
+    first = hb.row_first.astype(np.int64)
+    n = first.size
+    r = np.arange(n)
+    out = {"envelope nnz": (r - first + 1).sum() / (n * (n + 1) / 2), "sum (row length)^2": ((r - first) ** 2).sum() / (r ** 2).sum()}
+    rg, pc, tr = hb.row_groups(), hb.pair_columns(), hb.tile_rows()
+    if rg is not None and rg.ngroups > 0:
+        out["pair K-loop, regrouped"] = 1 - rg.skipped_fraction(hb.l_mask())[1]
+        if pc is not None:
+            out["pair K-loop, sorted columns"] = pc.executed_fraction(rg)[1][1]
+    if tr is not None:
+        out["SYRK executed"], out["SYRK busiest wave"] = tr.model()[1]
+        out["head tiles"] = tr.head_model()[1]
+    before, after = solve_bytes(first, 4, 64)
+    out["solve bytes"] = after / before
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--poses", type=int, default=256)
     ap.add_argument("--edges", type=int, default=1024)
     ap.add_argument("--topology-seed", type=int, default=0)
+    ap.add_argument("--order", default="natural", choices=["natural", "auto", "both"])
     a = ap.parse_args()
-    from theseus_amd.compiler import PoseGraphStructure
+    from theseus_amd.compiler import PoseGraphStructure, ordered_hessian_blocks
     from theseus_amd.utils.synthetic import pose_graph_topology
-    hb = PoseGraphStructure.build(a.poses, pose_graph_topology(a.poses, a.edges, a.topology_seed), [0], dof=6).hessian_blocks()
+    natural = PoseGraphStructure.build(a.poses, pose_graph_topology(a.poses, a.edges, a.topology_seed), [0], dof=6).hessian_blocks()
+    layouts = {"natural": natural}
+    if a.order != "natural":
+        oh = ordered_hessian_blocks(natural)
+        layouts["auto"] = oh.layout if oh is not None else natural
+        print("thx_hblock_order: " + ("the insertion order stands" if oh is None else
+                                      f"{oh.nswapped} of {natural.nblocks} blocks land transposed"))
+    for name in (["natural", "auto"] if a.order == "both" else [a.order]):
+        if a.order != "natural":
+            print(f"==== order: {name} " + "=" * 100)
+        detail(layouts[name])
+    if a.order == "both":
+        sn, sa = shares(layouts["natural"]), shares(layouts["auto"])
+        print("==== shares of dense, natural -> auto " + "=" * 80)
+        for k in sn:
+            print(f"{k:32s} {sn[k]:.3f} -> {sa[k]:.3f}" if k in sa else f"{k:32s} {sn[k]:.3f} -> (no table)")
+
+
+def detail(hb):
+    a_poses = hb.nvars
     rg, m, nt = hb.row_groups(), hb.l_mask(), hb.ntiles
     if rg is None:
         print("no pair of this layout would start a K-loop late: no row groups")
@@ -45,7 +89,7 @@ def main():
         return
     pop = lambda x: bin(int(x) & 15).count("1")   # noqa: E731
     per, total = rg.skipped_fraction(m)
-    print(f"n = {6 * a.poses}, {nt} block columns, {rg.ngroups} groups, at most {rg.max_tile_pieces} pieces per (group, block column), "
+    print(f"n = {6 * a_poses}, {nt} block columns, {rg.ngroups} groups, at most {rg.max_tile_pieces} pieces per (group, block column), "
           f"{int(np.diff(rg.tile_ptr).reshape(-1, 2).sum(1).max())} per group")
     print(f"{'pair':>5s} {'first chunks of the groups':40s} {'left out, regrouped':>20s} {'masks alone':>12s} {'column side':>12s}")
     all_p = today = cols_only = 0
