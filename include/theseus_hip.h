@@ -450,6 +450,51 @@ int thx_push2_eval(const thx_push2_term* terms, int32_t n_terms, const void* x, 
 int thx_push2_error(const thx_push2_term* terms, int32_t n_terms, const void* x, int32_t V, void* err, int32_t B, int dtype,
                     const thx_se2_eps* eps, void* stream);
 
+/* ---- SE2 motion planning (examples/se2_planning.py: MotionPlanner with pose_type=SE2): the planner's cost family in one launch.
+ *      The state x is (V, B, 4), one 4-element record per optimisation variable and problem: an SE2 pose [x, y, cos, sin] or a
+ *      velocity [v0, v1, v2, pad] (pad is written 0 and never read).  terms[t] (DEVICE array built by the host, sorted by kind) is
+ *      one cost function; var[s] = index of its s-th optimisation variable in the state (its tangent columns: 3 var[s] ...):
+ *        THX_TRAJSE2_COLLISION     Collision2D at xy(pose) (theseus/embodied/collision/collision.py:44-73), dim 1; variable pose;
+ *                                  aux = sdf_data (rows x cols, row major), sdf_origin (2), sdf_cell_size (1), cost_eps (1), weight (1)
+ *        THX_TRAJSE2_GP            GPMotionModel (theseus/embodied/motionmodel/double_integrator.py:48-80) weighted by GPCostWeight
+ *                                  (:131-152), formed here as chol(M)^T (x) chol(Qc_inv)^T, dim 6; variables pose1, vel1, pose2,
+ *                                  vel2;  aux = the cost's dt (1), the weight's dt (1), Qc_inv (3 x 3, its upper triangle is read)
+ *        THX_TRAJSE2_NONHOLONOMIC  Nonholonomic on SE2 (theseus/embodied/motionmodel/misc.py:97-186), dim 1; variables pose, vel;
+ *                                  aux = weight (1)
+ *        THX_TRAJSE2_HINGE         HingeCost on a 3-vector (misc.py:14-94), dim 3; variable vector;
+ *                                  aux = down_limit (3), up_limit (3), threshold (3), weight (wdim); the limits may be +-inf
+ *        THX_TRAJSE2_PRIOR_SE2     Difference on SE2 (theseus/embodied/misc/local_cost_fn.py:16-75), dim 3; aux = target (4), weight (wdim)
+ *        THX_TRAJSE2_PRIOR_VEC     Difference on a 3-vector, dim 3;  aux = target (3), weight (wdim)
+ *        THX_TRAJSE2_PRIOR_XY      xy(pose) - target (the planner's goal cost), dim 2;  aux = target (2), weight (wdim)
+ *      wdim = 1: ScaleCostWeight, the cost's dim: DiagonalCostWeight.  aux[k] are device pointers of the run's dtype, aux_bstride[k]
+ *      their element batch strides (0 = shared by all problems).  Blocks, errors, j_total, lde and the guards are thx_push2_eval's
+ *      (every block is dim x 3); thx_trajse2_error is thx_push2_error's twin.  Both compute in the run's dtype with contraction
+ *      off; x must be aligned to one record (4 elements).
+ *      thx_trajse2_retract: out[k] = x[k] exp(step * delta[b, 3k .. 3k+2]) where var_kind[k] == 0 (SE2, as thx_se2_retract),
+ *      [x + step * delta, 0] where var_kind[k] == 1; problems with ignore_mask[b] != 0 (ignore_mask may be null) copy x. */
+#define THX_TRAJSE2_COLLISION 0
+#define THX_TRAJSE2_GP 1
+#define THX_TRAJSE2_NONHOLONOMIC 2
+#define THX_TRAJSE2_HINGE 3
+#define THX_TRAJSE2_PRIOR_SE2 4
+#define THX_TRAJSE2_PRIOR_VEC 5
+#define THX_TRAJSE2_PRIOR_XY 6
+typedef struct {
+  int32_t kind, row0;
+  int32_t var[4]; /* index of each optimisation variable of the cost in the state (unused: -1) */
+  int32_t rows, cols; /* collision: the grid's size */
+  int64_t j_off;
+  const void* aux[5];
+  int64_t aux_bstride[5];
+  int32_t wdim, pad_;
+} thx_trajse2_term;
+int thx_trajse2_eval(const thx_trajse2_term* terms, int32_t n_terms, const void* x, int32_t V, void* J, int64_t j_total, void* e,
+                     int64_t lde, int32_t m, int32_t B, int dtype, const thx_se2_eps* eps, void* stream);
+int thx_trajse2_error(const thx_trajse2_term* terms, int32_t n_terms, const void* x, int32_t V, void* err, int32_t B, int dtype,
+                      const thx_se2_eps* eps, void* stream);
+int thx_trajse2_retract(const void* x, const uint8_t* var_kind, const void* delta, int64_t ldd, double step,
+                        const uint8_t* ignore_mask, void* out, int32_t V, int32_t B, int dtype, const thx_se2_eps* eps, void* stream);
+
 /* ---- Homography image alignment, dense Lucas-Kanade (examples/homography_estimation.py): the cost family of the example's
  *      objective.  terms[t] (DEVICE array built by the host, sorted by kind: the n_align alignment terms come first) is one cost
  *      function on the (B, n) Euclidean state x; col[0] = first state column of its 8-dof variable h, H = [h0 .. h7, 1] row major:

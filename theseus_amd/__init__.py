@@ -20,6 +20,7 @@ from .ba import HipSchurLinearization, HipSchurSolver, PackedBA  # noqa: F401
 from . import embodied as eb  # noqa: F401
 from .embodied import PackedTrajectory2D  # noqa: F401
 from .pushing import PackedPlanarPushing  # noqa: F401
+from .planning_se2 import PackedTrajectorySE2  # noqa: F401
 from .homography import PackedHomography  # noqa: F401
 
 # names a reference user would reach for on this path

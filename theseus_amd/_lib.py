@@ -21,6 +21,8 @@ THX_LU_MAX_N = 4096  # largest system of thx_lu_factor (include/theseus_hip.h)
 THX_BA_ERR_CHUNKS = 256
 TRAJ2_COLLISION, TRAJ2_GP, TRAJ2_PRIOR = 0, 1, 2  # THX_TRAJ2_* (kinds of a thx_traj2_term)
 PUSH2_QSP, PUSH2_MFB, PUSH2_CONTACT, PUSH2_PRIOR = 0, 1, 2, 3  # THX_PUSH2_* (kinds of a thx_push2_term)
+# THX_TRAJSE2_* (kinds of a thx_trajse2_term)
+TRAJSE2_COLLISION, TRAJSE2_GP, TRAJSE2_NONHOLONOMIC, TRAJSE2_HINGE, TRAJSE2_PRIOR_SE2, TRAJSE2_PRIOR_VEC, TRAJSE2_PRIOR_XY = range(7)
 HOMOG_ALIGN, HOMOG_PRIOR = 0, 1  # THX_HOMOG_* (kinds of a thx_homog_term)
 THX_HOMOG_CHUNK = 1024  # destination pixels per workgroup of thx_homog_eval / thx_homog_error's first stage
 THX_HOMOG_SUMS = 10  # doubles per (alignment term, problem, chunk) of their scratch
@@ -289,6 +291,11 @@ _SIGNATURES = {
     "thx_push2_eval": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int,
                        POINTER(SE2Eps), c_void_p],
     "thx_push2_error": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int, POINTER(SE2Eps), c_void_p],
+    "thx_trajse2_eval": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int,
+                         POINTER(SE2Eps), c_void_p],
+    "thx_trajse2_error": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int, POINTER(SE2Eps), c_void_p],
+    "thx_trajse2_retract": [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_int32, c_int32, c_int,
+                            POINTER(SE2Eps), c_void_p],
     "thx_homog_eval": [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64,
                        c_int32, c_int32, c_int, c_void_p],
     "thx_homog_error": [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int, c_void_p],

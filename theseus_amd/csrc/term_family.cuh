@@ -1,5 +1,6 @@
-// What the fused cost families (traj_kernels.hip, push_kernels.hip) share: a family evaluates a whole objective from a table of
-// 128-byte terms (thx_traj2_term, thx_push2_term of include/theseus_hip.h: the same layout, the variable field named by the family).
+// What the fused cost families (traj_kernels.hip, push_kernels.hip, trajse2_kernels.hip) share: a family evaluates a whole objective
+// from a table of 128-byte terms (thx_traj2_term, thx_push2_term, thx_trajse2_term of include/theseus_hip.h: the same layout, the
+// variable field named by the family).
 // Here: the per-term aux accessor, the bilinear signed-distance lookup, the fixed-order reduction of a *_error kernel and the host
 // checks of the exports.  The term functions, the two __global__ functions and the exports stay with the family.
 #pragma once

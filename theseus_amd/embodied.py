@@ -7,7 +7,9 @@
 They implement ``error`` / ``jacobians`` / ``weighted_jacobians_error``, so an objective made of them runs through the generic
 path (theseus_amd/euclidean.py: PackedEuclidean) with every backward mode; an objective made ONLY of Collision2D, GPMotionModel
 and 2-dof Difference priors is evaluated by the fused kernels of csrc/traj_kernels.hip (PackedTrajectory2D below), for which these
-classes are the fallback and the differentiable twin.  Further down: the planar-pushing costs on SE2 and HomographyAlignment, the
+classes are the fallback and the differentiable twin.  Collision2D and DoubleIntegrator / GPMotionModel also take SE2 poses (with
+Vector(3) velocities): with Nonholonomic, HingeCost and XYDifference below they make the SE2 motion planner's objective, fused by
+theseus_amd/planning_se2.py.  Further down: the planar-pushing costs on SE2 and HomographyAlignment, the
 dense image-alignment cost of examples/homography_estimation.py, with their own fused families.
 """
 from typing import List, Optional, Union
@@ -112,13 +114,12 @@ class SignedDistanceField2D:
 
 
 class Collision2D(CostFunction):
-    """error = clamp(cost_eps - d(pose), min=0), Jacobian = -dd/dpose where d <= cost_eps (collision.py:44-73)."""
+    """error = clamp(cost_eps - d(pose), min=0), Jacobian = -dd/dpose where d <= cost_eps (collision.py:44-73).  An SE2 pose is
+    looked up at its translation: the 1 x 2 SDF Jacobian times d xy / d pose = [R, 0] (se2_torch.xy)."""
 
     def __init__(self, pose: Point2, sdf_origin, sdf_data, sdf_cell_size, cost_eps, cost_weight: CostWeight,
                  name: Optional[str] = None):
-        if not isinstance(pose, Point2):
-            if "SE2" in _names(pose):
-                raise ValueError("Collision2D on an SE2 pose is out of scope on this back end: use a Point2 pose.")
+        if not isinstance(pose, Point2) and "SE2" not in _names(pose):
             raise ValueError("Collision2D only accepts Point2 or SE2 poses.")
         super().__init__(cost_weight, name)
         self.pose = pose
@@ -128,6 +129,13 @@ class Collision2D(CostFunction):
         self.cost_eps = _as_variable(cost_eps, dtype=pose.dtype)
         if self.cost_eps.tensor.ndim != 2:
             self.cost_eps._tensor = self.cost_eps.tensor.view(-1, 1)
+        if not isinstance(pose, Point2):
+            # the SE2 form is new here and strict from the start: one dtype for the pose, the grid and the weight, as Objective.add
+            # and the fused family's term table ask anyway (a float32 weight on a float64 pose would be promoted silently by torch)
+            for v in self.aux_vars():
+                if v.tensor.is_floating_point() and v.dtype != pose.dtype:
+                    raise ValueError(f"Collision2D on an SE2 pose ({pose.name}, {pose.dtype}): {v.name} has dtype {v.dtype}; the "
+                                     "pose, the signed-distance field, cost_eps and the cost weight must share one dtype.")
 
     def optim_vars(self):
         return [self.pose]
@@ -141,7 +149,12 @@ class Collision2D(CostFunction):
     def _distances(self):
         # (the variables are read at every evaluation: Objective.update may have replaced their tensors)
         sdf = SignedDistanceField2D(self.sdf_origin, self.sdf_cell_size, self.sdf_data)
-        return sdf.signed_distance(self.pose.tensor.view(-1, 2, 1))
+        if isinstance(self.pose, Point2):
+            return sdf.signed_distance(self.pose.tensor.view(-1, 2, 1))
+        from . import se2_torch as S
+        xy, J_xy = S.xy(self.pose.tensor, jac=True)
+        dist, jac = sdf.signed_distance(xy.reshape(-1, 2, 1))
+        return dist, jac @ J_xy
 
     def error(self) -> torch.Tensor:
         return (self.cost_eps.tensor.view(-1, 1) - self._distances()[0]).clamp(min=0)
@@ -200,15 +213,17 @@ class GPCostWeight(CostWeight):
 
 
 class DoubleIntegrator(CostFunction):
-    """error = [pose2 - pose1 - dt vel1 ; vel2 - vel1] on Euclidean variables (double_integrator.py:48-80)."""
+    """error = [pose1.local(pose2) - dt vel1 ; vel2 - vel1] (double_integrator.py:48-80): Euclidean variables, or SE2 poses with
+    Vector(3) velocities -- then ``local`` and its two Jacobians are se2_torch.local's."""
 
     def __init__(self, pose1: Vector, vel1: Vector, pose2: Vector, vel2: Vector, dt, cost_weight: CostWeight,
                  name: Optional[str] = None):
         super().__init__(cost_weight, name)
-        for v in (pose1, vel1, pose2, vel2):
+        self._se2 = "SE2" in _names(pose1) and "SE2" in _names(pose2)
+        for v in (vel1, vel2) if self._se2 else (pose1, vel1, pose2, vel2):
             if not _is_euclidean(v):
-                raise ValueError(f"DoubleIntegrator: the variables must be Euclidean (Vector / Point2 / Point3) on this back end; got "
-                                 f"{type(v).__name__} ({v.name}).")
+                raise ValueError(f"DoubleIntegrator: the variables must be Euclidean (Vector / Point2 / Point3), or the poses SE2 with "
+                                 f"Vector velocities, on this back end; got {type(v).__name__} ({v.name}).")
         dof = pose1.dof()
         if not (vel1.dof() == pose2.dof() == vel2.dof() == dof):
             raise ValueError("All variables for a DoubleIntegrator must have the same dimension.")
@@ -229,17 +244,31 @@ class DoubleIntegrator(CostFunction):
     def dim(self) -> int:
         return 2 * self.pose1.dof()
 
-    def error(self) -> torch.Tensor:
+    def _pose_diff(self, jac: bool):
+        """pose1.local(pose2) [, its Jacobians w.r.t. pose1 and pose2, None for Euclidean poses: -I and I]"""
+        if not self._se2:
+            return self.pose1.local(self.pose2), None
+        from . import se2_torch as S
+        return S.local(self.pose1.tensor, self.pose2.tensor, jac=True) if jac else (S.local(self.pose1.tensor, self.pose2.tensor), None)
+
+    def _error_from(self, diff):
         dt = self.dt.tensor.view(-1, 1)
-        return torch.cat([self.pose1.local(self.pose2) - dt * self.vel1.tensor, self.vel2.tensor - self.vel1.tensor], dim=1)
+        a, b = diff - dt * self.vel1.tensor, self.vel2.tensor - self.vel1.tensor
+        B = max(a.shape[0], b.shape[0])
+        return torch.cat([a.expand(B, -1), b.expand(B, -1)], dim=1)
+
+    def error(self) -> torch.Tensor:
+        return self._error_from(self._pose_diff(False)[0])
 
     def jacobians(self):
-        err = self.error()
+        diff, J_local = self._pose_diff(True)
+        err = self._error_from(diff)
         B, dof = err.shape[0], self.pose1.dof()
         eye = torch.eye(dof, dtype=err.dtype, device=err.device).expand(B, dof, dof)
         zero = torch.zeros_like(eye)
         dt = self.dt.tensor.view(-1, 1, 1)
-        return [torch.cat([-eye, zero], dim=1), torch.cat([-dt * eye, -eye], dim=1), torch.cat([eye, zero], dim=1),
+        J1, J2 = (-eye, eye) if J_local is None else (j.expand(B, dof, dof) for j in J_local)
+        return [torch.cat([J1, zero], dim=1), torch.cat([-dt * eye, -eye], dim=1), torch.cat([J2, zero], dim=1),
                 torch.cat([zero, eye], dim=1)], err
 
     def weighted_error(self) -> torch.Tensor:
@@ -260,6 +289,133 @@ class GPMotionModel(DoubleIntegrator):
             raise ValueError("GPMotionModel only accepts cost weights of type GPCostWeight. For other weight types, consider "
                              "using DoubleIntegrator instead.")
         super().__init__(pose1, vel1, pose2, vel2, dt, cost_weight, name=name)
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# the SE2 motion planner (examples/se2_planning.py: MotionPlanner with pose_type=SE2): torch restatements of
+#   Nonholonomic   theseus/embodied/motionmodel/misc.py:97-186
+#   HingeCost      theseus/embodied/motionmodel/misc.py:14-94
+#   XYDifference   the planner's private _XYDifference (theseus/utils/examples/motion_planning/motion_planner.py:15-54)
+# With Collision2D / GPMotionModel on SE2 poses and Difference priors they make the planner's objective, which is evaluated by the
+# fused kernels of csrc/trajse2_kernels.hip (theseus_amd/planning_se2.py: PackedTrajectorySE2); these classes are the
+# differentiable twin.
+# --------------------------------------------------------------------------------------------------------------------------------
+class Nonholonomic(CostFunction):
+    """The sideways velocity of a car-like robot.  SE2 pose: the velocity is in the body frame, error = vel_y, Jacobians 0 and
+    [0, 1, 0].  Vector pose (x, y, theta): the velocity is in the world frame, error = vel_y cos(theta) - vel_x sin(theta)."""
+
+    def __init__(self, pose, vel: Vector, cost_weight: CostWeight, name: Optional[str] = None):
+        super().__init__(cost_weight, name)
+        if vel.dof() != 3 or pose.dof() != 3:
+            raise ValueError("Nonholonomic only accepts 3D velocity or poses (x, y, theta dims). "
+                             "Poses can either be SE2 or Vector variables. Velocities only Vector.")
+        if not _is_euclidean(vel) or not ("SE2" in _names(pose) or _is_euclidean(pose)):
+            raise ValueError("Nonholonomic: poses can either be SE2 or Vector variables. Velocities only Vector.")
+        self.pose, self.vel = pose, vel
+        self._se2 = "SE2" in _names(pose)
+
+    def optim_vars(self):
+        return [self.pose, self.vel]
+
+    def aux_vars(self):
+        return self.weight.aux_vars()
+
+    def dim(self) -> int:
+        return 1
+
+    def error(self) -> torch.Tensor:
+        vel = self.vel.tensor
+        if self._se2:
+            return vel[:, 1].view(-1, 1)
+        th = self.pose.tensor[:, 2]
+        return (vel[:, 1] * th.cos() - vel[:, 0] * th.sin()).view(-1, 1)
+
+    def jacobians(self):
+        err, vel = self.error(), self.vel.tensor
+        zero, one = torch.zeros_like(err[:, 0]), torch.ones_like(err[:, 0])
+        if self._se2:
+            return [torch.stack([zero, zero, zero], dim=1).unsqueeze(1), torch.stack([zero, one, zero], dim=1).unsqueeze(1)], err
+        th = self.pose.tensor[:, 2]
+        cos, sin = th.cos(), th.sin()
+        J_pose = torch.stack([zero, zero, -(vel[:, 1] * sin + vel[:, 0] * cos) * one], dim=1).unsqueeze(1)
+        return [J_pose, torch.stack([-sin * one, cos * one, zero], dim=1).unsqueeze(1)], err
+
+
+class HingeCost(CostFunction):
+    """error_i = down_i + thr_i - v_i where v_i < down_i + thr_i, v_i - (up_i - thr_i) where v_i > up_i - thr_i (this one wins
+    where both hold), else 0; the Jacobian is diagonal: -1 / +1 / 0.  The limits may be +-inf."""
+
+    def __init__(self, vector: Vector, down_limit, up_limit, threshold, cost_weight: CostWeight, name: Optional[str] = None):
+        super().__init__(cost_weight, name)
+        self.vector = vector
+        dof = vector.dof()
+
+        def convert(value, what):
+            if isinstance(value, float):   # (a number: one value per component, where the vector lives)
+                value = torch.full((1, dof), value, dtype=vector.dtype, device=vector.device)
+            return _as_variable(value, name=f"{self.name}__{what}")
+        self.down_limit, self.up_limit = convert(down_limit, "downlimit"), convert(up_limit, "uplimit")
+        self.threshold = convert(threshold, "thres")
+        for v in (self.down_limit, self.up_limit, self.threshold):
+            if v.ndim != 2 or v.shape[1] != dof:
+                raise ValueError(f"Limit and threshold must be 1D variables with dimension equal to `vector.dof()` ({dof}).")
+        if not bool((self.down_limit.tensor <= self.up_limit.tensor).all()):
+            raise ValueError("All down_limit must be <= than up_limit.")
+        if self.threshold.tensor.max() < 0.0:
+            raise ValueError("Threshold values must be positive numbers.")
+
+    def optim_vars(self):
+        return [self.vector]
+
+    def aux_vars(self):
+        return [self.down_limit, self.up_limit, self.threshold] + self.weight.aux_vars()
+
+    def dim(self) -> int:
+        return self.vector.dof()
+
+    def _evaluate(self):
+        v, thr = self.vector.tensor, self.threshold.tensor
+        down, up = self.down_limit.tensor + thr, self.up_limit.tensor - thr
+        below, above = v < down, v > up
+        err = torch.where(below, down - v, torch.zeros_like(v))
+        return torch.where(above, v - up, err), below, above
+
+    def error(self) -> torch.Tensor:
+        return self._evaluate()[0]
+
+    def jacobians(self):
+        err, below, above = self._evaluate()
+        zero, one = torch.zeros_like(err), torch.ones_like(err)
+        return [torch.diag_embed(torch.where(above, one, torch.where(below, -one, zero)))], err
+
+
+class XYDifference(CostFunction):
+    """error = xy(var) - target for an SE2 ``var`` and a Point2 ``target``; Jacobian = d xy / d var = [R, 0]."""
+
+    def __init__(self, var, target: Point2, cost_weight: CostWeight, name: Optional[str] = None):
+        super().__init__(cost_weight, name)
+        if "SE2" not in _names(var) or not isinstance(target, Point2):
+            raise ValueError("XYDifference expects var of type SE2 and target of type Point2.")
+        self.var, self.target = var, target
+
+    def optim_vars(self):
+        return [self.var]
+
+    def aux_vars(self):
+        return [self.target] + self.weight.aux_vars()
+
+    def dim(self) -> int:
+        return 2
+
+    def error(self) -> torch.Tensor:
+        from . import se2_torch as S
+        return S.xy(self.var.tensor) - self.target.tensor
+
+    def jacobians(self):
+        from . import se2_torch as S
+        xy, J = S.xy(self.var.tensor, jac=True)
+        err = xy - self.target.tensor
+        return [J.expand(err.shape[0], 2, 3)], err
 
 
 # --------------------------------------------------------------------------------------------------------------------------------

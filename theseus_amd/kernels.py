@@ -748,6 +748,49 @@ class HipKernels:
         _lib.check(self.lib.thx_push2_error(_lib.ptr(table), int(n_terms), _lib.ptr(x), V, _lib.ptr(err), B,
                                             _lib.dtype_code(x.dtype), se2_eps(x.dtype), _lib.stream_ptr(x.device)), "thx_push2_error")
 
+    # ---- SE2 motion planning (csrc/trajse2_kernels.hip) ---------------------------------------------
+    @staticmethod
+    def _trajse2_state(what, x):
+        if x.ndim != 3 or x.shape[2] != 4 or not x.is_contiguous():
+            raise ValueError(f"{what}: the state must be a contiguous (V, B, 4) tensor")
+        return x.shape[:2]
+
+    def trajse2_eval(self, table, n_terms, x, J, j_total, e):
+        """table: uint8 device tensor of ``n_terms`` thx_trajse2_term; x (V, B, 4) state of SE2 and (v0, v1, v2, 0) records; J flat
+        block buffer (j_total * B); e (B, m)."""
+        V, B = self._trajse2_state("trajse2_eval", x)
+        if J.numel() < j_total * B or e.shape[0] != B or J.dtype != x.dtype or e.dtype != x.dtype:
+            raise ValueError("trajse2_eval: state / block buffers do not fit")
+        if not x.is_cuda:
+            raise RuntimeError(f"trajse2_eval: the state must live on a HIP device (got {x.device}); there is no CPU fallback")
+        _lib.check(self.lib.thx_trajse2_eval(_lib.ptr(table), int(n_terms), _lib.ptr(x), V, _lib.ptr(J), int(j_total), _lib.ptr(e),
+                                             e.stride(0), e.shape[1], B, _lib.dtype_code(x.dtype), se2_eps(x.dtype),
+                                             _lib.stream_ptr(x.device)), "thx_trajse2_eval")
+
+    def trajse2_error(self, table, n_terms, x, err):
+        V, B = self._trajse2_state("trajse2_error", x)
+        if err.shape != (B,) or err.dtype != x.dtype:
+            raise ValueError("trajse2_error: state / output do not fit")
+        if not x.is_cuda:
+            raise RuntimeError(f"trajse2_error: the state must live on a HIP device (got {x.device}); there is no CPU fallback")
+        _lib.check(self.lib.thx_trajse2_error(_lib.ptr(table), int(n_terms), _lib.ptr(x), V, _lib.ptr(err), B,
+                                              _lib.dtype_code(x.dtype), se2_eps(x.dtype), _lib.stream_ptr(x.device)),
+                   "thx_trajse2_error")
+
+    def trajse2_retract(self, x, var_kind, delta, step, ignore_mask, out):
+        """out[k] = x[k] exp(step * delta[:, 3k:3k+3]) for the SE2 records (var_kind[k] == 0), x[k] + step * delta[...] with a zero
+        pad element for the vector records (1); rows of ``ignore_mask`` copy x.  var_kind: (V,) uint8 device tensor."""
+        V, B = self._trajse2_state("trajse2_retract", x)
+        if (out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or delta.dtype != x.dtype or delta.ndim != 2
+                or delta.shape[0] != B or delta.shape[1] < 3 * V or delta.stride(1) != 1 or var_kind.dtype != torch.uint8
+                or var_kind.numel() != V or (ignore_mask is not None and ignore_mask.numel() != B)):
+            raise ValueError("trajse2_retract: state / delta / output do not fit")
+        if not x.is_cuda:
+            raise RuntimeError(f"trajse2_retract: the state must live on a HIP device (got {x.device}); there is no CPU fallback")
+        _lib.check(self.lib.thx_trajse2_retract(_lib.ptr(x), _lib.ptr(var_kind), ctypes.c_void_p(delta.data_ptr()), delta.stride(0),
+                                                float(step), _lib.ptr(ignore_mask), _lib.ptr(out), V, B, _lib.dtype_code(x.dtype),
+                                                se2_eps(x.dtype), _lib.stream_ptr(x.device)), "thx_trajse2_retract")
+
     # ---- implicit backward ----------------------------------------------------------------------
     def _retract_vjp(self, grp: PGGroup, poses, delta, step, grad_out, grad_delta):
         P, B = poses.shape[:2]
