@@ -535,6 +535,56 @@ int thx_homog_eval(const thx_homog_term* terms, int32_t n_terms, int32_t n_align
 int thx_homog_error(const thx_homog_term* terms, int32_t n_terms, int32_t n_align, const void* x, int64_t ldx, int32_t n,
                     void* scratch, int32_t chunks, void* err, int32_t B, int dtype, void* stream);
 
+/* ---- Inverse kinematics on URDF chains (examples/inverse_kinematics.py; torchkin's forward kinematics with body Jacobians): the
+ *      cost family of theseus_amd/kinematics.py.  terms[t] (DEVICE array built by the host, sorted by kind) is one cost function on
+ *      the (B, n) Euclidean state x; var[0] = first state column of its dof-wide variable theta:
+ *        THX_KIN_POSE      log(target^-1 T_link(theta)), dim 6, tangent order [v, w];  aux = target (3 x 4 row major), weight
+ *                          (wdim 1 | 6);  block = W Jlog J_body
+ *        THX_KIN_POSITION  t_link(theta) - target, dim 3;  aux = target (3), weight (wdim 1 | 3);  block = W R_link J_body[:3]
+ *        THX_KIN_HINGE     HingeCost on theta (joint limits, which may be +-inf), dim dof;  aux = down_limit, up_limit, threshold
+ *                          (dof each), weight (wdim 1 | dof)
+ *        THX_KIN_PRIOR     Difference on theta (rest pose), dim dof;  aux = target (dof), weight (wdim 1 | dof)
+ *      A link term names the path to its link: entries var[1] ... var[1] + var[2] - 1 of `paths` (DEVICE array of n_paths entries,
+ *      var[2] <= THX_KIN_MAX_PATH), the joints from the root to the link in that order.  An entry holds the joint's type, the
+ *      component of theta that moves it (-1: fixed), its origin (3 x 4 row major; fixed joints in front of it folded in) and its
+ *      UNIT axis -- fp64 in either dtype, holding the values rounded to the run's dtype.  The components named along a path must grow
+ *      strictly from the root to the link; T_link = prod origin_k motion_k(theta), revolute motion I + sin [a]x + (1 - cos) [a]x^2,
+ *      prismatic motion a translation by theta a.
+ *      thx_kin_eval: one thread per (term, problem) writes the WEIGHTED dim x dof block and the weighted error exactly where
+ *      thx_traj2_eval puts them with block width dof (the block of term t of problem b starts j_off * B + dim * dof * b elements
+ *      into J; e is (B, m) with row stride lde, the term's rows from row0); columns of joints that are no ancestors of the link are
+ *      written as zeros.  thx_kin_error: err[b] = 0.5 * sum of the squared weighted errors, one workgroup per problem, summed in
+ *      fp64 in a fixed order.  The Lie chain runs in fp64 registers in either dtype; eps: the so3 thresholds of log / Jlog.
+ *      Terms whose rows, columns, blocks, weights or paths fall outside m / n / j_total / n_paths / the limits above are skipped,
+ *      as is the motion of an entry whose component lies outside [0, dof). */
+#define THX_KIN_POSE 0
+#define THX_KIN_POSITION 1
+#define THX_KIN_HINGE 2
+#define THX_KIN_PRIOR 3
+#define THX_KIN_FIXED 0
+#define THX_KIN_REVOLUTE 1
+#define THX_KIN_PRISMATIC 2
+#define THX_KIN_MAX_PATH 64 /* the longest path (entries) of a link term; the host refuses longer ones */
+typedef struct {
+  int32_t type, theta; /* THX_KIN_FIXED | REVOLUTE | PRISMATIC; the component of theta that moves the joint (-1: fixed) */
+  double origin[12];
+  double axis[3];
+} thx_kin_joint;
+typedef struct {
+  int32_t kind, row0;
+  int32_t var[4]; /* first state column of theta, first path entry, path entries, unused (-1) */
+  int32_t rows_, cols_;
+  int64_t j_off;
+  const void* aux[5];
+  int64_t aux_bstride[5];
+  int32_t wdim, pad_;
+} thx_kin_term;
+int thx_kin_eval(const thx_kin_term* terms, int32_t n_terms, const thx_kin_joint* paths, int32_t n_paths, const void* x, int64_t ldx,
+                 int32_t n, int32_t dof, void* J, int64_t j_total, void* e, int64_t lde, int32_t m, int32_t B, int dtype,
+                 const thx_lie_eps* eps, void* stream);
+int thx_kin_error(const thx_kin_term* terms, int32_t n_terms, const thx_kin_joint* paths, int32_t n_paths, const void* x, int64_t ldx,
+                  int32_t n, int32_t dof, void* err, int32_t B, int dtype, const thx_lie_eps* eps, void* stream);
+
 /* ---- Objective.error_metric(): 0.5 * ||weighted error||^2 per problem (core/objective.py:37-38,
  *      562-641).  `partials` is a (B, THX_ERR_CHUNKS) scratch; the reduction order is fixed
  *      (deterministic).  err is (B). */

@@ -22,6 +22,7 @@ from .embodied import PackedTrajectory2D  # noqa: F401
 from .pushing import PackedPlanarPushing  # noqa: F401
 from .planning_se2 import PackedTrajectorySE2  # noqa: F401
 from .homography import PackedHomography  # noqa: F401
+from .kinematics import PackedKinematics  # noqa: F401
 
 # names a reference user would reach for on this path
 CholeskyDenseSolver = HipCholeskySolver

@@ -1,4 +1,4 @@
-// What the fused cost families (traj_kernels.hip, push_kernels.hip, trajse2_kernels.hip) share: a family evaluates a whole objective
+// What the fused cost families (traj_kernels.hip, push_kernels.hip, trajse2_kernels.hip, homog_kernels.hip, kin_kernels.hip) share: a family evaluates a whole objective
 // from a table of 128-byte terms (thx_traj2_term, thx_push2_term, thx_trajse2_term of include/theseus_hip.h: the same layout, the
 // variable field named by the family).
 // Here: the per-term aux accessor, the bilinear signed-distance lookup, the fixed-order reduction of a *_error kernel and the host

@@ -777,3 +777,7 @@ class PackedTrajectory2D(TermTable, PackedEuclidean):
 
     def _launch_error(self, state, err):
         self.K.traj2_error(self._table, len(self.costs), state, self.n, err)
+
+
+# robot kinematics and the inverse-kinematics cost family live in theseus_amd/kinematics.py; theseus_amd.eb exports them
+from .kinematics import (LinkPoseCost, LinkPositionCost, PackedKinematics, Robot, UrdfRobotModel)  # noqa: E402,F401

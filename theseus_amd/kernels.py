@@ -722,6 +722,34 @@ class HipKernels:
         _lib.check(self.lib.thx_homog_error(*args, _lib.ptr(err), B, _lib.dtype_code(x.dtype), _lib.stream_ptr(x.device)),
                    "thx_homog_error")
 
+    # ---- inverse kinematics on URDF chains (csrc/kin_kernels.hip) ------------------------------------------
+    def _kin_args(self, what, table, n_terms, paths, n_paths, x, n, dof):
+        """the leading arguments thx_kin_eval and thx_kin_error share"""
+        if x.ndim != 2 or x.stride(1) != 1 or paths.dtype != torch.uint8 or paths.numel() < 128 * max(int(n_paths), 1):
+            raise ValueError(f"{what}: state / path table do not fit")
+        if not x.is_cuda:
+            raise RuntimeError(f"{what}: the state must live on a HIP device (got {x.device}); there is no CPU fallback")
+        return (_lib.ptr(table), int(n_terms), _lib.ptr(paths), int(n_paths), ctypes.c_void_p(x.data_ptr()), x.stride(0), int(n),
+                int(dof))
+
+    def kin_eval(self, table, n_terms, paths, n_paths, x, n, dof, J, j_total, e):
+        """table: uint8 device tensor of ``n_terms`` thx_kin_term; paths: uint8 device tensor of ``n_paths`` thx_kin_joint; x (B, >= n)
+        state; J flat block buffer (j_total * B), blocks dim x dof; e (B, m)."""
+        B = x.shape[0]
+        if J.numel() < j_total * B or e.shape[0] != B or J.dtype != x.dtype or e.dtype != x.dtype:
+            raise ValueError("kin_eval: state / block buffers do not fit")
+        args = self._kin_args("kin_eval", table, n_terms, paths, n_paths, x, n, dof)
+        _lib.check(self.lib.thx_kin_eval(*args, _lib.ptr(J), int(j_total), _lib.ptr(e), e.stride(0), e.shape[1], B,
+                                         _lib.dtype_code(x.dtype), lie_eps(x.dtype), _lib.stream_ptr(x.device)), "thx_kin_eval")
+
+    def kin_error(self, table, n_terms, paths, n_paths, x, n, dof, err):
+        B = x.shape[0]
+        if err.shape != (B,) or err.dtype != x.dtype:
+            raise ValueError("kin_error: state / output do not fit")
+        args = self._kin_args("kin_error", table, n_terms, paths, n_paths, x, n, dof)
+        _lib.check(self.lib.thx_kin_error(*args, _lib.ptr(err), B, _lib.dtype_code(x.dtype), lie_eps(x.dtype),
+                                          _lib.stream_ptr(x.device)), "thx_kin_error")
+
     # ---- planar pushing on SE2 (csrc/push_kernels.hip) -----------------------------------------------
     def push2_eval(self, table, n_terms, x, J, j_total, e):
         """table: uint8 device tensor of ``n_terms`` thx_push2_term; x (V, B, 4) pose-major SE2 state; J flat block buffer

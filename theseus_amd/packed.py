@@ -454,12 +454,13 @@ def packed_for(objective: Objective, kernels=None, order=None):
     pose-graph one, the fused planar-pushing one (theseus_amd/pushing.py: PackedPlanarPushing), the fused SE2 motion-planning one
     (theseus_amd/planning_se2.py: PackedTrajectorySE2), the fused 2D motion-planning one
     (theseus_amd/embodied.py: PackedTrajectory2D), the fused homography-alignment one (theseus_amd/homography.py:
-    PackedHomography), or -- Euclidean variables with
+    PackedHomography), the fused inverse-kinematics one (theseus_amd/kinematics.py: PackedKinematics), or -- Euclidean variables with
     cost functions that hand over their Jacobian blocks -- the generic one of theseus_amd/euclidean.py."""
     from .embodied import PackedTrajectory2D
     from .euclidean import PackedEuclidean
     from .generic import PackedState
     from .homography import PackedHomography
+    from .kinematics import PackedKinematics
     from .planning_se2 import PackedTrajectorySE2
     from .pushing import PackedPlanarPushing
     p = getattr(objective, "_packed", None)
@@ -471,7 +472,7 @@ def packed_for(objective: Objective, kernels=None, order=None):
         except UnsupportedObjective as fused_error:
             if not isinstance(objective, Objective):   # the reference's own Objective: theseus_amd/plugin.py has its generic path
                 raise
-            for cls in (PackedPlanarPushing, PackedTrajectorySE2, PackedTrajectory2D, PackedHomography, PackedEuclidean):
+            for cls in (PackedPlanarPushing, PackedTrajectorySE2, PackedTrajectory2D, PackedHomography, PackedKinematics, PackedEuclidean):
                 try:
                     p = cls(objective, kernels, order)
                     break

@@ -1,6 +1,7 @@
 """The term table of the fused cost families (csrc/term_family.cuh; the families: theseus_amd/embodied.py PackedTrajectory2D on
 csrc/traj_kernels.hip, theseus_amd/pushing.py PackedPlanarPushing on csrc/push_kernels.hip, theseus_amd/planning_se2.py PackedTrajectorySE2 on csrc/trajse2_kernels.hip,
-theseus_amd/homography.py PackedHomography on csrc/homog_kernels.hip): one 128-byte record per cost function,
+theseus_amd/homography.py PackedHomography on csrc/homog_kernels.hip, theseus_amd/kinematics.py PackedKinematics on
+csrc/kin_kernels.hip): one 128-byte record per cost function,
 sorted by kind, holding where the cost's rows and Jacobian blocks go, which variables it reads and the device pointers of its
 auxiliary tensors themselves (an SDF grid shared by every cost is one tensor, stored once).  ``TermTable`` is a mixin for a packed
 class (``PackedState`` of theseus_amd/generic.py) whose NON-differentiated evaluation is such a kernel: ``assemble(graph=False)`` =
@@ -9,7 +10,7 @@ differentiated is the packed class's own torch path.
 
 A family supplies data and two launches:
   _TERM           its record (``term_dtype``)
-  _TANGENT        the tangent width of its variables (every block is (B, dim, _TANGENT))
+  _TANGENT        the tangent width of its variables (every block is (B, dim, _TANGENT)); PackedKinematics sets it per instance
   _KINDS          {kind: TermKind}
   _WEIGHT_WIDTHS  (allowed widths of a Scale / Diagonal weight, the message for any other)
   _term_vars(c)   what goes into the variable field of cost c's record
@@ -25,7 +26,7 @@ from .generic import _names
 
 
 def term_dtype(var_field: str) -> np.dtype:
-    """thx_traj2_term / thx_push2_term / thx_trajse2_term of include/theseus_hip.h; ``var_field``: the family's name of the variable field"""
+    """thx_traj2_term / thx_push2_term / thx_trajse2_term / thx_homog_term / thx_kin_term of include/theseus_hip.h; ``var_field``: the family's name of the variable field"""
     dt = np.dtype([("kind", "<i4"), ("row0", "<i4"), (var_field, "<i4", (4,)), ("rows", "<i4"), ("cols", "<i4"), ("j_off", "<i8"),
                    ("aux", "<u8", (5,)), ("aux_bstride", "<i8", (5,)), ("wdim", "<i4"), ("pad", "<i4")])
     assert dt.itemsize == 128
