@@ -585,6 +585,38 @@ int thx_kin_eval(const thx_kin_term* terms, int32_t n_terms, const thx_kin_joint
 int thx_kin_error(const thx_kin_term* terms, int32_t n_terms, const thx_kin_joint* paths, int32_t n_paths, const void* x, int64_t ldx,
                   int32_t n, int32_t dof, void* err, int32_t B, int dtype, const thx_lie_eps* eps, void* stream);
 
+/* ---- DCEM, the differentiable cross-entropy method (theseus/optimizer/nonlinear/dcem.py:94-158; the LML projection:
+ *      theseus/third_party/lml.py:53-177): what one iteration does with the S sampled states X (S, B, n) -- sample major, every
+ *      X[s] a contiguous (B, n) state -- and their errors fX (S, B), and its backward.  One workgroup per problem; values in the
+ *      run's dtype, every sum accumulated in fp64 in a fixed order (no atomics: two calls give the same bits).
+ *      thx_dcem_update:
+ *        scores   x = -temp * (fX - mean) / (std + 1e-6), std unbiased (normalize == 0: x = -temp * fX);
+ *        weights  temp = +inf (the reference's None): 1 for the n_elite smallest fX, ties to the lower sample index;
+ *                 n_elite == 1: softmax(x) over the samples;
+ *                 else the LML projection onto {0 <= w <= 1, sum w = n_elite}: w = sigmoid(x + nu), nu bracketed between the
+ *                 n_elite-th and the next largest score widened by 7, `branch` grid values sum sigmoid(x + nu_k) - n_elite per
+ *                 round (nu_k = (hi - lo) * linspace(0, 1, branch)[k] + lo), the new bracket the cell at count(values < 0) - 1,
+ *                 rounds while hi - lo > lml_eps, at most lml_n_iter; nu = lo + (hi - lo) / 2.  S <= n_elite: every w = 1 - 1e-5.
+ *        moments  mu = sum_s w_s X_s / n_elite, sigma = sqrt(sum_s w_s (X_s - mu)^2 / n_elite) (+ 1e-10 with temp = +inf):
+ *                 divided by n_elite, not by sum w, as the reference does.
+ *        Outputs mu, sigma (B, n); w (B, S); nu (B) and the final bracket (B, 2) (zeros outside the LML mode); flags (B) int32:
+ *        THX_DCEM_FLAG_NOT_CONVERGED the bracket is still wider than lml_eps after lml_n_iter rounds, THX_DCEM_FLAG_ALL_NONNEG a
+ *        round found every grid value non-negative (the search then goes on from 7 below the bracket).
+ *      thx_dcem_update_vjp: grad_X (S, B, n), grad_fX (S, B) from grad_mu, grad_sigma (B, n) and the saved X, fX, w, mu, sigma of
+ *        the forward call with the same n_elite, temp, normalize: the moments' derivatives (with the d sigma / d mu term that
+ *        sum w != n_elite leaves), then the LML backward (Hinv = 1 / (1 / w + 1 / (1 - w)), dnu = sum Hinv g / sum Hinv,
+ *        dx = Hinv (g - dnu)) or the softmax Jacobian or nothing (temp = +inf, S <= n_elite), then the standardisation's.
+ *      Refused before any launch: S > THX_DCEM_MAX_S (a problem's scores stay in LDS), S, n, n_elite < 1, branch < 2. */
+#define THX_DCEM_MAX_S 4096
+#define THX_DCEM_FLAG_NOT_CONVERGED 1
+#define THX_DCEM_FLAG_ALL_NONNEG 2
+int thx_dcem_update(const void* fX, const void* X, int32_t S, int32_t B, int32_t n, int32_t n_elite, double temp, int normalize,
+                    double lml_eps, int32_t lml_n_iter, int32_t branch, void* mu, void* sigma, void* w, void* nu, void* bracket,
+                    int32_t* flags, int dtype, void* stream);
+int thx_dcem_update_vjp(const void* grad_mu, const void* grad_sigma, const void* X, const void* fX, const void* w, const void* mu,
+                        const void* sigma, int32_t S, int32_t B, int32_t n, int32_t n_elite, double temp, int normalize,
+                        void* grad_X, void* grad_fX, int dtype, void* stream);
+
 /* ---- Objective.error_metric(): 0.5 * ||weighted error||^2 per problem (core/objective.py:37-38,
  *      562-641).  `partials` is a (B, THX_ERR_CHUNKS) scratch; the reduction order is fixed
  *      (deterministic).  err is (B). */

@@ -16,6 +16,7 @@ from .linearization import HipLinearization, Linearization, VariableOrdering  # 
 from .nonlinear import (BackwardMode, Dogleg, GaussNewton, LevenbergMarquardt, NonlinearLeastSquares,  # noqa: F401
                         NonlinearOptimizerInfo, NonlinearOptimizerStatus, TrustRegion)
 from .packed import PackedPoseGraph, UnsupportedObjective  # noqa: F401
+from .dcem import DCEM, DcemUpdate, dcem_update_torch  # noqa: F401
 from .ba import HipSchurLinearization, HipSchurSolver, PackedBA  # noqa: F401
 from . import embodied as eb  # noqa: F401
 from .embodied import PackedTrajectory2D  # noqa: F401

@@ -29,6 +29,8 @@ THX_HOMOG_SUMS = 10  # doubles per (alignment term, problem, chunk) of their scr
 KIN_POSE, KIN_POSITION, KIN_HINGE, KIN_PRIOR = 0, 1, 2, 3  # THX_KIN_* (kinds of a thx_kin_term)
 KIN_FIXED, KIN_REVOLUTE, KIN_PRISMATIC = 0, 1, 2  # THX_KIN_* (types of a thx_kin_joint)
 THX_KIN_MAX_PATH = 64  # the longest path (entries of the joint table) of a link term
+THX_DCEM_MAX_S = 4096  # most samples per problem of thx_dcem_update (its scores stay in LDS)
+DCEM_FLAG_NOT_CONVERGED, DCEM_FLAG_ALL_NONNEG = 1, 2  # THX_DCEM_FLAG_* (bits of thx_dcem_update's flag word)
 LOSS_NONE, LOSS_WELSCH, LOSS_HUBER, LOSS_HINGE = 0, 1, 2, 3  # THX_LOSS_* (theseus/core/robust_loss.py:33-62)
 LOSS_FLATTEN = 4  # THX_LOSS_FLATTEN: RobustCostFunction(flatten_dims=True), or-ed into a loss code
 LOSS_GEMAN_MCCLURE = 8  # THX_LOSS_GEMAN_MCCLURE (robust_loss.py:92-113; the radius entry carries log(mu * radius))
@@ -306,6 +308,10 @@ _SIGNATURES = {
                      c_int32, c_int32, c_int, POINTER(LieEps), c_void_p],
     "thx_kin_error": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_int,
                       POINTER(LieEps), c_void_p],
+    "thx_dcem_update": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_int, c_double, c_int32, c_int32, c_void_p,
+                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    "thx_dcem_update_vjp": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                            c_double, c_int, c_void_p, c_void_p, c_int, c_void_p],
     "thx_diag": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_int, c_void_p],
     "thx_lm_accept": [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
                       c_void_p, c_int, c_double, c_double, c_double, c_void_p, c_int, c_void_p],

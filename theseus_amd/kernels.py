@@ -750,6 +750,44 @@ class HipKernels:
         _lib.check(self.lib.thx_kin_error(*args, _lib.ptr(err), B, _lib.dtype_code(x.dtype), lie_eps(x.dtype),
                                           _lib.stream_ptr(x.device)), "thx_kin_error")
 
+    # ---- DCEM: weights and moments of one iteration, and their backward (csrc/dcem_kernels.hip) ------------
+    @staticmethod
+    def _dcem_shapes(what, fX, X, bn, bs, other=()):
+        """(S, B, n) of fX (S, B) and X (S, B, n); ``bn``: tensors that must be (B, n), ``bs``: (B, S), ``other``: [(tensor, shape)]
+        -- all of X's dtype."""
+        if X.ndim != 3 or fX.shape != X.shape[:2] or fX.dtype != X.dtype:
+            raise ValueError(f"{what}: fX must be (S, B) and X (S, B, n) of one dtype")
+        S, B, n = X.shape
+        for t, shape in [(t, (B, n)) for t in bn] + [(t, (B, S)) for t in bs] + list(other):
+            if tuple(t.shape) != tuple(shape) or t.dtype != X.dtype:
+                raise ValueError(f"{what}: a tensor of shape {tuple(t.shape)} / {t.dtype} where {tuple(shape)} / {X.dtype} is expected")
+        if not X.is_cuda:
+            raise RuntimeError(f"{what}: the samples must live on a HIP device (got {X.device}); there is no CPU fallback")
+        return S, B, n
+
+    def dcem_update(self, fX, X, n_elite, temp, normalize, lml_eps, lml_n_iter, branch, mu, sigma, w, nu, bracket, flags):
+        """fX (S, B), X (S, B, n) -> mu, sigma (B, n), w (B, S), nu (B), bracket (B, 2), flags (B) int32; ``temp`` None / inf:
+        hard top-k (include/theseus_hip.h: thx_dcem_update)."""
+        S, B, n = self._dcem_shapes("dcem_update", fX, X, (mu, sigma), (w,))
+        if nu.shape != (B,) or bracket.shape != (B, 2) or nu.dtype != X.dtype or bracket.dtype != X.dtype:
+            raise ValueError("dcem_update: nu must be (B,) and bracket (B, 2) of the samples' dtype")
+        if flags.shape != (B,) or flags.dtype != torch.int32:
+            raise ValueError("dcem_update: flags must be (B,) int32")
+        _lib.check(self.lib.thx_dcem_update(_lib.ptr(fX), _lib.ptr(X), S, B, n, int(n_elite), float("inf") if temp is None else float(temp),
+                                            int(bool(normalize)), float(lml_eps), int(lml_n_iter), int(branch), _lib.ptr(mu),
+                                            _lib.ptr(sigma), _lib.ptr(w), _lib.ptr(nu), _lib.ptr(bracket), _lib.ptr(flags),
+                                            _lib.dtype_code(X.dtype), _lib.stream_ptr(X.device)), "thx_dcem_update")
+
+    def dcem_update_vjp(self, grad_mu, grad_sigma, X, fX, w, mu, sigma, n_elite, temp, normalize, grad_X, grad_fX):
+        """grad_mu, grad_sigma (B, n) and what thx_dcem_update read and wrote -> grad_X (S, B, n), grad_fX (S, B)"""
+        S, B, n = self._dcem_shapes("dcem_update_vjp", fX, X, (grad_mu, grad_sigma, mu, sigma), (w,),
+                                    [(grad_X, X.shape), (grad_fX, fX.shape)])
+        _lib.check(self.lib.thx_dcem_update_vjp(_lib.ptr(grad_mu), _lib.ptr(grad_sigma), _lib.ptr(X), _lib.ptr(fX), _lib.ptr(w),
+                                                _lib.ptr(mu), _lib.ptr(sigma), S, B, n, int(n_elite),
+                                                float("inf") if temp is None else float(temp), int(bool(normalize)), _lib.ptr(grad_X),
+                                                _lib.ptr(grad_fX), _lib.dtype_code(X.dtype), _lib.stream_ptr(X.device)),
+                   "thx_dcem_update_vjp")
+
     # ---- planar pushing on SE2 (csrc/push_kernels.hip) -----------------------------------------------
     def push2_eval(self, table, n_terms, x, J, j_total, e):
         """table: uint8 device tensor of ``n_terms`` thx_push2_term; x (V, B, 4) pose-major SE2 state; J flat block buffer

@@ -1,13 +1,14 @@
 """TheseusLayer mirror (theseus/theseus_layer.py:29-174): forward = Objective.update + optimize."""
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Dict, Optional, Tuple, Union
 
 import torch
 
+from .dcem import DCEM
 from .nonlinear import NonlinearLeastSquares, NonlinearOptimizerInfo
 
 
 class TheseusLayer(torch.nn.Module):
-    def __init__(self, optimizer: NonlinearLeastSquares, vectorize: bool = True, **kwargs):
+    def __init__(self, optimizer: Union[NonlinearLeastSquares, DCEM], vectorize: bool = True, **kwargs):
         super().__init__()
         self.objective = optimizer.objective
         self.optimizer = optimizer
