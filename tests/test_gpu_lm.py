@@ -103,6 +103,40 @@ def test_lm_trajectory_matches_reference(name, tol):
     assert all(s == th.NonlinearOptimizerStatus.MAX_ITERATIONS for s in info.status)
 
 
+@pytest.mark.parametrize("name", ["pg_f64_lm_adaptive_rejects", "pg_f64_lm_converges"])
+def test_sync_free_and_synchronous_loops_report_the_same_run(name):
+    """The sync-free loop (no callback: device-side iteration counter, histories and best solution masked by the counted flag, the
+    cut at "everybody converged") and the synchronous loop (a no-op callback) with all three trackers on: the same kernels on the
+    same inputs, none of them with atomics, so every reported field is equal bit for bit.  pg_f64_lm_adaptive_rejects (9 poses, 16
+    edges, batch 6) has all-rejected attempts and masked rejects, pg_f64_lm_converges (8 poses, batch 5) converges before
+    max_iterations.  The CPU twin is tests/test_host_state.py::test_state_history_matches_the_iterates."""
+    import theseus_amd as th
+    g = load_golden(name)
+    _, _, kw = golden_problem(g)
+    kw = {k: v for k, v in kw.items() if k not in ("gauss_newton", "max_iterations", "step_size")}
+    tol = dict(abs_err_tolerance=1e-10, rel_err_tolerance=1e-4) if "converges" in name else dict(abs_err_tolerance=0.0, rel_err_tolerance=0.0)
+    runs = []
+    for callback in (None, lambda *a: None):
+        obj, _ = build_objective(th, g)
+        opt = th.LevenbergMarquardt(obj, linear_solver_cls=th.HipCholeskySolver, max_iterations=8, **tol)
+        sol, info = th.TheseusLayer(opt).forward(None, optimizer_kwargs=dict(
+            track_best_solution=True, track_err_history=True, track_state_history=True, end_iter_callback=callback, **kw))
+        runs.append((sol, info))
+    (sa, ia), (sb, ib) = runs
+    floats = dict(err_history=(ia.err_history, ib.err_history), best_err=(ia.best_err, ib.best_err),
+                  **{f"solution[{k}]": (sa[k], sb[k]) for k in sa}, **{f"best_solution[{k}]": (v, ib.best_solution[k]) for k, v in ia.best_solution.items()},
+                  **{f"state_history[{k}]": (v, ib.state_history[k]) for k, v in ia.state_history.items()})
+    assert ia.iters_done == ib.iters_done and ia.iters_done > 0
+    assert list(ia.status) == list(ib.status)
+    assert torch.equal(ia.converged_iter, ib.converged_iter) and torch.equal(ia.best_iter, ib.best_iter)
+    assert sa.keys() == sb.keys() and ia.best_solution.keys() == ib.best_solution.keys() == ia.state_history.keys() == ib.state_history.keys()
+    for k, (a, b) in floats.items():
+        assert torch.equal(a, b), k
+    if "converges" in name:   # the cut: the converging iteration is recorded, not counted; nothing behind it
+        assert ia.iters_done < 8 and all(s == th.NonlinearOptimizerStatus.CONVERGED for s in ia.status)
+        assert torch.isinf(ia.err_history[:, ia.iters_done + 2:]).all() and torch.isfinite(ia.err_history[:, :ia.iters_done + 2]).all()
+
+
 @pytest.mark.parametrize("name", ["pg_f32_lm", "pg_f32_lm_b16", "pg2_f32_lm", "pg3_f32_lm"])
 def test_lm_trajectory_fp32_inside_reference_band(name):
     """fp32 parity.  The reference's fp32 path is a noisy evaluation (catastrophic cancellation in the

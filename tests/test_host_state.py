@@ -151,7 +151,7 @@ def test_state_history_matches_the_iterates(name):
         obj, _ = build_objective(th, g, device="cpu")
         opt = th.LevenbergMarquardt(obj, linearization_kwargs=dict(kernels=OracleKernels()), max_iterations=8, **tol)
         seen = []
-        okw = dict(track_state_history=True, track_err_history=True, **kw)
+        okw = dict(track_state_history=True, track_err_history=True, track_best_solution=True, **kw)
         if not lazy:
             okw["end_iter_callback"] = lambda o, i, d, it: seen.append({k: v.tensor.clone() for k, v in o.objective.optim_vars.items()})
         start = {k: v.tensor.clone() for k, v in obj.optim_vars.items()}
@@ -168,6 +168,12 @@ def test_state_history_matches_the_iterates(name):
         last = ia.iters_done + (1 if "converges" in name else 0)    # (the converging iteration is recorded, not counted: :202-203)
         assert torch.isfinite(h[..., :last + 1]).all() and torch.isinf(h[..., last + 1:]).all()
     assert ia.iters_done == ib.iters_done
+    # all three trackers together: the best solution of the sync-free loop (device-side iteration index, masked by the counted
+    # flag) is the synchronous loop's, bit for bit
+    assert torch.equal(ia.best_iter, ib.best_iter) and torch.equal(ia.best_err, ib.best_err)
+    assert ia.best_solution.keys() == ib.best_solution.keys() == start.keys()
+    for k_ in ia.best_solution:
+        assert torch.equal(ia.best_solution[k_], ib.best_solution[k_]), k_
 
 
 def test_global_params_mirror(monkeypatch):

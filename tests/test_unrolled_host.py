@@ -77,10 +77,14 @@ def test_bundle_adjustment_unrolled_gradients_match_the_reference(name):
     check_ba_unrolled(g, run_ba_implicit(th, g, OracleKernels(), "cpu"))
 
 
-def test_best_solution_and_state_history_are_tracked_through_differentiated_iterations():
-    """track_best_solution / track_state_history together with backward_mode="unroll" (the reference's _update_info keeps detached
-    copies, nonlinear_optimizer.py:150-207): same gradients as without tracking, the history's last slot is the solution, the best
-    solution is the history's slot with the smallest error."""
+@pytest.mark.parametrize("mode", [dict(backward_mode="unroll"), dict(backward_mode="truncated", backward_num_iterations=2)],
+                         ids=["unroll", "truncated"])
+def test_best_solution_and_state_history_are_tracked_through_differentiated_iterations(mode):
+    """track_best_solution / track_state_history together with backward_mode="unroll" / "truncated" (the reference's _update_info
+    keeps detached copies, nonlinear_optimizer.py:150-207): same gradients as without tracking, the history's last slot is the
+    solution, the best solution is the history's slot with the smallest error.  best_iter is the iteration that first reached the
+    smallest error (:200-202) -- of all iterations in UNROLL's single loop, of the no-grad loop's alone in TRUNCATED, whose
+    _merge_infos (:220-266) merges best_solution / best_err and leaves best_iter the first loop's."""
     import torch
     import theseus_amd as th
     from tests.oracle_kernels import OracleKernels
@@ -101,8 +105,8 @@ def test_best_solution_and_state_history_are_tracked_through_differentiated_iter
         opt = th.LevenbergMarquardt(obj, max_iterations=4, abs_err_tolerance=0.0, rel_err_tolerance=0.0,
                                     linearization_kwargs=dict(kernels=OracleKernels()))
         sol, info = th.TheseusLayer(opt).forward(None, optimizer_kwargs=dict(
-            backward_mode="unroll", damping=0.05, adaptive_damping=True, track_err_history=True, track_best_solution=track,
-            track_state_history=track))
+            damping=0.05, adaptive_damping=True, track_err_history=True, track_best_solution=track, track_state_history=track,
+            **mode))
         final = torch.stack([sol[f"pose_{k}"] for k in range(P)], 1)
         (t(g["coef"]) * final).sum().backward()
         out[track] = (final.detach(), meas.grad.clone(), info)
@@ -116,6 +120,14 @@ def test_best_solution_and_state_history_are_tracked_through_differentiated_iter
     np.testing.assert_allclose(info.best_err.numpy(), errs.min(dim=1).values.numpy(), rtol=1e-6)
     for b in range(errs.shape[0]):
         np.testing.assert_allclose(info.best_solution["pose_3"][b].numpy(), hist[b, ..., int(k_best[b])].numpy(), rtol=0, atol=1e-6)
+    assert info.iters_done == 4 and torch.isfinite(errs).all() and torch.isfinite(hist).all()   # (tolerances 0: nobody converges)
+    competing = 4 if mode["backward_mode"] == "unroll" else 4 - mode["backward_num_iterations"]
+    for b in range(errs.shape[0]):
+        best, bi = errs[b, 0].item(), 0
+        for it in range(competing):
+            if errs[b, it + 1].item() < best:
+                best, bi = errs[b, it + 1].item(), it
+        assert int(info.best_iter[b]) == bi
 
 
 def test_unrolled_gradients_of_a_dropped_singular_item_are_zero():

@@ -349,6 +349,10 @@ class PackedBA(TrackedVariables):
     def dstruct(self):
         return self.structure.on(self.tensors.cams.device)
 
+    # ---- BackwardMode.IMPLICIT -------------------------------------------------------------------------------------------------
+    def implicit_step(self, opt, step: float, kwargs):
+        return ba_implicit_step(opt, self, step, kwargs)
+
     # ---- BackwardMode.UNROLL / TRUNCATED (theseus_amd/nonlinear.py: the differentiable tail loop) ------------------------------
     def prepare_unroll(self):
         """Before the differentiable tail loop: re-pack the auxiliary tensors WITH their autograd history (once)."""

@@ -9,6 +9,7 @@ What runs where:
                 (theseus_amd/term_table.py), the torch classes for generic objectives and whenever something is differentiated;
   update        ``thx_dcem_update`` (csrc/dcem_kernels.hip), one workgroup per problem, and ``thx_dcem_update_vjp`` behind it:
                 ``DcemUpdate`` below, one autograd node, used under no_grad and with gradients alike;
+  bookkeeping   histories, best solution, final info: the ``_RunTracker`` of theseus_amd/nonlinear.py (``record``, ``finish``), as in LM;
   no linear solver and no linearization are constructed.
 ``dcem_update_torch`` is the same function on plain torch, written from the formulas: the comparator of the tests (and of
 tools/bench_dcem.py).  The optimizer never calls it.
@@ -20,7 +21,6 @@ the reference does for every variable (``_mu_vec_to_dict`` slices ``var.tensor``
 import math
 from typing import Callable, Optional, Union
 
-import numpy as np
 import torch
 
 from . import _lib
@@ -28,7 +28,7 @@ from .core import Objective
 from .euclidean import _is_euclidean
 from .generic import PackedState
 from .linearization import VariableOrdering
-from .nonlinear import (BackwardMode, NonlinearOptimizerInfo, NonlinearOptimizerParams, NonlinearOptimizerStatus, _StateHistory)
+from .nonlinear import BackwardMode, NonlinearLeastSquares, NonlinearOptimizerInfo, NonlinearOptimizerParams, _RunTracker
 from .packed import UnsupportedObjective, packed_for
 
 LML_N_ITER = 100   # rounds of the LML bracketing at most (lml.py:39)
@@ -210,21 +210,13 @@ class DCEM:
         self._objective_version = objective.current_version
         self._X = self._fX = None
 
-    def set_params(self, **kwargs):
-        for k, v in kwargs.items():
-            if not hasattr(self.params, k):
-                raise ValueError(f"Invalid nonlinear optimizer parameter {k}.")
-            setattr(self.params, k, v)
+    set_params = NonlinearLeastSquares.set_params   # (it touches ``self.params`` alone)
 
     def reset_sigma(self, init_sigma: Union[float, torch.Tensor]) -> None:
         p = self.packed
         self.sigma = torch.ones(p.batch, self._tot_dof, dtype=self.objective.dtype, device=p.device) * init_sigma
 
-    def optimize(self, **kwargs) -> NonlinearOptimizerInfo:
-        if self._objective_version != self.objective.current_version:
-            raise RuntimeError("The objective was modified after optimizer construction, which is "
-                               "currently not supported.")
-        return self._optimize_impl(**kwargs)
+    optimize = NonlinearLeastSquares.optimize   # (the version check, then ``self._optimize_impl``)
 
     def _optimize_impl(self, **kwargs) -> NonlinearOptimizerInfo:
         """State ownership as in NonlinearLeastSquares._optimize_impl: the loop moves the state through private buffers and re-points
@@ -241,10 +233,8 @@ class DCEM:
 
     def _check_convergence(self, err, last_err):
         """nonlinear_optimizer.py:110-119, the mean test as a device-side select"""
-        p = self.params
-        change = last_err - err
-        conv = (change.abs() < p.abs_err_tolerance) | ((change / last_err).abs() < p.rel_err_tolerance)
-        return conv | (err.abs().mean() < p.abs_err_tolerance)
+        conv = NonlinearLeastSquares._check_convergence(self, err, last_err)   # (the per-problem tests, on ``self.params``)
+        return conv | (err.abs().mean() < self.params.abs_err_tolerance)
 
     def _optimize_loop(self, track_best_solution: bool = False, track_err_history: bool = False, track_state_history: bool = False,
                        verbose: bool = False, backward_mode: Union[str, BackwardMode] = BackwardMode.UNROLL,
@@ -277,18 +267,9 @@ class DCEM:
             self.reset_sigma(self.init_sigma if init_sigma is None else init_sigma)
             if tuple(self.sigma.shape) != (B, n):
                 raise ValueError(f"DCEM: init_sigma must broadcast to {(B, n)}")
-            last_err = packed.error_metric().clone()
-            err_hist = None
-            if track_err_history:
-                err_hist = torch.full((B, p.max_iterations + 1), math.inf, dtype=dt, device=dev)
-                err_hist[:, 0] = last_err
-            info = NonlinearOptimizerInfo(best_solution=None, status=np.array([NonlinearOptimizerStatus.START] * B),
-                                          converged_iter=torch.zeros(B, dtype=torch.long), best_iter=torch.zeros(B, dtype=torch.long),
-                                          err_history=err_hist, last_err=last_err, best_err=last_err.clone())
-            state_hist = _StateHistory(packed.state, p.max_iterations + 1) if track_state_history else None
-            if track_best_solution:
-                best_state, best_err = packed.clone_state(), last_err.clone()
-                best_iter = torch.zeros(B, dtype=torch.long, device=dev)
+            tracker = _RunTracker(packed, p, dt, track_best_solution, track_err_history, track_state_history)
+            info = tracker.info
+            last_err = info.last_err = info.last_err.clone()
             if verbose:
                 print(f"DCEM optimizer. Iteration: 0. Error: {last_err.mean().item()}")
             if self._X is None or tuple(self._X.shape) != (S, B, n) or self._X.dtype != dt or self._X.device != dev:
@@ -333,15 +314,7 @@ class DCEM:
                 err = packed.error_metric(state=mu.detach(), out=err_new)
                 # _update_info (nonlinear_optimizer.py:184-213), then the convergence test of dcem.py:188-195
                 conv_iter += 1 - conv.long()
-                if err_hist is not None:
-                    err_hist[:, it + 1] = err
-                if state_hist is not None:
-                    state_hist.record(it + 1, mu.detach())
-                if track_best_solution:
-                    better = err < best_err
-                    packed.copy_where(better, mu.detach(), best_state)
-                    best_err = torch.where(better, err, best_err)
-                    best_iter = torch.where(better, torch.full_like(best_iter, it), best_iter)
+                tracker.record(it, mu.detach(), err)
                 if verbose:
                     print(f"Nonlinear optimizer. Iteration: {it + 1}. Error: {err.mean().item()} ")
                 it += 1
@@ -365,15 +338,4 @@ class DCEM:
             self.lml_flags = flags_all
             if self.lml_verbose and bool(flags_all.ne(0).any()):
                 print("LML Warning: Did not converge, or an example has all positive iterates.")
-            info.status[ever_conv.cpu().numpy()] = NonlinearOptimizerStatus.CONVERGED
-            info.status[info.status == NonlinearOptimizerStatus.START] = NonlinearOptimizerStatus.MAX_ITERATIONS
-            info.converged_iter = conv_iter.cpu()
-            info.converged_iter[torch.from_numpy(info.status == NonlinearOptimizerStatus.MAX_ITERATIONS)] = -1
-            if err_hist is not None:
-                info.err_history = err_hist.cpu()
-            if state_hist is not None:
-                info.state_history = state_hist.to_dict(packed)
-            if track_best_solution:
-                info.best_err, info.best_iter = best_err, best_iter.cpu()
-                info.best_solution = packed.solution_dict(best_state)
-        return info
+            return tracker.finish(ever_conv, conv_iter)

@@ -136,6 +136,123 @@ class _StateHistory:
         return packed.history_dict(hist, torch.get_default_dtype())   # (the reference allocates it with torch.ones(...): default dtype)
 
 
+def _detached(state):
+    """A packed state is one tensor or a tuple of them (BA: (cams, points))."""
+    return tuple(x.detach() for x in state) if isinstance(state, tuple) else state.detach()
+
+
+class _RunTracker:
+    """What ``NonlinearOptimizerInfo`` reports, while a run is in flight: the info object, the error history, the state history and
+    the best solution, all on the device until ``finish``.  ``record`` is the reference's ``_update_info``
+    (nonlinear_optimizer.py:184-213) for every loop of this module and for DCEM: the iteration index ``it`` is a host int (the
+    synchronous loops) or a 0-dim device tensor (the sync-free loop), and with a device index a 0-dim ``counted`` mask leaves
+    everything untouched where it is false (an uncounted attempt)."""
+
+    def __init__(self, packed, params, dtype, track_best_solution: bool, track_err_history: bool, track_state_history: bool):
+        B, dev, K = packed.batch, packed.device, params.max_iterations
+        self.packed, self.max_iterations = packed, K
+        last = packed.error_metric()
+        self.err_hist = None
+        if track_err_history:
+            self.err_hist = torch.full((B, K + 1), float("inf"), dtype=dtype, device=dev)
+            self.err_hist[:, 0] = last
+        self.info = NonlinearOptimizerInfo(
+            best_solution=None, status=np.array([NonlinearOptimizerStatus.START] * B),
+            converged_iter=torch.full((B,), -1, dtype=torch.long), best_iter=torch.zeros(B, dtype=torch.long),
+            err_history=self.err_hist, last_err=last, best_err=last.clone())
+        self.state_hist = _StateHistory(packed.state, K + 1) if track_state_history else None
+        self.best_state = self.best_err = self.best_iter = None
+        if track_best_solution:
+            self.best_state = packed.clone_state()
+            self.best_err = last.clone()
+            self.best_iter = torch.zeros(B, dtype=torch.long, device=dev)
+
+    def record(self, it, state, err, counted=None):
+        """Iteration ``it`` (0-based) ended in ``state`` with error ``err``: error history, then state history, then best solution."""
+        self.record_history(it, state, err, counted)
+        self.keep_best(it, state, err, counted)
+
+    def record_history(self, it, state, err, counted=None):
+        """Column / slot ``it + 1`` of the two histories."""
+        if self.err_hist is not None:
+            if isinstance(it, int):
+                self.err_hist[:, it + 1] = err
+            else:
+                col = (it + 1).clamp(max=self.max_iterations).view(1)
+                cur = self.err_hist.index_select(1, col)
+                self.err_hist.index_copy_(1, col, err.unsqueeze(1) if counted is None else torch.where(counted, err.unsqueeze(1), cur))
+        if self.state_hist is not None:
+            self.state_hist.record(it + 1, state, counted)
+
+    def keep_best(self, it, state, err, counted=None):
+        """``state`` competes for the best solution; ``best_iter`` becomes ``it`` where it wins."""
+        if self.best_state is None:
+            return
+        better = err < self.best_err
+        if counted is not None:
+            better = better & counted
+        self.packed.copy_where(better, state, self.best_state)
+        self.best_err = torch.where(better, err, self.best_err)
+        at = torch.full_like(self.best_iter, it) if isinstance(it, int) else it
+        self.best_iter = torch.where(better, at, self.best_iter)  # nonlinear_optimizer.py:202
+
+    def cut(self, first_unused: int):
+        """Forget the history columns / slots from ``first_unused`` on (the sync-free loop queued past "everybody converged")."""
+        if self.err_hist is not None:
+            self.err_hist[:, first_unused:] = float("inf")
+        if self.state_hist is not None:
+            self.state_hist.cut(first_unused)
+
+    @property
+    def failed(self) -> bool:
+        return bool((self.info.status == NonlinearOptimizerStatus.FAIL).any())
+
+    def finish(self, converged, conv_iter) -> NonlinearOptimizerInfo:
+        """The final bookkeeping, one device->host copy: ``converged`` (B,) bool on the device or None == nobody, ``conv_iter`` (B,)."""
+        info = self.info
+        if converged is not None and not self.failed:
+            cm = converged.cpu().numpy()
+            info.status[cm] = NonlinearOptimizerStatus.CONVERGED
+            info.converged_iter = conv_iter.cpu()
+        info.status[info.status == NonlinearOptimizerStatus.START] = NonlinearOptimizerStatus.MAX_ITERATIONS
+        info.converged_iter[torch.from_numpy(info.status == NonlinearOptimizerStatus.MAX_ITERATIONS)] = -1
+        if self.err_hist is not None:
+            info.err_history = self.err_hist.cpu()
+        if self.state_hist is not None:
+            info.state_history = self.state_hist.to_dict(self.packed)
+        if self.best_state is not None:
+            info.best_err = self.best_err
+            info.best_iter = self.best_iter.cpu()
+            info.best_solution = self.packed.solution_dict(self.best_state)
+        return info
+
+
+@dataclass
+class _LoopState:
+    """What crosses the phases of ``NonlinearLeastSquares._optimize_loop``."""
+    backward_mode: BackwardMode
+    outer_grad: bool                  # the caller's grad mode
+    init_tensors: Optional[list]      # the caller's own tensors of the optimisation variables, where UNROLL starts its graph
+    verbose: bool
+    end_iter_callback: Optional[Callable]
+    kwargs: Dict[str, Any]            # the optimizer kwargs, as the hooks take them
+    loop_iters: int = 0               # iterations of the no-grad loop ...
+    tail_iters: int = 0               # ... and of the differentiable tail behind it (> 0: UNROLL / TRUNCATED with a graph)
+    need_conv: bool = False
+    tracker: Optional[_RunTracker] = None
+    last_err: Optional[torch.Tensor] = None
+    converged: Optional[torch.Tensor] = None          # (B,) bool on device, None == nobody
+    conv_iter: Optional[torch.Tensor] = None
+    spare: Any = None                 # the state buffer the next retraction writes
+    err_new: Optional[torch.Tensor] = None
+    it: int = 0
+    halt: bool = False                # a loop ended early: a failed solve, or everybody converged
+
+    def fail(self):
+        self.tracker.info.status[:] = NonlinearOptimizerStatus.FAIL   # (overrides every status: nonlinear_least_squares.py:147)
+        self.halt = True
+
+
 class NonlinearLeastSquares(abc.ABC):
     _MAX_ALL_REJECT_ATTEMPTS = 3  # nonlinear_optimizer.py:88
 
@@ -228,14 +345,47 @@ class NonlinearLeastSquares(abc.ABC):
                        track_state_history: bool = False, verbose: bool = False,
                        backward_mode: Union[str, BackwardMode] = BackwardMode.UNROLL,
                        end_iter_callback: Optional[Callable] = None, **kwargs) -> NonlinearOptimizerInfo:
+        """The phases of one optimize(), in order: ``_plan``, then ``_sync_free_iterations`` or ``_synchronous_iterations``,
+        ``_differentiable_tail``, ``_implicit_epilogue``, and the tracker's ``finish``."""
+        s = self._plan(backward_mode, verbose, end_iter_callback, kwargs)
+        packed = self.linear_solver.linearization.packed
+        with torch.no_grad():
+            packed.sync()
+            packed.privatize_state()   # never recycle the buffer the previous optimize() handed to the user
+            B, dev, dt = packed.batch, packed.device, self.objective.dtype
+            p = self.params
+            s.need_conv = p.abs_err_tolerance > 0 or p.rel_err_tolerance > 0
+            s.tracker = _RunTracker(packed, p, dt, track_best_solution, track_err_history, track_state_history)
+            s.last_err = s.tracker.info.last_err
+            if verbose:
+                print(f"Nonlinear optimizer. Iteration: 0. Error: {s.last_err.mean().item()}")
+            s.conv_iter = torch.full((B,), -1, dtype=torch.long, device=dev)
+            s.spare = packed.alloc_state()
+            s.err_new = torch.empty(B, dtype=dt, device=dev)
+            sync_free = (isinstance(self.reducer, LocalBatchReducer) and end_iter_callback is None and not verbose
+                         and s.loop_iters > 0)
+            if sync_free:
+                self._sync_free_iterations(s)
+            else:
+                self._synchronous_iterations(s)
+            if s.tail_iters > 0 and not s.tracker.failed:
+                self._differentiable_tail(s)
+            if s.backward_mode == BackwardMode.IMPLICIT and not s.tracker.failed:
+                self._implicit_epilogue(s)
+            packed.flush_variables()
+            if getattr(self.linear_solver, "_check_singular", False) and hasattr(self.linear_solver, "post_singular_warning"):
+                self.linear_solver.post_singular_warning()    # (check_singular=True: the reference warns from inside solve())
+            return s.tracker.finish(s.converged, s.conv_iter)
+
+    def _plan(self, backward_mode, verbose, end_iter_callback, kwargs) -> _LoopState:
+        """Resolve the backward mode, refuse what is refused (before the first sync), sync and ``reset``, and split
+        ``max_iterations`` between the no-grad loop and the differentiable tail."""
         backward_mode = BackwardMode.resolve(backward_mode)
         outer_grad = torch.is_grad_enabled()
         if backward_mode == BackwardMode.DLM:
             raise NotImplementedError("backward_mode=DLM is not supported by the HIP back end "
                                       "(supported: 'implicit'; 'unroll' / 'truncated' see below).")
-        implicit = backward_mode == BackwardMode.IMPLICIT
-        lin: HipLinearization = self.linear_solver.linearization
-        packed = lin.packed
+        packed = self.linear_solver.linearization.packed
         # Differentiating THROUGH iterations (UNROLL: all of them, TRUNCATED: the last ``backward_num_iterations``;
         # nonlinear_least_squares.py:222-282): the Hessian is part of the graph there, i.e. the derivatives of every cost's
         # Jacobian are needed.  The generic path has them (its blocks come from torch: theseus_amd/euclidean.py); the fused
@@ -268,401 +418,301 @@ class NonlinearLeastSquares(abc.ABC):
             finally:
                 packed._defer_repoint = False
         self.reset(**kwargs, backward_mode=backward_mode)
-        tail_iters = 0
-        if implicit:
-            _, loop_iters = self._split_backward_iters(backward_mode=backward_mode, **kwargs)
+        s = _LoopState(backward_mode, outer_grad, init_tensors, verbose, end_iter_callback, kwargs)
+        if backward_mode == BackwardMode.IMPLICIT:
+            _, s.loop_iters = self._split_backward_iters(backward_mode=backward_mode, **kwargs)
         elif backward_mode == BackwardMode.TRUNCATED:
             # (without anything to differentiate the two loops of the reference are one loop with a fresh convergence mask in
             #  between; run as the differentiable tail only when there is a graph to build)
             tail, head = self._split_backward_iters(backward_mode=backward_mode, **kwargs)
-            loop_iters, tail_iters = (head, tail) if unrolled else (self.params.max_iterations, 0)
+            s.loop_iters, s.tail_iters = (head, tail) if unrolled else (self.params.max_iterations, 0)
         else:
-            loop_iters, tail_iters = (0, self.params.max_iterations) if unrolled else (self.params.max_iterations, 0)
-        with torch.no_grad():
-            packed.sync()
-            packed.privatize_state()   # never recycle the buffer the previous optimize() handed to the user
-            B = packed.batch
-            dev, dt = packed.device, self.objective.dtype
-            p = self.params
-            need_conv = p.abs_err_tolerance > 0 or p.rel_err_tolerance > 0
-            adaptive = bool(kwargs.get("adaptive_damping", False))
-            inf = float("inf")
+            s.loop_iters, s.tail_iters = (0, self.params.max_iterations) if unrolled else (self.params.max_iterations, 0)
+        return s
 
-            def fresh_info():
-                last = packed.error_metric()
-                hist = None
-                if track_err_history:
-                    hist = torch.full((B, p.max_iterations + 1), inf, dtype=dt, device=dev)
-                    hist[:, 0] = last
-                return last, hist, NonlinearOptimizerInfo(
-                    best_solution=None, status=np.array([NonlinearOptimizerStatus.START] * B),
-                    converged_iter=torch.full((B,), -1, dtype=torch.long), best_iter=torch.zeros(B, dtype=torch.long),
-                    err_history=hist, last_err=last, best_err=last.clone())
+    def _warn_solver_failed(self, raised=None):
+        """A linear solve failed (nonlinear_least_squares.py:138-152): warn with the error ``raised`` on this rank, else the one
+        the solver's own info holds, else -- the flag came through an all-reduce -- that of another shard."""
+        try:
+            if raised is not None:
+                raise raised
+            self.linear_solver.check_info()
+            raise RuntimeError("the linear solve failed on another shard of the batch")
+        except RuntimeError as run_err:
+            warnings.warn(f"There was an error while running the linear optimizer. Original error message: {run_err}.",
+                          RuntimeWarning)
 
-            last_err, err_hist, info = fresh_info()
-            state_hist = _StateHistory(packed.state, p.max_iterations + 1) if track_state_history else None
-            if track_best_solution:
-                best_state = packed.clone_state()
-                best_err = last_err.clone()
-                best_iter = torch.zeros(B, dtype=torch.long, device=dev)
-            if verbose:
-                print(f"Nonlinear optimizer. Iteration: 0. Error: {last_err.mean().item()}")
-
-            converged = None          # (B,) bool on device, None == nobody
-            conv_iter = torch.full((B,), -1, dtype=torch.long, device=dev)
-            spare = packed.alloc_state()
-            err_new = torch.empty(B, dtype=dt, device=dev)
-            it, all_reject_attempts = 0, 0
-
-            def warn_failed(run_err):
-                warnings.warn(f"There was an error while running the linear optimizer. Original error message: {run_err}.",
-                              RuntimeWarning)
-
-            # ---- SYNC-FREE iterations.  The host decisions of the reference's iteration -- "did a linear
-            #      solve fail?" (nonlinear_least_squares.py:138-152), "were ALL steps rejected?" (:358-359, the retry that
-            #      does not count as an iteration), "has EVERY problem converged?" (:202) -- are evaluated on the device
-            #      (all-reduced over the shards when the batch is sharded) and kept there as three flags; everything else
-            #      of the iteration is per-problem masked work: rejected problems keep their state and error
-            #      (thx_copy_where), converged / failed ones are frozen through the retraction mask, lambda lives in a device
-            #      vector (thx_lm_accept).  The iterations are queued back to back and the flags are read ONCE after the loop:
-            #        * a failed solve froze every later update on the device: FAIL status, iters_done = the failing iteration;
-            #        * everybody converged at iteration k: later iterations were no-ops on frozen problems, the bookkeeping
-            #          is cut at k (a lagged, non-blocking poll of the flag stops the queueing a couple of iterations later);
-            #        * an ALL-rejected step is the reference's uncounted retry: the iteration counter itself lives on the
-            #          device (see below), nothing is replayed.
-            #      Callbacks and verbose printing need the host every iteration: synchronous path. ----
-            sync_free = (isinstance(self.reducer, LocalBatchReducer) and end_iter_callback is None and not verbose
-                         and loop_iters > 0)
-            halt = False
-            if sync_free:
-                # What the host queues are ATTEMPTS.  An all-rejected attempt leaves every problem's state and error where they
-                # were and has already moved lambda / the trust region -- which is precisely the reference's retry
-                # (nonlinear_least_squares.py:358-359: ``continue`` without counting the iteration; the third all-rejected attempt
-                # in a row is counted with err = last_err, nonlinear_optimizer.py:88).  So nothing is replayed: the ITERATION
-                # COUNTER lives on the device (``it_dev``), the histories are written at device-side column indices, and after the
-                # queued attempts the host reads the counter and queues what is missing (no all-rejection: one round, one sync).
-                flag = lambda v: torch.full((), v, dtype=torch.long, device=dev)  # noqa: E731
-                failed = torch.zeros((), dtype=torch.bool, device=dev)
-                first_fail, first_all_conv = flag(-1), flag(-1)
-                it_dev, attempts_dev = flag(0), flag(0)
-                true0 = torch.ones((), dtype=torch.bool, device=dev)
-                # (the lagged poll is a per-process decision: a sharded batch runs all its attempts, so that every rank
-                #  issues the same all-reduces)
-                poll = _LaggedFlag(dev) if (need_conv and self.reducer.world_size == 1) else None
-                raised = None
-                while True:
-                    for _ in range(loop_iters - it):
-                        if poll is not None and poll.seen():
-                            break   # everybody converged a moment ago: stop queueing (the cut below is exact)
-                        local_fail = None
-                        if raised is None:
-                            lin.linearize()
-                            try:
-                                delta = self.compute_delta(**kwargs)
-                                local_fail = self.linear_solver.info.ne(0).any()
-                            except RuntimeError as run_err:
-                                # a host-side error on THIS rank: the other shards are (or will be) waiting in device_any()'s
-                                # all-reduce -- keep taking part in it with the flag raised instead of leaving the loop
-                                raised = run_err
-                        if raised is not None:
-                            self._join_compute_delta()
-                            delta = torch.zeros(B, lin.num_cols, dtype=dt, device=dev)
-                            local_fail = torch.ones((), dtype=torch.bool, device=dev)
-                        now = self.reducer.device_any(local_fail)
-                        first_fail = torch.where(now & ~failed, it_dev, first_fail)
-                        failed = failed | now
-                        stop = failed | it_dev.ge(loop_iters)        # nothing moves after a failure / beyond the last iteration
-                        frozen = stop.expand(B) if converged is None else (converged | stop)
-                        packed.retract(delta, p.step_size, frozen.to(torch.uint8).contiguous(), spare)
-                        packed.error_metric(state=spare, out=err_new)
-                        reject = self._complete_step(delta, err_new, last_err, step_size=p.step_size, **kwargs)
-                        counted = ~stop
-                        if reject is not None:
-                            rb = reject.bool()
-                            all_rej = self.reducer.device_all(rb.all())
-                            forced = attempts_dev.ge(self._MAX_ALL_REJECT_ATTEMPTS - 1)
-                            counted = counted & (~all_rej | forced)
-                            attempts_dev = torch.where(all_rej & ~forced & ~stop, attempts_dev + 1, torch.zeros_like(attempts_dev))
-                            packed.keep_where(rb, spare)                                   # rejected problems keep their state
-                            packed.K.copy_where(rb, last_err.view(1, -1, 1), err_new.view(1, -1, 1))   # ... and their error
-                        err = torch.where(stop, last_err, err_new)
-                        spare = packed.swap_state(spare)
-                        if err_hist is not None:
-                            col = (it_dev + 1).clamp(max=p.max_iterations).view(1)
-                            cur = err_hist.index_select(1, col)
-                            err_hist.index_copy_(1, col, torch.where(counted, err.unsqueeze(1), cur))
-                        if state_hist is not None:
-                            state_hist.record(it_dev + 1, packed.state, counted)
-                        if track_best_solution:
-                            better = (err < best_err) & counted
-                            packed.copy_where(better, packed.state, best_state)
-                            best_err = torch.where(better, err, best_err)
-                            best_iter = torch.where(better, it_dev, best_iter)  # nonlinear_optimizer.py:202
-                        if need_conv:
-                            small = self.reducer.device_mean_abs_below(err, p.abs_err_tolerance)
-                            conv_now = self._check_convergence(err, last_err) | small
-                            # (an uncounted attempt -- all rejected, err == last_err everywhere -- converges nobody)
-                            converged = (conv_now & counted) if converged is None else torch.where(counted, conv_now, converged)
-                            conv_iter = torch.where(converged & (conv_iter < 0) & counted, it_dev + 1, conv_iter)
-                            all_conv = self.reducer.device_all(converged.all()) & counted
-                            first_all_conv = torch.where(all_conv & (first_all_conv < 0), it_dev + 1, first_all_conv)
-                            if poll is not None:
-                                poll.post(first_all_conv >= 0)
-                        last_err = err
-                        it_dev = it_dev + counted.long()
-                    # ---- the one host sync of the round ----
-                    f_fail, f_conv, it_now = torch.stack([first_fail, first_all_conv, it_dev]).tolist()
-                    if f_fail >= 0 and not (f_conv >= 0 and f_conv < f_fail + 1):
-                        try:
-                            if raised is not None:
-                                raise raised
-                            self.linear_solver.check_info()
-                            raise RuntimeError("the linear solve failed on another shard of the batch")
-                        except RuntimeError as run_err:
-                            warn_failed(run_err)
-                        info.status[:] = NonlinearOptimizerStatus.FAIL   # (overrides every status: nonlinear_least_squares.py:147)
-                        it = f_fail
-                        halt = True
-                    elif f_conv >= 0:
-                        # the reference broke out of its loop here, BEFORE counting the converging iteration (:202-203): its error
-                        # is in err_history[:, f_conv], the iteration count stays at f_conv - 1 (the synchronous path below and
-                        # the implicit epilogue -- which writes its error at [iters_done + 1], as _merge_infos does -- agree)
-                        it = f_conv - 1
-                        if err_hist is not None:
-                            err_hist[:, f_conv + 1:] = inf
-                        if state_hist is not None:
-                            state_hist.cut(f_conv + 1)
-                        converged = conv_iter.ge(0) & conv_iter.le(f_conv)   # (later iterations only re-marked frozen problems)
-                        conv_iter = torch.where(converged, conv_iter, torch.full_like(conv_iter, -1))
-                        halt = True
-                    else:
-                        it = it_now
-                    if halt or it >= loop_iters:
-                        break
-                info.last_err = last_err   # (frozen / failed problems kept their error: this is the error AT ``it``)
-                info.iters_done = it
-            else:
-                # ---- synchronous path (callbacks, verbose): one host decision per iteration ----
-                while it < loop_iters:
+    def _sync_free_iterations(self, s: _LoopState):
+        # ---- SYNC-FREE iterations (SURVEY.md §8f-1).  The host decisions of the reference's iteration -- "did a linear
+        #      solve fail?" (nonlinear_least_squares.py:138-152), "were ALL steps rejected?" (:358-359, the retry that
+        #      does not count as an iteration), "has EVERY problem converged?" (:202) -- are evaluated on the device
+        #      (all-reduced over the shards when the batch is sharded) and kept there as three flags; everything else
+        #      of the iteration is per-problem masked work: rejected problems keep their state and error
+        #      (thx_copy_where), converged / failed ones are frozen through the retraction mask, lambda lives in a device
+        #      vector (thx_lm_accept).  The iterations are queued back to back and the flags are read ONCE after the loop:
+        #        * a failed solve froze every later update on the device: FAIL status, iters_done = the failing iteration;
+        #        * everybody converged at iteration k: later iterations were no-ops on frozen problems, the bookkeeping
+        #          is cut at k (a lagged, non-blocking poll of the flag stops the queueing a couple of iterations later);
+        #        * an ALL-rejected step is the reference's uncounted retry: the iteration counter itself lives on the
+        #          device (see below), nothing is replayed.
+        #      Callbacks and verbose printing need the host every iteration: synchronous path. ----
+        # What the host queues are ATTEMPTS.  An all-rejected attempt leaves every problem's state and error where they
+        # were and has already moved lambda / the trust region -- which is precisely the reference's retry
+        # (nonlinear_least_squares.py:358-359: ``continue`` without counting the iteration; the third all-rejected attempt
+        # in a row is counted with err = last_err, nonlinear_optimizer.py:88).  So nothing is replayed: the ITERATION
+        # COUNTER lives on the device (``it_dev``), the histories are written at device-side column indices, and after the
+        # queued attempts the host reads the counter and queues what is missing (no all-rejection: one round, one sync).
+        lin: HipLinearization = self.linear_solver.linearization
+        packed, p, tr, kwargs, loop_iters = lin.packed, self.params, s.tracker, s.kwargs, s.loop_iters
+        B, dev, dt = packed.batch, packed.device, self.objective.dtype
+        flag = lambda v: torch.full((), v, dtype=torch.long, device=dev)  # noqa: E731
+        failed = torch.zeros((), dtype=torch.bool, device=dev)
+        first_fail, first_all_conv = flag(-1), flag(-1)
+        it_dev, attempts_dev = flag(0), flag(0)
+        # (the lagged poll is a per-process decision: a sharded batch runs all its attempts, so that every rank
+        #  issues the same all-reduces)
+        poll = _LaggedFlag(dev) if (s.need_conv and self.reducer.world_size == 1) else None
+        raised = None
+        while True:
+            for _ in range(loop_iters - s.it):
+                if poll is not None and poll.seen():
+                    break   # everybody converged a moment ago: stop queueing (the cut below is exact)
+                local_fail = None
+                if raised is None:
                     lin.linearize()
                     try:
                         delta = self.compute_delta(**kwargs)
+                        local_fail = self.linear_solver.info.ne(0).any()
                     except RuntimeError as run_err:
-                        if self.reducer.world_size > 1:
-                            # the other shards are (or will be) waiting in compute_delta's collectives and in this iteration's
-                            # decide(): take part in both with the failure flag raised, so that EVERY rank leaves the loop here
-                            self._join_compute_delta()
-                            one = torch.ones(1, dtype=torch.bool, device=dev)
-                            rej = [one] if self._may_reject(kwargs) else []
-                            self.reducer.decide([one] + rej, rej)
-                        warn_failed(run_err)
-                        info.status[:] = NonlinearOptimizerStatus.FAIL
-                        halt = True
-                        break
-                    # retract (converged problems frozen) + error of the candidate, fused HIP kernels
-                    packed.retract(delta, p.step_size, converged, spare)
-                    packed.error_metric(state=spare, out=err_new)
-                    reject = self._complete_step(delta, err_new, last_err, step_size=p.step_size, **kwargs)
-                    # ---- the only host sync of the iteration: [solver failed | all rejected, any rejected], over
-                    #      the GLOBAL batch (self.reducer all-reduces across shards when the batch is sharded) ----
-                    any_f = [self.linear_solver.info.ne(0)]
-                    all_f = []
-                    if reject is not None:
-                        rb = reject.bool()
-                        any_f.append(rb)
-                        all_f.append(rb)
-                    any_r, all_r = self.reducer.decide(any_f, all_f)
-                    if any_r[0]:
-                        try:
-                            self.linear_solver.check_info()
-                            raise RuntimeError("the linear solve failed on another shard of the batch")
-                        except RuntimeError as run_err:
-                            warn_failed(run_err)
-                        info.status[:] = NonlinearOptimizerStatus.FAIL
-                        halt = True
-                        break
-                    if reject is not None:
-                        all_rej, any_rej = all_r[0], any_r[1]
-                        if all_rej:
-                            all_reject_attempts += 1
-                            if all_reject_attempts < self._MAX_ALL_REJECT_ATTEMPTS:
-                                continue
-                            err = last_err
-                        else:
-                            if any_rej:
-                                rb = reject.bool()
-                                packed.keep_where(rb, spare)
-                                packed.K.copy_where(rb, last_err.view(1, -1, 1), err_new.view(1, -1, 1))
-                                err = err_new.clone()
-                            else:
-                                err = err_new.clone()
-                            spare = packed.swap_state(spare)
-                    else:
-                        err = err_new.clone()
-                        spare = packed.swap_state(spare)
-                    all_reject_attempts = 0
-                    if err_hist is not None:
-                        err_hist[:, it + 1] = err
-                    if state_hist is not None:
-                        state_hist.record(it + 1, packed.state)
-                    if track_best_solution:
-                        better = err < best_err
-                        packed.copy_where(better, packed.state, best_state)
-                        best_err = torch.where(better, err, best_err)
-                        best_iter = torch.where(better, torch.full_like(best_iter, it), best_iter)  # nonlinear_optimizer.py:202
-                    if verbose:
-                        print(f"Nonlinear optimizer. Iteration: {it + 1}. Error: {err.mean().item()}")
-                    if need_conv:
-                        if self.reducer.mean_abs(err) < p.abs_err_tolerance:
-                            converged = torch.ones(B, dtype=torch.bool, device=dev)
-                        else:
-                            converged = self._check_convergence(err, last_err)
-                        conv_iter = torch.where(converged & (conv_iter < 0), torch.full_like(conv_iter, it + 1), conv_iter)
-                        if self.reducer.decide([], [converged])[1][0]:
-                            info.last_err = err
-                            halt = True
-                            break
-                    last_err = err
+                        # a host-side error on THIS rank: the other shards are (or will be) waiting in device_any()'s
+                        # all-reduce -- keep taking part in it with the flag raised instead of leaving the loop
+                        raised = run_err
+                if raised is not None:
+                    self._join_compute_delta()
+                    delta = torch.zeros(B, lin.num_cols, dtype=dt, device=dev)
+                    local_fail = torch.ones((), dtype=torch.bool, device=dev)
+                now = self.reducer.device_any(local_fail)
+                first_fail = torch.where(now & ~failed, it_dev, first_fail)
+                failed = failed | now
+                stop = failed | it_dev.ge(loop_iters)        # nothing moves after a failure / beyond the last iteration
+                frozen = stop.expand(B) if s.converged is None else (s.converged | stop)
+                packed.retract(delta, p.step_size, frozen.to(torch.uint8).contiguous(), s.spare)
+                packed.error_metric(state=s.spare, out=s.err_new)
+                reject = self._complete_step(delta, s.err_new, s.last_err, step_size=p.step_size, **kwargs)
+                counted = ~stop
+                if reject is not None:
+                    rb = reject.bool()
+                    all_rej = self.reducer.device_all(rb.all())
+                    forced = attempts_dev.ge(self._MAX_ALL_REJECT_ATTEMPTS - 1)
+                    counted = counted & (~all_rej | forced)
+                    attempts_dev = torch.where(all_rej & ~forced & ~stop, attempts_dev + 1, torch.zeros_like(attempts_dev))
+                    packed.keep_where(rb, s.spare)                                   # rejected problems keep their state
+                    packed.K.copy_where(rb, s.last_err.view(1, -1, 1), s.err_new.view(1, -1, 1))   # ... and their error
+                err = torch.where(stop, s.last_err, s.err_new)
+                s.spare = packed.swap_state(s.spare)
+                tr.record(it_dev, packed.state, err, counted)
+                if s.need_conv:
+                    small = self.reducer.device_mean_abs_below(err, p.abs_err_tolerance)
+                    conv_now = self._check_convergence(err, s.last_err) | small
+                    # (an uncounted attempt -- all rejected, err == last_err everywhere -- converges nobody)
+                    s.converged = (conv_now & counted) if s.converged is None else torch.where(counted, conv_now, s.converged)
+                    s.conv_iter = torch.where(s.converged & (s.conv_iter < 0) & counted, it_dev + 1, s.conv_iter)
+                    all_conv = self.reducer.device_all(s.converged.all()) & counted
+                    first_all_conv = torch.where(all_conv & (first_all_conv < 0), it_dev + 1, first_all_conv)
+                    if poll is not None:
+                        poll.post(first_all_conv >= 0)
+                s.last_err = err
+                it_dev = it_dev + counted.long()
+            # ---- the one host sync of the round ----
+            f_fail, f_conv, it_now = torch.stack([first_fail, first_all_conv, it_dev]).tolist()
+            if f_fail >= 0 and not (f_conv >= 0 and f_conv < f_fail + 1):
+                self._warn_solver_failed(raised)
+                s.fail()
+                s.it = f_fail
+            elif f_conv >= 0:
+                # the reference broke out of its loop here, BEFORE counting the converging iteration (:202-203): its error
+                # is in err_history[:, f_conv], the iteration count stays at f_conv - 1 (the synchronous path below and
+                # the implicit epilogue -- which writes its error at [iters_done + 1], as _merge_infos does -- agree)
+                s.it = f_conv - 1
+                tr.cut(f_conv + 1)
+                s.converged = s.conv_iter.ge(0) & s.conv_iter.le(f_conv)   # (later iterations only re-marked frozen problems)
+                s.conv_iter = torch.where(s.converged, s.conv_iter, torch.full_like(s.conv_iter, -1))
+                s.halt = True
+            else:
+                s.it = it_now
+            if s.halt or s.it >= loop_iters:
+                break
+        tr.info.last_err = s.last_err   # (frozen / failed problems kept their error: this is the error AT ``it``)
+        tr.info.iters_done = s.it
+
+    def _synchronous_iterations(self, s: _LoopState):
+        # ---- synchronous path (callbacks, verbose): one host decision per iteration ----
+        lin: HipLinearization = self.linear_solver.linearization
+        packed, p, tr, kwargs = lin.packed, self.params, s.tracker, s.kwargs
+        B, dev, info = packed.batch, packed.device, tr.info
+        all_reject_attempts = 0
+        while s.it < s.loop_iters:
+            lin.linearize()
+            try:
+                delta = self.compute_delta(**kwargs)
+            except RuntimeError as run_err:
+                if self.reducer.world_size > 1:
+                    # the other shards are (or will be) waiting in compute_delta's collectives and in this iteration's
+                    # decide(): take part in both with the failure flag raised, so that EVERY rank leaves the loop here
+                    self._join_compute_delta()
+                    one = torch.ones(1, dtype=torch.bool, device=dev)
+                    rej = [one] if self._may_reject(kwargs) else []
+                    self.reducer.decide([one] + rej, rej)
+                self._warn_solver_failed(run_err)
+                s.fail()
+                break
+            # retract (converged problems frozen) + error of the candidate, fused HIP kernels
+            packed.retract(delta, p.step_size, s.converged, s.spare)
+            packed.error_metric(state=s.spare, out=s.err_new)
+            reject = self._complete_step(delta, s.err_new, s.last_err, step_size=p.step_size, **kwargs)
+            # ---- the only host sync of the iteration: [solver failed | all rejected, any rejected], over
+            #      the GLOBAL batch (self.reducer all-reduces across shards when the batch is sharded) ----
+            solver_failed = self.linear_solver.info.ne(0)
+            rej = [] if reject is None else [reject.bool()]
+            any_r, all_r = self.reducer.decide([solver_failed] + rej, rej)
+            if any_r[0]:
+                self._warn_solver_failed()
+                s.fail()
+                break
+            if reject is not None and all_r[0]:       # all rejected: the reference's uncounted retry, counted the third time
+                all_reject_attempts += 1
+                if all_reject_attempts < self._MAX_ALL_REJECT_ATTEMPTS:
+                    continue
+                err = s.last_err
+            else:
+                if reject is not None and any_r[1]:   # rejected problems keep their state and their error
+                    rb = reject.bool()
+                    packed.keep_where(rb, s.spare)
+                    packed.K.copy_where(rb, s.last_err.view(1, -1, 1), s.err_new.view(1, -1, 1))
+                err = s.err_new.clone()
+                s.spare = packed.swap_state(s.spare)
+            all_reject_attempts = 0
+            tr.record(s.it, packed.state, err)
+            if s.verbose:
+                print(f"Nonlinear optimizer. Iteration: {s.it + 1}. Error: {err.mean().item()}")
+            if s.need_conv:
+                if self.reducer.mean_abs(err) < p.abs_err_tolerance:
+                    s.converged = torch.ones(B, dtype=torch.bool, device=dev)
+                else:
+                    s.converged = self._check_convergence(err, s.last_err)
+                s.conv_iter = torch.where(s.converged & (s.conv_iter < 0), torch.full_like(s.conv_iter, s.it + 1), s.conv_iter)
+                if self.reducer.decide([], [s.converged])[1][0]:
                     info.last_err = err
-                    if end_iter_callback is not None:
-                        packed.flush_variables()
-                        end_iter_callback(self, info, delta, it)
-                    it += 1
-                    info.iters_done = it
+                    s.halt = True
+                    break
+            self._iteration_done(s, err, delta)
 
-            # ---- BackwardMode.UNROLL / TRUNCATED with a graph: the reference's SECOND loop (nonlinear_least_squares.py:264-282)
-            #      -- same iteration, caller's grad mode, a fresh convergence mask -- then _merge_infos
-            #      (nonlinear_optimizer.py:220-266).  Host-synchronous: these are a handful of small iterations. ----
-            if tail_iters > 0 and not (info.status == NonlinearOptimizerStatus.FAIL).any():
-                packed.flush_variables()
-                with torch.set_grad_enabled(outer_grad):
-                    packed.prepare_unroll()
-                det = lambda x: tuple(y.detach() for y in x) if isinstance(x, tuple) else x.detach()  # noqa: E731  (BA: (cams, points))
-                X = det(packed.state)
-                if init_tensors is not None and it == 0 and hasattr(packed, "state_with_graph"):
-                    with torch.set_grad_enabled(outer_grad):
-                        X = packed.state_with_graph(init_tensors)     # same values, the caller's autograd history
-                g_conv = torch.zeros(B, dtype=torch.bool, device=dev)
-                g_conv_iter = torch.zeros(B, dtype=torch.long, device=dev)   # the reference's counter: += 1 while not converged
-                g_status_conv = torch.zeros(B, dtype=torch.bool, device=dev)
-                g_last, g_it, attempts, g_errs = last_err, 0, 0, []
-                while g_it < tail_iters:
-                    with torch.set_grad_enabled(outer_grad):
-                        X_cand, delta = packed.unrolled_step(self, X, g_conv, kwargs)
-                    err_new = packed.error_metric(state=det(X_cand))
-                    reject = self._complete_step(delta.detach(), err_new, g_last, step_size=p.step_size, **kwargs)
-                    if reject is not None:
-                        rb = reject.bool()
-                        if bool(rb.all()):
-                            attempts += 1
-                            if attempts < self._MAX_ALL_REJECT_ATTEMPTS:
-                                continue
-                        with torch.set_grad_enabled(outer_grad):
-                            X_cand = packed.where_state(rb, X, X_cand)
-                        err = torch.where(rb, g_last, err_new)
-                    else:
-                        err = err_new
-                    attempts = 0
-                    X = X_cand
-                    # _update_info, THEN _check_convergence (nonlinear_least_squares.py:192-203): the iteration on which everybody
-                    # converges is not counted, but it has been through _update_info -- it competes for best_solution, and in UNROLL's
-                    # single loop its error / state are in the histories at [it + 1].  TRUNCATED's second loop has its own info, of
-                    # which _merge_infos (nonlinear_optimizer.py:220-266) copies ``grad_iters_done`` history columns (not the
-                    # converging iteration's), merges best_solution / best_err, and leaves best_iter the first loop's.
-                    single_loop = backward_mode == BackwardMode.UNROLL
-                    g_conv_iter = g_conv_iter + (~g_conv).long()
-                    if verbose:
-                        print(f"Nonlinear optimizer. Iteration: {it + g_it + 1}. Error: {err.mean().item()}")
-                    conv_new, everybody = g_conv, False
-                    if need_conv:
-                        conv_new = (torch.ones_like(g_conv) if self.reducer.mean_abs(err) < p.abs_err_tolerance
-                                    else self._check_convergence(err, g_last))
-                        everybody = bool(conv_new.all())
-                    if single_loop or not everybody:
-                        g_errs.append(err)
-                        if state_hist is not None:         # (detached copies, nonlinear_optimizer.py:150-207)
-                            state_hist.record(it + g_it + 1, det(X))
-                    if track_best_solution:
-                        better = err < best_err
-                        packed.copy_where(better, det(X), best_state)
-                        best_err = torch.where(better, err, best_err)
-                        if single_loop:
-                            best_iter = torch.where(better, torch.full_like(best_iter, it + g_it), best_iter)
-                    if need_conv:
-                        g_conv = conv_new
-                        g_status_conv = g_status_conv | g_conv
-                        if everybody:
-                            break
-                    g_last = err
-                    if end_iter_callback is not None:
-                        packed.swap_state(X, repoint=True)
-                        end_iter_callback(self, info, delta.detach(), it + g_it)
-                    g_it += 1
-                packed.swap_state(X, repoint=True)      # the variables view the (graph-carrying) result
-                # _merge_infos
-                if err_hist is not None and g_errs:
-                    err_hist[:, it + 1:it + 1 + len(g_errs)] = torch.stack(g_errs, 1)   # (UNROLL: the converging iteration's too)
-                undecided = ~(converged if converged is not None else torch.zeros(B, dtype=torch.bool, device=dev))
-                if need_conv:
-                    # problems the first loop left at MAX_ITERATIONS take the second loop's verdict; their counters add up
-                    first_count = torch.full_like(conv_iter, it)
-                    newly = undecided & g_status_conv
-                    conv_iter = torch.where(newly, first_count + g_conv_iter, conv_iter)
-                    converged = newly if converged is None else (converged | newly)
-                # TRUNCATED: _merge_infos leaves the FIRST loop's last_err in the merged info (nonlinear_optimizer.py:220-266);
-                # UNROLL is ONE loop in the reference (nonlinear_least_squares.py:252-268), whose _update_info sets it every iteration
-                info.last_err = g_last.detach() if backward_mode == BackwardMode.UNROLL else last_err
-                it += g_it
-                info.iters_done = it
+    def _iteration_done(self, s: _LoopState, err, delta):
+        """The end of a counted iteration of the no-grad loop or of the implicit epilogue: the callback sees the new state."""
+        info = s.tracker.info
+        s.last_err = info.last_err = err
+        if s.end_iter_callback is not None:
+            self.linear_solver.linearization.packed.flush_variables()
+            s.end_iter_callback(self, info, delta, s.it)
+        s.it += 1
+        info.iters_done = s.it
 
-            # ---- BackwardMode.IMPLICIT: the last step is an undamped Gauss-Newton step with the Hessian detached,
-            #      executed under the caller's grad mode (nonlinear_least_squares.py:121-135,265-292) ----
-            if implicit and not (info.status == NonlinearOptimizerStatus.FAIL).any():
-                X_new, delta = self._implicit_last_step(packed, outer_grad, kwargs)
-                X_det = tuple(x.detach() for x in X_new) if isinstance(X_new, tuple) else X_new.detach()
-                err = packed.error_metric(state=X_det)
-                packed.swap_state(X_new)
-                if err_hist is not None:
-                    err_hist[:, it + 1] = err
-                if state_hist is not None:
-                    state_hist.record(it + 1, X_det)
-                if track_best_solution:
-                    better = err < best_err
-                    packed.copy_where(better, X_det, best_state)
-                    best_err = torch.where(better, err, best_err)
-                    best_iter = torch.where(better, torch.full_like(best_iter, it), best_iter)  # nonlinear_optimizer.py:202
-                if need_conv:
-                    # _merge_infos (nonlinear_least_squares.py:216-263): a problem that converged in the no-grad loop stays
-                    # CONVERGED whatever the final Gauss-Newton step does
-                    last_step = self._check_convergence(err, last_err)
-                    converged = last_step if converged is None else (converged | last_step)
-                    conv_iter = torch.where(converged & (conv_iter < 0), torch.full_like(conv_iter, it + 1), conv_iter)
-                last_err = err
-                info.last_err = err
-                if end_iter_callback is not None:
-                    packed.flush_variables()
-                    end_iter_callback(self, info, delta.detach(), it)
-                it += 1
-                info.iters_done = it
-            packed.flush_variables()
-            # ---- bookkeeping, one device->host copy ----
-            if getattr(self.linear_solver, "_check_singular", False) and hasattr(self.linear_solver, "post_singular_warning"):
-                self.linear_solver.post_singular_warning()    # (check_singular=True: the reference warns from inside solve())
-            if converged is not None and not (info.status == NonlinearOptimizerStatus.FAIL).any():
-                cm = converged.cpu().numpy()
-                info.status[cm] = NonlinearOptimizerStatus.CONVERGED
-                info.converged_iter = conv_iter.cpu()
-            info.status[info.status == NonlinearOptimizerStatus.START] = NonlinearOptimizerStatus.MAX_ITERATIONS
-            info.converged_iter[torch.from_numpy(info.status == NonlinearOptimizerStatus.MAX_ITERATIONS)] = -1
-            if err_hist is not None:
-                info.err_history = err_hist.cpu()
-            if state_hist is not None:
-                info.state_history = state_hist.to_dict(packed)
-            if track_best_solution:
-                info.best_err = best_err
-                info.best_iter = best_iter.cpu()
-                info.best_solution = packed.solution_dict(best_state)
-        return info
+    def _differentiable_tail(self, s: _LoopState):
+        # ---- BackwardMode.UNROLL / TRUNCATED with a graph: the reference's SECOND loop (nonlinear_least_squares.py:264-282)
+        #      -- same iteration, caller's grad mode, a fresh convergence mask -- then _merge_infos
+        #      (nonlinear_optimizer.py:220-266).  Host-synchronous: these are a handful of small iterations. ----
+        packed, p, tr, kwargs = self.linear_solver.linearization.packed, self.params, s.tracker, s.kwargs
+        B, dev, it = packed.batch, packed.device, s.it
+        packed.flush_variables()
+        with torch.set_grad_enabled(s.outer_grad):
+            packed.prepare_unroll()
+        X = _detached(packed.state)
+        if s.init_tensors is not None and it == 0 and hasattr(packed, "state_with_graph"):
+            with torch.set_grad_enabled(s.outer_grad):
+                X = packed.state_with_graph(s.init_tensors)     # same values, the caller's autograd history
+        g_conv = torch.zeros(B, dtype=torch.bool, device=dev)
+        g_conv_iter = torch.zeros(B, dtype=torch.long, device=dev)   # the reference's counter: += 1 while not converged
+        g_status_conv = torch.zeros(B, dtype=torch.bool, device=dev)
+        g_last, g_it, attempts = s.last_err, 0, 0
+        single_loop = s.backward_mode == BackwardMode.UNROLL
+        first_best_iter = tr.best_iter   # (keep_best rebinds tr.best_iter to a new tensor: this one is never written)
+        while g_it < s.tail_iters:
+            with torch.set_grad_enabled(s.outer_grad):
+                X_cand, delta = packed.unrolled_step(self, X, g_conv, kwargs)
+            err_new = packed.error_metric(state=_detached(X_cand))
+            reject = self._complete_step(delta.detach(), err_new, g_last, step_size=p.step_size, **kwargs)
+            if reject is not None:
+                rb = reject.bool()
+                if bool(rb.all()):
+                    attempts += 1
+                    if attempts < self._MAX_ALL_REJECT_ATTEMPTS:
+                        continue
+                with torch.set_grad_enabled(s.outer_grad):
+                    X_cand = packed.where_state(rb, X, X_cand)
+                err = torch.where(rb, g_last, err_new)
+            else:
+                err = err_new
+            attempts = 0
+            X = X_cand
+            # _update_info, THEN _check_convergence (nonlinear_least_squares.py:192-203): the iteration on which everybody
+            # converges is not counted, but it has been through _update_info -- it competes for best_solution, and in UNROLL's
+            # single loop its error / state are in the histories at [it + 1].  TRUNCATED's second loop has its own info, of
+            # which _merge_infos (nonlinear_optimizer.py:220-266) copies ``grad_iters_done`` history columns (not the
+            # converging iteration's), merges best_solution / best_err, and leaves best_iter the first loop's.
+            g_conv_iter = g_conv_iter + (~g_conv).long()
+            if s.verbose:
+                print(f"Nonlinear optimizer. Iteration: {it + g_it + 1}. Error: {err.mean().item()}")
+            conv_new, everybody = g_conv, False
+            if s.need_conv:
+                conv_new = (torch.ones_like(g_conv) if self.reducer.mean_abs(err) < p.abs_err_tolerance
+                            else self._check_convergence(err, g_last))
+                everybody = bool(conv_new.all())
+            if single_loop or not everybody:
+                tr.record_history(it + g_it, _detached(X), err)   # (detached copies, nonlinear_optimizer.py:150-207)
+            tr.keep_best(it + g_it, _detached(X), err)
+            if s.need_conv:
+                g_conv = conv_new
+                g_status_conv = g_status_conv | g_conv
+                if everybody:
+                    break
+            g_last = err
+            if s.end_iter_callback is not None:
+                packed.swap_state(X, repoint=True)
+                s.end_iter_callback(self, tr.info, delta.detach(), it + g_it)
+            g_it += 1
+        packed.swap_state(X, repoint=True)      # the variables view the (graph-carrying) result
+        # _merge_infos
+        if not single_loop:
+            tr.best_iter = first_best_iter   # (TRUNCATED: best_iter stays the first loop's)
+        undecided = ~(s.converged if s.converged is not None else torch.zeros(B, dtype=torch.bool, device=dev))
+        if s.need_conv:
+            # problems the first loop left at MAX_ITERATIONS take the second loop's verdict; their counters add up
+            first_count = torch.full_like(s.conv_iter, it)
+            newly = undecided & g_status_conv
+            s.conv_iter = torch.where(newly, first_count + g_conv_iter, s.conv_iter)
+            s.converged = newly if s.converged is None else (s.converged | newly)
+        # TRUNCATED: _merge_infos leaves the FIRST loop's last_err in the merged info (nonlinear_optimizer.py:220-266);
+        # UNROLL is ONE loop in the reference (nonlinear_least_squares.py:252-268), whose _update_info sets it every iteration
+        tr.info.last_err = g_last.detach() if single_loop else s.last_err
+        s.it = it + g_it
+        tr.info.iters_done = s.it
+
+    def _implicit_epilogue(self, s: _LoopState):
+        # ---- BackwardMode.IMPLICIT: the last step is an undamped Gauss-Newton step with the Hessian detached,
+        #      executed under the caller's grad mode (nonlinear_least_squares.py:121-135,265-292) ----
+        packed, tr = self.linear_solver.linearization.packed, s.tracker
+        X_new, delta = self._implicit_last_step(packed, s.outer_grad, s.kwargs)
+        X_det = _detached(X_new)
+        err = packed.error_metric(state=X_det)
+        packed.swap_state(X_new)
+        tr.record(s.it, X_det, err)
+        if s.need_conv:
+            # _merge_infos (nonlinear_least_squares.py:216-263): a problem that converged in the no-grad loop stays
+            # CONVERGED whatever the final Gauss-Newton step does
+            last_step = self._check_convergence(err, s.last_err)
+            s.converged = last_step if s.converged is None else (s.converged | last_step)
+            s.conv_iter = torch.where(s.converged & (s.conv_iter < 0), torch.full_like(s.conv_iter, s.it + 1), s.conv_iter)
+        self._iteration_done(s, err, delta.detach())
 
     def _needs_grad(self):
         return any(v.tensor.requires_grad for v in self.linear_solver.linearization.packed.tracked_list())
@@ -670,24 +720,11 @@ class NonlinearLeastSquares(abc.ABC):
     def _implicit_last_step(self, packed, outer_grad: bool, kwargs):
         """X_new = X exp(delta), delta = H^-1 g(theta): H is built outside autograd (i.e. detached, as
         dense_linearization.py:61 does for this step), the graph runs through g only and its backward is one
-        linear solve with the cached factor + the fused VJP kernel (theseus_amd/autograd.py)."""
-        from .autograd import ImplicitStep
+        linear solve with the cached factor + the fused VJP kernel (theseus_amd/autograd.py).  Every packer brings its ``implicit_step``:
+        pose graphs packed.py, bundle adjustment ba.py (thx_ba_vjp), generic objectives generic.py (torch forms g, cached-factor solve)."""
         step = self.params.step_size if kwargs.get("__keep_final_step_size__", False) else 1.0
-        if getattr(packed, "group", None) == "BA":   # bundle adjustment: theseus_amd/ba.py (thx_ba_vjp)
-            from .ba import ba_implicit_step
-            with torch.set_grad_enabled(outer_grad):
-                return ba_implicit_step(self, packed, float(step), kwargs)
-        # generic objectives: theseus_amd/euclidean.py (torch forms g, cached-factor solve); a packed class of another group that
-        # brings its own ``implicit_step`` says so (theseus_amd/pushing.py)
-        if packed.group == "Euclidean" or getattr(packed, "own_implicit_step", False):
-            with torch.set_grad_enabled(outer_grad):
-                return packed.implicit_step(self, float(step), kwargs)
         with torch.set_grad_enabled(outer_grad):
-            packed.flush_variables()
-            packed.sync(force=True)  # re-pack the auxiliary tensors WITH their autograd history
-            t = packed.tensors
-            return ImplicitStep.apply(self, float(step), kwargs, t.meas, t.w_between, t.prior_target, t.w_prior,
-                                      t.log_radius_between, t.log_radius_prior)
+            return packed.implicit_step(self, float(step), kwargs)
 
 
 class GaussNewton(NonlinearLeastSquares):

@@ -258,6 +258,16 @@ class PackedPoseGraph(TrackedVariables):
                 return buf
         return None
 
+    # ---- BackwardMode.IMPLICIT (theseus_amd/autograd.py:ImplicitStep) ---------------------------------------------------------
+    def implicit_step(self, opt, step: float, kwargs):
+        """-> (X_new, delta): called by NonlinearLeastSquares._implicit_last_step under the caller's grad mode."""
+        from .autograd import ImplicitStep
+        self.flush_variables()
+        self.sync(force=True)  # re-pack the auxiliary tensors WITH their autograd history
+        t = self.tensors
+        return ImplicitStep.apply(opt, step, kwargs, t.meas, t.w_between, t.prior_target, t.w_prior,
+                                  t.log_radius_between, t.log_radius_prior)
+
     # ---- BackwardMode.UNROLL / TRUNCATED (theseus_amd/autograd.py:PGUnrolledIteration) ---------------------------------------
     def prepare_unroll(self):
         """Before the differentiable tail loop: re-pack the auxiliary tensors WITH their autograd history (once)."""

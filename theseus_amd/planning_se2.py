@@ -66,7 +66,6 @@ def _trajse2_kind(c):
 class PackedTrajectorySE2(TermTable, PackedState):
     group = "SE2+R3"
     family = "SE2 motion planning"
-    own_implicit_step = True    # the optimizer's implicit last step is ``implicit_step`` (PackedState's, retracting per record kind)
 
     _TERM, _TANGENT = TRAJSE2_TERM, 3
     _KINDS = {

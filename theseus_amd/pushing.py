@@ -40,7 +40,6 @@ def _push2_kind(c):
 class PackedPlanarPushing(TermTable, PackedState):
     group = "SE2"
     family = "planar pushing (SE2)"
-    own_implicit_step = True    # the optimizer's implicit last step is ``implicit_step`` (PackedState's, retracting on SE2)
 
     _TERM, _TANGENT = PUSH2_TERM, 3
     _KINDS = {
