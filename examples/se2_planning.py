@@ -82,6 +82,8 @@ def main():
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--dtype", choices=["f32", "f64"], default="f64")
     ap.add_argument("--kernels", default=None)
+    ap.add_argument("--solver", choices=["dense", "banded"], default="dense",
+                    help="banded: HipBandedCholeskySolver (the chain's Hessian is banded after a reordering of its variables)")
     a = ap.parse_args()
     dtype = torch.float64 if a.dtype == "f64" else torch.float32
     kernels = None
@@ -89,10 +91,11 @@ def main():
         mod, cls = a.kernels.split(":")
         kernels = getattr(importlib.import_module(mod), cls)()
     obj = make_objective(th, a.intervals, a.batch, dtype, a.device)
-    opt = th.LevenbergMarquardt(obj, max_iterations=a.iters, step_size=0.25,
+    solver = th.HipBandedCholeskySolver if a.solver == "banded" else th.HipCholeskySolver
+    opt = th.LevenbergMarquardt(obj, linear_solver_cls=solver, max_iterations=a.iters, step_size=0.25,
                                 linearization_kwargs=dict(kernels=kernels) if kernels else None)
     print(f"{len(obj.cost_functions)} costs, n = {opt.linear_solver.linearization.n}, batch {a.batch}, "
-          f"packed family: {type(opt.linear_solver.linearization.packed).__name__}")
+          f"packed family: {type(opt.linear_solver.linearization.packed).__name__}, solver: {type(opt.linear_solver).__name__}")
     sideways = lambda: max(float(obj.optim_vars[f"vel_{i}"].tensor[:, 1].abs().max()) for i in range(1, a.intervals + 1))  # noqa: E731
     before = sideways()
     with torch.no_grad():

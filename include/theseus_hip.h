@@ -913,6 +913,37 @@ int thx_lu_solve_backward(const void* LU, int64_t ld, int32_t n, int32_t B, cons
 int thx_lu_solve(const void* LU, int64_t ld, int32_t n, int32_t B, const int32_t* piv, const void* rhs, void* x, int64_t ldv,
                  int dtype, void* stream);
 
+/* ---- LinearSolver.solve() with a BANDED Cholesky: for objectives whose Hessian is banded in some order of its variables
+ *      (trajectories: theseus/embodied/motionmodel + collision costs, odometry chains with short loop closures) -- LAPACK's
+ *      pbtrf / pbtrs, n kd^2 / 2 flops per problem instead of n^3 / 3, one wave per problem, one launch (csrc/band_kernels.hip).
+ *      thx_band_factor: P (H + damping) P^T = L L^T, out of place.
+ *        H: the (B, ld, ld) frame thx_block_assemble / thx_pg*_assemble write, left undamped; only its lower triangle is read:
+ *          element (i, j) of the banded matrix is H[max(perm[i], perm[j]), min(perm[i], perm[j])], and only the n (kd + 1) elements
+ *          with 0 <= i - j <= kd are read -- whatever else the frame holds is taken to be zero;
+ *        perm: DEVICE (n) int32, perm[k] = the column of H at banded position k.  The caller guarantees a permutation of 0..n-1
+ *          (the host wrapper checks it before the upload; the C side cannot);
+ *        kd: half-bandwidth, 0 <= kd < n and kd <= THX_BAND_MAX_KD (one window row per lane of a wave);
+ *        damping / ellipsoidal / damping_eps: as thx_chol_factor (NULL: none);
+ *        Lb: (B, n, kd + 1) column-major band, Lb[b, j, i] = L(j + i, j); position 0 holds the DIAGONAL L(j, j) itself (not its
+ *          reciprocal); every element is written, zeros where j + i >= n;
+ *        info: (B) int32, 0 = ok, k + 1 = the pivot of BANDED column k is not positive, for the first such k; the pivot is taken
+ *          as one and the item is finished (as thx_chol_factor does), the other items are not affected;
+ *        rhs / y: optional (both or neither) fused forward substitution y = L^-1 P rhs: rhs (B, n) in H's column order, y (B, n)
+ *          in BANDED order, row stride ldv; y must not alias rhs.
+ *      thx_band_solve_backward: x = P^T L^-T y for such a y, x in H's column order.  x may alias y while n elements fit in 64 KB.
+ *      thx_band_solve: x = (H + damping)^-1 rhs with a cached factor, rhs and x in H's column order (gather and scatter through
+ *        perm inside the kernel); x may alias rhs.  Bit-identical to thx_band_factor with rhs followed by thx_band_solve_backward.
+ *      Refused before any launch: null pointers, kd < 0, kd >= n, kd > THX_BAND_MAX_KD, ld < n, ldv < n, a bad dtype, Lb == H.
+ *      No atomics: results do not depend on what the output buffers held and are the same bits from run to run. */
+#define THX_BAND_MAX_KD 63
+int thx_band_factor(const void* H, int64_t ld, int32_t n, int32_t kd, int32_t B, const int32_t* perm, const void* damping,
+                    int ellipsoidal, double damping_eps, void* Lb, int32_t* info, const void* rhs, void* y, int64_t ldv, int dtype,
+                    void* stream);
+int thx_band_solve(const void* Lb, int32_t n, int32_t kd, int32_t B, const int32_t* perm, const void* rhs, void* x, int64_t ldv,
+                   int dtype, void* stream);
+int thx_band_solve_backward(const void* Lb, int32_t n, int32_t kd, int32_t B, const int32_t* perm, const void* y, void* x,
+                            int64_t ldv, int dtype, void* stream);
+
 /* ---- Implicit backward (BackwardMode.IMPLICIT, nonlinear/nonlinear_least_squares.py:121-135,265-292): the
  *      grad-enabled last step is X_new = X exp(step * delta), delta = H^-1 g(theta) with H detached
  *      (dense_linearization.py:61).  The backward pass is

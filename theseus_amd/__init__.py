@@ -10,7 +10,7 @@ from .core import (AutoDiffCostFunction, Between, CostFunction, CostWeight, Diag
 from .kernels import (HipKernels, default_kernels, reset_global_params, set_global_params, set_lie_eps,  # noqa: F401
                       set_se2_eps)
 from .layer import TheseusLayer  # noqa: F401
-from .linear_solver import HipCholeskySolver, HipLUSolver, LinearSolver  # noqa: F401
+from .linear_solver import HipBandedCholeskySolver, HipCholeskySolver, HipLUSolver, LinearSolver  # noqa: F401
 from .sparse import HipSparseCholeskySolver, fill_reducing_ordering, level_ordering  # noqa: F401
 from .linearization import HipLinearization, Linearization, VariableOrdering  # noqa: F401
 from .nonlinear import (BackwardMode, Dogleg, GaussNewton, LevenbergMarquardt, NonlinearLeastSquares,  # noqa: F401

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("THESEUS_HIP_LIB") or os.path.join(_HERE, "lib", "libt
 THX_TILE = 128
 THX_ERR_CHUNKS = 128
 THX_LU_MAX_N = 4096  # largest system of thx_lu_factor (include/theseus_hip.h)
+THX_BAND_MAX_KD = 63  # largest half-bandwidth of thx_band_factor (one window row per lane)
 THX_BA_ERR_CHUNKS = 256
 TRAJ2_COLLISION, TRAJ2_GP, TRAJ2_PRIOR = 0, 1, 2  # THX_TRAJ2_* (kinds of a thx_traj2_term)
 PUSH2_QSP, PUSH2_MFB, PUSH2_CONTACT, PUSH2_PRIOR = 0, 1, 2, 3  # THX_PUSH2_* (kinds of a thx_push2_term)
@@ -278,6 +279,10 @@ _SIGNATURES = {
     "thx_lu_solve_forward": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],
     "thx_lu_solve_backward": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_int, c_void_p],
     "thx_lu_solve": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],
+    "thx_band_factor": [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p,
+                        c_void_p, c_int64, c_int, c_void_p],
+    "thx_band_solve": [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],
+    "thx_band_solve_backward": [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],
     "thx_se3_retract_vjp": [c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int,
                             POINTER(LieEps), c_void_p],
     "thx_pg_vjp": [POINTER(PGStructure), POINTER(PGData), c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,

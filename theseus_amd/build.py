@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libtheseus_hip.so")
-SOURCES = ["pg_kernels.hip", "chol_kernels.hip", "hblock_order.hip", "pg_vjp_kernels.hip", "block_kernels.hip", "pg2_kernels.hip", "ba_kernels.hip", "pgso3_kernels.hip", "pgso2_kernels.hip", "ba_vjp_kernels.hip", "vjp_unroll_ba_kernels.hip", "lu_kernels.hip", "multi_solve_kernels.hip", "traj_kernels.hip", "push_kernels.hip", "trajse2_kernels.hip", "homog_kernels.hip", "kin_kernels.hip", "dcem_kernels.hip"]
+SOURCES = ["pg_kernels.hip", "chol_kernels.hip", "hblock_order.hip", "pg_vjp_kernels.hip", "block_kernels.hip", "pg2_kernels.hip", "ba_kernels.hip", "pgso3_kernels.hip", "pgso2_kernels.hip", "ba_vjp_kernels.hip", "vjp_unroll_ba_kernels.hip", "lu_kernels.hip", "multi_solve_kernels.hip", "traj_kernels.hip", "push_kernels.hip", "trajse2_kernels.hip", "homog_kernels.hip", "kin_kernels.hip", "dcem_kernels.hip", "band_kernels.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-pass-failed"]
 
 

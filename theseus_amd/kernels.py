@@ -1062,6 +1062,57 @@ class HipKernels:
         _lib.check(self.lib.thx_lu_solve(_lib.ptr(LU), ld, n, B, _lib.ptr(piv), _lib.ptr(rhs), _lib.ptr(x), rhs.stride(0),
                                          _lib.dtype_code(LU.dtype), _lib.stream_ptr(LU.device)), "thx_lu_solve")
 
+    # ---- banded Cholesky (include/theseus_hip.h: thx_band_factor) --------------------------------------
+    @staticmethod
+    def _band_shapes(what, Lb, n, kd, perm, vecs=()):
+        B = Lb.shape[0]
+        if tuple(Lb.shape) != (B, n, kd + 1):
+            raise ValueError(f"{what}: Lb must be (B, n = {n}, kd + 1 = {kd + 1}), got {tuple(Lb.shape)}")
+        if perm.dtype != torch.int32 or tuple(perm.shape) != (n,):
+            raise ValueError(f"{what}: perm must be (n = {n}) int32 on the device (theseus_amd.banded.BandPlan.device_perm)")
+        for name, v in vecs:
+            if v.dtype != Lb.dtype or v.dim() != 2 or v.shape[0] != B or v.shape[1] != n or v.stride(1) != 1:
+                raise ValueError(f"{what}: {name} must be (B = {B}, n = {n}) of {Lb.dtype} with unit column stride, got {tuple(v.shape)}")
+        return B
+
+    @staticmethod
+    def _band_ldv(v, n):
+        return v.stride(0) if v.shape[0] > 1 else max(v.stride(0), n)   # (one row: its stride is arbitrary)
+
+    def band_factor(self, H, n, kd, perm, damping, ellipsoidal, damping_eps, Lb, info, rhs=None, y=None):
+        """P (H + damping) P^T = L L^T on the band: ``H`` the (B, ld, ld) frame (lower triangle read through ``perm``, a DEVICE
+        int32 permutation -- validated where it is made, banded.BandPlan), ``Lb`` (B, n, kd + 1) and ``info`` (B) int32 overwritten
+        entirely.  With ``rhs`` (linearization order) the forward substitution is fused: ``y`` (B, n) in banded order."""
+        B = self._band_shapes("band_factor", Lb, n, kd, perm, [(k, v) for k, v in (("rhs", rhs), ("y", y)) if v is not None])
+        ld = H.shape[-1]
+        if tuple(H.shape) != (B, ld, ld) or H.dtype != Lb.dtype or info.dtype != torch.int32 or tuple(info.shape) != (B,):
+            raise ValueError(f"band_factor: H (B, ld, ld) of Lb's dtype, info (B) int32; got H {tuple(H.shape)}")
+        if (rhs is None) != (y is None):
+            raise ValueError("band_factor: rhs and y go together")
+        if rhs is not None and self._band_ldv(rhs, n) != self._band_ldv(y, n):
+            raise ValueError("band_factor: rhs and y must have the same row stride")
+        _lib.check(self.lib.thx_band_factor(_lib.ptr(H, "H"), ld, n, kd, B, _lib.ptr(perm, "perm"), _lib.ptr(damping),
+                                            int(bool(ellipsoidal)), float(damping_eps), _lib.ptr(Lb, "Lb"), _lib.ptr(info, "info"),
+                                            _lib.ptr(rhs), _lib.ptr(y), self._band_ldv(rhs, n) if rhs is not None else n,
+                                            _lib.dtype_code(Lb.dtype), _lib.stream_ptr(Lb.device)), "thx_band_factor")
+
+    def band_solve(self, Lb, n, kd, perm, rhs, x):
+        """x = (L L^T)^-1 rhs on a factor of ``band_factor``; rhs and x in the linearization's order (x may be rhs)."""
+        B = self._band_shapes("band_solve", Lb, n, kd, perm, (("rhs", rhs), ("x", x)))
+        if self._band_ldv(rhs, n) != self._band_ldv(x, n):
+            raise ValueError("band_solve: rhs and x must have the same row stride")
+        _lib.check(self.lib.thx_band_solve(_lib.ptr(Lb, "Lb"), n, kd, B, _lib.ptr(perm, "perm"), _lib.ptr(rhs), _lib.ptr(x),
+                                           self._band_ldv(rhs, n), _lib.dtype_code(Lb.dtype), _lib.stream_ptr(Lb.device)), "thx_band_solve")
+
+    def band_solve_backward(self, Lb, n, kd, perm, y, x):
+        """x = P^T L^-T y: ``y`` in banded order (the y of ``band_factor``), x in the linearization's order (x may be y)."""
+        B = self._band_shapes("band_solve_backward", Lb, n, kd, perm, (("y", y), ("x", x)))
+        if self._band_ldv(y, n) != self._band_ldv(x, n):
+            raise ValueError("band_solve_backward: y and x must have the same row stride")
+        _lib.check(self.lib.thx_band_solve_backward(_lib.ptr(Lb, "Lb"), n, kd, B, _lib.ptr(perm, "perm"), _lib.ptr(y), _lib.ptr(x),
+                                                    self._band_ldv(y, n), _lib.dtype_code(Lb.dtype), _lib.stream_ptr(Lb.device)),
+                   "thx_band_solve_backward")
+
     def diag(self, H, n, d):
         B, ld = H.shape[0], H.shape[-1]
         _lib.check(self.lib.thx_diag(_lib.ptr(H), ld, n, B, _lib.ptr(d), d.stride(0), _lib.dtype_code(H.dtype),

@@ -541,3 +541,96 @@ class HipLUSolver(HipLUCore, LinearSolver):
     def solve(self, damping: Optional[Union[float, torch.Tensor]] = None, ellipsoidal_damping: bool = True,
               damping_eps: float = 1e-8, check_info: bool = True, **kwargs) -> torch.Tensor:
         return self._solve(damping, ellipsoidal_damping, damping_eps, check_info)
+
+
+class HipBandedCholeskyCore(DenseCholeskyOnly, HipCholeskyCore):
+    """Back-end half of the banded Cholesky solver: the surface of ``HipCholeskyCore`` that the loops and the autograd nodes call,
+    on thx_band_factor / thx_band_solve* (include/theseus_hip.h).  P (AtA + damping) P^T = L L^T with P the band plan's column
+    order (theseus_amd/banded.py), found once per structure; the factor is ``Lb`` (B, n, kd + 1), L's band by columns.  The
+    linearization's dense frame is read in place through P -- n (kd + 1) elements of it -- and everything a caller hands in or gets
+    back stays in the linearization's order.  A failed item raises the RuntimeError of ``HipCholeskyCore.check_info``; the "leading
+    minor of order k" it names counts columns in the BANDED order (``band_plan().perm[k - 1]`` is the linearization's column)."""
+
+    def _core_init(self):
+        self.K = self.linearization.K
+        self.Lb = self.info = self._y = None
+        self._lam = self._frame = None
+        self._plan = self._perm = None
+        self.factor_version = 0
+
+    def band_plan(self):
+        """The ``banded.BandPlan`` of the linearization's structure (made on first use, kept)."""
+        if self._plan is None:
+            from .banded import band_plan
+            self._plan = band_plan(self.linearization, "natural" if self.ordering == "natural" else "auto")
+        return self._plan
+
+    def _ensure_buffers(self):
+        lin = self.linearization
+        g = lin.g
+        plan = self.band_plan()
+        B, n = g.shape[0], lin.n
+        if plan.n != n:
+            raise RuntimeError(f"HipBandedCholeskySolver: the band plan was made for {plan.n} columns, the linearization has {n}")
+        shape = (B, n, plan.kd + 1)
+        if self.Lb is None or tuple(self.Lb.shape) != shape or self.Lb.device != g.device or self.Lb.dtype != g.dtype:
+            # (every buffer is written entirely by the kernels: no initial contents needed)
+            self.Lb = torch.empty(shape, dtype=g.dtype, device=g.device)
+            self._y = torch.empty(B, n, dtype=g.dtype, device=g.device)
+            self.info = torch.zeros(B, dtype=torch.int32, device=g.device)
+            self._lam = torch.empty(B, dtype=g.dtype, device=g.device)
+            self._perm = plan.device_perm(g.device)
+            self._frame = None
+
+    def _factor_call(self, lam, ellipsoidal_damping, damping_eps, rhs, y, pattern=None):
+        lin, plan = self.linearization, self._plan
+        if getattr(lin, "_compact", False):
+            # block-compact Hessian: one extra pass expands it into a dense frame (blocks are rewritten each time, the zeros
+            # between them are written once)
+            if self._frame is None:
+                self._frame = torch.zeros(self.Lb.shape[0], lin.ld, lin.ld, dtype=self.Lb.dtype, device=self.Lb.device)
+            self.K.hblocks_expand(lin.hblocks, lin.Hc, self._frame)
+            H = self._frame
+        else:
+            H = lin.H
+        self.K.band_factor(H, lin.n, plan.kd, self._perm, lam, ellipsoidal_damping, damping_eps, self.Lb, self.info,
+                           rhs=rhs.contiguous() if rhs is not None else None, y=y)
+
+    def factor_snapshot(self):
+        return self.Lb.clone()
+
+    def solve_with_snapshot(self, snapshot, rhs: torch.Tensor) -> torch.Tensor:
+        rhs = rhs.contiguous()
+        x = torch.empty_like(rhs)
+        self.K.band_solve(snapshot, self.linearization.n, self._plan.kd, self._perm, rhs, x)
+        return x
+
+    def _substitute(self, rhs, x, backward_only: bool):
+        """x = P^T L^-T rhs (``backward_only``: rhs is the y of ``factorize``, in banded order) or (AtA + damping)^-1 rhs with the
+        current factor."""
+        solve = self.K.band_solve_backward if backward_only else self.K.band_solve
+        solve(self.Lb, self.linearization.n, self._plan.kd, self._perm, rhs, x)
+
+
+class HipBandedCholeskySolver(HipBandedCholeskyCore, LinearSolver):
+    def __init__(self, objective: Objective, linearization_cls: Optional[Type[Linearization]] = None,
+                 linearization_kwargs: Optional[Dict[str, Any]] = None, check_singular: bool = False, ordering: str = "auto",
+                 **kwargs):
+        """Opt-in solver for objectives whose Hessian is banded in some order of the variables (trajectories, odometry chains):
+        ``linear_solver_cls=HipBandedCholeskySolver``.  ``ordering``: "auto" (default) -- reverse Cuthill-McKee on the variable
+        graph unless the linearization's own order is no wider; "natural" -- the linearization's own order.  The first solve raises
+        ``UnsupportedObjective`` when the half-bandwidth exceeds ``THX_BAND_MAX_KD``."""
+        if ordering not in ("auto", "natural"):
+            raise ValueError(f"ordering must be 'auto' or 'natural', got {ordering!r}")
+        self.ordering = ordering
+        linearization_cls = linearization_cls or HipLinearization
+        if not (isinstance(linearization_cls, type) and issubclass(linearization_cls, HipLinearization)):
+            raise RuntimeError("HipBandedCholeskySolver only works with theseus_amd.HipLinearization, "
+                               f"but {linearization_cls} was provided.")
+        LinearSolver.__init__(self, objective, linearization_cls, linearization_kwargs)
+        self._check_singular = check_singular
+        self._core_init()
+
+    def solve(self, damping: Optional[Union[float, torch.Tensor]] = None, ellipsoidal_damping: bool = True,
+              damping_eps: float = 1e-8, check_info: bool = True, **kwargs) -> torch.Tensor:
+        return self._solve(damping, ellipsoidal_damping, damping_eps, check_info)

@@ -42,7 +42,7 @@ from theseus.global_params import _THESEUS_GLOBAL_PARAMS as _REF_GLOBAL_PARAMS
 from .generic import BlockAssembler
 from .autograd import detached_tensors, pg_vjp_grads
 from .kernels import default_kernels, round_up
-from .linear_solver import HipCholeskyCore, HipLUCore
+from .linear_solver import HipBandedCholeskyCore, HipCholeskyCore, HipLUCore
 from .linearization import HipLinearizationCore
 from .packed import UnsupportedObjective
 from . import kernels as _kernels
@@ -771,6 +771,50 @@ class HipLUSolver(HipLUCore, _RefLUDenseSolver):
 
     def _solve_sytem(self, Atb: torch.Tensor, AtA: torch.Tensor) -> torch.Tensor:  # abstract in DenseSolver
         raise NotImplementedError("HipLUSolver.solve() factorises its linearization's packed Hessian")
+
+
+class HipBandedCholeskySolver(HipBandedCholeskyCore, _RefCholeskyDenseSolver):
+    """``linear_solver_cls`` for the REAL theseus loop on objectives whose Hessian is banded in some order of the variables
+    (motion planning, odometry chains): thx_band_factor / thx_band_solve* instead of the dense factorisation
+    (theseus_amd/linear_solver.py: HipBandedCholeskyCore).  Subclasses the reference's ``CholeskyDenseSolver`` (LM's isinstance
+    whitelists) and calls ``LinearSolver.__init__`` directly, as ``HipCholeskySolver`` above and for the same reason.  A system
+    handed over as plain tensors has no block pattern to find a band in: NotImplementedError."""
+
+    def __init__(self, objective: th.Objective, linearization_cls: Optional[Type[_RefLinearization]] = None,
+                 linearization_kwargs: Optional[Dict[str, Any]] = None, check_singular: bool = False, ordering: str = "auto",
+                 **kwargs):
+        if ordering not in ("auto", "natural"):
+            raise ValueError(f"ordering must be 'auto' or 'natural', got {ordering!r}")
+        self.ordering = ordering
+        linearization_cls = linearization_cls or HipLinearization
+        if not (isinstance(linearization_cls, type) and issubclass(linearization_cls, HipLinearization)):
+            raise RuntimeError("HipBandedCholeskySolver only works with theseus_amd.plugin.HipLinearization, "
+                               f"but {linearization_cls} was provided.")
+        _RefLinearSolver.__init__(self, objective, linearization_cls, linearization_kwargs)
+        self._check_singular = check_singular
+        self._core_init()
+
+    def solve(self, damping: Optional[Union[float, torch.Tensor]] = None, ellipsoidal_damping: bool = True,
+              damping_eps: float = 1e-8, **kwargs) -> torch.Tensor:
+        # the dispatch of HipLUSolver.solve; a failed factorisation = RuntimeError = FAIL status under no_grad
+        lin = self.linearization
+        if not isinstance(lin, HipLinearization) or lin._ext_AtA is not None or lin._ext_Atb is not None:
+            raise NotImplementedError("HipBandedCholeskySolver: a system handed over as plain tensors has no block pattern to find "
+                                      "a band in; use HipCholeskySolver (or HipLUSolver) for it.")
+        if damping is not None and isinstance(damping, torch.Tensor) and damping.ndim > 1:
+            raise ValueError("Damping must be a float or a 1-D tensor.")
+        if getattr(lin, "_unroll", None) is not None and torch.is_grad_enabled():
+            return _FusedUnrolledSolve.apply(self, damping, ellipsoidal_damping, damping_eps, *lin._unroll)
+        g = lin._g_graph
+        if g is not None and torch.is_grad_enabled():
+            Hg = getattr(lin, "_H_graph", None)
+            if Hg is not None:
+                return _UnrolledFactorSolve.apply(self, damping, ellipsoidal_damping, damping_eps, Hg, g)
+            return _CachedFactorSolve.apply(self, damping, ellipsoidal_damping, damping_eps, g)
+        return self._solve(damping, ellipsoidal_damping, damping_eps, check_info=True)
+
+    def _solve_sytem(self, Atb: torch.Tensor, AtA: torch.Tensor) -> torch.Tensor:  # abstract in DenseSolver
+        raise NotImplementedError("HipBandedCholeskySolver.solve() factorises its linearization's packed Hessian")
 
 
 # ---- large pose graphs (theseus_amd/sparse.py): tile-sparse Cholesky under a fill-reducing ordering ----------------------------
