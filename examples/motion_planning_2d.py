@@ -3,7 +3,7 @@ a batch of point robots crossing a map of discs.  Collision2D on every pose, GPM
 pairs, Difference priors on the start and goal states; straight-line initialisation; Levenberg-Marquardt on the fused path
 (theseus_amd/embodied.py: PackedTrajectory2D -- thx_traj2_eval + thx_block_assemble + the tiled Cholesky at n = 4 (N + 1)).
 The map is synthetic: the analytic signed distance of a few discs sampled on a grid (no dataset file).
-usage: python examples/motion_planning_2d.py [--intervals 100] [--batch 16] [--iters 30] [--device cuda] [--dtype f64]
+usage: python examples/motion_planning_2d.py [--intervals 100] [--batch 16] [--iters 30] [--device cuda] [--dtype f64] [--covariances]
        (--kernels module:Class substitutes the kernel set -- the tests' CPU stand-in, for machines without a GPU)
 """
 import argparse
@@ -71,6 +71,9 @@ def main():
     ap.add_argument("--kernels", default=None)
     ap.add_argument("--solver", choices=["dense", "banded"], default="dense",
                     help="banded: HipBandedCholeskySolver (the chain's Hessian is banded after a reordering of its variables)")
+    ap.add_argument("--covariances", action="store_true",
+                    help="after the solve, print the trace of every state's marginal covariance along the trajectory "
+                         "(HipBandedCholeskySolver.marginal_covariances: one launch for all of them; implies --solver banded)")
     a = ap.parse_args()
     dtype = torch.float64 if a.dtype == "f64" else torch.float32
     kernels = None
@@ -78,7 +81,7 @@ def main():
         mod, cls = a.kernels.split(":")
         kernels = getattr(importlib.import_module(mod), cls)()
     obj = make_objective(th, a.intervals, a.batch, dtype, a.device)
-    solver = th.HipBandedCholeskySolver if a.solver == "banded" else th.HipCholeskySolver
+    solver = th.HipBandedCholeskySolver if a.solver == "banded" or a.covariances else th.HipCholeskySolver
     opt = th.LevenbergMarquardt(obj, linear_solver_cls=solver, max_iterations=a.iters, step_size=1.0,
                                 linearization_kwargs=dict(kernels=kernels) if kernels else None)
     print(f"{len(obj.cost_functions)} costs, n = {opt.linear_solver.linearization.n}, batch {a.batch}, "
@@ -92,6 +95,15 @@ def main():
     sdf = th.eb.SignedDistanceField2D(obj.aux_vars["sdf_origin"], obj.aux_vars["cell_size"], obj.aux_vars["sdf_data"])
     d, _ = sdf.signed_distance(traj.permute(0, 2, 1).contiguous())
     print(f"smallest clearance along the trajectories: {float(d.min()):.3f} (discs are entered where it is negative)")
+    if a.covariances:
+        with torch.no_grad():
+            obj.update()
+            opt.linear_solver.linearization.linearize()
+            cov = opt.linear_solver.marginal_covariances()
+        tr = torch.stack([sum(cov[f"{k}_{i}"].diagonal(dim1=1, dim2=2).sum(1) for k in ("pose", "vel"))
+                          for i in range(a.intervals + 1)], dim=1)                                             # (B, N + 1)
+        print("trace of each state's (pose, velocity) marginal covariance (problem 0), start to goal:")
+        print(" ".join(f"{float(v):.2e}" for v in tr[0]))
 
 
 if __name__ == "__main__":

@@ -943,6 +943,26 @@ int thx_band_solve(const void* Lb, int32_t n, int32_t kd, int32_t B, const int32
                    int dtype, void* stream);
 int thx_band_solve_backward(const void* Lb, int32_t n, int32_t kd, int32_t B, const int32_t* perm, const void* y, void* x,
                             int64_t ldv, int dtype, void* stream);
+/*      Blocks of right-hand sides and the band of the inverse on such a factor (csrc/band_multi_kernels.hip): posterior samples
+ *      (delta + sqrt(t) P^T L^-T y) and marginal covariances for the banded solver.
+ *      thx_pb_solve_multi: Lb (B, n, kd + 1) and perm exactly as thx_band_factor writes / takes them.  rhs / x: (B, nrhs, n), one
+ *        vector per row, with the ldv / bstride contract of thx_chol_solve_multi: element (b, s, i) at b * bstride + s * ldv + i,
+ *        ldv >= n, bstride >= nrhs * ldv.  which (the codes of thx_chol_solve_multi), with P the order perm stands for:
+ *          0: x = (H + damping)^-1 rhs   rhs and x in H's column order
+ *          2: x = L^-1 P rhs             rhs in H's column order, x in BANDED order
+ *          1: x = P^T L^-T rhs           rhs in BANDED order, x in H's column order           (1 after 2 equals 0, bitwise)
+ *        One wave per (problem, group of up to 64 vectors), lane = vector; any n and nrhs.  x may alias rhs (exactly: x == rhs);
+ *        with which = 1 or 2 an aliased call permutes each row through LDS and is refused when n elements exceed 64 KB.  A
+ *        vector's result does not depend on the other vectors of the call nor on what x held; nothing outside nrhs rows of n
+ *        elements is read or written.
+ *        Refused before any launch: null pointers, kd < 0, kd >= n, kd > THX_BAND_MAX_KD, nrhs < 1, ldv < n, bstride < nrhs * ldv,
+ *        which outside 0..2, a bad dtype.
+ *      thx_pb_inverse_band: Zb (B, n, kd + 1) laid out like Lb, Zb[b, j, i] = S(j + i, j) with S = (L L^T)^-1 in BANDED order --
+ *        the band of the inverse by selected inversion (Takahashi's equations), n kd^2 flops per problem, one wave per problem, one
+ *        launch.  Every element is written, zeros where j + i >= n.  Zb must not be Lb.  Argument checks as thx_band_solve. */
+int thx_pb_solve_multi(const void* Lb, int32_t n, int32_t kd, int32_t B, const int32_t* perm, const void* rhs, void* x, int32_t nrhs,
+                       int64_t ldv, int64_t bstride, int which, int dtype, void* stream);
+int thx_pb_inverse_band(const void* Lb, int32_t n, int32_t kd, int32_t B, void* Zb, int dtype, void* stream);
 
 /* ---- Implicit backward (BackwardMode.IMPLICIT, nonlinear/nonlinear_least_squares.py:121-135,265-292): the
  *      grad-enabled last step is X_new = X exp(step * delta), delta = H^-1 g(theta) with H detached

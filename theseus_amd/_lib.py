@@ -283,6 +283,9 @@ _SIGNATURES = {
                         c_void_p, c_int64, c_int, c_void_p],
     "thx_band_solve": [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],
     "thx_band_solve_backward": [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],
+    "thx_pb_solve_multi": [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int, c_int,
+                           c_void_p],
+    "thx_pb_inverse_band": [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int, c_void_p],
     "thx_se3_retract_vjp": [c_void_p, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int,
                             POINTER(LieEps), c_void_p],
     "thx_pg_vjp": [POINTER(PGStructure), POINTER(PGData), c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -31,34 +31,12 @@
 // A pivot that is not positive is replaced by one and the item goes on (info = banded column + 1, first such), as
 // thx_chol_factor finishes a failed item.  Every element of Lb, y, x and info is written; nothing is accumulated in memory: the
 // result is independent of what the buffers held and the same from run to run.  Accumulation in the working dtype (as pbtrf).
-#include "common.cuh"
+#include "band_common.cuh"
 
 namespace thx {
 
-constexpr int BAND_MAX_KD = THX_BAND_MAX_KD;
-constexpr int BAND_CH = 8;                 // columns gathered / fetched per chunk
-constexpr int BAND_WAVES = 4;              // problems per workgroup at most
-constexpr size_t BAND_LDS_BUDGET = 65536;  // dynamic LDS per workgroup
-
-static_assert(BAND_MAX_KD == 63, "one row per lane: the window has at most 64 rows");
-
-__device__ __forceinline__ float lane_bcast(float x, int l) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l));
-}
-__device__ __forceinline__ double lane_bcast(double x, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(x), l), hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
-  return __hiloint2double(hi, lo);
-}
-
 // LDS elements of one wave of the factorisation: the window's sums, two chunks of H's band, the finished column
 __host__ __device__ inline size_t band_wave_elems(int w, int S) { return (size_t)(w + 2 * BAND_CH) * S + 64; }
-
-// the wave's own LDS writes become visible to its reads.  LDS only ("local"): a fence over every address space also orders the
-// column's store to Lb and the band columns in flight
-__device__ __forceinline__ void band_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront", "local");
-  __builtin_amdgcn_wave_barrier();
-}
 
 template <typename T>
 __global__ __launch_bounds__(64 * BAND_WAVES) void band_factor_kernel(const T* __restrict__ H, int64_t ld, int n, int kd, int B,
@@ -388,16 +366,6 @@ __global__ __launch_bounds__(64 * BAND_WAVES) void band_backward_kernel(const T*
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-static int check_band_sizes(const char* who, int n, int kd, int B) {
-  if (n <= 0 || B <= 0) return fail(who, ": need n > 0, B > 0");
-  if (kd < 0 || kd >= n) return fail(who, ": need 0 <= kd < n");
-  if (kd > BAND_MAX_KD) {
-    const std::string msg = ": kd above the limit of " + std::to_string(BAND_MAX_KD) + " of the banded solver (one window row per lane)";
-    return fail(who, msg.c_str());
-  }
-  return 0;
-}
-
 template <typename T>
 int band_factor_impl(const void* H, int64_t ld, int n, int kd, int B, const int32_t* perm, const void* damping, int ellipsoidal,
                      double eps, void* Lb, int32_t* info, const void* rhs, void* y, int64_t ldv, hipStream_t st) {

@@ -1113,6 +1113,35 @@ class HipKernels:
                                                     self._band_ldv(y, n), _lib.dtype_code(Lb.dtype), _lib.stream_ptr(Lb.device)),
                    "thx_band_solve_backward")
 
+    def band_solve_multi(self, Lb, n, kd, perm, rhs, x, which=0):
+        """thx_pb_solve_multi on a factor of ``band_factor``: ``rhs`` / ``x`` (B, nrhs, n), one vector per row (unit stride along n,
+        any row / batch strides that do not overlap).  which = 0: (L L^T)^-1 rhs, both in the linearization's order; 2: L^-1 P rhs,
+        linearization's order in, banded order out; 1: P^T L^-T rhs, banded order in, linearization's out.  ``x`` may be ``rhs``."""
+        B = self._band_shapes("band_solve_multi", Lb, n, kd, perm)
+        if rhs.dim() != 3 or rhs.shape[0] != B or rhs.shape[2] != n or rhs.shape[1] < 1 or x.shape != rhs.shape:
+            raise ValueError(f"band_solve_multi: rhs {tuple(rhs.shape)} / x {tuple(x.shape)} must both be (B = {B}, nrhs >= 1, n = {n})")
+        if not (Lb.dtype == rhs.dtype == x.dtype):
+            raise ValueError("band_solve_multi: Lb, rhs and x must have one dtype")
+        if rhs.stride() != x.stride() or rhs.stride(2) != 1:
+            raise ValueError("band_solve_multi: rhs and x need the same strides, unit stride along n")
+        for t, name in ((rhs, "rhs"), (x, "x")):
+            if not t.is_cuda:
+                raise RuntimeError(f"{name} must live on a HIP device (got {t.device}); there is no CPU fallback")
+        nrhs, ldv = rhs.shape[1], (rhs.stride(1) if rhs.shape[1] > 1 else max(rhs.stride(1), n))
+        bstride = rhs.stride(0) if B > 1 else max(rhs.stride(0), nrhs * ldv)
+        _lib.check(self.lib.thx_pb_solve_multi(_lib.ptr(Lb, "Lb"), n, kd, B, _lib.ptr(perm, "perm"), _lib.c_void_p(rhs.data_ptr()),
+                                               _lib.c_void_p(x.data_ptr()), nrhs, ldv, bstride, int(which), _lib.dtype_code(Lb.dtype),
+                                               _lib.stream_ptr(Lb.device)), "thx_pb_solve_multi")
+
+    def band_inverse(self, Lb, n, kd, Zb):
+        """thx_pb_inverse_band: ``Zb`` (B, n, kd + 1), Zb[b, j, i] = ((L L^T)^-1)(j + i, j) in banded order, overwritten entirely."""
+        B = Lb.shape[0]
+        if tuple(Lb.shape) != (B, n, kd + 1) or Zb.shape != Lb.shape or Zb.dtype != Lb.dtype:
+            raise ValueError(f"band_inverse: Lb and Zb must both be (B, n = {n}, kd + 1 = {kd + 1}) of one dtype, got "
+                             f"{tuple(Lb.shape)} / {tuple(Zb.shape)}")
+        _lib.check(self.lib.thx_pb_inverse_band(_lib.ptr(Lb, "Lb"), n, kd, B, _lib.ptr(Zb, "Zb"), _lib.dtype_code(Lb.dtype),
+                                                _lib.stream_ptr(Lb.device)), "thx_pb_inverse_band")
+
     def diag(self, H, n, d):
         B, ld = H.shape[0], H.shape[-1]
         _lib.check(self.lib.thx_diag(_lib.ptr(H), ld, n, B, _lib.ptr(d), d.stride(0), _lib.dtype_code(H.dtype),

@@ -555,7 +555,7 @@ class HipBandedCholeskyCore(DenseCholeskyOnly, HipCholeskyCore):
         self.K = self.linearization.K
         self.Lb = self.info = self._y = None
         self._lam = self._frame = None
-        self._plan = self._perm = None
+        self._plan = self._perm = self._marg_index = None
         self.factor_version = 0
 
     def band_plan(self):
@@ -610,6 +610,137 @@ class HipBandedCholeskyCore(DenseCholeskyOnly, HipCholeskyCore):
         current factor."""
         solve = self.K.band_solve_backward if backward_only else self.K.band_solve
         solve(self.Lb, self.linearization.n, self._plan.kd, self._perm, rhs, x)
+
+
+    # ---- blocks of right-hand sides on the band factor (thx_pb_solve_multi, thx_pb_inverse_band) ------------------------------------
+    def _need_multi(self, name: str):
+        """The kernel set must carry the band factor's multi-vector kernels; one that does not (a kernel set handed in through
+        ``linearization_kwargs`` that predates them) is an error here, never a detour through another path."""
+        if not (hasattr(self.K, "band_solve_multi") and hasattr(self.K, "band_inverse")):
+            raise NotImplementedError(f"{type(self).__name__}.{name}: the kernel set {type(self.K).__name__} has no band_solve_multi / "
+                                      "band_inverse (thx_pb_solve_multi, thx_pb_inverse_band) for the band factor; HipCholeskySolver "
+                                      "serves blocks of right-hand sides on its dense factor frame (thx_chol_solve_multi).")
+
+    def _factorize_undamped(self):
+        self.factorize(None)
+        self.check_info()
+        return self
+
+    def solve_multi_with_factor(self, rhs: torch.Tensor, which: int = 0) -> torch.Tensor:
+        """``rhs`` (B, k, n), one vector per row, against the CURRENT band factor P (AtA + damping) P^T = L L^T (thx_pb_solve_multi,
+        one wave per 64 vectors).  which = 0: (L L^T)^-1 rhs, in and out in the linearization's order; 2: L^-1 P rhs --
+        linearization's order in, the solver's banded order out; 1: P^T L^-T rhs -- banded order in, linearization's out (the
+        conventions of ``HipCholeskyCore.solve_multi_with_factor`` for a factor in the solver's own order: 1 after 2 is 0).
+        Returns a new tensor."""
+        self._need_multi("solve_multi_with_factor")
+        if self.Lb is None or self.factor_version == 0:
+            raise RuntimeError("solve_multi_with_factor: nothing has been factorised yet (solve() or factorize() first).")
+        B, n = self.Lb.shape[0], self.linearization.n
+        if rhs.dim() != 3 or rhs.shape[0] != B or rhs.shape[2] != n or rhs.shape[1] < 1:
+            raise ValueError(f"solve_multi_with_factor: rhs must be (B = {B}, k >= 1, n = {n}), got {tuple(rhs.shape)}")
+        src = rhs.detach().to(device=self.Lb.device, dtype=self.Lb.dtype).contiguous()
+        x = torch.empty_like(src)
+        self.K.band_solve_multi(self.Lb, n, self._plan.kd, self._perm, src, x, which=which)
+        return x
+
+    @torch.no_grad()
+    def sample_deltas(self, n_samples: int = 10, temperature: float = 1.0, noise: Optional[torch.Tensor] = None,
+                      generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """The ``delta_samples`` of TheseusLayer.compute_samples, (B, n, n_samples): draws from N(delta, (AtA / temperature)^-1) as
+        delta + sqrt(temperature) P^T L^-T y  with delta = ``solve()`` (undamped, on the linearization as it stands) and L the band
+        factor that solve left, P AtA P^T = L L^T.  ``noise`` / ``generator``: as ``HipCholeskyCore.sample_deltas``.  The
+        distribution is the dense solver's; the DRAW that a given ``noise`` stands for is not: there it is defined through the
+        factor of AtA in the linearization's order, here through the factor in the banded order (P^T L^-T has the same covariance,
+        another square root of it)."""
+        self._need_multi("sample_deltas")
+        if not temperature > 0:
+            raise ValueError(f"sample_deltas: temperature must be positive, got {temperature}")
+        if int(n_samples) < 1:
+            raise ValueError(f"sample_deltas: n_samples must be at least 1, got {n_samples}")
+        delta = self.solve()
+        B, n = delta.shape
+        if noise is None:
+            noise = torch.randn(n, int(n_samples), generator=generator, device=delta.device, dtype=delta.dtype)
+        if noise.dim() == 2 and tuple(noise.shape) == (n, n_samples):
+            y = noise.t().unsqueeze(0).expand(B, n_samples, n)
+        elif noise.dim() == 3 and tuple(noise.shape) == (B, n, n_samples):
+            y = noise.transpose(1, 2)
+        else:
+            raise ValueError(f"sample_deltas: noise must be ({n}, {n_samples}) or ({B}, {n}, {n_samples}), got {tuple(noise.shape)}")
+        y = y.to(device=delta.device, dtype=delta.dtype).contiguous()
+        out = torch.empty_like(y)
+        self.K.band_solve_multi(self.Lb, n, self._plan.kd, self._perm, y, out, which=1)
+        out.mul_(math.sqrt(float(temperature))).add_(delta.unsqueeze(1))
+        return out.transpose(1, 2)
+
+    def _var_cols(self, what: str, name: str):
+        lin = self.linearization
+        try:
+            k = lin.ordering.index_of(name)
+        except KeyError:
+            raise ValueError(f"{what}: {name!r} is not an optimisation variable of the objective") from None
+        return range(lin.var_start_cols[k], lin.var_start_cols[k] + lin.var_dims[k])
+
+    @torch.no_grad()
+    def marginal_covariance(self, var_names: Sequence[str]) -> torch.Tensor:
+        """(B, d, d): the rows and columns of (AtA)^-1 at the columns of the named optimisation variables, in the order given (any
+        set of variables).  Factorises undamped and solves against the d unit vectors of those columns, one thx_pb_solve_multi
+        call, everything in the linearization's order."""
+        self._need_multi("marginal_covariance")
+        names = list(var_names)
+        if len(set(names)) != len(names):
+            raise ValueError(f"marginal_covariance: repeated variable names in {names}")
+        cols = [c for name in names for c in self._var_cols("marginal_covariance", name)]
+        if not cols:
+            raise ValueError("marginal_covariance: no variables named")
+        self._factorize_undamped()
+        B, n, d = self.Lb.shape[0], self.linearization.n, len(cols)
+        idx = torch.tensor(cols, dtype=torch.long, device=self.Lb.device)
+        E = torch.zeros(B, d, n, dtype=self.Lb.dtype, device=self.Lb.device)
+        E[:, torch.arange(d, device=idx.device), idx] = 1
+        X = torch.empty_like(E)
+        self.K.band_solve_multi(self.Lb, n, self._plan.kd, self._perm, E, X, which=0)
+        C = X[:, :, idx]
+        return (C + C.transpose(1, 2)) / 2
+
+    @torch.no_grad()
+    def marginal_covariances(self) -> Dict[str, torch.Tensor]:
+        """{name: (B, d_k, d_k)}: EVERY optimisation variable's own marginal covariance -- the diagonal blocks of (AtA)^-1 -- from
+        one undamped factorisation and ONE thx_pb_inverse_band launch (the band of the inverse by selected inversion, n kd^2 flops:
+        the cost of the factorisation, where unit-vector solves cost n^2 kd).  A variable's columns are contiguous in the banded
+        order, so its block lies inside the band when d_k - 1 <= kd; a wider variable raises."""
+        self._need_multi("marginal_covariances")
+        lin = self.linearization
+        plan = self.band_plan()
+        wide = [lin.ordering[k].name for k, d in enumerate(lin.var_dims) if d - 1 > plan.kd]
+        if wide:
+            raise RuntimeError(f"marginal_covariances: the blocks of {wide} are wider than the band (kd = {plan.kd}); use "
+                               "marginal_covariance(names) for them.")
+        self._factorize_undamped()
+        n = lin.n
+        Zb = torch.empty_like(self.Lb)
+        self.K.band_inverse(self.Lb, n, plan.kd, Zb)
+        if getattr(self, "_marg_index", None) is None or self._marg_index[0] is not plan or self._marg_index[1] != Zb.device:
+            # per block size d: (variables, J, I) with block k of that size = Zb[:, J[k], I[k]] -- S(p0 + hi, p0 + lo), symmetric
+            pos = torch.empty(n, dtype=torch.long)
+            pos[torch.from_numpy(plan.perm).long()] = torch.arange(n)      # banded position of a linearization column
+            groups = {}
+            for k, (c0, d) in enumerate(zip(lin.var_start_cols, lin.var_dims)):
+                p0 = int(pos[c0])
+                if pos[c0:c0 + d].tolist() != list(range(p0, p0 + d)):
+                    raise RuntimeError(f"marginal_covariances: the columns of {lin.ordering[k].name!r} are not contiguous in the band plan")
+                groups.setdefault(int(d), []).append((lin.ordering[k].name, p0))
+            index = []
+            for d, members in groups.items():
+                r = torch.arange(d)
+                hi, lo = torch.maximum(r[:, None], r[None, :]), torch.minimum(r[:, None], r[None, :])
+                p0 = torch.tensor([p for _, p in members]).view(-1, 1, 1)
+                index.append(([name for name, _ in members], (p0 + lo).to(Zb.device), (hi - lo).expand(len(members), d, d).to(Zb.device)))
+            self._marg_index = (plan, Zb.device, index)
+        out = {}
+        for names, J, I in self._marg_index[2]:        # one gather per block size
+            out.update(zip(names, Zb[:, J, I].unbind(1)))
+        return out
 
 
 class HipBandedCholeskySolver(HipBandedCholeskyCore, LinearSolver):
