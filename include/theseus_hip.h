@@ -413,6 +413,57 @@ int thx_traj2_eval(const thx_traj2_term* terms, int32_t n_terms, const void* x, 
 int thx_traj2_error(const thx_traj2_term* terms, int32_t n_terms, const void* x, int64_t ldx, int32_t n, void* err,
                     int32_t B, int dtype, void* stream);
 
+/* ---- ... and the backward of its implicit step: with g = -sum_t J_t^T e_t what thx_traj2_eval + thx_block_assemble form at the
+ *      (detached) state x and u (B, n) a cotangent of g, the gradient of u^T g w.r.t. every auxiliary tensor that asks for one.
+ *      Deterministic (no atomics, fixed reduction orders), two stages:
+ *      A  one thread per (term, problem): the term's partial derivatives in fp64 (the geometry -- cell, in-grid test,
+ *         distance > eps test -- in the run's dtype exactly as thx_traj2_eval decides it) into a record of THX_TRAJ2_REC doubles,
+ *         entry k of term t of problem b at rec[(t * THX_TRAJ2_REC + k) * B + b]:
+ *           collision  0-3 d/d corner value (ll, hl, lh, hh), 4-7 their cell indices row * cols + col, 8-9 origin, 10 cell size,
+ *                      11 cost_eps, 12 scale            (all zero outside the grid or where distance > eps)
+ *           GP         0 the cost's dt, 1 the weight's dt, 2-5 Qc_inv (row major; the off-diagonal derivative is split evenly,
+ *                      as the backward of torch.linalg.cholesky returns it)
+ *           prior      0-1 target, 2-3 weight (wdim = 1: their sum in 2)
+ *         terms that thx_traj2_eval skips write zeros.
+ *      B  small tensors: one workgroup per (tensor, problem), or per tensor that all problems share, sums the record entries its
+ *         (term, entry) pairs name, thread i the contributions i, i + 256, ... and then a fixed tree, in fp64, and writes
+ *         ``count`` values of the run's dtype at grad_out + out_off (+ b * count).  Grids: one workgroup per (grid, problem)
+ *         sorts the (cell, value) pairs of the collision terms that read the grid in LDS, THX_TRAJ2_SORT_CHUNK at a time, by
+ *         (cell, position in the list), sums equal cells in that order and adds the sums into the problem's fp64 grid in
+ *         grid_work (zeroed by the same workgroup first); one thread per cell then writes grad_out, for a shared grid the sum
+ *         over the problems in index order.
+ *      The plan is a HOST struct of counts and DEVICE tables; grad_out has plan->out_elems elements of the run's dtype,
+ *      grid_work plan->work_elems doubles (may be null without grids), rec n_terms * THX_TRAJ2_REC * B doubles.  Table entries
+ *      that point outside these sizes are skipped. */
+#define THX_TRAJ2_REC 16
+#define THX_TRAJ2_SORT_CHUNK 1024
+typedef struct {
+  int32_t term, entry; /* record entry ``entry`` (+ 0 .. count - 1) of term ``term`` */
+} thx_traj2_grad_pair;
+typedef struct {
+  int32_t pair_begin, pair_end; /* its pairs */
+  int32_t count, shared;        /* elements per problem; 1: one tensor for all problems */
+  int64_t out_off;
+} thx_traj2_grad_tensor;
+typedef struct {
+  int32_t term_begin, term_end; /* its collision terms in grid_terms */
+  int32_t rows, cols;
+  int32_t shared, pad_;
+  int64_t out_off, work_off;
+} thx_traj2_grad_grid;
+typedef struct {
+  int32_t n_tensors, n_pairs, n_grids, n_grid_terms;
+  int32_t max_cells, pad_; /* largest rows * cols of the grids */
+  const thx_traj2_grad_tensor* tensors;
+  const thx_traj2_grad_pair* pairs;
+  const thx_traj2_grad_grid* grids;
+  const int32_t* grid_terms;
+  int64_t out_elems, work_elems;
+} thx_traj2_grad_plan;
+int thx_traj2_vjp(const thx_traj2_term* terms, int32_t n_terms, const void* x, int64_t ldx, int32_t n, const void* u, int64_t ldu,
+                  int32_t m, int64_t j_total, double* rec, const thx_traj2_grad_plan* plan, void* grad_out, double* grid_work,
+                  int32_t B, int dtype, void* stream);
+
 /* ---- Planar pushing on SE2 (examples/tactile_pose_estimation.py): the cost family of the pose estimator in one launch.
  *      terms[t] (DEVICE array built by the host, sorted by kind) is one cost function on the pose-major SE2 state x (V, B, 4)
  *      = [x, y, cos, sin]; pose[s] = index of the cost's s-th optimisation variable in it (its tangent columns: 3 pose[s] ...):

@@ -21,6 +21,8 @@ THX_LU_MAX_N = 4096  # largest system of thx_lu_factor (include/theseus_hip.h)
 THX_BAND_MAX_KD = 63  # largest half-bandwidth of thx_band_factor (one window row per lane)
 THX_BA_ERR_CHUNKS = 256
 TRAJ2_COLLISION, TRAJ2_GP, TRAJ2_PRIOR = 0, 1, 2  # THX_TRAJ2_* (kinds of a thx_traj2_term)
+THX_TRAJ2_REC = 16  # doubles per (term, problem) record of thx_traj2_vjp
+THX_TRAJ2_SORT_CHUNK = 1024  # (cell, value) pairs its grid scatter sorts at a time
 PUSH2_QSP, PUSH2_MFB, PUSH2_CONTACT, PUSH2_PRIOR = 0, 1, 2, 3  # THX_PUSH2_* (kinds of a thx_push2_term)
 # THX_TRAJSE2_* (kinds of a thx_trajse2_term)
 TRAJSE2_COLLISION, TRAJSE2_GP, TRAJSE2_NONHOLONOMIC, TRAJSE2_HINGE, TRAJSE2_PRIOR_SE2, TRAJSE2_PRIOR_VEC, TRAJSE2_PRIOR_XY = range(7)
@@ -170,6 +172,11 @@ class PGData(Structure):
     ]
 
 
+class Traj2GradPlan(Structure):  # thx_traj2_grad_plan: counts (host) + device tables of thx_traj2_vjp's second stage
+    _fields_ = [(k, c_int32) for k in ("n_tensors", "n_pairs", "n_grids", "n_grid_terms", "max_cells", "pad")] + [
+        (k, c_void_p) for k in ("tensors", "pairs", "grids", "grid_terms")] + [("out_elems", c_int64), ("work_elems", c_int64)]
+
+
 # name -> (argtypes) ; every entry point returns int (0 = ok)
 _SIGNATURES = {
     "thx_se3_exp": [c_void_p, c_void_p, c_void_p, c_int64, c_int, POINTER(LieEps), c_void_p],
@@ -301,6 +308,8 @@ _SIGNATURES = {
     "thx_traj2_eval": [c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int,
                        c_void_p],
     "thx_traj2_error": [c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int, c_void_p],
+    "thx_traj2_vjp": [c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int64, c_void_p, POINTER(Traj2GradPlan),
+                      c_void_p, c_void_p, c_int32, c_int, c_void_p],
     "thx_push2_eval": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int,
                        POINTER(SE2Eps), c_void_p],
     "thx_push2_error": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int, POINTER(SE2Eps), c_void_p],

@@ -19,12 +19,21 @@ __device__ __forceinline__ T aux_at(const Term& tm, int k, int b, int i = 0) {
 // SignedDistanceField2D.signed_distance (signed_distance_field.py:163-241) at one point (px, py) of an R x C grid with origin
 // (ox, oy): the bilinear value and its derivatives w.r.t. px, py; all three zero outside the grid (sdf_boundary_value = 0).  Runs in
 // the run's dtype with contraction off and in the reference's operation order, so a kink lands where the torch classes put it.
+// ... what a backward kernel needs on top of the value: the clamped corner indices, the unclamped corner coordinates, the four
+// corner values and the in-grid test
 template <typename T>
-__device__ __forceinline__ void sdf_bilinear(const T* __restrict__ sdf, int R, int C, T ox, T oy, T cell, T px, T py, T& dist, T& j1,
-                                             T& j2) {
+struct SdfCells {
+  int lri, lci, hri, hci;
+  T lr, lc, sll, shl, slh, shh;
+  bool oob;
+};
+
+template <typename T>
+__device__ __forceinline__ void sdf_bilinear_cells(const T* __restrict__ sdf, int R, int C, T ox, T oy, T cell, T px, T py, T& dist,
+                                                   T& j1, T& j2, SdfCells<T>& k) {
 #pragma clang fp contract(off)
   // signed_distance_field.py:179-187
-  const bool oob = (px < ox) || (px > (ox + (T)(C - 1.0) * cell)) || (py < oy) || (py > (oy + (T)(R - 1.0) * cell));
+  k.oob = (px < ox) || (px > (ox + (T)(C - 1.0) * cell)) || (py < oy) || (py > (oy + (T)(R - 1.0) * cell));
   const T col = (px - ox) / cell, row = (py - oy) / cell;
   // :198-205 (the clamp is applied before the conversion: the same indices, and no out-of-range conversion)
   const T lr = floor(row), lc = floor(col), hr = lr + (T)1, hc = lc + (T)1;
@@ -39,7 +48,16 @@ __device__ __forceinline__ void sdf_bilinear(const T* __restrict__ sdf, int R, i
   dist = hrd * hcd * sll + lrd * hcd * shl + hrd * lcd * slh + lrd * lcd * shh;   // :215-220
   j1 = (hrd * (slh - sll) + lrd * (shh - shl)) / cell;                             // :231-238
   j2 = (hcd * (shl - sll) + lcd * (shh - slh)) / cell;
-  if (oob) dist = (T)0, j1 = (T)0, j2 = (T)0;
+  if (k.oob) dist = (T)0, j1 = (T)0, j2 = (T)0;
+  k.lri = lri, k.lci = lci, k.hri = hri, k.hci = hci;
+  k.lr = lr, k.lc = lc, k.sll = sll, k.shl = shl, k.slh = slh, k.shh = shh;
+}
+
+template <typename T>
+__device__ __forceinline__ void sdf_bilinear(const T* __restrict__ sdf, int R, int C, T ox, T oy, T cell, T px, T py, T& dist, T& j1,
+                                             T& j2) {
+  SdfCells<T> k;
+  sdf_bilinear_cells<T>(sdf, R, C, ox, oy, cell, px, py, dist, j1, j2, k);
 }
 
 // err = 0.5 * (sum of the workgroup's kErrThreads fp64 partials), by a fixed-order tree: deterministic, no atomics

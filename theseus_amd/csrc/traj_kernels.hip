@@ -146,6 +146,251 @@ traj2_error_kernel(const thx_traj2_term* __restrict__ terms, int n_terms, const 
   store_half_sum(acc, err + b);
 }
 
+// ---- thx_traj2_vjp: the gradient of u^T g, g = -sum_t J_t^T e_t at a detached state, w.r.t. the auxiliary tensors ------------------
+// Per term phi_t = -(sum_s J_s u_s) . e_t; floor(), the in-grid test and the distance > eps test are constants, as in the torch
+// classes.  Stage A (traj2_vjp_terms_kernel) writes each term's partial derivatives, stage B gathers them per tensor
+// (traj2_vjp_reduce_kernel) or scatters them into the grids (traj2_vjp_scatter_kernel + traj2_vjp_grid_out_kernel).
+constexpr int kRec = THX_TRAJ2_REC;
+constexpr int kSortChunk = THX_TRAJ2_SORT_CHUNK;
+
+// Collision2D: phi = w^2 s (eps - d), s = j1 u_x + j2 u_y.  The branches are collision_term's, in T; the derivatives in fp64.
+template <typename T>
+__device__ inline void collision_vjp(const thx_traj2_term& tm, const T* __restrict__ x, const T* __restrict__ u, int b, double* o) {
+  const T* sdf = static_cast<const T*>(tm.aux[0]) + (int64_t)b * tm.aux_bstride[0];
+  const T eps_t = aux_at<T>(tm, 3, b), ox_t = aux_at<T>(tm, 1, b, 0), oy_t = aux_at<T>(tm, 1, b, 1), cell_t = aux_at<T>(tm, 2, b);
+  const T px_t = x[tm.col[0]], py_t = x[tm.col[0] + 1];
+  T dist, j1, j2;
+  SdfCells<T> k;
+  sdf_bilinear_cells<T>(sdf, tm.rows, tm.cols, ox_t, oy_t, cell_t, px_t, py_t, dist, j1, j2, k);
+  if (k.oob || dist > eps_t) return;   // (the error and the block are constants there)
+  const double w = (double)aux_at<T>(tm, 4, b), eps = (double)eps_t, cell = (double)cell_t;
+  const double ux = (double)u[tm.col[0]], uy = (double)u[tm.col[0] + 1];
+  const double col = ((double)px_t - (double)ox_t) / cell, row = ((double)py_t - (double)oy_t) / cell;
+  const double lr = (double)k.lr, lc = (double)k.lc;
+  const double hrd = lr + 1.0 - row, hcd = lc + 1.0 - col, lrd = row - lr, lcd = col - lc;
+  const double sll = (double)k.sll, shl = (double)k.shl, slh = (double)k.slh, shh = (double)k.shh;
+  const double d = hrd * hcd * sll + lrd * hcd * shl + hrd * lcd * slh + lrd * lcd * shh;
+  const double dc = hrd * (slh - sll) + lrd * (shh - shl), dr = hcd * (shl - sll) + lcd * (shh - slh);   // d d / d col, d d / d row
+  const double s = (dc * ux + dr * uy) / cell, gap = eps - d, w2 = w * w;
+  // d s / d corner from the j1 / j2 formulas; the corner's bilinear weight is d d / d corner
+  o[0] = w2 * (gap * (-hrd * ux - hcd * uy) / cell - s * hrd * hcd);
+  o[1] = w2 * (gap * (-lrd * ux + hcd * uy) / cell - s * lrd * hcd);
+  o[2] = w2 * (gap * (hrd * ux - lcd * uy) / cell - s * hrd * lcd);
+  o[3] = w2 * (gap * (lrd * ux + lcd * uy) / cell - s * lrd * lcd);
+  o[4] = (double)((int64_t)k.lri * tm.cols + k.lci);
+  o[5] = (double)((int64_t)k.hri * tm.cols + k.lci);
+  o[6] = (double)((int64_t)k.lri * tm.cols + k.hci);
+  o[7] = (double)((int64_t)k.hri * tm.cols + k.hci);
+  // through col = (px - ox) / cell, row = (py - oy) / cell; the only second derivative of the bilinear form is the mixed one
+  const double mixed = sll - shl - slh + shh;
+  const double pcol = w2 * (gap * mixed * uy / cell - s * dc), prow = w2 * (gap * mixed * ux / cell - s * dr);
+  o[8] = -pcol / cell;
+  o[9] = -prow / cell;
+  o[10] = -(pcol * col + prow * row + w2 * gap * s) / cell;   // (the last: j1, j2 divide by the cell size themselves)
+  o[11] = w2 * s;
+  o[12] = 2.0 * w * s * gap;
+}
+
+// GPMotionModel: phi = -rho^T W r, W = M(dt_w) (x) Qc_inv, rho = [u_p2 - u_p1 - dt u_v1 ; u_v2 - u_v1]; no Cholesky is differentiated.
+// For a Qc_inv that is not symmetric the torch twin decides what each derivative sees: its Cholesky returns the symmetrised
+// cotangent, so d / d Qc_inv has the off-diagonal split evenly and d / d dt_w (through the twin's blocks 12 dt^-3 Qc_inv, ...) sees
+// (Qc_inv + Qc_inv^T) / 2; d / d dt sees the matrix that Cholesky factorises (below).
+template <typename T>
+__device__ inline void gp_vjp(const thx_traj2_term& tm, const T* __restrict__ x, const T* __restrict__ u, int b, double* o) {
+  const double dt = (double)aux_at<T>(tm, 0, b), dtw = (double)aux_at<T>(tm, 1, b);
+  const double q00 = (double)aux_at<T>(tm, 2, b, 0), q01 = (double)aux_at<T>(tm, 2, b, 1), q10 = (double)aux_at<T>(tm, 2, b, 2),
+               q11 = (double)aux_at<T>(tm, 2, b, 3);
+  const double M[2][2] = {{12.0 / (dtw * dtw * dtw), -6.0 / (dtw * dtw)}, {-6.0 / (dtw * dtw), 4.0 / dtw}};
+  const double dM[2][2] = {{-36.0 / (dtw * dtw * dtw * dtw), 12.0 / (dtw * dtw * dtw)}, {12.0 / (dtw * dtw * dtw), -4.0 / (dtw * dtw)}};
+  double r[2][2], rho[2][2], v1[2], uv1[2];
+  for (int i = 0; i < 2; ++i) {
+    v1[i] = (double)x[tm.col[1] + i], uv1[i] = (double)u[tm.col[1] + i];
+    r[0][i] = (double)x[tm.col[2] + i] - (double)x[tm.col[0] + i] - dt * v1[i];
+    r[1][i] = (double)x[tm.col[3] + i] - v1[i];
+    rho[0][i] = (double)u[tm.col[2] + i] - (double)u[tm.col[0] + i] - dt * uv1[i];
+    rho[1][i] = (double)u[tm.col[3] + i] - uv1[i];
+  }
+  auto form = [](const double* a, double m00, double m01, double m10, double m11, const double* c) {   // a^T [[m00, m01], [m10, m11]] c
+    return a[0] * (m00 * c[0] + m01 * c[1]) + a[1] * (m10 * c[0] + m11 * c[1]);
+  };
+  // the matrix the twin's Cholesky factorises is the lower triangle of W^T completed symmetrically: its diagonal blocks see the
+  // upper triangle of Qc_inv, the block below the diagonal all of Qc_inv^T (and the one above, by symmetry, Qc_inv)
+  const double qs = 0.5 * (q01 + q10);
+  double g_dtw = 0.0, G[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+  const double g_dt = M[0][0] * (form(uv1, q00, q01, q01, q11, r[0]) + form(rho[0], q00, q01, q01, q11, v1)) +
+         M[0][1] * (form(uv1, q00, q01, q10, q11, r[1]) + form(rho[1], q00, q10, q01, q11, v1));
+  for (int a = 0; a < 2; ++a) {
+    for (int c = 0; c < 2; ++c) {
+      g_dtw -= dM[a][c] * form(rho[a], q00, qs, qs, q11, r[c]);
+      for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j) G[i][j] -= M[a][c] * rho[a][i] * r[c][j];
+    }
+  }
+  o[0] = g_dt, o[1] = g_dtw;
+  o[2] = G[0][0], o[3] = o[4] = 0.5 * (G[0][1] + G[1][0]), o[5] = G[1][1];
+}
+
+// Difference: phi = -sum_i u_i w_i^2 (x_i - t_i)
+template <typename T>
+__device__ inline void prior_vjp(const thx_traj2_term& tm, const T* __restrict__ x, const T* __restrict__ u, int b, double* o) {
+  double gw[2];
+  for (int i = 0; i < 2; ++i) {
+    const double w = (double)aux_at<T>(tm, 1, b, tm.wdim == 2 ? i : 0), ui = (double)u[tm.col[0] + i];
+    o[i] = ui * w * w;
+    gw[i] = -2.0 * ui * w * ((double)x[tm.col[0] + i] - (double)aux_at<T>(tm, 0, b, i));
+  }
+  if (tm.wdim == 2) o[2] = gw[0], o[3] = gw[1];
+  else o[2] = gw[0] + gw[1];
+}
+
+// stage A: traj2_eval_kernel's map and guards; every (term, problem) writes its whole record, zeros where the term is skipped
+template <typename T>
+__global__ void __launch_bounds__(256)
+traj2_vjp_terms_kernel(const thx_traj2_term* __restrict__ terms, int n_terms, const T* __restrict__ x, int64_t ldx, int n,
+                       const T* __restrict__ u, int64_t ldu, int m, int64_t j_total, double* __restrict__ rec, int B) {
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (int64_t)n_terms * B) return;
+  const int t = (int)(gid / B), b = (int)(gid % B);
+  const thx_traj2_term tm = terms[t];
+  double o[kRec];
+  for (int k = 0; k < kRec; ++k) o[k] = 0.0;
+  bool ok = term_reads_ok(tm, n);
+  if (ok) {
+    const int dim = term_dim(tm.kind), nv = term_vars(tm.kind);
+    ok = !(tm.row0 < 0 || tm.row0 + dim > m || tm.j_off < 0 || tm.j_off + (int64_t)2 * dim * nv > j_total);
+  }
+  if (ok) {
+    const T* xb = x + (int64_t)b * ldx;
+    const T* ub = u + (int64_t)b * ldu;
+    if (tm.kind == THX_TRAJ2_COLLISION) collision_vjp<T>(tm, xb, ub, b, o);
+    else if (tm.kind == THX_TRAJ2_GP) gp_vjp<T>(tm, xb, ub, b, o);
+    else prior_vjp<T>(tm, xb, ub, b, o);
+  }
+  for (int k = 0; k < kRec; ++k) rec[((int64_t)t * kRec + k) * B + b] = o[k];
+}
+
+// stage B, small tensors: workgroup = (tensor, problem), or the tensor when it is shared; fixed-order sums in fp64
+template <typename T>
+__global__ void __launch_bounds__(256)
+traj2_vjp_reduce_kernel(const double* __restrict__ rec, int n_terms, const thx_traj2_grad_tensor* __restrict__ tensors,
+                        const thx_traj2_grad_pair* __restrict__ pairs, int n_pairs, T* __restrict__ out, int64_t out_elems, int B) {
+  __shared__ double part[256];
+  const int g = (int)(blockIdx.x / (unsigned)B), b = (int)(blockIdx.x % (unsigned)B);
+  const thx_traj2_grad_tensor tg = tensors[g];
+  // (everything below is uniform over the workgroup)
+  if (tg.shared && b > 0) return;
+  if (tg.pair_begin < 0 || tg.pair_end < tg.pair_begin || tg.pair_end > n_pairs || tg.count < 1 || tg.count > kRec) return;
+  const int64_t o0 = tg.out_off + (tg.shared ? 0 : (int64_t)b * tg.count);
+  if (tg.out_off < 0 || o0 + tg.count > out_elems) return;
+  const int64_t contributions = (int64_t)(tg.pair_end - tg.pair_begin) * (tg.shared ? B : 1);
+  for (int j = 0; j < tg.count; ++j) {
+    double acc = 0.0;
+    for (int64_t c = threadIdx.x; c < contributions; c += 256) {
+      const thx_traj2_grad_pair pr = pairs[tg.pair_begin + (tg.shared ? c / B : c)];
+      const int bb = tg.shared ? (int)(c % B) : b;
+      if (pr.term < 0 || pr.term >= n_terms || pr.entry < 0 || pr.entry + tg.count > kRec) continue;
+      acc += rec[((int64_t)pr.term * kRec + pr.entry + j) * B + bb];
+    }
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) out[o0 + j] = (T)part[0];
+    __syncthreads();
+  }
+}
+
+// stage B, grids: workgroup = (problem, grid).  The four (cell, value) pairs of each collision term on this grid go through LDS a
+// chunk at a time: a bitonic network sorts the chunk by (cell, position in the list) -- a unique key, so the order of equal cells
+// is fixed --, the head of each run of equal cells sums the run in that order and adds it into the problem's fp64 grid.  Within a
+// chunk a cell has one head; chunks follow one another behind a barrier, so a cell two chunks touch is updated in chunk order.
+__global__ void __launch_bounds__(256)
+traj2_vjp_scatter_kernel(const double* __restrict__ rec, const thx_traj2_term* __restrict__ terms, int n_terms,
+                         const thx_traj2_grad_grid* __restrict__ grids, const int32_t* __restrict__ grid_terms, int n_grid_terms,
+                         double* __restrict__ work, int64_t work_elems, int B) {
+  __shared__ unsigned long long key[kSortChunk];
+  __shared__ double val[kSortChunk];
+  constexpr unsigned long long kPad = ~0ull;
+  const int b = blockIdx.x;
+  const thx_traj2_grad_grid gd = grids[blockIdx.y];
+  const int64_t cells = (int64_t)gd.rows * gd.cols;
+  if (gd.rows < 1 || gd.cols < 1 || cells > INT32_MAX || gd.term_begin < 0 || gd.term_end < gd.term_begin || gd.term_end > n_grid_terms)
+    return;
+  if (gd.work_off < 0 || gd.work_off + cells * B > work_elems) return;
+  double* gg = work + gd.work_off + cells * b;
+  for (int64_t c = threadIdx.x; c < cells; c += 256) gg[c] = 0.0;
+  __syncthreads();
+  const int64_t n_src = (int64_t)4 * (gd.term_end - gd.term_begin);
+  for (int64_t base = 0; base < n_src; base += kSortChunk) {
+    for (int i = threadIdx.x; i < kSortChunk; i += 256) {
+      const int64_t p = base + i;
+      unsigned long long kk = kPad;
+      double v = 0.0;
+      if (p < n_src) {
+        const int t = grid_terms[gd.term_begin + p / 4], c = (int)(p % 4);
+        if (t >= 0 && t < n_terms && terms[t].kind == THX_TRAJ2_COLLISION && terms[t].rows == gd.rows && terms[t].cols == gd.cols) {
+          const double cell = rec[((int64_t)t * kRec + 4 + c) * B + b];
+          if (cell >= 0.0 && cell < (double)cells) {
+            kk = ((unsigned long long)cell << 32) | (unsigned long long)i;   // (i: the position within the chunk, p - base)
+            v = rec[((int64_t)t * kRec + c) * B + b];
+          }
+        }
+      }
+      key[i] = kk, val[i] = v;
+    }
+    __syncthreads();
+    for (int k = 2; k <= kSortChunk; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int i = threadIdx.x; i < kSortChunk; i += 256) {
+          const int l = i ^ j;
+          if (l > i) {
+            const unsigned long long a = key[i], c = key[l];
+            if ((a > c) == ((i & k) == 0)) {
+              const double va = val[i];
+              key[i] = c, key[l] = a, val[i] = val[l], val[l] = va;
+            }
+          }
+        }
+        __syncthreads();
+      }
+    for (int i = threadIdx.x; i < kSortChunk; i += 256) {
+      const unsigned long long a = key[i];
+      if (a == kPad || (i > 0 && (key[i - 1] >> 32) == (a >> 32))) continue;   // padding, or inside a run
+      double acc = 0.0;
+      for (int q = i; q < kSortChunk && (key[q] >> 32) == (a >> 32); ++q) acc += val[q];
+      gg[a >> 32] += acc;
+    }
+    __syncthreads();
+  }
+}
+
+// ... and out of the fp64 grids: one thread per (problem, cell), cells fastest; a shared grid is summed over the problems in index order
+template <typename T>
+__global__ void __launch_bounds__(256)
+traj2_vjp_grid_out_kernel(const double* __restrict__ work, int64_t work_elems, const thx_traj2_grad_grid* __restrict__ grids,
+                          int max_cells, T* __restrict__ out, int64_t out_elems, int B) {
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (int64_t)max_cells * B) return;
+  const int b = (int)(gid / max_cells);
+  const int64_t c = gid % max_cells;
+  const thx_traj2_grad_grid gd = grids[blockIdx.y];
+  const int64_t cells = (int64_t)gd.rows * gd.cols;
+  if (gd.rows < 1 || gd.cols < 1 || c >= cells || (gd.shared && b > 0)) return;
+  if (gd.work_off < 0 || gd.work_off + cells * B > work_elems || gd.out_off < 0) return;
+  const double* gg = work + gd.work_off;
+  if (gd.shared) {
+    if (gd.out_off + cells > out_elems) return;
+    double acc = 0.0;
+    for (int bb = 0; bb < B; ++bb) acc += gg[cells * bb + c];
+    out[gd.out_off + c] = (T)acc;
+  } else {
+    if (gd.out_off + cells * B > out_elems) return;
+    out[gd.out_off + cells * b + c] = (T)gg[cells * b + c];
+  }
+}
+
 // the family's own size checks: the message of the first that fails
 inline const char* traj2_bad_size(int64_t ldx, int32_t n) { return n < 2 ? ": n < 2" : (ldx < n ? ": ldx < n" : nullptr); }
 
@@ -165,6 +410,55 @@ extern "C" int thx_traj2_eval(const thx_traj2_term* terms, int32_t n_terms, cons
                                   ldx, n, (float*)J, j_total, (float*)e, lde, m, B),
                hipLaunchKernelGGL(traj2_eval_kernel<double>, grid, block, 0, as_stream(stream), terms, n_terms, (const double*)x,
                                   ldx, n, (double*)J, j_total, (double*)e, lde, m, B));
+  return check_launch(who);
+}
+
+extern "C" int thx_traj2_vjp(const thx_traj2_term* terms, int32_t n_terms, const void* x, int64_t ldx, int32_t n, const void* u,
+                             int64_t ldu, int32_t m, int64_t j_total, double* rec, const thx_traj2_grad_plan* plan, void* grad_out,
+                             double* grid_work, int32_t B, int dtype, void* stream) {
+  const char* who = "thx_traj2_vjp";
+  if (int rc = family_check(who, !u || !rec || !plan || !grad_out, terms, n_terms, x, 1, B, dtype, traj2_bad_size(ldx, n))) return rc;
+  if (ldu < n) return fail(who, ": ldu < n");
+  if (m < 1 || j_total < 2) return fail(who, ": m < 1 or j_total < 2");
+  const thx_traj2_grad_plan p = *plan;
+  if (p.n_tensors < 0 || p.n_pairs < 0 || p.n_grids < 0 || p.n_grid_terms < 0 || p.max_cells < 0 || p.out_elems < 1 || p.work_elems < 0)
+    return fail(who, ": negative size in the plan");
+  if ((p.n_tensors > 0 && (!p.tensors || !p.pairs)) || (p.n_grids > 0 && (!p.grids || !p.grid_terms || !grid_work || p.max_cells < 1)))
+    return fail(who, ": null pointer in the plan");
+  const uintptr_t el = dtype == THX_F32 ? 4 : 8;
+  auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+  if (at(u) % el || at(grad_out) % el || at(rec) % 8 || at(grid_work) % 8 || at(p.tensors) % 8 || at(p.pairs) % 4 || at(p.grids) % 8 ||
+      at(p.grid_terms) % 4)
+    return fail(who, ": pointer not aligned");
+  const int64_t term_blocks = ((int64_t)n_terms * B + 255) / 256, out_blocks = ((int64_t)p.max_cells * B + 255) / 256;
+  if (term_blocks > (int64_t)INT32_MAX || (int64_t)p.n_tensors * B > (int64_t)INT32_MAX || out_blocks > (int64_t)INT32_MAX ||
+      p.n_grids > 65535)
+    return fail(who, ": grid limit exceeded (n_terms * B, tensors * B, cells * B or the number of grids)");
+  hipStream_t s = as_stream(stream);
+  const dim3 block(256);
+  THX_DISPATCH(dtype,
+               hipLaunchKernelGGL(traj2_vjp_terms_kernel<float>, dim3((unsigned)term_blocks), block, 0, s, terms, n_terms,
+                                  (const float*)x, ldx, n, (const float*)u, ldu, m, j_total, rec, B),
+               hipLaunchKernelGGL(traj2_vjp_terms_kernel<double>, dim3((unsigned)term_blocks), block, 0, s, terms, n_terms,
+                                  (const double*)x, ldx, n, (const double*)u, ldu, m, j_total, rec, B));
+  if (p.n_tensors > 0) {
+    const dim3 grid((unsigned)((int64_t)p.n_tensors * B));
+    THX_DISPATCH(dtype,
+                 hipLaunchKernelGGL(traj2_vjp_reduce_kernel<float>, grid, block, 0, s, rec, n_terms, p.tensors, p.pairs, p.n_pairs,
+                                    (float*)grad_out, p.out_elems, B),
+                 hipLaunchKernelGGL(traj2_vjp_reduce_kernel<double>, grid, block, 0, s, rec, n_terms, p.tensors, p.pairs, p.n_pairs,
+                                    (double*)grad_out, p.out_elems, B));
+  }
+  if (p.n_grids > 0) {
+    hipLaunchKernelGGL(traj2_vjp_scatter_kernel, dim3((unsigned)B, (unsigned)p.n_grids), block, 0, s, rec, terms, n_terms, p.grids,
+                       p.grid_terms, p.n_grid_terms, grid_work, p.work_elems, B);
+    const dim3 grid((unsigned)out_blocks, (unsigned)p.n_grids);
+    THX_DISPATCH(dtype,
+                 hipLaunchKernelGGL(traj2_vjp_grid_out_kernel<float>, grid, block, 0, s, grid_work, p.work_elems, p.grids, p.max_cells,
+                                    (float*)grad_out, p.out_elems, B),
+                 hipLaunchKernelGGL(traj2_vjp_grid_out_kernel<double>, grid, block, 0, s, grid_work, p.work_elems, p.grids, p.max_cells,
+                                    (double*)grad_out, p.out_elems, B));
+  }
   return check_launch(who);
 }
 

@@ -744,8 +744,9 @@ def _traj2_kind(c):
 
 class PackedTrajectory2D(TermTable, PackedEuclidean):
     """PackedEuclidean whose NON-differentiated evaluation is fused (theseus_amd/term_table.py): ``assemble(graph=False)`` =
-    thx_traj2_eval into persistent block buffers + thx_block_assemble on them, ``error_metric`` = thx_traj2_error.  Everything
-    differentiated (``assemble(graph=True)``, ``unrolled_step``) is the parent's."""
+    thx_traj2_eval into persistent block buffers + thx_block_assemble on them, ``error_metric`` = thx_traj2_error.  The implicit
+    step (``assemble(graph=True)`` with an auxiliary tensor that requires grad) is the same forward with thx_traj2_vjp as its
+    backward; ``unrolled_step`` is the parent's."""
 
     _TERM, _TANGENT = TRAJ2_TERM, 2
     _KINDS = {
@@ -777,6 +778,13 @@ class PackedTrajectory2D(TermTable, PackedEuclidean):
 
     def _launch_error(self, state, err):
         self.K.traj2_error(self._table, len(self.costs), state, self.n, err)
+
+    # the implicit step's backward (thx_traj2_vjp): where each aux slot's derivative sits in a term's record
+    _VJP_KERNEL, _VJP_REC = "traj2_vjp", _lib.THX_TRAJ2_REC
+    _VJP_ENTRIES = {_lib.TRAJ2_COLLISION: (0, 8, 10, 11, 12), _lib.TRAJ2_GP: (0, 1, 2), _lib.TRAJ2_PRIOR: (0, 2)}
+
+    def _launch_vjp(self, table, state, u, rec, plan, grad_out, grid_work):
+        self.K.traj2_vjp(table, len(self.costs), state, self.n, u, self.m, self.j_total, rec, plan, grad_out, grid_work)
 
 
 # robot kinematics and the inverse-kinematics cost family live in theseus_amd/kinematics.py; theseus_amd.eb exports them

@@ -693,6 +693,22 @@ class HipKernels:
         _lib.check(self.lib.thx_traj2_error(_lib.ptr(table), int(n_terms), ctypes.c_void_p(x.data_ptr()), x.stride(0), int(n),
                                             _lib.ptr(err), B, _lib.dtype_code(x.dtype), _lib.stream_ptr(x.device)), "thx_traj2_error")
 
+    def traj2_vjp(self, table, n_terms, x, n, u, m, j_total, rec, plan, grad_out, grid_work):
+        """The gradient of (u * g).sum(), g what ``traj2_eval`` + the block assembly form at x, w.r.t. the auxiliary tensors of the
+        gradient plan: x, u (B, >= n); rec fp64 scratch (n_terms * THX_TRAJ2_REC * B); plan a ``_lib.Traj2GradPlan`` whose tables are
+        device tensors; grad_out (plan.out_elems) of x's dtype; grid_work fp64 (plan.work_elems), None without grids."""
+        B = x.shape[0]
+        if (x.stride(1) != 1 or u.stride(1) != 1 or u.shape[0] != B or u.dtype != x.dtype or grad_out.dtype != x.dtype
+                or rec.dtype != torch.float64 or rec.numel() < n_terms * _lib.THX_TRAJ2_REC * B or grad_out.numel() < plan.out_elems
+                or (plan.n_grids and (grid_work is None or grid_work.dtype != torch.float64 or grid_work.numel() < plan.work_elems))):
+            raise ValueError("traj2_vjp: state / cotangent / scratch do not fit")
+        if not x.is_cuda or not u.is_cuda:
+            raise RuntimeError(f"traj2_vjp: the state must live on a HIP device (got {x.device}); there is no CPU fallback")
+        _lib.check(self.lib.thx_traj2_vjp(_lib.ptr(table), int(n_terms), ctypes.c_void_p(x.data_ptr()), x.stride(0), int(n),
+                                          ctypes.c_void_p(u.data_ptr()), u.stride(0), int(m), int(j_total), _lib.ptr(rec),
+                                          ctypes.byref(plan), _lib.ptr(grad_out), _lib.ptr(grid_work), B, _lib.dtype_code(x.dtype),
+                                          _lib.stream_ptr(x.device)), "thx_traj2_vjp")
+
     # ---- homography image alignment (csrc/homog_kernels.hip) -------------------------------------------
     def _homog_args(self, what, table, n_terms, n_align, x, n, scratch, chunks):
         """the leading arguments thx_homog_eval and thx_homog_error share"""

@@ -15,14 +15,29 @@ A family supplies data and two launches:
   _WEIGHT_WIDTHS  (allowed widths of a Scale / Diagonal weight, the message for any other)
   _term_vars(c)   what goes into the variable field of cost c's record
   _launch_eval(state), _launch_error(state, err)
-and sets ``self.kinds`` (one per cost function, objective order) before or in the packed class's constructor."""
+and sets ``self.kinds`` (one per cost function, objective order) before or in the packed class's constructor.
+
+Optional, the backward of the implicit step (``assemble(graph=True)`` with an auxiliary tensor that requires grad) in kernels too:
+  _VJP_KERNEL     the name of the kernel set's method, _VJP_REC the doubles of its per-(term, problem) record
+  _VJP_ENTRIES    {kind: the record entry of each aux slot}
+  _launch_vjp(table, state, u, rec, plan, grad_out, grid_work)
+A family without them, or a kernel set without the method, stays on the torch path for everything differentiated."""
 from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
+from . import _lib
 from .core import Variable
 from .generic import _names
+
+# thx_traj2_grad_pair / thx_traj2_grad_tensor / thx_traj2_grad_grid of include/theseus_hip.h
+GRAD_PAIR = np.dtype([("term", "<i4"), ("entry", "<i4")])
+GRAD_TENSOR = np.dtype([("pair_begin", "<i4"), ("pair_end", "<i4"), ("count", "<i4"), ("shared", "<i4"), ("out_off", "<i8")])
+GRAD_GRID = np.dtype([("term_begin", "<i4"), ("term_end", "<i4"), ("rows", "<i4"), ("cols", "<i4"), ("shared", "<i4"), ("pad", "<i4"),
+                      ("out_off", "<i8"), ("work_off", "<i8")])
+assert (GRAD_PAIR.itemsize, GRAD_TENSOR.itemsize, GRAD_GRID.itemsize) == (8, 24, 40)
 
 
 def term_dtype(var_field: str) -> np.dtype:
@@ -45,8 +60,37 @@ class TermKind(NamedTuple):
     weight: Optional[int] = None   # ... or the aux slot of a Scale / Diagonal weight whose width it is
 
 
+class GradPlan(NamedTuple):
+    """Which record entries of which terms feed the gradient of every DISTINCT auxiliary tensor that requires grad."""
+    inputs: list      # the distinct auxiliary tensors, in table order
+    offsets: list     # per input: where its gradient starts in the kernel's output, None where none is asked for
+    struct: object    # _lib.Traj2GradPlan (counts + the device pointers of ``tables``)
+    tables: tuple     # the uploaded tables (kept alive)
+
+    def asked(self):
+        return tuple(o is not None for o in self.offsets)
+
+
+class _FusedGradient(torch.autograd.Function):
+    """g as a function of the auxiliary tensors: forward hands over the gradient the kernels formed, backward is the family's VJP
+    kernel at the state of the forward.  The state is cloned: the optimiser loop retracts its state buffer in place, so a later
+    ``forward()`` on the same objective would otherwise move it under a pending ``backward()``."""
+
+    @staticmethod
+    def forward(ctx, packed, g, *inputs):
+        ctx.packed, ctx.plan, ctx.table, ctx.refs = packed, packed._grad_plan, packed._table, packed._aux_refs
+        ctx.state = packed._state.detach().clone()
+        return g.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, u):
+        return (None, None) + ctx.packed._vjp(ctx.plan, ctx.table, ctx.state, u.contiguous())
+
+
 class TermTable:
     fused = True    # False: the same packed class on the torch classes (tools/bench_push2.py's baseline)
+    fused_backward = True   # False: the implicit step's backward through the torch classes (tools/bench_traj2_backward.py's baseline)
 
     def __init__(self, objective, kernels=None, order=None):
         super().__init__(objective, kernels, order)
@@ -59,7 +103,8 @@ class TermTable:
             j += self._TANGENT * c.dim() * len(vs)
         self.rows, self.joff, self.j_total = rows, joff, j
         self.term_order = sorted(range(len(self.costs)), key=lambda c: kinds[c])   # (stable: by kind, then the objective's order)
-        self._aux_refs = self._aux_key = self._table = None
+        self._aux_refs = self._aux_key = self._table = self._grad_plan = None
+        self._vjp_rec = self._vjp_work = None
         self._aux_stamp = -1
         self._J = self._e = self._Jv = self._ev = None
         self._asm_cache = {}
@@ -77,7 +122,8 @@ class TermTable:
         tensors = [[a.tensor for a, _ in ts] for ts in aux]
         # which tensor every slot holds, and where each DISTINCT tensor lives (most are shared by many costs)
         key = tuple(id(t) for ts in tensors for t in ts)
-        key += tuple((t.data_ptr(), t.shape[0], t.stride(0)) for t in {id(t): t for ts in tensors for t in ts}.values()) + (str(dev), B)
+        distinct = {id(t): t for ts in tensors for t in ts}
+        key += tuple((t.data_ptr(), t.shape[0], t.stride(0), t.requires_grad) for t in distinct.values()) + (str(dev), B)
         self._aux_stamp = Variable._global_updates
         if self._table is not None and key == self._aux_key:
             return
@@ -122,8 +168,65 @@ class TermTable:
                     raise ValueError(message)
         self._table = torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).to(dev)
         self._aux_refs, self._aux_key = (tensors, refs), key
+        self._grad_plan = self._build_grad_plan(tensors, dev) if hasattr(self, "_launch_vjp") else None
         if key is None:
             self._aux_stamp = -1
+
+    def _build_grad_plan(self, tensors, dev) -> GradPlan:
+        """Stage B of the family's VJP kernel (include/theseus_hip.h: thx_traj2_grad_plan), built with the term table: per distinct
+        tensor that requires grad the (term slot, record entry) pairs that feed it, or for a grid the collision terms that read it."""
+        B = self.batch
+        feeds = {}   # id -> (tensor, [(slot, entry)], [slot of a term that reads it as its grid])
+        for slot, c in enumerate(self.term_order):
+            kind, entries = self._KINDS[self.kinds[c]], self._VJP_ENTRIES[self.kinds[c]]
+            for k, t in enumerate(tensors[c]):
+                _, pairs, grid_terms = feeds.setdefault(id(t), (t, [], []))
+                if k == kind.grid:
+                    grid_terms.append(slot)
+                else:
+                    pairs.append((slot, entries[k]))
+        inputs, offsets = [t for t, _, _ in feeds.values()], []
+        pairs_all, terms_all, rows_t, rows_g, out, work = [], [], [], [], 0, 0
+        for t, pairs, grid_terms in feeds.values():
+            if not t.requires_grad:
+                offsets.append(None)
+                continue
+            if pairs and grid_terms:
+                raise ValueError("an auxiliary tensor that requires grad is both a grid and a parameter of the objective")
+            shared = int(t.shape[0] == 1)
+            if grid_terms:
+                cells = t.shape[-2] * t.shape[-1]
+                rows_g.append((len(terms_all), len(terms_all) + len(grid_terms), t.shape[-2], t.shape[-1], shared, 0, out, work))
+                terms_all += grid_terms
+                work += cells * B
+            else:
+                rows_t.append((len(pairs_all), len(pairs_all) + len(pairs), t[0].numel(), shared, out))
+                pairs_all += pairs
+            offsets.append(out)
+            out += t.numel()
+        arrays = (np.array(rows_t, GRAD_TENSOR), np.array(pairs_all, GRAD_PAIR), np.array(rows_g, GRAD_GRID), np.array(terms_all, np.int32))
+        tables = tuple(torch.from_numpy(np.frombuffer(a.tobytes() or bytes(8), np.uint8).copy()).to(dev) for a in arrays)
+        struct = _lib.Traj2GradPlan(len(rows_t), len(pairs_all), len(rows_g), len(terms_all), max([r[2] * r[3] for r in rows_g] + [0]), 0,
+                                    *[t.data_ptr() for t in tables], out, work)
+        return GradPlan(inputs, offsets, struct, tables)
+
+    def _fused_backward_route(self) -> bool:
+        """the gate of the fused backward: a property of the family and the kernel set, never a fallback after a failure"""
+        return (self.fused_backward and hasattr(self, "_launch_vjp") and hasattr(self.K, self._VJP_KERNEL)
+                and not self._state.requires_grad and any(t.requires_grad for t in self._grad_plan.inputs))
+
+    def _vjp(self, plan: GradPlan, table, state, u):
+        """-> one gradient per input of the plan, in that input's shape (None where none is asked for)"""
+        dev = state.device
+        need = len(self.costs) * self._VJP_REC * state.shape[0]
+        if self._vjp_rec is None or self._vjp_rec.numel() < need or self._vjp_rec.device != dev:
+            self._vjp_rec = torch.empty(need, dtype=torch.float64, device=dev)
+        need = plan.struct.work_elems
+        if need and (self._vjp_work is None or self._vjp_work.numel() < need or self._vjp_work.device != dev):
+            self._vjp_work = torch.empty(need, dtype=torch.float64, device=dev)
+        out = torch.zeros(plan.struct.out_elems, dtype=state.dtype, device=dev)
+        self._launch_vjp(table, state, u, self._vjp_rec, plan.struct, out, self._vjp_work if need else None)
+        return tuple(None if o is None else out[o:o + t.numel()].view(t.shape) for t, o in zip(plan.inputs, plan.offsets))
 
     def _buffers(self):
         B, dev, dt, w = self.batch, self._state.device, self._state.dtype, self._TANGENT
@@ -155,13 +258,24 @@ class TermTable:
 
     def assemble(self, H: torch.Tensor, g: torch.Tensor, graph: bool = False):
         """``graph`` with nothing to differentiate (the implicit step under no_grad, or no leaf requires grad) is fused as well: the
-        returned gradient is the one the kernels formed."""
-        if not self.fused or (graph and self._differentiated()):
+        returned gradient is the one the kernels formed.  With something to differentiate it is fused where the family has a VJP
+        kernel (``_fused_backward_route``): the returned gradient is then a function of the auxiliary tensors whose backward is that
+        kernel; the optimisation variables get no gradient, as on the torch path of the implicit step."""
+        if not self.fused:
             return super().assemble(H, g, graph)
+        differentiated = graph and self._differentiated()
+        if differentiated:
+            self.sync()
+            if not self._fused_backward_route():
+                return super().assemble(H, g, graph)
         Jv, ev = self._eval()
         self.K.block_assemble_strided(self.asm, Jv, ev, H, g, self._asm_cache)
         self._blocks = (Jv, ev)
-        return g.clone() if graph else None
+        if not differentiated:
+            return g.clone() if graph else None
+        if self._grad_plan.asked() != tuple(t.requires_grad for t in self._grad_plan.inputs):
+            self._sync_aux(deep=True)   # (requires_grad_() on a tensor the table already holds)
+        return _FusedGradient.apply(self, g, *self._grad_plan.inputs)
 
     def error_metric(self, state=None, out: Optional[torch.Tensor] = None, poses=None):
         self.sync()
