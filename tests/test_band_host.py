@@ -70,8 +70,11 @@ def test_header_library_ctypes_table_and_build_agree_on_the_band_names(lib_path)
 
 def test_banded_solver_is_exported_with_the_cholesky_solvers_constructor():
     import theseus_amd as th
-    from theseus_amd.linear_solver import DenseCholeskyOnly, HipBandedCholeskyCore, HipCholeskyCore
-    assert issubclass(th.HipBandedCholeskySolver, HipBandedCholeskyCore) and issubclass(HipBandedCholeskyCore, DenseCholeskyOnly)
+    from theseus_amd.linear_solver import HipBandedCholeskyCore, HipCholeskyCore
+    assert issubclass(th.HipBandedCholeskySolver, HipBandedCholeskyCore)
+    # siblings under one core: nothing of the dense frame is reachable on the band core
+    for name in ("_natural_factor", "_ordered", "_solve_frame", "_envelope"):
+        assert not hasattr(HipBandedCholeskyCore, name) and hasattr(HipCholeskyCore, name), name
     assert list(inspect.signature(th.HipBandedCholeskySolver.__init__).parameters) == \
         list(inspect.signature(th.HipCholeskySolver.__init__).parameters)
     # the surface the loops and the autograd nodes call on the Cholesky core (tests/test_lu_host.py lists it for the LU core)

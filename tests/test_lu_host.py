@@ -64,6 +64,9 @@ def test_lu_solver_is_exported_with_the_cholesky_solvers_constructor():
     for name in ("factorize", "_substitute", "solve_with_factor", "factor_snapshot", "solve_with_snapshot", "check_info",
                  "singular_mask", "dropped_mask", "post_singular_warning", "_solve"):
         assert callable(getattr(HipLUCore, name)) and callable(getattr(HipCholeskyCore, name)), name
+    # siblings under one core: nothing of the dense frame is reachable on the LU core
+    for name in ("_natural_factor", "_ordered", "_solve_frame", "_envelope"):
+        assert not hasattr(HipLUCore, name) and hasattr(HipCholeskyCore, name), name
     with pytest.raises(RuntimeError, match="HipLUSolver only works with theseus_amd.HipLinearization"):
         th.HipLUSolver(th.Objective(), linearization_cls=dict)
 
@@ -101,6 +104,15 @@ def test_plugin_lu_solver_passes_the_reference_whitelists(ref):
     assert isinstance(opt.linear_solver, thp.HipLUSolver)
     # levenberg_marquardt.py:16-32,82-87: both damping variants are whitelisted by isinstance on the solver, at construction
     assert opt._allows_ellipsoidal and opt._allows_adaptive
+
+
+@needs_reference
+@pytest.mark.reference
+def test_plugin_lu_solver_has_the_cholesky_solvers_constructor_without_the_lagged_check(ref):
+    import inspect
+    _, thp = ref
+    want = [p for p in inspect.signature(thp.HipCholeskySolver.__init__).parameters if p != "lagged_failure_check"]
+    assert list(inspect.signature(thp.HipLUSolver.__init__).parameters) == want
 
 
 @needs_reference

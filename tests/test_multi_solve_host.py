@@ -67,16 +67,32 @@ def test_cores_without_a_dense_cholesky_frame_raise(core):
             obj.marginal_covariance(["a"])
         with pytest.raises(NotImplementedError, match="HipCholeskySolver"):
             obj.solve_multi_with_factor(torch.zeros(1, 1, 1))
-    import theseus_amd as th
-    for solver in (th.HipLUSolver, sparse.HipSparseCholeskySolver, ba.HipSchurSolver):
-        assert issubclass(solver, linear_solver.DenseCholeskyOnly)
-        assert solver.sample_deltas is linear_solver.DenseCholeskyOnly.sample_deltas
-    assert th.HipCholeskySolver.sample_deltas is linear_solver.HipCholeskyCore.sample_deltas
 
 
-@pytest.fixture
-def solver_and_layer():
+def _refuses_all_three(solver_cls):
+    obj = object.__new__(solver_cls)
+    for call in (lambda: obj.sample_deltas(3), lambda: obj.marginal_covariance(["a"]),
+                 lambda: obj.solve_multi_with_factor(torch.zeros(1, 1, 1))):
+        with pytest.raises(NotImplementedError, match="HipCholeskySolver"):
+            call()
+
+
+def test_solver_classes_without_the_multi_hook_raise_and_the_others_share_one_surface():
     import theseus_amd as th
+    from theseus_amd import ba, linear_solver, sparse
+    for solver_cls in (th.HipLUSolver, sparse.HipSparseCholeskySolver, ba.HipSchurSolver):
+        _refuses_all_three(solver_cls)
+    for name in ("sample_deltas", "marginal_covariance", "solve_multi_with_factor"):
+        shared = getattr(linear_solver.FactorCore, name)
+        assert getattr(th.HipCholeskySolver, name) is shared and getattr(th.HipBandedCholeskySolver, name) is shared, name
+
+
+@pytest.fixture(params=["dense", "banded"])
+def solver_and_layer(request):
+    """(solver, layer) on two Vector variables with one prior each, chained by a cost between them; "banded": the same objective
+    on HipBandedCholeskySolver with the band stand-ins that carry band_solve_multi (tests/band_multi_oracle_kernels.py)."""
+    import theseus_amd as th
+    from tests.band_multi_oracle_kernels import BandMultiOracleKernels
     from tests.oracle_kernels import OracleKernels
     dt = torch.float64
     obj = th.Objective(dtype=dt)
@@ -87,13 +103,17 @@ def solver_and_layer():
         target = th.Variable(torch.ones(2, width, dtype=dt), name="t" + v.name)
         obj.add(th.AutoDiffCostFunction([v], lambda optim_vars, aux_vars: optim_vars[0].tensor - aux_vars[0].tensor, width,
                                         aux_vars=[target], cost_weight=one, name="d" + v.name))
-    opt = th.GaussNewton(obj, max_iterations=2, linearization_kwargs=dict(kernels=OracleKernels()))
+    obj.add(th.AutoDiffCostFunction([a, b], lambda optim_vars, aux_vars: optim_vars[0].tensor[:, :2] - optim_vars[1].tensor, 2,
+                                    cost_weight=one, name="chain"))
+    kw = dict(linearization_kwargs=dict(kernels=OracleKernels())) if request.param == "dense" else \
+        dict(linear_solver_cls=th.HipBandedCholeskySolver, linearization_kwargs=dict(kernels=BandMultiOracleKernels()))
+    opt = th.GaussNewton(obj, max_iterations=2, **kw)
+    assert type(opt.linear_solver).__name__ == {"dense": "HipCholeskySolver", "banded": "HipBandedCholeskySolver"}[request.param]
     return opt.linear_solver, th.TheseusLayer(opt)
 
 
 def test_argument_checks_that_need_no_device(solver_and_layer):
     solver, layer = solver_and_layer
-    assert type(solver).__name__ == "HipCholeskySolver"
     with pytest.raises(ValueError, match="not an optimisation variable"):
         solver.marginal_covariance(["a", "nope"])
     with pytest.raises(ValueError, match="repeated"):
@@ -140,6 +160,14 @@ def ref():
     import theseus as th
     import theseus_amd.plugin as thp
     return th, thp
+
+
+@needs_reference
+@pytest.mark.reference
+def test_plugin_solver_classes_without_the_multi_hook_raise(ref):
+    _, thp = ref
+    for solver_cls in (thp.HipLUSolver, thp.HipSparseCholeskySolver, thp.HipSchurSolver):
+        _refuses_all_three(solver_cls)
 
 
 def _standin_kernels():

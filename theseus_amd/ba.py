@@ -19,7 +19,7 @@ from . import _lib
 from .core import Objective
 from .compiler import PoseGraphStructure
 from .kernels import PGTensors, fast_approx_local_jacobians, round_up
-from .linear_solver import DenseCholeskyOnly, LinearSolver
+from .linear_solver import FactorCore, LinearSolver, check_damping, checked_linearization_cls
 from .linearization import Linearization, VariableOrdering
 from .packed import UnsupportedObjective, _aux_vars, _kind, _radius_vars, _unwrap_robust, _weight_diag
 from .packer_base import TrackedVariables
@@ -589,9 +589,11 @@ class _SchurBlockList:
         return self._dev[key]
 
 
-class HipSchurSolverCore(DenseCholeskyOnly):
+class HipSchurSolverCore(FactorCore):
     """(H + damping) delta = g of a bundle-adjustment linearization by block elimination of the points + the tiled dense
-    Cholesky on the reduced camera system.  Same ``solve`` contract and failure behaviour as ``HipCholeskySolver``."""
+    Cholesky on the reduced camera system.  Same ``solve`` contract and failure behaviour as ``HipCholeskySolver``.  The
+    elimination wraps the factorisation, so this core writes ``_solve`` and ``solve_with_factor`` whole instead of the factor
+    hooks of ``FactorCore``; the factor of the reduced system serves no blocks of right-hand sides."""
 
     def _schur_solver_init(self, sparse_reduced_system: bool = True, ordering: str = "auto"):
         self.K = self.linearization.K
@@ -733,16 +735,9 @@ class HipSchurSolverCore(DenseCholeskyOnly):
         lin = self.linearization
         if lin.g is None:
             raise RuntimeError("linearize() must be called before solve().")
-        if damping is not None and isinstance(damping, torch.Tensor) and damping.ndim > 1:
-            raise ValueError("Damping must be a float or a 1-D tensor.")
+        check_damping(damping)
         self._ensure_buffers()
-        lam = None
-        if damping is not None:
-            lam = self._lam
-            if isinstance(damping, torch.Tensor):
-                lam.copy_(damping.to(lam.dtype).expand(lam.shape[0]))
-            else:
-                lam.fill_(float(damping))
+        lam = self._lam_of(damping)
         p = lin.packed
         self.factor_version += 1
         self._factor_args = (lam.clone() if lam is not None else None, ellipsoidal_damping, damping_eps)
@@ -1064,9 +1059,7 @@ class HipSchurSolver(HipSchurSolverCore, LinearSolver):
         """``sparse_reduced_system=False``: factorise the reduced camera system as a dense matrix even where its tile pattern
         has holes (for comparisons; the result is the same bit for bit).  ``ordering``: "auto" | "nd" | "md" | "natural" -- the
         camera order of the reduced system's factorisation (HipSchurSolverCore._schur_solver_init)."""
-        linearization_cls = linearization_cls or HipSchurLinearization
-        if not (isinstance(linearization_cls, type) and issubclass(linearization_cls, HipSchurLinearization)):
-            raise RuntimeError(f"HipSchurSolver only works with HipSchurLinearization, but {linearization_cls} was provided.")
+        linearization_cls = checked_linearization_cls("HipSchurSolver", linearization_cls, HipSchurLinearization, "HipSchurLinearization")
         LinearSolver.__init__(self, objective, linearization_cls, linearization_kwargs)
         self._schur_solver_init(sparse_reduced_system, ordering)
 

@@ -1027,6 +1027,22 @@ class HipKernels:
                                                         self._row_first_ptr(row_first, n), _lib.dtype_code(L.dtype),
                                                         _lib.stream_ptr(L.device)), "thx_chol_solve_backward")
 
+    @staticmethod
+    def _rhs_block(what, factor_names, factor, B, n, rhs, x):
+        """-> (nrhs, ldv, bstride) of a (B, nrhs, n) block ``rhs`` and its result ``x`` for the multi-vector solves on ``factor``
+        (its tensors; ``factor_names``: as the error text lists them): shapes, one dtype, equal strides, on a HIP device."""
+        if rhs.dim() != 3 or rhs.shape[0] != B or rhs.shape[2] != n or rhs.shape[1] < 1 or x.shape != rhs.shape:
+            raise ValueError(f"{what}: rhs {tuple(rhs.shape)} / x {tuple(x.shape)} must both be (B = {B}, nrhs >= 1, n = {n})")
+        if not all(t.dtype == rhs.dtype for t in (*factor, x)):
+            raise ValueError(f"{what}: {factor_names}, rhs and x must have one dtype")
+        if rhs.stride() != x.stride() or rhs.stride(2) != 1:
+            raise ValueError(f"{what}: rhs and x need the same strides, unit stride along n")
+        for t, name in ((rhs, "rhs"), (x, "x")):
+            if not t.is_cuda:
+                raise RuntimeError(f"{name} must live on a HIP device (got {t.device}); there is no CPU fallback")
+        nrhs, ldv = rhs.shape[1], (rhs.stride(1) if rhs.shape[1] > 1 else max(rhs.stride(1), n))   # (one row: its stride is arbitrary)
+        return nrhs, ldv, (rhs.stride(0) if B > 1 else max(rhs.stride(0), nrhs * ldv))
+
     def chol_solve_multi(self, L, n, panels, rhs, x, which=0):
         """thx_chol_solve_multi: ``rhs`` / ``x`` (B, nrhs, n), one vector per row (unit stride along n, any row / batch strides
         that do not overlap); which = 0: (L L^T)^-1 rhs, 1: L^-T rhs, 2: L^-1 rhs.  ``x`` may be ``rhs``."""
@@ -1034,17 +1050,7 @@ class HipKernels:
         nt = (n + _lib.THX_TILE - 1) // _lib.THX_TILE
         if L.dim() != 3 or L.shape[1] != ld or tuple(panels.shape) != (B, nt, _lib.THX_TILE, _lib.THX_TILE):
             raise ValueError(f"chol_solve_multi: L {tuple(L.shape)} / panels {tuple(panels.shape)} are not a dense factor frame of order {n}")
-        if rhs.dim() != 3 or rhs.shape[0] != B or rhs.shape[2] != n or rhs.shape[1] < 1 or x.shape != rhs.shape:
-            raise ValueError(f"chol_solve_multi: rhs {tuple(rhs.shape)} / x {tuple(x.shape)} must both be (B = {B}, nrhs >= 1, n = {n})")
-        if not (L.dtype == panels.dtype == rhs.dtype == x.dtype):
-            raise ValueError("chol_solve_multi: L, panels, rhs and x must have one dtype")
-        if rhs.stride() != x.stride() or rhs.stride(2) != 1:
-            raise ValueError("chol_solve_multi: rhs and x need the same strides, unit stride along n")
-        for t, name in ((rhs, "rhs"), (x, "x")):
-            if not t.is_cuda:
-                raise RuntimeError(f"{name} must live on a HIP device (got {t.device}); there is no CPU fallback")
-        nrhs, ldv = rhs.shape[1], (rhs.stride(1) if rhs.shape[1] > 1 else max(rhs.stride(1), n))
-        bstride = rhs.stride(0) if B > 1 else max(rhs.stride(0), nrhs * ldv)
+        nrhs, ldv, bstride = self._rhs_block("chol_solve_multi", "L, panels", (L, panels), B, n, rhs, x)
         _lib.check(self.lib.thx_chol_solve_multi(_lib.ptr(L, "L"), ld, n, B, _lib.ptr(panels, "panels"), _lib.c_void_p(rhs.data_ptr()),
                                                  _lib.c_void_p(x.data_ptr()), nrhs, ldv, bstride, int(which), _lib.dtype_code(L.dtype),
                                                  _lib.stream_ptr(L.device)), "thx_chol_solve_multi")
@@ -1134,17 +1140,7 @@ class HipKernels:
         any row / batch strides that do not overlap).  which = 0: (L L^T)^-1 rhs, both in the linearization's order; 2: L^-1 P rhs,
         linearization's order in, banded order out; 1: P^T L^-T rhs, banded order in, linearization's out.  ``x`` may be ``rhs``."""
         B = self._band_shapes("band_solve_multi", Lb, n, kd, perm)
-        if rhs.dim() != 3 or rhs.shape[0] != B or rhs.shape[2] != n or rhs.shape[1] < 1 or x.shape != rhs.shape:
-            raise ValueError(f"band_solve_multi: rhs {tuple(rhs.shape)} / x {tuple(x.shape)} must both be (B = {B}, nrhs >= 1, n = {n})")
-        if not (Lb.dtype == rhs.dtype == x.dtype):
-            raise ValueError("band_solve_multi: Lb, rhs and x must have one dtype")
-        if rhs.stride() != x.stride() or rhs.stride(2) != 1:
-            raise ValueError("band_solve_multi: rhs and x need the same strides, unit stride along n")
-        for t, name in ((rhs, "rhs"), (x, "x")):
-            if not t.is_cuda:
-                raise RuntimeError(f"{name} must live on a HIP device (got {t.device}); there is no CPU fallback")
-        nrhs, ldv = rhs.shape[1], (rhs.stride(1) if rhs.shape[1] > 1 else max(rhs.stride(1), n))
-        bstride = rhs.stride(0) if B > 1 else max(rhs.stride(0), nrhs * ldv)
+        nrhs, ldv, bstride = self._rhs_block("band_solve_multi", "Lb", (Lb,), B, n, rhs, x)
         _lib.check(self.lib.thx_pb_solve_multi(_lib.ptr(Lb, "Lb"), n, kd, B, _lib.ptr(perm, "perm"), _lib.c_void_p(rhs.data_ptr()),
                                                _lib.c_void_p(x.data_ptr()), nrhs, ldv, bstride, int(which), _lib.dtype_code(Lb.dtype),
                                                _lib.stream_ptr(Lb.device)), "thx_pb_solve_multi")

@@ -27,6 +27,7 @@ pose-graph / bundle-adjustment paths make ``solve()`` one autograd node over the
 ``theseus`` is imported at module import: this file is only usable where the reference is installed (it is not on
 the GPU box of this build; tests/test_plugin_reference.py exercises it in the container that has /root/reference).
 """
+import functools
 from typing import Any, Dict, List, Optional, Type, Union
 
 import torch
@@ -42,7 +43,8 @@ from theseus.global_params import _THESEUS_GLOBAL_PARAMS as _REF_GLOBAL_PARAMS
 from .generic import BlockAssembler
 from .autograd import detached_tensors, pg_vjp_grads
 from .kernels import default_kernels, round_up
-from .linear_solver import HipBandedCholeskyCore, HipCholeskyCore, HipLUCore
+from .linear_solver import (HipBandedCholeskyCore, HipCholeskyCore, HipLUCore, check_damping, checked_linearization_cls,
+                            init_solver)
 from .linearization import HipLinearizationCore
 from .packed import UnsupportedObjective
 from . import kernels as _kernels
@@ -599,14 +601,74 @@ class _TensorSystem:
         return d
 
 
-class _TensorSystemSolver(HipCholeskyCore):
+class _TensorSystemCore:
+    """Mixed in front of a core: that core on a ``_TensorSystem`` instead of a solver's linearization."""
+
     def __init__(self, K, check_singular: bool):
         self.linearization = _TensorSystem(K)
         self._check_singular = check_singular
         self._core_init()
 
 
-class HipCholeskySolver(HipCholeskyCore, _RefCholeskyDenseSolver):
+class _TensorSystemSolver(_TensorSystemCore, HipCholeskyCore):
+    pass
+
+
+class _TensorSystemLUSolver(_TensorSystemCore, HipLUCore):
+    pass
+
+
+_init_solver = functools.partial(init_solver, base=_RefLinearSolver, required=HipLinearization,
+                                 required_name="theseus_amd.plugin.HipLinearization")
+
+
+class _SolveDispatch:
+    """``solve()`` of the solvers on a ``HipLinearization``, in the reference's signature: a system handed over as plain tensors
+    -> the differentiated nodes, where the linearization carries a graph -> the plain solve.  A failure is a RuntimeError, which
+    the reference loop turns into FAIL status under no_grad (nonlinear_least_squares.py:138-152)."""
+
+    _tensor_solver_cls: Optional[type] = None   # the core ``_solve_tensor_system`` solves a system handed over as tensors with
+
+    def solve(self, damping: Optional[Union[float, torch.Tensor]] = None, ellipsoidal_damping: bool = True,
+              damping_eps: float = 1e-8, **kwargs) -> torch.Tensor:
+        check_damping(damping)
+        lin = self.linearization
+        if self._external_system():
+            return self._solve_tensor_system(lin.AtA, lin.Atb, damping, ellipsoidal_damping, damping_eps)
+        if getattr(lin, "_unroll", None) is not None and torch.is_grad_enabled():
+            # backward_mode "unroll" / "truncated" on a fused pose graph: one node, whose backward solves with a copy of this
+            # call's factor (dense frame, band, or the tile-packed factor along its pattern)
+            return _FusedUnrolledSolve.apply(self, damping, ellipsoidal_damping, damping_eps, *lin._unroll)
+        g = lin._g_graph
+        if g is not None and torch.is_grad_enabled():
+            Hg = getattr(lin, "_H_graph", None)   # (the generic path's Hessian in the graph; a fused linearization has none)
+            if Hg is not None:
+                return _UnrolledFactorSolve.apply(self, damping, ellipsoidal_damping, damping_eps, Hg, g)
+            return _CachedFactorSolve.apply(self, damping, ellipsoidal_damping, damping_eps, g)
+        return self._plain_solve(damping, ellipsoidal_damping, damping_eps)
+
+    def _plain_solve(self, damping, ellipsoidal_damping, damping_eps) -> torch.Tensor:
+        return self._solve(damping, ellipsoidal_damping, damping_eps, check_info=True)
+
+    def _external_system(self) -> bool:
+        lin = self.linearization
+        return not isinstance(lin, HipLinearization) or lin._ext_AtA is not None or lin._ext_Atb is not None
+
+    def _solve_tensor_system(self, AtA, Atb, damping, ellipsoidal_damping, damping_eps) -> torch.Tensor:
+        """``solve()`` on whatever ``linearization.AtA`` / ``.Atb`` return (dense_solver.py:84-123 reads nothing else): same
+        kernels, the system copied into their frame first (``_TensorSystem``; the LU core factorises the matrix as it is, general
+        mode of thx_lu_factor).  Gradients through it assume a symmetric system, as ``_UnrolledFactorSolve`` does."""
+        sub = getattr(self, "_tensor_solver", None)
+        if sub is None:
+            sub = self._tensor_solver = self._tensor_solver_cls(self.K, self._check_singular)
+        sub.linearization.load(AtA, Atb)
+        if torch.is_grad_enabled() and (AtA.requires_grad or Atb.requires_grad):
+            return _UnrolledFactorSolve.apply(sub, damping, ellipsoidal_damping, damping_eps, AtA,
+                                              Atb.reshape(AtA.shape[0], AtA.shape[1]))
+        return sub._solve(damping, ellipsoidal_damping, damping_eps, check_info=True)
+
+
+class HipCholeskySolver(_SolveDispatch, HipCholeskyCore, _RefCholeskyDenseSolver):
     """Replaces ``th.CholeskyDenseSolver`` (theseus/optimizer/linear/dense_solver.py:20-161).
 
     It subclasses the reference's class so that ``LevenbergMarquardt``'s isinstance whitelists for ellipsoidal /
@@ -614,19 +676,13 @@ class HipCholeskySolver(HipCholeskyCore, _RefCholeskyDenseSolver):
     ``DenseSolver.__init__`` rejects every linearization class that is not literally ``DenseLinearization``
     (dense_solver.py:28-32)."""
 
+    _tensor_solver_cls = _TensorSystemSolver
+
     def __init__(self, objective: th.Objective, linearization_cls: Optional[Type[_RefLinearization]] = None,
                  linearization_kwargs: Optional[Dict[str, Any]] = None, check_singular: bool = False,
                  lagged_failure_check: bool = False, ordering: str = "auto", **kwargs):
-        if ordering not in ("auto", "natural"):   # (theseus_amd/linear_solver.py: HipCholeskyCore.ordering)
-            raise ValueError(f"ordering must be 'auto' or 'natural', got {ordering!r}")
-        self.ordering = ordering
-        linearization_cls = linearization_cls or HipLinearization
-        if not (isinstance(linearization_cls, type) and issubclass(linearization_cls, HipLinearization)):
-            raise RuntimeError("HipCholeskySolver only works with theseus_amd.plugin.HipLinearization, "
-                               f"but {linearization_cls} was provided.")
-        _RefLinearSolver.__init__(self, objective, linearization_cls, linearization_kwargs)
-        self._check_singular = check_singular
-        self._core_init()
+        # (``ordering``: theseus_amd/linear_solver.py: HipCholeskyCore.ordering)
+        _init_solver(self, "HipCholeskySolver", objective, linearization_cls, linearization_kwargs, check_singular, ordering)
         self._lagged = bool(lagged_failure_check)
         self._lag = None
 
@@ -649,7 +705,9 @@ class HipCholeskySolver(HipCholeskyCore, _RefCholeskyDenseSolver):
                           "(not positive definite); its step was dropped.", RuntimeWarning)
         self._lag = None
 
-    def _lagged_solve(self, damping, ellipsoidal_damping, damping_eps) -> torch.Tensor:
+    def _plain_solve(self, damping, ellipsoidal_damping, damping_eps) -> torch.Tensor:
+        if not self._lagged:
+            return self._solve(damping, ellipsoidal_damping, damping_eps, check_info=True)
         from .nonlinear import _LaggedFlag
         if self._lag is not None and self._lag.seen():
             self._lag = None
@@ -663,45 +721,6 @@ class HipCholeskySolver(HipCholeskyCore, _RefCholeskyDenseSolver):
             self._lag = _LaggedFlag(delta.device)
         self._lag.post(failed.any())
         return delta
-
-    def solve(self, damping: Optional[Union[float, torch.Tensor]] = None, ellipsoidal_damping: bool = True,
-              damping_eps: float = 1e-8, **kwargs) -> torch.Tensor:
-        # failure = RuntimeError, which the reference loop turns into FAIL status under no_grad
-        # (nonlinear_least_squares.py:138-152)
-        lin = self.linearization
-        if not isinstance(lin, HipLinearization) or lin._ext_AtA is not None or lin._ext_Atb is not None:
-            return self._solve_tensor_system(lin.AtA, lin.Atb, damping, ellipsoidal_damping, damping_eps)
-        if getattr(lin, "_unroll", None) is not None and torch.is_grad_enabled():
-            if damping is not None and isinstance(damping, torch.Tensor) and damping.ndim > 1:
-                raise ValueError("Damping must be a float or a 1-D tensor.")
-            return _FusedUnrolledSolve.apply(self, damping, ellipsoidal_damping, damping_eps, *lin._unroll)
-        g = lin._g_graph
-        if g is not None and torch.is_grad_enabled():
-            if damping is not None and isinstance(damping, torch.Tensor) and damping.ndim > 1:
-                raise ValueError("Damping must be a float or a 1-D tensor.")
-            Hg = getattr(lin, "_H_graph", None)
-            if Hg is not None:
-                return _UnrolledFactorSolve.apply(self, damping, ellipsoidal_damping, damping_eps, Hg, g)
-            return _CachedFactorSolve.apply(self, damping, ellipsoidal_damping, damping_eps, g)
-        if self._lagged:
-            return self._lagged_solve(damping, ellipsoidal_damping, damping_eps)
-        return self._solve(damping, ellipsoidal_damping, damping_eps, check_info=True)
-
-    def _solve_tensor_system(self, AtA, Atb, damping, ellipsoidal_damping, damping_eps) -> torch.Tensor:
-        """``solve()`` on whatever ``linearization.AtA`` / ``.Atb`` return (dense_solver.py:84-123 reads nothing else): same
-        kernels, the system copied into their frame first (``_TensorSystem``)."""
-        sub = getattr(self, "_tensor_solver", None)
-        if sub is None:
-            sub = self._tensor_solver = _TensorSystemSolver(self.K, self._check_singular)
-        sub.linearization.load(AtA, Atb)
-        if torch.is_grad_enabled() and (AtA.requires_grad or Atb.requires_grad):
-            return _UnrolledFactorSolve.apply(sub, damping, ellipsoidal_damping, damping_eps, AtA,
-                                              Atb.reshape(AtA.shape[0], AtA.shape[1]))
-        return sub._solve(damping, ellipsoidal_damping, damping_eps, check_info=True)
-
-    def _external_system(self) -> bool:
-        lin = self.linearization
-        return not isinstance(lin, HipLinearization) or lin._ext_AtA is not None or lin._ext_Atb is not None
 
     def _factor_owner(self):
         # (a system handed over as tensors is factorised by the tensor solver's core: None until solve() has built it)
@@ -717,63 +736,25 @@ class HipCholeskySolver(HipCholeskyCore, _RefCholeskyDenseSolver):
         raise NotImplementedError("HipCholeskySolver.solve() factorises its linearization's packed Hessian")
 
 
-class _TensorSystemLUSolver(HipLUCore):
-    def __init__(self, K, check_singular: bool):
-        self.linearization = _TensorSystem(K)
-        self._check_singular = check_singular
-        self._core_init()
-
-
-class HipLUSolver(HipLUCore, _RefLUDenseSolver):
+class HipLUSolver(_SolveDispatch, HipLUCore, _RefLUDenseSolver):
     """Replaces ``th.LUDenseSolver`` (theseus/optimizer/linear/dense_solver.py:125-141) -- the solver for systems that are not
     numerically positive definite.  Subclasses the reference's class (LM's isinstance whitelists) and calls
-    ``LinearSolver.__init__`` directly, as ``HipCholeskySolver`` above and for the same reason."""
+    ``LinearSolver.__init__`` directly, as ``HipCholeskySolver`` above and for the same reason.  A singular system is the
+    RuntimeError of ``HipLUCore.check_info``."""
+
+    _tensor_solver_cls = _TensorSystemLUSolver
 
     def __init__(self, objective: th.Objective, linearization_cls: Optional[Type[_RefLinearization]] = None,
-                 linearization_kwargs: Optional[Dict[str, Any]] = None, check_singular: bool = False, **kwargs):
-        linearization_cls = linearization_cls or HipLinearization
-        if not (isinstance(linearization_cls, type) and issubclass(linearization_cls, HipLinearization)):
-            raise RuntimeError("HipLUSolver only works with theseus_amd.plugin.HipLinearization, "
-                               f"but {linearization_cls} was provided.")
-        _RefLinearSolver.__init__(self, objective, linearization_cls, linearization_kwargs)
-        self._check_singular = check_singular
-        self._core_init()
-
-    def solve(self, damping: Optional[Union[float, torch.Tensor]] = None, ellipsoidal_damping: bool = True,
-              damping_eps: float = 1e-8, **kwargs) -> torch.Tensor:
-        # the dispatch of HipCholeskySolver.solve; a singular system = RuntimeError = FAIL status under no_grad
-        lin = self.linearization
-        if not isinstance(lin, HipLinearization) or lin._ext_AtA is not None or lin._ext_Atb is not None:
-            return self._solve_tensor_system(lin.AtA, lin.Atb, damping, ellipsoidal_damping, damping_eps)
-        if damping is not None and isinstance(damping, torch.Tensor) and damping.ndim > 1:
-            raise ValueError("Damping must be a float or a 1-D tensor.")
-        if getattr(lin, "_unroll", None) is not None and torch.is_grad_enabled():
-            return _FusedUnrolledSolve.apply(self, damping, ellipsoidal_damping, damping_eps, *lin._unroll)
-        g = lin._g_graph
-        if g is not None and torch.is_grad_enabled():
-            Hg = getattr(lin, "_H_graph", None)
-            if Hg is not None:
-                return _UnrolledFactorSolve.apply(self, damping, ellipsoidal_damping, damping_eps, Hg, g)
-            return _CachedFactorSolve.apply(self, damping, ellipsoidal_damping, damping_eps, g)
-        return self._solve(damping, ellipsoidal_damping, damping_eps, check_info=True)
-
-    def _solve_tensor_system(self, AtA, Atb, damping, ellipsoidal_damping, damping_eps) -> torch.Tensor:
-        """``solve()`` on whatever ``linearization.AtA`` / ``.Atb`` return: the matrix is factorised as it is (general mode of
-        thx_lu_factor).  Gradients through it assume a symmetric system, as ``_UnrolledFactorSolve`` does."""
-        sub = getattr(self, "_tensor_solver", None)
-        if sub is None:
-            sub = self._tensor_solver = _TensorSystemLUSolver(self.K, self._check_singular)
-        sub.linearization.load(AtA, Atb)
-        if torch.is_grad_enabled() and (AtA.requires_grad or Atb.requires_grad):
-            return _UnrolledFactorSolve.apply(sub, damping, ellipsoidal_damping, damping_eps, AtA,
-                                              Atb.reshape(AtA.shape[0], AtA.shape[1]))
-        return sub._solve(damping, ellipsoidal_damping, damping_eps, check_info=True)
+                 linearization_kwargs: Optional[Dict[str, Any]] = None, check_singular: bool = False, ordering: str = "auto",
+                 **kwargs):
+        # (``ordering``: accepted and unused, theseus_amd/linear_solver.py: HipLUSolver)
+        _init_solver(self, "HipLUSolver", objective, linearization_cls, linearization_kwargs, check_singular)
 
     def _solve_sytem(self, Atb: torch.Tensor, AtA: torch.Tensor) -> torch.Tensor:  # abstract in DenseSolver
         raise NotImplementedError("HipLUSolver.solve() factorises its linearization's packed Hessian")
 
 
-class HipBandedCholeskySolver(HipBandedCholeskyCore, _RefCholeskyDenseSolver):
+class HipBandedCholeskySolver(_SolveDispatch, HipBandedCholeskyCore, _RefCholeskyDenseSolver):
     """``linear_solver_cls`` for the REAL theseus loop on objectives whose Hessian is banded in some order of the variables
     (motion planning, odometry chains): thx_band_factor / thx_band_solve* instead of the dense factorisation
     (theseus_amd/linear_solver.py: HipBandedCholeskyCore).  Subclasses the reference's ``CholeskyDenseSolver`` (LM's isinstance
@@ -783,35 +764,11 @@ class HipBandedCholeskySolver(HipBandedCholeskyCore, _RefCholeskyDenseSolver):
     def __init__(self, objective: th.Objective, linearization_cls: Optional[Type[_RefLinearization]] = None,
                  linearization_kwargs: Optional[Dict[str, Any]] = None, check_singular: bool = False, ordering: str = "auto",
                  **kwargs):
-        if ordering not in ("auto", "natural"):
-            raise ValueError(f"ordering must be 'auto' or 'natural', got {ordering!r}")
-        self.ordering = ordering
-        linearization_cls = linearization_cls or HipLinearization
-        if not (isinstance(linearization_cls, type) and issubclass(linearization_cls, HipLinearization)):
-            raise RuntimeError("HipBandedCholeskySolver only works with theseus_amd.plugin.HipLinearization, "
-                               f"but {linearization_cls} was provided.")
-        _RefLinearSolver.__init__(self, objective, linearization_cls, linearization_kwargs)
-        self._check_singular = check_singular
-        self._core_init()
+        _init_solver(self, "HipBandedCholeskySolver", objective, linearization_cls, linearization_kwargs, check_singular, ordering)
 
-    def solve(self, damping: Optional[Union[float, torch.Tensor]] = None, ellipsoidal_damping: bool = True,
-              damping_eps: float = 1e-8, **kwargs) -> torch.Tensor:
-        # the dispatch of HipLUSolver.solve; a failed factorisation = RuntimeError = FAIL status under no_grad
-        lin = self.linearization
-        if not isinstance(lin, HipLinearization) or lin._ext_AtA is not None or lin._ext_Atb is not None:
-            raise NotImplementedError("HipBandedCholeskySolver: a system handed over as plain tensors has no block pattern to find "
-                                      "a band in; use HipCholeskySolver (or HipLUSolver) for it.")
-        if damping is not None and isinstance(damping, torch.Tensor) and damping.ndim > 1:
-            raise ValueError("Damping must be a float or a 1-D tensor.")
-        if getattr(lin, "_unroll", None) is not None and torch.is_grad_enabled():
-            return _FusedUnrolledSolve.apply(self, damping, ellipsoidal_damping, damping_eps, *lin._unroll)
-        g = lin._g_graph
-        if g is not None and torch.is_grad_enabled():
-            Hg = getattr(lin, "_H_graph", None)
-            if Hg is not None:
-                return _UnrolledFactorSolve.apply(self, damping, ellipsoidal_damping, damping_eps, Hg, g)
-            return _CachedFactorSolve.apply(self, damping, ellipsoidal_damping, damping_eps, g)
-        return self._solve(damping, ellipsoidal_damping, damping_eps, check_info=True)
+    def _solve_tensor_system(self, AtA, Atb, damping, ellipsoidal_damping, damping_eps) -> torch.Tensor:
+        raise NotImplementedError("HipBandedCholeskySolver: a system handed over as plain tensors has no block pattern to find "
+                                  "a band in; use HipCholeskySolver (or HipLUSolver) for it.")
 
     def _solve_sytem(self, Atb: torch.Tensor, AtA: torch.Tensor) -> torch.Tensor:  # abstract in DenseSolver
         raise NotImplementedError("HipBandedCholeskySolver.solve() factorises its linearization's packed Hessian")
@@ -821,17 +778,15 @@ class HipBandedCholeskySolver(HipBandedCholeskyCore, _RefCholeskyDenseSolver):
 from .sparse import HipSparseCholeskyCore, fill_reducing_ordering  # noqa: E402
 
 
-class HipSparseCholeskySolver(HipSparseCholeskyCore, _RefCholeskyDenseSolver):
+class HipSparseCholeskySolver(_SolveDispatch, HipSparseCholeskyCore, _RefCholeskyDenseSolver):
     """``linear_solver_cls`` for the REAL theseus loop in BaspachoSparseSolver's role (baspacho_sparse_solver.py:23-148) on
     SE3 / SE2 / SO3 pose graphs.  The fill-reducing ordering is a ``th.optimizer.VariableOrdering`` given to the linearization:
     the reference loop retracts and reads ``delta`` through it (nonlinear_least_squares.py:97)."""
 
     def __init__(self, objective: th.Objective, linearization_cls: Optional[Type[_RefLinearization]] = None,
                  linearization_kwargs: Optional[Dict[str, Any]] = None, check_singular: bool = False, **kwargs):
-        linearization_cls = linearization_cls or HipLinearization
-        if not (isinstance(linearization_cls, type) and issubclass(linearization_cls, HipLinearization)):
-            raise RuntimeError(f"HipSparseCholeskySolver only works with theseus_amd.plugin.HipLinearization, but "
-                               f"{linearization_cls} was provided.")
+        linearization_cls = checked_linearization_cls("HipSparseCholeskySolver", linearization_cls, HipLinearization,
+                                                      "theseus_amd.plugin.HipLinearization")
         linearization_kwargs = dict(linearization_kwargs or {})
         if linearization_kwargs.get("ordering") is None:
             linearization_kwargs["ordering"] = fill_reducing_ordering(objective, th.optimizer.VariableOrdering)
@@ -841,21 +796,8 @@ class HipSparseCholeskySolver(HipSparseCholeskyCore, _RefCholeskyDenseSolver):
         self._check_singular = check_singular
         self._sparse_init()
 
-    def solve(self, damping: Optional[Union[float, torch.Tensor]] = None, ellipsoidal_damping: bool = True,
-              damping_eps: float = 1e-8, **kwargs) -> torch.Tensor:
-        lin = self.linearization
-        if getattr(lin, "_unroll", None) is not None and torch.is_grad_enabled():
-            # backward_mode "unroll" / "truncated": the same node as the dense solver's; its backward solves along the tile pattern
-            # with a copy of this call's (tile-packed) factor
-            if damping is not None and isinstance(damping, torch.Tensor) and damping.ndim > 1:
-                raise ValueError("Damping must be a float or a 1-D tensor.")
-            return _FusedUnrolledSolve.apply(self, damping, ellipsoidal_damping, damping_eps, *lin._unroll)
-        g = lin._g_graph
-        if g is not None and torch.is_grad_enabled():
-            if damping is not None and isinstance(damping, torch.Tensor) and damping.ndim > 1:
-                raise ValueError("Damping must be a float or a 1-D tensor.")
-            return _CachedFactorSolve.apply(self, damping, ellipsoidal_damping, damping_eps, g)
-        return self._solve(damping, ellipsoidal_damping, damping_eps, check_info=True)
+    def _external_system(self) -> bool:
+        return False   # (never looked for: the tile pattern is the fused linearization's own)
 
     def _solve_sytem(self, Atb: torch.Tensor, AtA: torch.Tensor) -> torch.Tensor:  # abstract in DenseSolver
         raise NotImplementedError("HipSparseCholeskySolver.solve() factorises its linearization's packed Hessian")
@@ -1009,24 +951,19 @@ class HipSchurSolver(HipSchurSolverCore, _RefCholeskyDenseSolver):
 
     def __init__(self, objective: th.Objective, linearization_cls=None, linearization_kwargs=None, check_singular: bool = False,
                  sparse_reduced_system: bool = True, **kwargs):
-        linearization_cls = linearization_cls or HipSchurLinearization
-        if not (isinstance(linearization_cls, type) and issubclass(linearization_cls, HipSchurLinearization)):
-            raise RuntimeError(f"HipSchurSolver only works with theseus_amd.plugin.HipSchurLinearization, but "
-                               f"{linearization_cls} was provided.")
+        linearization_cls = checked_linearization_cls("HipSchurSolver", linearization_cls, HipSchurLinearization,
+                                                      "theseus_amd.plugin.HipSchurLinearization")
         _RefLinearSolver.__init__(self, objective, linearization_cls, linearization_kwargs)
         self._check_singular = check_singular
         self._schur_solver_init(sparse_reduced_system)
 
     def solve(self, damping=None, ellipsoidal_damping: bool = True, damping_eps: float = 1e-8, **kwargs) -> torch.Tensor:
+        check_damping(damping)
         g = self.linearization._g_graph
         unroll = getattr(self.linearization, "_unroll", None)
         if unroll is not None and torch.is_grad_enabled():
-            if damping is not None and isinstance(damping, torch.Tensor) and damping.ndim > 1:
-                raise ValueError("Damping must be a float or a 1-D tensor.")
             return _FusedUnrolledSchurSolve.apply(self, damping, ellipsoidal_damping, damping_eps, *unroll)
         if g is not None and torch.is_grad_enabled():
-            if damping is not None and isinstance(damping, torch.Tensor) and damping.ndim > 1:
-                raise ValueError("Damping must be a float or a 1-D tensor.")
             return _CachedSchurSolve.apply(self, damping, ellipsoidal_damping, damping_eps, g)
         return self._solve(damping, ellipsoidal_damping, damping_eps, check_info=True).clone()
 

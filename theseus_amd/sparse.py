@@ -22,8 +22,8 @@ import torch
 
 from . import _lib
 from .core import Objective
-from .linear_solver import DenseCholeskyOnly, HipCholeskyCore, LinearSolver
-from .linearization import HipLinearization, Linearization, VariableOrdering
+from .linear_solver import DenseFrameCore, LinearSolver, checked_linearization_cls
+from .linearization import Linearization, VariableOrdering
 
 TILE = _lib.THX_TILE
 
@@ -642,8 +642,8 @@ class _LevelLayout:
         self.c, self._base = c, base
 
 
-class HipSparseCholeskyCore(DenseCholeskyOnly, HipCholeskyCore):
-    """HipCholeskyCore whose factorisation follows the tile pattern of its linearization."""
+class HipSparseCholeskyCore(DenseFrameCore):
+    """The dense core's frame (or a tile-packed one) factorised and solved along the tile pattern of its linearization."""
 
     levels = False   # True: LevelPattern + thx_chol_factor_levels / thx_chol_solve_levels (elimination-tree parallelism)
 
@@ -681,7 +681,7 @@ class HipSparseCholeskyCore(DenseCholeskyOnly, HipCholeskyCore):
 
     def _ensure_buffers(self):
         if not self.packed_factor:
-            return HipCholeskyCore._ensure_buffers(self)
+            return DenseFrameCore._ensure_buffers(self)
         lin = self.linearization
         g = lin.g
         shape = (g.shape[0], self.pattern.nslots, TILE, TILE)
@@ -710,36 +710,21 @@ class HipSparseCholeskyCore(DenseCholeskyOnly, HipCholeskyCore):
             out[:, TILE * i:r1, TILE * j:c1] = self.L[:, slot, :r1 - TILE * i, :c1 - TILE * j]
         return out
 
-    def factorize(self, damping: Optional[Union[float, torch.Tensor]] = None, ellipsoidal_damping: bool = True,
-                  damping_eps: float = 1e-8, rhs: Optional[torch.Tensor] = None):
-        if not self._linearized():
-            raise RuntimeError("linearize() must be called before solve().")
-        self._ensure_buffers()
-        lam = None
-        if damping is not None:
-            lam = self._lam
-            if isinstance(damping, torch.Tensor):
-                lam.copy_(damping.to(lam.dtype).expand(lam.shape[0]))
-            else:
-                lam.fill_(float(damping))
-        y = self._y if rhs is not None else None
-        self.factor_version += 1
-        self._factored_with = (lam is not None, bool(ellipsoidal_damping), float(damping_eps))   # (what L L^T is the factor of)
-        if self.levels:
-            lin = self.linearization
-            dev = self.L.device
-            if rhs is None:
-                self.K.chol_factor_levels(self._level_layout(dev), lin.Hc, lam, ellipsoidal_damping, damping_eps, self.L, self.panels,
-                                          self.info, self.pattern)
-                return None
-            # y = L^-1 rhs in the padded order, fused into the diagonal launches (a handle _substitute recognises: the backward
-            # half needs no second gather)
-            self.K.vec_gather(rhs.contiguous(), self._xp, self.pattern.vec_maps(dev)["col_of_pad"])
+    def _factor_call(self, lam, ellipsoidal_damping, damping_eps, rhs):
+        if not self.levels:
+            return DenseFrameCore._factor_call(self, lam, ellipsoidal_damping, damping_eps, rhs, pattern=self.pattern)
+        lin = self.linearization
+        dev = self.L.device
+        if rhs is None:
             self.K.chol_factor_levels(self._level_layout(dev), lin.Hc, lam, ellipsoidal_damping, damping_eps, self.L, self.panels,
-                                      self.info, self.pattern, rhs=self._xp, y=self._yp)
-            return self._yp
-        self._factor_call(lam, ellipsoidal_damping, damping_eps, rhs, y, pattern=self.pattern)
-        return y
+                                      self.info, self.pattern)
+            return None
+        # y = L^-1 rhs in the padded order, fused into the diagonal launches (a handle _substitute recognises: the backward
+        # half needs no second gather)
+        self.K.vec_gather(rhs.contiguous(), self._xp, self.pattern.vec_maps(dev)["col_of_pad"])
+        self.K.chol_factor_levels(self._level_layout(dev), lin.Hc, lam, ellipsoidal_damping, damping_eps, self.L, self.panels,
+                                  self.info, self.pattern, rhs=self._xp, y=self._yp)
+        return self._yp
 
     def _solve_levels(self, L, panels, rhs, x, backward_only: bool):
         maps = self.pattern.vec_maps(L.device)
@@ -781,10 +766,7 @@ class HipSparseCholeskySolver(HipSparseCholeskyCore, LinearSolver):
     def __init__(self, objective: Objective, linearization_cls: Optional[Type[Linearization]] = None,
                  linearization_kwargs: Optional[Dict[str, Any]] = None, check_singular: bool = False,
                  packed_factor: Optional[bool] = None, ordering: str = "auto", batch_hint: Optional[int] = None, **kwargs):
-        linearization_cls = linearization_cls or HipLinearization
-        if not (isinstance(linearization_cls, type) and issubclass(linearization_cls, HipLinearization)):
-            raise RuntimeError(f"HipSparseCholeskySolver only works with theseus_amd.HipLinearization, but {linearization_cls} "
-                               "was provided.")
+        linearization_cls = checked_linearization_cls("HipSparseCholeskySolver", linearization_cls)
         linearization_kwargs = dict(linearization_kwargs or {})
         tile_count = None
         self.ordering_info: Dict[str, Any] = dict(method="given")
