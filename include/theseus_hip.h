@@ -586,6 +586,45 @@ int thx_homog_eval(const thx_homog_term* terms, int32_t n_terms, int32_t n_align
 int thx_homog_error(const thx_homog_term* terms, int32_t n_terms, int32_t n_align, const void* x, int64_t ldx, int32_t n,
                     void* scratch, int32_t chunks, void* err, int32_t B, int dtype, void* stream);
 
+/* ---- ... and the backward of its implicit step: with g = -sum_t J_t^T e_t what thx_homog_eval + thx_block_assemble form at the
+ *      (detached) state x and u (B, n) a cotangent of g, the gradient of psi = u^T g w.r.t. every auxiliary tensor that asks for
+ *      one.  floor(), the clamping, the mask and the count N are constants, as in the torch class.  Deterministic: no atomics,
+ *      fixed reduction orders, two calls give the same bits.  Four launches on `stream`:
+ *      1  stage (a) of thx_homog_eval (the ten sums per alignment term and problem, into `scratch`), then one thread per (term,
+ *         problem) writes a record of THX_HOMOG_REC doubles, entry k of term t of problem b at rec[(t * THX_HOMOG_REC + k) * B + b]:
+ *           alignment  0 d psi / d weight = -2 w A err, 1 c1 = -2 w^2 err / N, 2 c2 = -2 w^2 A / N   (err = sum m d^2 / N,
+ *                      A = the unweighted 1 x 8 block times u's eight entries at the term's columns)
+ *           prior      0-7 target, 8-15 weight (wdim = 1: their sum in 8)
+ *         terms that thx_homog_eval skips write zeros.
+ *      2  the pixel pass: one 256-thread workgroup per (alignment term, problem, slice of THX_HOMOG_VJP_SLICE channels) walks the
+ *         chunks of THX_HOMOG_CHUNK destination pixels in index order, with the pixel geometry of thx_homog_eval (same device
+ *         function, the run's dtype) and everything differentiated in fp64.  grad feat_dst[c, p] = -m (c1 S + c2 d), S the
+ *         directional derivative of the sample along u, has one writer per element.  grad feat_src gets four (cell, value) pairs
+ *         per (pixel, channel): the chunk's 4096 keys cell * 4096 + slot are sorted once in LDS (32-bit keys: rows * cols <
+ *         THX_HOMOG_MAX_CELLS, larger maps are refused), per channel the values are placed in sorted order, every run of equal
+ *         cells is summed by a fixed tree (a thread's 16 consecutive positions serially, then a segmented scan over the threads)
+ *         and added to grad_src[b, c, cell] by one writer.  A cell two chunks touch is updated in chunk order.
+ *      3  small tensors (weights, prior targets): stage B of thx_traj2_vjp on the records, same tables.
+ *      The plan is a HOST struct of counts and DEVICE tables: map_off holds two int64 per alignment term, where the gradients of
+ *      its feat_src and feat_dst start in grad_out (-1: none asked for); each is (B, chans, rows, cols) dense, ZEROED by the
+ *      caller, and no two of them may be the same buffer.  n_maps = 0 (no feature map asks) or n_align; max_cells / max_chans: the
+ *      largest rows * cols / chans of the alignment terms.  grad_out has plan->out_elems elements of the run's dtype, rec n_terms *
+ *      THX_HOMOG_REC * B doubles, scratch as for thx_homog_eval.  Table entries that point outside these sizes are skipped. */
+#define THX_HOMOG_REC 16
+#define THX_HOMOG_VJP_SLICE 4
+#define THX_HOMOG_MAX_CELLS (1 << 20)
+typedef struct {
+  int32_t n_tensors, n_pairs, n_maps, max_cells;
+  int32_t max_chans, pad_;
+  const thx_traj2_grad_tensor* tensors;
+  const thx_traj2_grad_pair* pairs;
+  const int64_t* map_off;
+  int64_t out_elems;
+} thx_homog_grad_plan;
+int thx_homog_vjp(const thx_homog_term* terms, int32_t n_terms, int32_t n_align, const void* x, int64_t ldx, int32_t n, const void* u,
+                  int64_t ldu, int32_t m, int64_t j_total, void* scratch, int32_t chunks, double* rec,
+                  const thx_homog_grad_plan* plan, void* grad_out, int32_t B, int dtype, void* stream);
+
 /* ---- Inverse kinematics on URDF chains (examples/inverse_kinematics.py; torchkin's forward kinematics with body Jacobians): the
  *      cost family of theseus_amd/kinematics.py.  terms[t] (DEVICE array built by the host, sorted by kind) is one cost function on
  *      the (B, n) Euclidean state x; var[0] = first state column of its dof-wide variable theta:

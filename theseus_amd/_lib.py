@@ -29,6 +29,9 @@ TRAJSE2_COLLISION, TRAJSE2_GP, TRAJSE2_NONHOLONOMIC, TRAJSE2_HINGE, TRAJSE2_PRIO
 HOMOG_ALIGN, HOMOG_PRIOR = 0, 1  # THX_HOMOG_* (kinds of a thx_homog_term)
 THX_HOMOG_CHUNK = 1024  # destination pixels per workgroup of thx_homog_eval / thx_homog_error's first stage
 THX_HOMOG_SUMS = 10  # doubles per (alignment term, problem, chunk) of their scratch
+THX_HOMOG_REC = 16  # doubles per (term, problem) record of thx_homog_vjp
+THX_HOMOG_VJP_SLICE = 4  # channels per workgroup of its pixel pass
+THX_HOMOG_MAX_CELLS = 1 << 20  # its feat_src scatter sorts 32-bit keys: rows * cols stays below this
 KIN_POSE, KIN_POSITION, KIN_HINGE, KIN_PRIOR = 0, 1, 2, 3  # THX_KIN_* (kinds of a thx_kin_term)
 KIN_FIXED, KIN_REVOLUTE, KIN_PRISMATIC = 0, 1, 2  # THX_KIN_* (types of a thx_kin_joint)
 THX_KIN_MAX_PATH = 64  # the longest path (entries of the joint table) of a link term
@@ -177,6 +180,11 @@ class Traj2GradPlan(Structure):  # thx_traj2_grad_plan: counts (host) + device t
         (k, c_void_p) for k in ("tensors", "pairs", "grids", "grid_terms")] + [("out_elems", c_int64), ("work_elems", c_int64)]
 
 
+class HomogGradPlan(Structure):  # thx_homog_grad_plan: counts (host) + device tables of thx_homog_vjp
+    _fields_ = [(k, c_int32) for k in ("n_tensors", "n_pairs", "n_maps", "max_cells", "max_chans", "pad")] + [
+        (k, c_void_p) for k in ("tensors", "pairs", "map_off")] + [("out_elems", c_int64)]
+
+
 # name -> (argtypes) ; every entry point returns int (0 = ok)
 _SIGNATURES = {
     "thx_se3_exp": [c_void_p, c_void_p, c_void_p, c_int64, c_int, POINTER(LieEps), c_void_p],
@@ -321,6 +329,8 @@ _SIGNATURES = {
     "thx_homog_eval": [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64,
                        c_int32, c_int32, c_int, c_void_p],
     "thx_homog_error": [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int, c_void_p],
+    "thx_homog_vjp": [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int64, c_void_p, c_int32,
+                      c_void_p, POINTER(HomogGradPlan), c_void_p, c_int32, c_int, c_void_p],
     "thx_kin_eval": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64,
                      c_int32, c_int32, c_int, POINTER(LieEps), c_void_p],
     "thx_kin_error": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_int,

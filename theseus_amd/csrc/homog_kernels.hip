@@ -4,7 +4,7 @@
 // (theseus/embodied/misc/local_cost_fn.py:16-75).  The torch twin is theseus_amd/embodied.py: HomographyAlignment; the
 // per-pixel arithmetic below follows it operation for operation.
 //
-// Both exports are two launches.
+// thx_homog_eval and thx_homog_error are two launches each; thx_homog_vjp, the backward of the implicit step, is homog_vjp_kernels.hip.
 // (a) homog_partial_kernel: one 256-thread workgroup per (alignment term, problem, chunk of THX_HOMOG_CHUNK destination pixels).
 //     A thread takes pixels tid, tid + 256, ... of the chunk (feat_dst is read coalesced), computes the pixel's source point, the
 //     four bilinear weights and the four clamped corner offsets ONCE, then loops over the channels: four gathers from feat_src, one
@@ -19,41 +19,9 @@
 // Per-pixel arithmetic runs in the run's dtype with contraction off, so floor() and the mask test see the values the torch class
 // computes.  Registers: 20 for the fp64 accumulators of the eval stage; LDS: 4 x 10 doubles.
 #pragma clang fp contract(off)
-#include "term_family.cuh"
+#include "homog_family.cuh"
 
 namespace thx {
-
-constexpr int kHomogThreads = 256;
-constexpr int kHomogWaves = kHomogThreads / 64;
-
-// the clamped index of a floor()ed coordinate (the clamp is applied before the conversion: no out-of-range conversion, NaN -> 0)
-template <typename T>
-__device__ __forceinline__ int homog_idx(T v, int hi) {
-  if (!(v > (T)0)) return 0;
-  return v < (T)hi ? (int)v : hi;
-}
-
-// G = adj(H) / det(H), H = [h0 .. h7, 1] row major, by the cofactor formula (HomographyAlignment._inverse)
-template <typename T>
-__device__ __forceinline__ void homog_inverse(const T* __restrict__ h, T* __restrict__ G) {
-  const T a = h[0], b = h[1], c = h[2], d = h[3], e = h[4], f = h[5], g = h[6], k = h[7], i = (T)1;
-  const T A[9] = {e * i - f * k, c * k - b * i, b * f - c * e,
-                  f * g - d * i, a * i - c * g, c * d - a * f,
-                  d * k - e * g, b * g - a * k, a * e - b * d};
-  const T det = (a * A[0] + b * A[3]) + c * A[6];
-#pragma unroll
-  for (int n = 0; n < 9; ++n) G[n] = A[n] / det;
-}
-
-// the alignment term reads inside the state and its sizes are usable
-__device__ __forceinline__ bool homog_align_ok(const thx_homog_term& tm, int n) {
-  return tm.kind == THX_HOMOG_ALIGN && tm.col[0] >= 0 && tm.col[0] + 8 <= n && tm.rows >= 2 && tm.cols >= 2 && tm.chans >= 1;
-}
-
-__device__ __forceinline__ int homog_term_chunks(const thx_homog_term& tm, int chunks) {
-  const int64_t own = ((int64_t)tm.rows * tm.cols + THX_HOMOG_CHUNK - 1) / THX_HOMOG_CHUNK;
-  return own < (int64_t)chunks ? (int)own : chunks;
-}
 
 // acc[0 .. NS) of the workgroup's threads -> out[0 .. NS): lanes by __shfl_down, waves in index order
 template <int NS>
@@ -97,24 +65,16 @@ homog_partial_kernel(const thx_homog_term* __restrict__ terms, int n_align, cons
 #pragma unroll
     for (int k = 0; k < 8; ++k) h[k] = x[(int64_t)b * ldx + tm.col[0] + k];
     homog_inverse<T>(h, G);
-    const T wm1 = (T)(Ww - 1), hm1 = (T)(Hh - 1);
+    const T wm1 = (T)(Ww - 1), hm1 = (T)(Hh - 1);   // (the Jacobian's factors; homog_pixel has its own)
     for (int r = 0; r < THX_HOMOG_CHUNK / kHomogThreads; ++r) {
       const int64_t pix = p0 + (int64_t)r * kHomogThreads + threadIdx.x;
       if (pix >= P) break;
-      const int i = (int)(pix / Ww), j = (int)(pix % Ww);
-      // destination pixel -> source point
-      const T px = (T)(2 * j) / wm1 - (T)1, py = (T)(2 * i) / hm1 - (T)1;
-      const T q0 = (G[0] * px + G[1] * py) + G[2], q1 = (G[3] * px + G[4] * py) + G[5], q2 = (G[6] * px + G[7] * py) + G[8];
-      const T u = q0 / q2, v = q1 / q2;
-      const T ix = ((u + (T)1) / (T)2) * wm1, iy = ((v + (T)1) / (T)2) * hm1;
-      const T x0 = floor(ix), y0 = floor(iy), x1 = x0 + (T)1, y1 = y0 + (T)1;
-      // bilinear weights from the unclamped corners (utils.py:25-28)
-      const T wx1 = x1 - ix, wx0 = ix - x0, wy1 = y1 - iy, wy0 = iy - y0;
-      const T nw = wx1 * wy1, ne = wx0 * wy1, sw = wx1 * wy0, se = wx0 * wy0;
-      if (!((((nw + ne) + sw) + se) > (T)0.9)) continue;   // the mask (also NaN)
-      const int xi0 = homog_idx(x0, Ww - 1), xi1 = homog_idx(x1, Ww - 1), yi0 = homog_idx(y0, Hh - 1), yi1 = homog_idx(y1, Hh - 1);
-      const int64_t onw = (int64_t)yi0 * Ww + xi0, one = (int64_t)yi0 * Ww + xi1, osw = (int64_t)yi1 * Ww + xi0,
-                    ose = (int64_t)yi1 * Ww + xi1;
+      HomogPixel<T> g;
+      homog_pixel<T>(G, Hh, Ww, pix, g);
+      if (!g.mask) continue;   // (also NaN)
+      const T q0 = g.q0, q1 = g.q1, q2 = g.q2, u = g.u, v = g.v, wx1 = g.wx1, wx0 = g.wx0, wy1 = g.wy1, wy0 = g.wy0;
+      const T nw = g.nw, ne = g.ne, sw = g.sw, se = g.se;
+      const int64_t onw = g.cell[0], one = g.cell[1], osw = g.cell[2], ose = g.cell[3];
       double sse = 0.0, A = 0.0, Bv = 0.0;
       for (int c = 0; c < C; ++c) {
         const T* __restrict__ sc = src + (int64_t)c * P;
@@ -161,23 +121,6 @@ __device__ __forceinline__ void homog_prior(const thx_homog_term& tm, const T* _
       for (int k = 0; k < 8; ++k) J[8 * i + k] = i == k ? w : (T)0;
     }
   }
-}
-
-__device__ __forceinline__ bool homog_prior_ok(const thx_homog_term& tm, int n) {
-  return tm.kind == THX_HOMOG_PRIOR && tm.col[0] >= 0 && tm.col[0] + 8 <= n && (tm.wdim == 1 || tm.wdim == 8);
-}
-
-// the chunks of alignment term t, problem b, added in index order -> sums[0 .. NS)
-template <int NS>
-__device__ __forceinline__ void homog_sum_chunks(const double* __restrict__ scratch, const thx_homog_term& tm, int t, int b, int B,
-                                                 int chunks, double* sums) {
-  const double* p = scratch + ((int64_t)t * B + b) * chunks * THX_HOMOG_SUMS;
-  const int own = homog_term_chunks(tm, chunks);
-#pragma unroll
-  for (int s = 0; s < NS; ++s) sums[s] = 0.0;
-  for (int c = 0; c < own; ++c)
-#pragma unroll
-    for (int s = 0; s < NS; ++s) sums[s] += p[(int64_t)c * THX_HOMOG_SUMS + s];
 }
 
 // the weighted error of an alignment term from its two sums
@@ -241,22 +184,16 @@ homog_finish_error_kernel(const thx_homog_term* __restrict__ terms, int n_terms,
   store_half_sum(acc, err + b);
 }
 
-// the family's own size checks: the message of the first that fails
-inline const char* homog_bad_size(int64_t ldx, int32_t n, int32_t n_terms, int32_t n_align, int32_t chunks) {
-  if (n < 8) return ": n < 8";
-  if (ldx < n) return ": ldx < n";
-  if (n_align < 1 || n_align > n_terms) return ": n_align outside 1 ... n_terms";
-  if (chunks < 1) return ": chunks < 1";
-  return nullptr;
-}
-
-// ... and what both exports check after family_check: the scratch's alignment, the grid of stage (a) -> ``blocks``
-inline int homog_check_partial(const char* who, const void* scratch, int32_t n_align, int32_t B, int32_t chunks, unsigned* blocks) {
-  if (reinterpret_cast<uintptr_t>(scratch) % 8) return fail(who, ": pointer not aligned");
-  const int64_t ab = (int64_t)n_align * B;   // (< 2^62)
-  if (ab > (int64_t)INT32_MAX || ab * chunks > (int64_t)INT32_MAX) return fail(who, ": grid limit exceeded (n_align * B * chunks)");
-  *blocks = (unsigned)(ab * chunks);
-  return 0;
+// stage (a) with the Jacobian sums, for the backward's source too (homog_family.cuh)
+int homog_launch_partial(const char* who, const thx_homog_term* terms, int32_t n_align, const void* x, int64_t ldx, int32_t n,
+                         double* scratch, int32_t chunks, unsigned blocks, int32_t B, int dtype, hipStream_t stream) {
+  const dim3 pgrid(blocks), pblock(kHomogThreads);
+  THX_DISPATCH(dtype,
+               hipLaunchKernelGGL((homog_partial_kernel<float, true>), pgrid, pblock, 0, stream, terms, n_align, (const float*)x, ldx,
+                                  n, scratch, chunks, B),
+               hipLaunchKernelGGL((homog_partial_kernel<double, true>), pgrid, pblock, 0, stream, terms, n_align, (const double*)x, ldx,
+                                  n, scratch, chunks, B));
+  return check_launch(who);
 }
 
 }  // namespace thx

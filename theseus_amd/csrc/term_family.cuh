@@ -1,4 +1,4 @@
-// What the fused cost families (traj_kernels.hip, push_kernels.hip, trajse2_kernels.hip, homog_kernels.hip, kin_kernels.hip) share: a family evaluates a whole objective
+// What the fused cost families (traj_kernels.hip, push_kernels.hip, trajse2_kernels.hip, homog_kernels.hip + homog_vjp_kernels.hip, kin_kernels.hip) share: a family evaluates a whole objective
 // from a table of 128-byte terms (thx_traj2_term, thx_push2_term, thx_trajse2_term of include/theseus_hip.h: the same layout, the
 // variable field named by the family).
 // Here: the per-term aux accessor, the bilinear signed-distance lookup, the fixed-order reduction of a *_error kernel and the host
@@ -71,6 +71,41 @@ __device__ __forceinline__ void store_half_sum(double acc, T* __restrict__ err) 
     __syncthreads();
   }
   if (threadIdx.x == 0) *err = (T)(0.5 * part[0]);
+}
+
+// The small-tensor stage of a family's VJP export (thx_traj2_vjp, thx_homog_vjp): rec holds REC doubles per (term, problem), entry k
+// of term t of problem b at rec[(t * REC + k) * B + b].  Workgroup = (tensor, problem), or the tensor when it is shared; fixed-order
+// sums in fp64
+template <typename T, int REC>
+__global__ void __launch_bounds__(256)
+vjp_reduce_kernel(const double* __restrict__ rec, int n_terms, const thx_traj2_grad_tensor* __restrict__ tensors,
+                        const thx_traj2_grad_pair* __restrict__ pairs, int n_pairs, T* __restrict__ out, int64_t out_elems, int B) {
+  __shared__ double part[256];
+  const int g = (int)(blockIdx.x / (unsigned)B), b = (int)(blockIdx.x % (unsigned)B);
+  const thx_traj2_grad_tensor tg = tensors[g];
+  // (everything below is uniform over the workgroup)
+  if (tg.shared && b > 0) return;
+  if (tg.pair_begin < 0 || tg.pair_end < tg.pair_begin || tg.pair_end > n_pairs || tg.count < 1 || tg.count > REC) return;
+  const int64_t o0 = tg.out_off + (tg.shared ? 0 : (int64_t)b * tg.count);
+  if (tg.out_off < 0 || o0 + tg.count > out_elems) return;
+  const int64_t contributions = (int64_t)(tg.pair_end - tg.pair_begin) * (tg.shared ? B : 1);
+  for (int j = 0; j < tg.count; ++j) {
+    double acc = 0.0;
+    for (int64_t c = threadIdx.x; c < contributions; c += 256) {
+      const thx_traj2_grad_pair pr = pairs[tg.pair_begin + (tg.shared ? c / B : c)];
+      const int bb = tg.shared ? (int)(c % B) : b;
+      if (pr.term < 0 || pr.term >= n_terms || pr.entry < 0 || pr.entry + tg.count > REC) continue;
+      acc += rec[((int64_t)pr.term * REC + pr.entry + j) * B + bb];
+    }
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) out[o0 + j] = (T)part[0];
+    __syncthreads();
+  }
 }
 
 // What every export checks on the host before any launch.  ``any_null``: one of the family's pointers is null; ``bad_size``: the

@@ -149,7 +149,7 @@ traj2_error_kernel(const thx_traj2_term* __restrict__ terms, int n_terms, const 
 // ---- thx_traj2_vjp: the gradient of u^T g, g = -sum_t J_t^T e_t at a detached state, w.r.t. the auxiliary tensors ------------------
 // Per term phi_t = -(sum_s J_s u_s) . e_t; floor(), the in-grid test and the distance > eps test are constants, as in the torch
 // classes.  Stage A (traj2_vjp_terms_kernel) writes each term's partial derivatives, stage B gathers them per tensor
-// (traj2_vjp_reduce_kernel) or scatters them into the grids (traj2_vjp_scatter_kernel + traj2_vjp_grid_out_kernel).
+// (vjp_reduce_kernel of term_family.cuh) or scatters them into the grids (traj2_vjp_scatter_kernel + traj2_vjp_grid_out_kernel).
 constexpr int kRec = THX_TRAJ2_REC;
 constexpr int kSortChunk = THX_TRAJ2_SORT_CHUNK;
 
@@ -269,38 +269,7 @@ traj2_vjp_terms_kernel(const thx_traj2_term* __restrict__ terms, int n_terms, co
   for (int k = 0; k < kRec; ++k) rec[((int64_t)t * kRec + k) * B + b] = o[k];
 }
 
-// stage B, small tensors: workgroup = (tensor, problem), or the tensor when it is shared; fixed-order sums in fp64
-template <typename T>
-__global__ void __launch_bounds__(256)
-traj2_vjp_reduce_kernel(const double* __restrict__ rec, int n_terms, const thx_traj2_grad_tensor* __restrict__ tensors,
-                        const thx_traj2_grad_pair* __restrict__ pairs, int n_pairs, T* __restrict__ out, int64_t out_elems, int B) {
-  __shared__ double part[256];
-  const int g = (int)(blockIdx.x / (unsigned)B), b = (int)(blockIdx.x % (unsigned)B);
-  const thx_traj2_grad_tensor tg = tensors[g];
-  // (everything below is uniform over the workgroup)
-  if (tg.shared && b > 0) return;
-  if (tg.pair_begin < 0 || tg.pair_end < tg.pair_begin || tg.pair_end > n_pairs || tg.count < 1 || tg.count > kRec) return;
-  const int64_t o0 = tg.out_off + (tg.shared ? 0 : (int64_t)b * tg.count);
-  if (tg.out_off < 0 || o0 + tg.count > out_elems) return;
-  const int64_t contributions = (int64_t)(tg.pair_end - tg.pair_begin) * (tg.shared ? B : 1);
-  for (int j = 0; j < tg.count; ++j) {
-    double acc = 0.0;
-    for (int64_t c = threadIdx.x; c < contributions; c += 256) {
-      const thx_traj2_grad_pair pr = pairs[tg.pair_begin + (tg.shared ? c / B : c)];
-      const int bb = tg.shared ? (int)(c % B) : b;
-      if (pr.term < 0 || pr.term >= n_terms || pr.entry < 0 || pr.entry + tg.count > kRec) continue;
-      acc += rec[((int64_t)pr.term * kRec + pr.entry + j) * B + bb];
-    }
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-      if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) out[o0 + j] = (T)part[0];
-    __syncthreads();
-  }
-}
+// stage B, small tensors: vjp_reduce_kernel of term_family.cuh
 
 // stage B, grids: workgroup = (problem, grid).  The four (cell, value) pairs of each collision term on this grid go through LDS a
 // chunk at a time: a bitonic network sorts the chunk by (cell, position in the list) -- a unique key, so the order of equal cells
@@ -444,9 +413,9 @@ extern "C" int thx_traj2_vjp(const thx_traj2_term* terms, int32_t n_terms, const
   if (p.n_tensors > 0) {
     const dim3 grid((unsigned)((int64_t)p.n_tensors * B));
     THX_DISPATCH(dtype,
-                 hipLaunchKernelGGL(traj2_vjp_reduce_kernel<float>, grid, block, 0, s, rec, n_terms, p.tensors, p.pairs, p.n_pairs,
+                 hipLaunchKernelGGL((vjp_reduce_kernel<float, kRec>), grid, block, 0, s, rec, n_terms, p.tensors, p.pairs, p.n_pairs,
                                     (float*)grad_out, p.out_elems, B),
-                 hipLaunchKernelGGL(traj2_vjp_reduce_kernel<double>, grid, block, 0, s, rec, n_terms, p.tensors, p.pairs, p.n_pairs,
+                 hipLaunchKernelGGL((vjp_reduce_kernel<double, kRec>), grid, block, 0, s, rec, n_terms, p.tensors, p.pairs, p.n_pairs,
                                     (double*)grad_out, p.out_elems, B));
   }
   if (p.n_grids > 0) {

@@ -709,7 +709,7 @@ class HipKernels:
                                           ctypes.byref(plan), _lib.ptr(grad_out), _lib.ptr(grid_work), B, _lib.dtype_code(x.dtype),
                                           _lib.stream_ptr(x.device)), "thx_traj2_vjp")
 
-    # ---- homography image alignment (csrc/homog_kernels.hip) -------------------------------------------
+    # ---- homography image alignment (csrc/homog_kernels.hip, csrc/homog_vjp_kernels.hip) -----------------
     def _homog_args(self, what, table, n_terms, n_align, x, n, scratch, chunks):
         """the leading arguments thx_homog_eval and thx_homog_error share"""
         B = x.shape[0]
@@ -737,6 +737,24 @@ class HipKernels:
         args = self._homog_args("homog_error", table, n_terms, n_align, x, n, scratch, chunks)
         _lib.check(self.lib.thx_homog_error(*args, _lib.ptr(err), B, _lib.dtype_code(x.dtype), _lib.stream_ptr(x.device)),
                    "thx_homog_error")
+
+    def homog_vjp(self, table, n_terms, n_align, x, n, u, m, j_total, scratch, chunks, rec, plan, grad_out):
+        """The gradient of (u * g).sum(), g what ``homog_eval`` + the block assembly form at x, w.r.t. the auxiliary tensors of the
+        gradient plan: x, u (B, >= n); scratch as for ``homog_eval``; rec fp64 scratch (n_terms * THX_HOMOG_REC * B); plan a
+        ``_lib.HomogGradPlan`` whose tables are device tensors; grad_out (plan.out_elems) ZEROS of x's dtype."""
+        B = x.shape[0]
+        if (u.ndim != 2 or u.stride(1) != 1 or u.shape[0] != B or u.shape[1] < n or u.dtype != x.dtype or grad_out.dtype != x.dtype
+                or rec.dtype != torch.float64 or rec.numel() < n_terms * _lib.THX_HOMOG_REC * B or grad_out.numel() < plan.out_elems):
+            raise ValueError("homog_vjp: state / cotangent / scratch do not fit")
+        if not u.is_cuda or not rec.is_cuda or not grad_out.is_cuda:
+            raise RuntimeError(f"homog_vjp: the cotangent must live on a HIP device (got {u.device}); there is no CPU fallback")
+        if plan.n_maps and plan.max_cells >= _lib.THX_HOMOG_MAX_CELLS:
+            raise ValueError(f"homog_vjp: a feature map of {plan.max_cells} pixels is too large for the fused backward (its scatter "
+                             f"sorts 32-bit keys: fewer than {_lib.THX_HOMOG_MAX_CELLS} pixels); set fused_backward = False")
+        args = self._homog_args("homog_vjp", table, n_terms, n_align, x, n, scratch, chunks)
+        _lib.check(self.lib.thx_homog_vjp(*args[:6], ctypes.c_void_p(u.data_ptr()), u.stride(0), int(m), int(j_total), *args[6:],
+                                          _lib.ptr(rec), ctypes.byref(plan), _lib.ptr(grad_out), B, _lib.dtype_code(x.dtype),
+                                          _lib.stream_ptr(x.device)), "thx_homog_vjp")
 
     # ---- inverse kinematics on URDF chains (csrc/kin_kernels.hip) ------------------------------------------
     def _kin_args(self, what, table, n_terms, paths, n_paths, x, n, dof):

@@ -21,7 +21,9 @@ Optional, the backward of the implicit step (``assemble(graph=True)`` with an au
   _VJP_KERNEL     the name of the kernel set's method, _VJP_REC the doubles of its per-(term, problem) record
   _VJP_ENTRIES    {kind: the record entry of each aux slot}
   _launch_vjp(table, state, u, rec, plan, grad_out, grid_work)
-A family without them, or a kernel set without the method, stays on the torch path for everything differentiated."""
+A family whose gradients are not a handful of record entries per term and 2-D fp64 grids (PackedHomography: feature maps) overrides
+``_build_grad_plan`` (-> anything with GradPlan's ``inputs``, ``offsets`` and ``asked()``), ``_vjp`` and, for a gate of its own,
+``_fused_backward_route``.  A family without them, or a kernel set without the method, stays on the torch path for everything differentiated."""
 from typing import Callable, NamedTuple, Optional
 
 import numpy as np
