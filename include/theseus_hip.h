@@ -501,6 +501,27 @@ int thx_push2_eval(const thx_push2_term* terms, int32_t n_terms, const void* x, 
 int thx_push2_error(const thx_push2_term* terms, int32_t n_terms, const void* x, int32_t V, void* err, int32_t B, int dtype,
                     const thx_se2_eps* eps, void* stream);
 
+/* ---- ... and the backward of its implicit step, thx_traj2_vjp's twin: with g = -sum_t J_t^T e_t what thx_push2_eval +
+ *      thx_block_assemble form at the (detached) state x and u (B, 3 V, row stride ldu) a cotangent of g, the gradient of u^T g
+ *      w.r.t. every auxiliary tensor the plan (a thx_traj2_grad_plan, above) asks for.  Deterministic, no atomics, two stages:
+ *      A  one thread per (term, problem): the term's partial derivatives in fp64 -- every branch (in-grid test, floor, d < r, the
+ *         Taylor switches of the SE2 log) decided in the run's dtype exactly as thx_push2_eval decides it -- into a record of
+ *         THX_PUSH2_REC doubles, entry k of term t of problem b at rec[(t * THX_PUSH2_REC + k) * B + b]:
+ *           QSP      0 c_square, 1-3 weight (wdim = 1: their sum in 1)
+ *           MFB      0-3 measurement, as the four raw components (x, y, cos, sin), 4-6 weight (wdim = 1: their sum in 4)
+ *           contact  0-3 d/d corner value (ll, hl, lh, hh), 4-7 their cell indices row * cols + col, 8-9 origin, 10 cell size,
+ *                    11 effector radius, 12 weight            (all zero outside the grid)
+ *           prior    0-3 target, as the four raw components, 4-6 weight (wdim = 1: their sum in 4)
+ *         every (term, problem) writes its whole record; terms that thx_push2_eval skips write zeros.
+ *      B  stage B of thx_traj2_vjp on the records: the small tensors by (term, entry) pairs, the grids by the LDS sort of the
+ *         contact terms' (cell, value) pairs.
+ *      grad_out has plan->out_elems elements of the run's dtype, grid_work plan->work_elems doubles (may be null without grids),
+ *      rec n_terms * THX_PUSH2_REC * B doubles; x must be aligned to one record (4 elements). */
+#define THX_PUSH2_REC 16
+int thx_push2_vjp(const thx_push2_term* terms, int32_t n_terms, const void* x, int32_t V, const void* u, int64_t ldu, int32_t m,
+                  int64_t j_total, double* rec, const thx_traj2_grad_plan* plan, void* grad_out, double* grid_work, int32_t B,
+                  int dtype, const thx_se2_eps* eps, void* stream);
+
 /* ---- SE2 motion planning (examples/se2_planning.py: MotionPlanner with pose_type=SE2): the planner's cost family in one launch.
  *      The state x is (V, B, 4), one 4-element record per optimisation variable and problem: an SE2 pose [x, y, cos, sin] or a
  *      velocity [v0, v1, v2, pad] (pad is written 0 and never read).  terms[t] (DEVICE array built by the host, sorted by kind) is

@@ -24,6 +24,7 @@ TRAJ2_COLLISION, TRAJ2_GP, TRAJ2_PRIOR = 0, 1, 2  # THX_TRAJ2_* (kinds of a thx_
 THX_TRAJ2_REC = 16  # doubles per (term, problem) record of thx_traj2_vjp
 THX_TRAJ2_SORT_CHUNK = 1024  # (cell, value) pairs its grid scatter sorts at a time
 PUSH2_QSP, PUSH2_MFB, PUSH2_CONTACT, PUSH2_PRIOR = 0, 1, 2, 3  # THX_PUSH2_* (kinds of a thx_push2_term)
+THX_PUSH2_REC = 16  # doubles per (term, problem) record of thx_push2_vjp
 # THX_TRAJSE2_* (kinds of a thx_trajse2_term)
 TRAJSE2_COLLISION, TRAJSE2_GP, TRAJSE2_NONHOLONOMIC, TRAJSE2_HINGE, TRAJSE2_PRIOR_SE2, TRAJSE2_PRIOR_VEC, TRAJSE2_PRIOR_XY = range(7)
 HOMOG_ALIGN, HOMOG_PRIOR = 0, 1  # THX_HOMOG_* (kinds of a thx_homog_term)
@@ -321,6 +322,8 @@ _SIGNATURES = {
     "thx_push2_eval": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int,
                        POINTER(SE2Eps), c_void_p],
     "thx_push2_error": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int, POINTER(SE2Eps), c_void_p],
+    "thx_push2_vjp": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_int64, c_void_p, POINTER(Traj2GradPlan), c_void_p,
+                      c_void_p, c_int32, c_int, POINTER(SE2Eps), c_void_p],
     "thx_trajse2_eval": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int,
                          POINTER(SE2Eps), c_void_p],
     "thx_trajse2_error": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int, POINTER(SE2Eps), c_void_p],

@@ -1,8 +1,10 @@
-// What the fused cost families (traj_kernels.hip, push_kernels.hip, trajse2_kernels.hip, homog_kernels.hip + homog_vjp_kernels.hip, kin_kernels.hip) share: a family evaluates a whole objective
-// from a table of 128-byte terms (thx_traj2_term, thx_push2_term, thx_trajse2_term of include/theseus_hip.h: the same layout, the
-// variable field named by the family).
-// Here: the per-term aux accessor, the bilinear signed-distance lookup, the fixed-order reduction of a *_error kernel and the host
-// checks of the exports.  The term functions, the two __global__ functions and the exports stay with the family.
+// What the fused cost families (traj_kernels.hip, push_kernels.hip + push_vjp_kernels.hip, trajse2_kernels.hip, homog_kernels.hip +
+// homog_vjp_kernels.hip, kin_kernels.hip) share: a family evaluates a whole objective from a table of 128-byte terms (thx_traj2_term,
+// thx_push2_term, thx_trajse2_term of include/theseus_hip.h: the same layout, the variable field named by the family).
+// Here: the per-term aux accessor, the bilinear signed-distance lookup, the fixed-order reduction of a *_error kernel, stage B of a
+// *_vjp export on its per-(term, problem) records (vjp_reduce_kernel for the small tensors; vjp_scatter_kernel + vjp_grid_out_kernel
+// for 2-D grids, templated on the term type and the kind that reads the grid) and the host checks and stage-B launches of the
+// exports.  The term functions, stage A, the *_eval / *_error __global__ functions and the exports stay with the family.
 #pragma once
 #include "common.cuh"
 
@@ -73,7 +75,7 @@ __device__ __forceinline__ void store_half_sum(double acc, T* __restrict__ err) 
   if (threadIdx.x == 0) *err = (T)(0.5 * part[0]);
 }
 
-// The small-tensor stage of a family's VJP export (thx_traj2_vjp, thx_homog_vjp): rec holds REC doubles per (term, problem), entry k
+// The small-tensor stage of a family's VJP export (thx_traj2_vjp, thx_push2_vjp, thx_homog_vjp): rec holds REC doubles per (term, problem), entry k
 // of term t of problem b at rec[(t * REC + k) * B + b].  Workgroup = (tensor, problem), or the tensor when it is shared; fixed-order
 // sums in fp64
 template <typename T, int REC>
@@ -108,6 +110,98 @@ vjp_reduce_kernel(const double* __restrict__ rec, int n_terms, const thx_traj2_g
   }
 }
 
+constexpr int kSortChunk = THX_TRAJ2_SORT_CHUNK;   // (cell, value) pairs the grid scatter sorts at a time
+
+// The grid stage of a family's VJP export (thx_traj2_vjp, thx_push2_vjp): workgroup = (problem, grid).  The four (cell, value)
+// pairs (record entries 4-7 and 0-3) of each term of kind GRID_KIND on this grid go through LDS a chunk at a time: a bitonic network
+// sorts the chunk by (cell, position in the list) -- a unique key, so the order of equal cells is fixed --, the head of each run of equal cells sums the run in that order and adds it into the problem's fp64 grid.  Within a
+// chunk a cell has one head; chunks follow one another behind a barrier, so a cell two chunks touch is updated in chunk order.
+template <typename Term, int GRID_KIND, int REC>
+__global__ void __launch_bounds__(256)
+vjp_scatter_kernel(const double* __restrict__ rec, const Term* __restrict__ terms, int n_terms,
+                   const thx_traj2_grad_grid* __restrict__ grids, const int32_t* __restrict__ grid_terms, int n_grid_terms,
+                   double* __restrict__ work, int64_t work_elems, int B) {
+  __shared__ unsigned long long key[kSortChunk];
+  __shared__ double val[kSortChunk];
+  constexpr unsigned long long kPad = ~0ull;
+  const int b = blockIdx.x;
+  const thx_traj2_grad_grid gd = grids[blockIdx.y];
+  const int64_t cells = (int64_t)gd.rows * gd.cols;
+  if (gd.rows < 1 || gd.cols < 1 || cells > INT32_MAX || gd.term_begin < 0 || gd.term_end < gd.term_begin || gd.term_end > n_grid_terms)
+    return;
+  if (gd.work_off < 0 || gd.work_off + cells * B > work_elems) return;
+  double* gg = work + gd.work_off + cells * b;
+  for (int64_t c = threadIdx.x; c < cells; c += 256) gg[c] = 0.0;
+  __syncthreads();
+  const int64_t n_src = (int64_t)4 * (gd.term_end - gd.term_begin);
+  for (int64_t base = 0; base < n_src; base += kSortChunk) {
+    for (int i = threadIdx.x; i < kSortChunk; i += 256) {
+      const int64_t p = base + i;
+      unsigned long long kk = kPad;
+      double v = 0.0;
+      if (p < n_src) {
+        const int t = grid_terms[gd.term_begin + p / 4], c = (int)(p % 4);
+        if (t >= 0 && t < n_terms && terms[t].kind == GRID_KIND && terms[t].rows == gd.rows && terms[t].cols == gd.cols) {
+          const double cell = rec[((int64_t)t * REC + 4 + c) * B + b];
+          if (cell >= 0.0 && cell < (double)cells) {
+            kk = ((unsigned long long)cell << 32) | (unsigned long long)i;   // (i: the position within the chunk, p - base)
+            v = rec[((int64_t)t * REC + c) * B + b];
+          }
+        }
+      }
+      key[i] = kk, val[i] = v;
+    }
+    __syncthreads();
+    for (int k = 2; k <= kSortChunk; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int i = threadIdx.x; i < kSortChunk; i += 256) {
+          const int l = i ^ j;
+          if (l > i) {
+            const unsigned long long a = key[i], c = key[l];
+            if ((a > c) == ((i & k) == 0)) {
+              const double va = val[i];
+              key[i] = c, key[l] = a, val[i] = val[l], val[l] = va;
+            }
+          }
+        }
+        __syncthreads();
+      }
+    for (int i = threadIdx.x; i < kSortChunk; i += 256) {
+      const unsigned long long a = key[i];
+      if (a == kPad || (i > 0 && (key[i - 1] >> 32) == (a >> 32))) continue;   // padding, or inside a run
+      double acc = 0.0;
+      for (int q = i; q < kSortChunk && (key[q] >> 32) == (a >> 32); ++q) acc += val[q];
+      gg[a >> 32] += acc;
+    }
+    __syncthreads();
+  }
+}
+
+// ... and out of the fp64 grids: one thread per (problem, cell), cells fastest; a shared grid is summed over the problems in index order
+template <typename T>
+__global__ void __launch_bounds__(256)
+vjp_grid_out_kernel(const double* __restrict__ work, int64_t work_elems, const thx_traj2_grad_grid* __restrict__ grids,
+                    int max_cells, T* __restrict__ out, int64_t out_elems, int B) {
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (int64_t)max_cells * B) return;
+  const int b = (int)(gid / max_cells);
+  const int64_t c = gid % max_cells;
+  const thx_traj2_grad_grid gd = grids[blockIdx.y];
+  const int64_t cells = (int64_t)gd.rows * gd.cols;
+  if (gd.rows < 1 || gd.cols < 1 || c >= cells || (gd.shared && b > 0)) return;
+  if (gd.work_off < 0 || gd.work_off + cells * B > work_elems || gd.out_off < 0) return;
+  const double* gg = work + gd.work_off;
+  if (gd.shared) {
+    if (gd.out_off + cells > out_elems) return;
+    double acc = 0.0;
+    for (int bb = 0; bb < B; ++bb) acc += gg[cells * bb + c];
+    out[gd.out_off + c] = (T)acc;
+  } else {
+    if (gd.out_off + cells * B > out_elems) return;
+    out[gd.out_off + cells * b + c] = (T)gg[cells * b + c];
+  }
+}
+
 // What every export checks on the host before any launch.  ``any_null``: one of the family's pointers is null; ``bad_size``: the
 // message of the family's own size check that fails (it comes after the batch, before the alignment), or nullptr; ``x_vec``: the
 // elements of the state that one load reads.
@@ -134,6 +228,52 @@ inline int family_check_eval(const char* who, const void* J, const char* short_j
   const int64_t total = ((int64_t)n_terms * B + 255) / 256;
   if (total > (int64_t)INT32_MAX) return fail(who, ": grid limit exceeded (n_terms * B)");
   *blocks = (unsigned)total;
+  return 0;
+}
+
+// ... and what a *_vjp export with a thx_traj2_grad_plan checks after family_check and its own sizes: the plan, the alignment of the
+// cotangent, the record and the outputs, the grids of both stages.  -> the grid of stage A in ``term_blocks``
+inline int family_check_vjp(const char* who, const void* u, const double* rec, const thx_traj2_grad_plan& p, const void* grad_out,
+                            const double* grid_work, int32_t n_terms, int32_t B, int dtype, unsigned* term_blocks) {
+  if (p.n_tensors < 0 || p.n_pairs < 0 || p.n_grids < 0 || p.n_grid_terms < 0 || p.max_cells < 0 || p.out_elems < 1 || p.work_elems < 0)
+    return fail(who, ": negative size in the plan");
+  if ((p.n_tensors > 0 && (!p.tensors || !p.pairs)) || (p.n_grids > 0 && (!p.grids || !p.grid_terms || !grid_work || p.max_cells < 1)))
+    return fail(who, ": null pointer in the plan");
+  const uintptr_t el = dtype == THX_F32 ? 4 : 8;
+  auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+  if (at(u) % el || at(grad_out) % el || at(rec) % 8 || at(grid_work) % 8 || at(p.tensors) % 8 || at(p.pairs) % 4 || at(p.grids) % 8 ||
+      at(p.grid_terms) % 4)
+    return fail(who, ": pointer not aligned");
+  const int64_t blocks = ((int64_t)n_terms * B + 255) / 256, out_blocks = ((int64_t)p.max_cells * B + 255) / 256;
+  if (blocks > (int64_t)INT32_MAX || (int64_t)p.n_tensors * B > (int64_t)INT32_MAX || out_blocks > (int64_t)INT32_MAX || p.n_grids > 65535)
+    return fail(who, ": grid limit exceeded (n_terms * B, tensors * B, cells * B or the number of grids)");
+  *term_blocks = (unsigned)blocks;
+  return 0;
+}
+
+// stage B of such an export on the records stage A wrote: the small tensors, then the grids read by the terms of kind GRID_KIND
+template <typename Term, int GRID_KIND, int REC>
+inline int family_vjp_stage_b(const double* rec, const Term* terms, int32_t n_terms, const thx_traj2_grad_plan& p, void* grad_out,
+                               double* grid_work, int32_t B, int dtype, hipStream_t s) {
+  const dim3 block(256);
+  if (p.n_tensors > 0) {
+    const dim3 grid((unsigned)((int64_t)p.n_tensors * B));
+    THX_DISPATCH(dtype,
+                 hipLaunchKernelGGL((vjp_reduce_kernel<float, REC>), grid, block, 0, s, rec, n_terms, p.tensors, p.pairs, p.n_pairs,
+                                    (float*)grad_out, p.out_elems, B),
+                 hipLaunchKernelGGL((vjp_reduce_kernel<double, REC>), grid, block, 0, s, rec, n_terms, p.tensors, p.pairs, p.n_pairs,
+                                    (double*)grad_out, p.out_elems, B));
+  }
+  if (p.n_grids > 0) {
+    hipLaunchKernelGGL((vjp_scatter_kernel<Term, GRID_KIND, REC>), dim3((unsigned)B, (unsigned)p.n_grids), block, 0, s, rec, terms,
+                       n_terms, p.grids, p.grid_terms, p.n_grid_terms, grid_work, p.work_elems, B);
+    const dim3 grid((unsigned)(((int64_t)p.max_cells * B + 255) / 256), (unsigned)p.n_grids);
+    THX_DISPATCH(dtype,
+                 hipLaunchKernelGGL(vjp_grid_out_kernel<float>, grid, block, 0, s, grid_work, p.work_elems, p.grids, p.max_cells,
+                                    (float*)grad_out, p.out_elems, B),
+                 hipLaunchKernelGGL(vjp_grid_out_kernel<double>, grid, block, 0, s, grid_work, p.work_elems, p.grids, p.max_cells,
+                                    (double*)grad_out, p.out_elems, B));
+  }
   return 0;
 }
 

@@ -149,9 +149,8 @@ traj2_error_kernel(const thx_traj2_term* __restrict__ terms, int n_terms, const 
 // ---- thx_traj2_vjp: the gradient of u^T g, g = -sum_t J_t^T e_t at a detached state, w.r.t. the auxiliary tensors ------------------
 // Per term phi_t = -(sum_s J_s u_s) . e_t; floor(), the in-grid test and the distance > eps test are constants, as in the torch
 // classes.  Stage A (traj2_vjp_terms_kernel) writes each term's partial derivatives, stage B gathers them per tensor
-// (vjp_reduce_kernel of term_family.cuh) or scatters them into the grids (traj2_vjp_scatter_kernel + traj2_vjp_grid_out_kernel).
+// or scatters them into the grids (vjp_reduce_kernel, vjp_scatter_kernel + vjp_grid_out_kernel of term_family.cuh).
 constexpr int kRec = THX_TRAJ2_REC;
-constexpr int kSortChunk = THX_TRAJ2_SORT_CHUNK;
 
 // Collision2D: phi = w^2 s (eps - d), s = j1 u_x + j2 u_y.  The branches are collision_term's, in T; the derivatives in fp64.
 template <typename T>
@@ -271,94 +270,7 @@ traj2_vjp_terms_kernel(const thx_traj2_term* __restrict__ terms, int n_terms, co
 
 // stage B, small tensors: vjp_reduce_kernel of term_family.cuh
 
-// stage B, grids: workgroup = (problem, grid).  The four (cell, value) pairs of each collision term on this grid go through LDS a
-// chunk at a time: a bitonic network sorts the chunk by (cell, position in the list) -- a unique key, so the order of equal cells
-// is fixed --, the head of each run of equal cells sums the run in that order and adds it into the problem's fp64 grid.  Within a
-// chunk a cell has one head; chunks follow one another behind a barrier, so a cell two chunks touch is updated in chunk order.
-__global__ void __launch_bounds__(256)
-traj2_vjp_scatter_kernel(const double* __restrict__ rec, const thx_traj2_term* __restrict__ terms, int n_terms,
-                         const thx_traj2_grad_grid* __restrict__ grids, const int32_t* __restrict__ grid_terms, int n_grid_terms,
-                         double* __restrict__ work, int64_t work_elems, int B) {
-  __shared__ unsigned long long key[kSortChunk];
-  __shared__ double val[kSortChunk];
-  constexpr unsigned long long kPad = ~0ull;
-  const int b = blockIdx.x;
-  const thx_traj2_grad_grid gd = grids[blockIdx.y];
-  const int64_t cells = (int64_t)gd.rows * gd.cols;
-  if (gd.rows < 1 || gd.cols < 1 || cells > INT32_MAX || gd.term_begin < 0 || gd.term_end < gd.term_begin || gd.term_end > n_grid_terms)
-    return;
-  if (gd.work_off < 0 || gd.work_off + cells * B > work_elems) return;
-  double* gg = work + gd.work_off + cells * b;
-  for (int64_t c = threadIdx.x; c < cells; c += 256) gg[c] = 0.0;
-  __syncthreads();
-  const int64_t n_src = (int64_t)4 * (gd.term_end - gd.term_begin);
-  for (int64_t base = 0; base < n_src; base += kSortChunk) {
-    for (int i = threadIdx.x; i < kSortChunk; i += 256) {
-      const int64_t p = base + i;
-      unsigned long long kk = kPad;
-      double v = 0.0;
-      if (p < n_src) {
-        const int t = grid_terms[gd.term_begin + p / 4], c = (int)(p % 4);
-        if (t >= 0 && t < n_terms && terms[t].kind == THX_TRAJ2_COLLISION && terms[t].rows == gd.rows && terms[t].cols == gd.cols) {
-          const double cell = rec[((int64_t)t * kRec + 4 + c) * B + b];
-          if (cell >= 0.0 && cell < (double)cells) {
-            kk = ((unsigned long long)cell << 32) | (unsigned long long)i;   // (i: the position within the chunk, p - base)
-            v = rec[((int64_t)t * kRec + c) * B + b];
-          }
-        }
-      }
-      key[i] = kk, val[i] = v;
-    }
-    __syncthreads();
-    for (int k = 2; k <= kSortChunk; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int i = threadIdx.x; i < kSortChunk; i += 256) {
-          const int l = i ^ j;
-          if (l > i) {
-            const unsigned long long a = key[i], c = key[l];
-            if ((a > c) == ((i & k) == 0)) {
-              const double va = val[i];
-              key[i] = c, key[l] = a, val[i] = val[l], val[l] = va;
-            }
-          }
-        }
-        __syncthreads();
-      }
-    for (int i = threadIdx.x; i < kSortChunk; i += 256) {
-      const unsigned long long a = key[i];
-      if (a == kPad || (i > 0 && (key[i - 1] >> 32) == (a >> 32))) continue;   // padding, or inside a run
-      double acc = 0.0;
-      for (int q = i; q < kSortChunk && (key[q] >> 32) == (a >> 32); ++q) acc += val[q];
-      gg[a >> 32] += acc;
-    }
-    __syncthreads();
-  }
-}
-
-// ... and out of the fp64 grids: one thread per (problem, cell), cells fastest; a shared grid is summed over the problems in index order
-template <typename T>
-__global__ void __launch_bounds__(256)
-traj2_vjp_grid_out_kernel(const double* __restrict__ work, int64_t work_elems, const thx_traj2_grad_grid* __restrict__ grids,
-                          int max_cells, T* __restrict__ out, int64_t out_elems, int B) {
-  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= (int64_t)max_cells * B) return;
-  const int b = (int)(gid / max_cells);
-  const int64_t c = gid % max_cells;
-  const thx_traj2_grad_grid gd = grids[blockIdx.y];
-  const int64_t cells = (int64_t)gd.rows * gd.cols;
-  if (gd.rows < 1 || gd.cols < 1 || c >= cells || (gd.shared && b > 0)) return;
-  if (gd.work_off < 0 || gd.work_off + cells * B > work_elems || gd.out_off < 0) return;
-  const double* gg = work + gd.work_off;
-  if (gd.shared) {
-    if (gd.out_off + cells > out_elems) return;
-    double acc = 0.0;
-    for (int bb = 0; bb < B; ++bb) acc += gg[cells * bb + c];
-    out[gd.out_off + c] = (T)acc;
-  } else {
-    if (gd.out_off + cells * B > out_elems) return;
-    out[gd.out_off + cells * b + c] = (T)gg[cells * b + c];
-  }
-}
+// stage B, grids: vjp_scatter_kernel + vjp_grid_out_kernel of term_family.cuh
 
 // the family's own size checks: the message of the first that fails
 inline const char* traj2_bad_size(int64_t ldx, int32_t n) { return n < 2 ? ": n < 2" : (ldx < n ? ": ldx < n" : nullptr); }
@@ -390,44 +302,16 @@ extern "C" int thx_traj2_vjp(const thx_traj2_term* terms, int32_t n_terms, const
   if (ldu < n) return fail(who, ": ldu < n");
   if (m < 1 || j_total < 2) return fail(who, ": m < 1 or j_total < 2");
   const thx_traj2_grad_plan p = *plan;
-  if (p.n_tensors < 0 || p.n_pairs < 0 || p.n_grids < 0 || p.n_grid_terms < 0 || p.max_cells < 0 || p.out_elems < 1 || p.work_elems < 0)
-    return fail(who, ": negative size in the plan");
-  if ((p.n_tensors > 0 && (!p.tensors || !p.pairs)) || (p.n_grids > 0 && (!p.grids || !p.grid_terms || !grid_work || p.max_cells < 1)))
-    return fail(who, ": null pointer in the plan");
-  const uintptr_t el = dtype == THX_F32 ? 4 : 8;
-  auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
-  if (at(u) % el || at(grad_out) % el || at(rec) % 8 || at(grid_work) % 8 || at(p.tensors) % 8 || at(p.pairs) % 4 || at(p.grids) % 8 ||
-      at(p.grid_terms) % 4)
-    return fail(who, ": pointer not aligned");
-  const int64_t term_blocks = ((int64_t)n_terms * B + 255) / 256, out_blocks = ((int64_t)p.max_cells * B + 255) / 256;
-  if (term_blocks > (int64_t)INT32_MAX || (int64_t)p.n_tensors * B > (int64_t)INT32_MAX || out_blocks > (int64_t)INT32_MAX ||
-      p.n_grids > 65535)
-    return fail(who, ": grid limit exceeded (n_terms * B, tensors * B, cells * B or the number of grids)");
+  unsigned term_blocks = 0;
+  if (int rc = family_check_vjp(who, u, rec, p, grad_out, grid_work, n_terms, B, dtype, &term_blocks)) return rc;
   hipStream_t s = as_stream(stream);
   const dim3 block(256);
   THX_DISPATCH(dtype,
-               hipLaunchKernelGGL(traj2_vjp_terms_kernel<float>, dim3((unsigned)term_blocks), block, 0, s, terms, n_terms,
+               hipLaunchKernelGGL(traj2_vjp_terms_kernel<float>, dim3(term_blocks), block, 0, s, terms, n_terms,
                                   (const float*)x, ldx, n, (const float*)u, ldu, m, j_total, rec, B),
-               hipLaunchKernelGGL(traj2_vjp_terms_kernel<double>, dim3((unsigned)term_blocks), block, 0, s, terms, n_terms,
+               hipLaunchKernelGGL(traj2_vjp_terms_kernel<double>, dim3(term_blocks), block, 0, s, terms, n_terms,
                                   (const double*)x, ldx, n, (const double*)u, ldu, m, j_total, rec, B));
-  if (p.n_tensors > 0) {
-    const dim3 grid((unsigned)((int64_t)p.n_tensors * B));
-    THX_DISPATCH(dtype,
-                 hipLaunchKernelGGL((vjp_reduce_kernel<float, kRec>), grid, block, 0, s, rec, n_terms, p.tensors, p.pairs, p.n_pairs,
-                                    (float*)grad_out, p.out_elems, B),
-                 hipLaunchKernelGGL((vjp_reduce_kernel<double, kRec>), grid, block, 0, s, rec, n_terms, p.tensors, p.pairs, p.n_pairs,
-                                    (double*)grad_out, p.out_elems, B));
-  }
-  if (p.n_grids > 0) {
-    hipLaunchKernelGGL(traj2_vjp_scatter_kernel, dim3((unsigned)B, (unsigned)p.n_grids), block, 0, s, rec, terms, n_terms, p.grids,
-                       p.grid_terms, p.n_grid_terms, grid_work, p.work_elems, B);
-    const dim3 grid((unsigned)out_blocks, (unsigned)p.n_grids);
-    THX_DISPATCH(dtype,
-                 hipLaunchKernelGGL(traj2_vjp_grid_out_kernel<float>, grid, block, 0, s, grid_work, p.work_elems, p.grids, p.max_cells,
-                                    (float*)grad_out, p.out_elems, B),
-                 hipLaunchKernelGGL(traj2_vjp_grid_out_kernel<double>, grid, block, 0, s, grid_work, p.work_elems, p.grids, p.max_cells,
-                                    (double*)grad_out, p.out_elems, B));
-  }
+  if (int rc = family_vjp_stage_b<thx_traj2_term, THX_TRAJ2_COLLISION, kRec>(rec, terms, n_terms, p, grad_out, grid_work, B, dtype, s)) return rc;
   return check_launch(who);
 }
 

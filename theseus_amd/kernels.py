@@ -848,6 +848,24 @@ class HipKernels:
         _lib.check(self.lib.thx_push2_error(_lib.ptr(table), int(n_terms), _lib.ptr(x), V, _lib.ptr(err), B,
                                             _lib.dtype_code(x.dtype), se2_eps(x.dtype), _lib.stream_ptr(x.device)), "thx_push2_error")
 
+    def push2_vjp(self, table, n_terms, x, u, m, j_total, rec, plan, grad_out, grid_work):
+        """The gradient of (u * g).sum(), g what ``push2_eval`` + the block assembly form at x, w.r.t. the auxiliary tensors of the
+        gradient plan: x (V, B, 4), u (B, >= 3 V); rec fp64 scratch (n_terms * THX_PUSH2_REC * B); plan a ``_lib.Traj2GradPlan`` whose
+        tables are device tensors; grad_out (plan.out_elems) of x's dtype; grid_work fp64 (plan.work_elems), None without grids."""
+        if x.ndim != 3 or x.shape[2] != 4 or not x.is_contiguous():
+            raise ValueError("push2_vjp: the state must be a contiguous (V, B, 4) tensor")
+        V, B = x.shape[:2]
+        if (u.ndim != 2 or u.stride(1) != 1 or u.shape[0] != B or u.shape[1] < 3 * V or u.dtype != x.dtype or grad_out.dtype != x.dtype
+                or rec.dtype != torch.float64 or rec.numel() < n_terms * _lib.THX_PUSH2_REC * B or grad_out.numel() < plan.out_elems
+                or (plan.n_grids and (grid_work is None or grid_work.dtype != torch.float64 or grid_work.numel() < plan.work_elems))):
+            raise ValueError("push2_vjp: state / cotangent / scratch do not fit")
+        if not x.is_cuda or not u.is_cuda:
+            raise RuntimeError(f"push2_vjp: the state must live on a HIP device (got {x.device}); there is no CPU fallback")
+        _lib.check(self.lib.thx_push2_vjp(_lib.ptr(table), int(n_terms), _lib.ptr(x), V, ctypes.c_void_p(u.data_ptr()), u.stride(0),
+                                          int(m), int(j_total), _lib.ptr(rec), ctypes.byref(plan), _lib.ptr(grad_out),
+                                          _lib.ptr(grid_work), B, _lib.dtype_code(x.dtype), se2_eps(x.dtype),
+                                          _lib.stream_ptr(x.device)), "thx_push2_vjp")
+
     # ---- SE2 motion planning (csrc/trajse2_kernels.hip) ---------------------------------------------
     @staticmethod
     def _trajse2_state(what, x):

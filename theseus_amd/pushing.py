@@ -7,8 +7,13 @@ the variables' tensors are the (B, 4) slices.  Tangent columns of variable k: 3k
 
 Non-differentiated path (under no_grad, or nothing tracked requires grad): ``assemble`` = thx_push2_eval into persistent block
 buffers + thx_block_assemble on them, ``error_metric`` = thx_push2_error; no cost function is evaluated by torch.
-``backward_mode="implicit"``: the last step evaluates the torch classes at the detached state with the graph, forms g by torch,
-H from the detached blocks on the kernels, solves through the cached factor and retracts with the torch SE2 functions.
+``backward_mode="implicit"`` with an auxiliary tensor that requires grad (weights, measurements, c_square, the SDF and its origin /
+cell size, the effector radius, prior targets): the last step is the same fused forward, and g is returned through
+``term_table._FusedGradient``, whose backward is thx_push2_vjp (csrc/push_vjp_kernels.hip) -- no cost function is evaluated by
+torch there either.  The gate is ``TermTable._fused_backward_route``; a kernel set without ``push2_vjp``, ``fused_backward =
+False``, ``fused = False`` and a state that requires grad keep the torch route: the last step evaluates the torch classes at the
+detached state with the graph, forms g by torch, H from the detached blocks on the kernels.  Both routes solve through the cached
+factor and retract with the torch SE2 functions.
 ``"unroll"`` / ``"truncated"`` with something to differentiate are refused by the optimizer (no ``unrolled_step`` here).
 """
 from typing import Optional
@@ -121,6 +126,13 @@ class PackedPlanarPushing(TermTable, PackedState):
     def _launch_error(self, state, err):
         self.K.push2_error(self._table, len(self.costs), state, err)
 
+    # the implicit step's backward (thx_push2_vjp): where each aux slot's derivative sits in a term's record
+    _VJP_KERNEL, _VJP_REC = "push2_vjp", _lib.THX_PUSH2_REC
+    _VJP_ENTRIES = {_lib.PUSH2_QSP: (0, 1), _lib.PUSH2_MFB: (0, 4), _lib.PUSH2_CONTACT: (0, 8, 10, 11, 12), _lib.PUSH2_PRIOR: (0, 4)}
+
+    def _launch_vjp(self, table, state, u, rec, plan, grad_out, grid_work):
+        self.K.push2_vjp(table, len(self.costs), state, u, self.m, self.j_total, rec, plan, grad_out, grid_work)
+
     def _cost_error(self, c):   # (Difference.error() on SE2 is a kernel of its own, outside autograd: the torch Jacobians' error)
         return c.weighted_jacobians_error()[1]
 
@@ -131,10 +143,15 @@ class PackedPlanarPushing(TermTable, PackedState):
         return self._e
 
     def assemble(self, H: torch.Tensor, g: torch.Tensor, graph: bool = False):
-        """H (lower blocks) and g.  ``graph``: the blocks come from the torch classes, g is ALSO returned as a differentiable
-        function of whatever they depend on (the implicit step); H stays outside autograd."""
+        """H (lower blocks) and g.  ``graph``: g is ALSO returned as a differentiable function of the auxiliary tensors (the implicit
+        step), H stays outside autograd -- through the fused forward and thx_push2_vjp where ``_fused_backward_route`` holds,
+        otherwise (also with nothing to differentiate) with the blocks from the torch classes."""
         if fast_approx_local_jacobians() and _lib.PUSH2_PRIOR in self.kinds:
             raise NotImplementedError("HIP backend, fused planar pushing: fast_approx_local_jacobians=True is not fused into the kernels.")
-        if graph:   # (always the torch classes, whether or not anything requires grad)
+        if graph:
+            if self.fused and self._differentiated():
+                self.sync()
+                if self._fused_backward_route():
+                    return super().assemble(H, g, True)
             return PackedState.assemble(self, H, g, True)
         return super().assemble(H, g)

@@ -220,7 +220,7 @@ class TermTable:
     def _vjp(self, plan: GradPlan, table, state, u):
         """-> one gradient per input of the plan, in that input's shape (None where none is asked for)"""
         dev = state.device
-        need = len(self.costs) * self._VJP_REC * state.shape[0]
+        need = len(self.costs) * self._VJP_REC * u.shape[0]   # (u is (B, n) in every family)
         if self._vjp_rec is None or self._vjp_rec.numel() < need or self._vjp_rec.device != dev:
             self._vjp_rec = torch.empty(need, dtype=torch.float64, device=dev)
         need = plan.struct.work_elems
