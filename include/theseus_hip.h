@@ -567,6 +567,34 @@ int thx_trajse2_error(const thx_trajse2_term* terms, int32_t n_terms, const void
 int thx_trajse2_retract(const void* x, const uint8_t* var_kind, const void* delta, int64_t ldd, double step,
                         const uint8_t* ignore_mask, void* out, int32_t V, int32_t B, int dtype, const thx_se2_eps* eps, void* stream);
 
+/* ---- ... and the backward of its implicit step, thx_push2_vjp's twin: with g = -sum_t J_t^T e_t what thx_trajse2_eval +
+ *      thx_block_assemble form at the (detached) state x and u (B, 3 V, row stride ldu) a cotangent of g, the gradient of u^T g
+ *      w.r.t. every auxiliary tensor the plan (a thx_traj2_grad_plan, above) asks for.  Deterministic, no atomics, two stages:
+ *      A  one thread per (term, problem): the term's partial derivatives in fp64 -- every branch (in-grid test, floor, dist > eps,
+ *         the hinge's strict comparisons, the Taylor switches of the SE2 log) decided in the run's dtype exactly as thx_trajse2_eval
+ *         decides it -- into a record of THX_TRAJSE2_REC doubles, entry k of term t of problem b at
+ *         rec[(t * THX_TRAJSE2_REC + k) * B + b]:
+ *           COLLISION     0-3 d/d corner value (ll, hl, lh, hh), 4-7 their cell indices row * cols + col, 8-9 origin, 10 cell size,
+ *                         11 cost_eps, 12 weight            (all zero outside the grid and where the distance exceeds cost_eps)
+ *           GP            0 dt (the cost's), 1 dt (the weight's), 2-10 Qc_inv row major (symmetric: the symmetrised cotangent, as
+ *                         the backward of torch.linalg.cholesky returns it)
+ *           NONHOLONOMIC  0 weight
+ *           HINGE         0-2 down_limit, 3-5 up_limit, 6-8 threshold, 9-11 weight (wdim = 1: their sum in 9); a limit whose
+ *                         comparison does not hold gets exactly 0, also where it is +-inf
+ *           PRIOR_SE2     0-3 target, as the four raw components (x, y, cos, sin), 4-6 weight (wdim = 1: their sum in 4)
+ *           PRIOR_VEC     0-2 target, 3-5 weight (wdim = 1: their sum in 3)
+ *           PRIOR_XY      0-1 target, 2-3 weight (wdim = 1: their sum in 2)
+ *         a (term, problem) writes the entries its kind defines (13, 11, 1, 12, 7, 6, 4) and no others; terms that
+ *         thx_trajse2_eval skips write zeros to them.  The rest of a record is never read: plan pairs must stay inside these.
+ *      B  stage B of thx_traj2_vjp on the records: the small tensors by (term, entry) pairs, the grids by the LDS sort of the
+ *         collision terms' (cell, value) pairs.
+ *      grad_out has plan->out_elems elements of the run's dtype, grid_work plan->work_elems doubles (may be null without grids),
+ *      rec n_terms * THX_TRAJSE2_REC * B doubles; x must be aligned to one record (4 elements). */
+#define THX_TRAJSE2_REC 16
+int thx_trajse2_vjp(const thx_trajse2_term* terms, int32_t n_terms, const void* x, int32_t V, const void* u, int64_t ldu, int32_t m,
+                    int64_t j_total, double* rec, const thx_traj2_grad_plan* plan, void* grad_out, double* grid_work, int32_t B,
+                    int dtype, const thx_se2_eps* eps, void* stream);
+
 /* ---- Homography image alignment, dense Lucas-Kanade (examples/homography_estimation.py): the cost family of the example's
  *      objective.  terms[t] (DEVICE array built by the host, sorted by kind: the n_align alignment terms come first) is one cost
  *      function on the (B, n) Euclidean state x; col[0] = first state column of its 8-dof variable h, H = [h0 .. h7, 1] row major:

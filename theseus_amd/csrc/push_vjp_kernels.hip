@@ -11,55 +11,19 @@
 //   QuasiStaticPushingPlanar     closed forms: c is the directional derivative of D V - Vp along u, c_square enters e_2 and c_2 only
 //   MovingFrameBetween           c from the chain of the three betweens; d log(meas^-1 D) / d meas by the SE2 helpers on
 //                                Dual<double>, one pass per raw component (x, y, cos, sin), the Taylor branch forced to the forward's
-//   Difference on SE2            the same passes through the error AND the block (Jlog depends on the target)
+//   Difference on SE2            the same passes through the error AND the block (Jlog depends on the target): se2_vjp.cuh
 //   EffectorObjectContactPlanar  phi = -w^2 sgn s |d - r|, s = (j1, j2) . (G u_obj + H u_eff): collision_vjp's structure
 //                                (traj_kernels.hip) with the gap |d - r|; sgn and sign(d - r) are constants, as in the torch class
 // Stage B: vjp_reduce_kernel, vjp_scatter_kernel and vjp_grid_out_kernel of term_family.cuh on the records.  No atomics.
 #pragma clang fp contract(off)
-#include <cmath>
-
 #include "push_family.cuh"
-#include "dual.cuh"
+#include "se2_vjp.cuh"
 
 namespace thx {
 
 constexpr int kRec = THX_PUSH2_REC;
-using D64 = Dual<double>;
+using RecOut = RecOutT<kRec>;   // (RecOutT, widen, seeded, forced, load_u: se2_vjp.cuh)
 
-// where one (term, problem) stores its record: entry k at p[k * B]
-struct RecOut {
-  double* __restrict__ p;
-  int64_t B;
-  __device__ __forceinline__ void put(int k, double v) const { p[k * B] = v; }
-  __device__ __forceinline__ void zeros(int from) const {
-    for (int k = from; k < kRec; ++k) p[k * B] = 0.0;
-  }
-  // d phi / d row weights from the per-row values: three entries for a DiagonalCostWeight, their sum for a ScaleCostWeight
-  __device__ __forceinline__ void weights(int k, int wdim, const double* gw) const {
-    put(k, wdim == 3 ? gw[0] : gw[0] + gw[1] + gw[2]);
-    put(k + 1, wdim == 3 ? gw[1] : 0.0);
-    put(k + 2, wdim == 3 ? gw[2] : 0.0);
-  }
-};
-
-template <typename T>
-__device__ __forceinline__ SE2<double> widen(const SE2<T>& X) {
-  return SE2<double>{(double)X.x, (double)X.y, (double)X.c, (double)X.s};
-}
-// SE2<Dual>: X with the unit tangent on raw component k (k < 0: a constant)
-__device__ __forceinline__ SE2<D64> seeded(const SE2<double>& X, int k) {
-  return SE2<D64>{D64(X.x, k == 0 ? 1.0 : 0.0), D64(X.y, k == 1 ? 1.0 : 0.0), D64(X.c, k == 2 ? 1.0 : 0.0),
-                  D64(X.s, k == 3 ? 1.0 : 0.0)};
-}
-// thresholds that make the Dual<double> helpers take the branches the forward took in the run's dtype
-__device__ __forceinline__ Eps2<D64> forced(bool small, bool dsmall) {
-  return Eps2<D64>{D64(small ? HUGE_VAL : 0.0), D64(dsmall ? HUGE_VAL : 0.0)};
-}
-// the cotangent's three columns of state pose ``pose``
-template <typename T>
-__device__ __forceinline__ void load_u(const T* __restrict__ ub, int pose, double* o) {
-  o[0] = (double)ub[3 * pose], o[1] = (double)ub[3 * pose + 1], o[2] = (double)ub[3 * pose + 2];
-}
 template <typename T>
 __device__ __forceinline__ void row_weights64(const thx_push2_term& tm, int k, int b, double* w) {
   T wt[3];
@@ -155,45 +119,14 @@ __device__ __forceinline__ void mfb_vjp(const thx_push2_term& tm, const SE2<T>& 
   out.zeros(7);
 }
 
-// record: 0-3 target (raw x, y, cos, sin), 4-6 weight
+// record: 0-3 target (raw x, y, cos, sin), 4-6 weight: se2_prior_vjp of se2_vjp.cuh, through both the error and the block
 template <typename T>
 __device__ __forceinline__ void prior_vjp(const thx_push2_term& tm, const SE2<T>& var_t, const T* __restrict__ ub, int b,
                                           const Eps2<T>& eps, const RecOut& out) {
-  const SE2<T> target_t = aux_pose<T>(tm, 0, b);
-  // the forward's Taylor decisions (local_eval2, se2_log_jlog), in the run's dtype
-  bool small, dsmall;
-  {
-    SE2<T> ti, D;
-    se2_inv(target_t, ti);
-    se2_mul(ti, var_t, D);
-    const T th = t_abs(t_atan2(D.s, D.c));
-    small = th < eps.nz, dsmall = th < eps.dnz;
-  }
   double w[3], uu[3];
   row_weights64<T>(tm, 1, b, w);
   load_u(ub, tm.pose[0], uu);
-  const SE2<double> target = widen(target_t);
-  const SE2<D64> var = seeded(widen(var_t), -1);
-  const Eps2<D64> branch = forced(small, dsmall);
-  double gw[3] = {0.0, 0.0, 0.0};
-  // both the error and the block (Jlog) depend on the target: phi = -sum_i w_i^2 (Jlog u)_i xi_i
-#pragma unroll 1
-  for (int k = 0; k < 4; ++k) {
-    SE2<D64> ti, D;
-    D64 xi[3], Jl[9];
-    se2_inv(seeded(target, k), ti);
-    se2_mul(ti, var, D);
-    se2_log_jlog<D64>(D, branch, xi, Jl, true);
-    double acc = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const D64 q = (Jl[3 * i] * D64(uu[0]) + Jl[3 * i + 1] * D64(uu[1]) + Jl[3 * i + 2] * D64(uu[2])) * xi[i];
-      acc += w[i] * w[i] * q.d;
-      gw[i] = -2.0 * w[i] * q.v;
-    }
-    out.put(k, -acc);
-  }
-  out.weights(4, tm.wdim, gw);
+  se2_prior_vjp<T>(aux_pose<T>(tm, 0, b), var_t, w, uu, tm.wdim, eps, out);
   out.zeros(7);
 }
 

@@ -1,7 +1,7 @@
-// What the fused cost families (traj_kernels.hip, push_kernels.hip + push_vjp_kernels.hip, trajse2_kernels.hip, homog_kernels.hip +
+// What the fused cost families (traj_kernels.hip, push_kernels.hip + push_vjp_kernels.hip, trajse2_kernels.hip + trajse2_vjp_kernels.hip, homog_kernels.hip +
 // homog_vjp_kernels.hip, kin_kernels.hip) share: a family evaluates a whole objective from a table of 128-byte terms (thx_traj2_term,
 // thx_push2_term, thx_trajse2_term of include/theseus_hip.h: the same layout, the variable field named by the family).
-// Here: the per-term aux accessor, the bilinear signed-distance lookup, the fixed-order reduction of a *_error kernel, stage B of a
+// Here: the per-term aux accessor, the bilinear signed-distance lookup and the backward of a Collision2D term on it, the fixed-order reduction of a *_error kernel, stage B of a
 // *_vjp export on its per-(term, problem) records (vjp_reduce_kernel for the small tensors; vjp_scatter_kernel + vjp_grid_out_kernel
 // for 2-D grids, templated on the term type and the kind that reads the grid) and the host checks and stage-B launches of the
 // exports.  The term functions, stage A, the *_eval / *_error __global__ functions and the exports stay with the family.
@@ -60,6 +60,47 @@ __device__ __forceinline__ void sdf_bilinear(const T* __restrict__ sdf, int R, i
                                              T& j2) {
   SdfCells<T> k;
   sdf_bilinear_cells<T>(sdf, R, C, ox, oy, cell, px, py, dist, j1, j2, k);
+}
+
+// The backward of a Collision2D term (thx_traj2_vjp, thx_trajse2_vjp): phi = w^2 s (eps - d), s = j1 u_x + j2 u_y, with (u_x, u_y)
+// the cotangent of the looked-up point (px, py) in the world frame.  The branches are the forward's, in T; the derivatives in fp64.
+// Record entries through out.put(k, v): 0-3 d / d corner value (ll, hl, lh, hh), 4-7 their cell indices row * cols + col, 8-9 origin,
+// 10 cell size, 11 cost_eps, 12 weight.  -> false, and nothing is written, outside the grid or where the distance exceeds eps (the
+// error and the block are constants there)
+template <typename T, typename Term, typename Out>
+__device__ __forceinline__ bool collision_vjp_at(const Term& tm, T px_t, T py_t, double ux, double uy, int b, const Out& out) {
+  const T* sdf = static_cast<const T*>(tm.aux[0]) + (int64_t)b * tm.aux_bstride[0];
+  const T eps_t = aux_at<T>(tm, 3, b), ox_t = aux_at<T>(tm, 1, b, 0), oy_t = aux_at<T>(tm, 1, b, 1), cell_t = aux_at<T>(tm, 2, b);
+  T dist, j1, j2;
+  SdfCells<T> k;
+  sdf_bilinear_cells<T>(sdf, tm.rows, tm.cols, ox_t, oy_t, cell_t, px_t, py_t, dist, j1, j2, k);
+  if (k.oob || dist > eps_t) return false;
+  const double w = (double)aux_at<T>(tm, 4, b), eps = (double)eps_t, cell = (double)cell_t;
+  const double col = ((double)px_t - (double)ox_t) / cell, row = ((double)py_t - (double)oy_t) / cell;
+  const double lr = (double)k.lr, lc = (double)k.lc;
+  const double hrd = lr + 1.0 - row, hcd = lc + 1.0 - col, lrd = row - lr, lcd = col - lc;
+  const double sll = (double)k.sll, shl = (double)k.shl, slh = (double)k.slh, shh = (double)k.shh;
+  const double d = hrd * hcd * sll + lrd * hcd * shl + hrd * lcd * slh + lrd * lcd * shh;
+  const double dc = hrd * (slh - sll) + lrd * (shh - shl), dr = hcd * (shl - sll) + lcd * (shh - slh);   // d d / d col, d d / d row
+  const double s = (dc * ux + dr * uy) / cell, gap = eps - d, w2 = w * w;
+  // d s / d corner from the j1 / j2 formulas; the corner's bilinear weight is d d / d corner
+  out.put(0, w2 * (gap * (-hrd * ux - hcd * uy) / cell - s * hrd * hcd));
+  out.put(1, w2 * (gap * (-lrd * ux + hcd * uy) / cell - s * lrd * hcd));
+  out.put(2, w2 * (gap * (hrd * ux - lcd * uy) / cell - s * hrd * lcd));
+  out.put(3, w2 * (gap * (lrd * ux + lcd * uy) / cell - s * lrd * lcd));
+  out.put(4, (double)((int64_t)k.lri * tm.cols + k.lci));
+  out.put(5, (double)((int64_t)k.hri * tm.cols + k.lci));
+  out.put(6, (double)((int64_t)k.lri * tm.cols + k.hci));
+  out.put(7, (double)((int64_t)k.hri * tm.cols + k.hci));
+  // through col = (px - ox) / cell, row = (py - oy) / cell; the only second derivative of the bilinear form is the mixed one
+  const double mixed = sll - shl - slh + shh;
+  const double pcol = w2 * (gap * mixed * uy / cell - s * dc), prow = w2 * (gap * mixed * ux / cell - s * dr);
+  out.put(8, -pcol / cell);
+  out.put(9, -prow / cell);
+  out.put(10, -(pcol * col + prow * row + w2 * gap * s) / cell);   // (the last: j1, j2 divide by the cell size themselves)
+  out.put(11, w2 * s);
+  out.put(12, 2.0 * w * s * gap);
+  return true;
 }
 
 // err = 0.5 * (sum of the workgroup's kErrThreads fp64 partials), by a fixed-order tree: deterministic, no atomics

@@ -152,42 +152,14 @@ traj2_error_kernel(const thx_traj2_term* __restrict__ terms, int n_terms, const 
 // or scatters them into the grids (vjp_reduce_kernel, vjp_scatter_kernel + vjp_grid_out_kernel of term_family.cuh).
 constexpr int kRec = THX_TRAJ2_REC;
 
-// Collision2D: phi = w^2 s (eps - d), s = j1 u_x + j2 u_y.  The branches are collision_term's, in T; the derivatives in fp64.
+// Collision2D on a Point2: collision_vjp_at of term_family.cuh at the point itself, with the point's own cotangent columns
+struct RecArray {
+  double* o;
+  __device__ __forceinline__ void put(int k, double v) const { o[k] = v; }
+};
 template <typename T>
 __device__ inline void collision_vjp(const thx_traj2_term& tm, const T* __restrict__ x, const T* __restrict__ u, int b, double* o) {
-  const T* sdf = static_cast<const T*>(tm.aux[0]) + (int64_t)b * tm.aux_bstride[0];
-  const T eps_t = aux_at<T>(tm, 3, b), ox_t = aux_at<T>(tm, 1, b, 0), oy_t = aux_at<T>(tm, 1, b, 1), cell_t = aux_at<T>(tm, 2, b);
-  const T px_t = x[tm.col[0]], py_t = x[tm.col[0] + 1];
-  T dist, j1, j2;
-  SdfCells<T> k;
-  sdf_bilinear_cells<T>(sdf, tm.rows, tm.cols, ox_t, oy_t, cell_t, px_t, py_t, dist, j1, j2, k);
-  if (k.oob || dist > eps_t) return;   // (the error and the block are constants there)
-  const double w = (double)aux_at<T>(tm, 4, b), eps = (double)eps_t, cell = (double)cell_t;
-  const double ux = (double)u[tm.col[0]], uy = (double)u[tm.col[0] + 1];
-  const double col = ((double)px_t - (double)ox_t) / cell, row = ((double)py_t - (double)oy_t) / cell;
-  const double lr = (double)k.lr, lc = (double)k.lc;
-  const double hrd = lr + 1.0 - row, hcd = lc + 1.0 - col, lrd = row - lr, lcd = col - lc;
-  const double sll = (double)k.sll, shl = (double)k.shl, slh = (double)k.slh, shh = (double)k.shh;
-  const double d = hrd * hcd * sll + lrd * hcd * shl + hrd * lcd * slh + lrd * lcd * shh;
-  const double dc = hrd * (slh - sll) + lrd * (shh - shl), dr = hcd * (shl - sll) + lcd * (shh - slh);   // d d / d col, d d / d row
-  const double s = (dc * ux + dr * uy) / cell, gap = eps - d, w2 = w * w;
-  // d s / d corner from the j1 / j2 formulas; the corner's bilinear weight is d d / d corner
-  o[0] = w2 * (gap * (-hrd * ux - hcd * uy) / cell - s * hrd * hcd);
-  o[1] = w2 * (gap * (-lrd * ux + hcd * uy) / cell - s * lrd * hcd);
-  o[2] = w2 * (gap * (hrd * ux - lcd * uy) / cell - s * hrd * lcd);
-  o[3] = w2 * (gap * (lrd * ux + lcd * uy) / cell - s * lrd * lcd);
-  o[4] = (double)((int64_t)k.lri * tm.cols + k.lci);
-  o[5] = (double)((int64_t)k.hri * tm.cols + k.lci);
-  o[6] = (double)((int64_t)k.lri * tm.cols + k.hci);
-  o[7] = (double)((int64_t)k.hri * tm.cols + k.hci);
-  // through col = (px - ox) / cell, row = (py - oy) / cell; the only second derivative of the bilinear form is the mixed one
-  const double mixed = sll - shl - slh + shh;
-  const double pcol = w2 * (gap * mixed * uy / cell - s * dc), prow = w2 * (gap * mixed * ux / cell - s * dr);
-  o[8] = -pcol / cell;
-  o[9] = -prow / cell;
-  o[10] = -(pcol * col + prow * row + w2 * gap * s) / cell;   // (the last: j1, j2 divide by the cell size themselves)
-  o[11] = w2 * s;
-  o[12] = 2.0 * w * s * gap;
+  collision_vjp_at<T>(tm, x[tm.col[0]], x[tm.col[0] + 1], (double)u[tm.col[0]], (double)u[tm.col[0] + 1], b, RecArray{o});
 }
 
 // GPMotionModel: phi = -rho^T W r, W = M(dt_w) (x) Qc_inv, rho = [u_p2 - u_p1 - dt u_v1 ; u_v2 - u_v1]; no Cholesky is differentiated.

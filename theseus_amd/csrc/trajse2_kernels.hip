@@ -20,33 +20,15 @@
 // atan2 arguments), so a kink lands where the torch classes of theseus_amd/embodied.py put it.  Registers only; LDS: the reduction
 // of thx_trajse2_error.
 #pragma clang fp contract(off)
-#include "term_family.cuh"
-#include "lie_se2.cuh"
+#include "trajse2_family.cuh"
 
 namespace thx {
 
-// one state record as ONE vector load (the record is 4 * sizeof(T) aligned: checked on the host)
-__device__ __forceinline__ SE2<float> tse2_load(const float* __restrict__ x, int64_t rec) {
-  const float4 v = reinterpret_cast<const float4*>(x)[rec];
-  return SE2<float>{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ SE2<double> tse2_load(const double* __restrict__ x, int64_t rec) {
-  const double4 v = reinterpret_cast<const double4*>(x)[rec];
-  return SE2<double>{v.x, v.y, v.z, v.w};
-}
 __device__ __forceinline__ void tse2_store(float* __restrict__ x, int64_t rec, float a, float b, float c, float d) {
   reinterpret_cast<float4*>(x)[rec] = make_float4(a, b, c, d);
 }
 __device__ __forceinline__ void tse2_store(double* __restrict__ x, int64_t rec, double a, double b, double c, double d) {
   reinterpret_cast<double4*>(x)[rec] = make_double4(a, b, c, d);
-}
-
-// the row weights of a Scale (wdim 1) / DiagonalCostWeight (wdim = n) at aux slot k
-template <typename T, int n>
-__device__ __forceinline__ void tse2_weights(const thx_trajse2_term& tm, int k, int b, T* w) {
-  w[0] = aux_at<T>(tm, k, b, 0);
-#pragma unroll
-  for (int i = 1; i < n; ++i) w[i] = tm.wdim == n ? aux_at<T>(tm, k, b, i) : w[0];
 }
 
 // Collision2D at the pose's translation: weighted error (1) and the weighted 1 x 3 block  -(dd/dxy) [R, 0]
@@ -217,27 +199,6 @@ __device__ __forceinline__ void tse2_prior_xy(const thx_trajse2_term& tm, const 
   }
 }
 
-__device__ __forceinline__ int tse2_dim(int kind) {
-  return kind == THX_TRAJSE2_GP ? 6
-         : (kind == THX_TRAJSE2_COLLISION || kind == THX_TRAJSE2_NONHOLONOMIC) ? 1
-         : (kind == THX_TRAJSE2_PRIOR_XY ? 2 : 3);
-}
-__device__ __forceinline__ int tse2_vars(int kind) {
-  return kind == THX_TRAJSE2_GP ? 4 : (kind == THX_TRAJSE2_NONHOLONOMIC ? 2 : 1);
-}
-
-// the kind is one of the seven, every record a term reads lies inside the state, a weight is as wide as 1 or as the cost
-__device__ __forceinline__ bool tse2_reads_ok(const thx_trajse2_term& tm, int V) {
-  if (tm.kind < THX_TRAJSE2_COLLISION || tm.kind > THX_TRAJSE2_PRIOR_XY) return false;
-  const int nv = tse2_vars(tm.kind);
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-    if (s < nv && (tm.var[s] < 0 || tm.var[s] >= V)) return false;
-  if (tm.kind == THX_TRAJSE2_COLLISION) return tm.rows >= 1 && tm.cols >= 1;
-  if (tm.kind == THX_TRAJSE2_GP || tm.kind == THX_TRAJSE2_NONHOLONOMIC) return true;
-  return tm.wdim == 1 || tm.wdim == tse2_dim(tm.kind);
-}
-
 // weighted error of term tm for problem b into ev (dim values); Jb != nullptr: also the weighted blocks, block s at Jb + s * jstep
 template <typename T>
 __device__ __forceinline__ void tse2_term(const thx_trajse2_term& tm, const T* __restrict__ x, int B, int b, const Eps2<T>& eps,
@@ -327,11 +288,6 @@ trajse2_retract_kernel(const T* __restrict__ x, const uint8_t* __restrict__ var_
   se2_exp<double>(xi, eps, Ex, nullptr);
   se2_mul(SE2<double>{(double)r.x, (double)r.y, (double)r.c, (double)r.s}, Ex, Y);
   tse2_store(out, gid, (T)Y.x, (T)Y.y, (T)Y.c, (T)Y.s);
-}
-
-template <typename T>
-inline Eps2<T> tse2_eps(const thx_se2_eps* e) {
-  return Eps2<T>{(T)e->near_zero, (T)e->d_near_zero};
 }
 
 }  // namespace thx

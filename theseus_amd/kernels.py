@@ -909,6 +909,22 @@ class HipKernels:
                                                 float(step), _lib.ptr(ignore_mask), _lib.ptr(out), V, B, _lib.dtype_code(x.dtype),
                                                 se2_eps(x.dtype), _lib.stream_ptr(x.device)), "thx_trajse2_retract")
 
+    def trajse2_vjp(self, table, n_terms, x, u, m, j_total, rec, plan, grad_out, grid_work):
+        """The gradient of (u * g).sum(), g what ``trajse2_eval`` + the block assembly form at x, w.r.t. the auxiliary tensors of the
+        gradient plan: x (V, B, 4), u (B, >= 3 V); rec fp64 scratch (n_terms * THX_TRAJSE2_REC * B); plan a ``_lib.Traj2GradPlan``
+        whose tables are device tensors; grad_out (plan.out_elems) of x's dtype; grid_work fp64 (plan.work_elems), None without grids."""
+        V, B = self._trajse2_state("trajse2_vjp", x)
+        if (u.ndim != 2 or u.stride(1) != 1 or u.shape[0] != B or u.shape[1] < 3 * V or u.dtype != x.dtype or grad_out.dtype != x.dtype
+                or rec.dtype != torch.float64 or rec.numel() < n_terms * _lib.THX_TRAJSE2_REC * B or grad_out.numel() < plan.out_elems
+                or (plan.n_grids and (grid_work is None or grid_work.dtype != torch.float64 or grid_work.numel() < plan.work_elems))):
+            raise ValueError("trajse2_vjp: state / cotangent / scratch do not fit")
+        if not x.is_cuda or not u.is_cuda:
+            raise RuntimeError(f"trajse2_vjp: the state must live on a HIP device (got {x.device}); there is no CPU fallback")
+        _lib.check(self.lib.thx_trajse2_vjp(_lib.ptr(table), int(n_terms), _lib.ptr(x), V, ctypes.c_void_p(u.data_ptr()), u.stride(0),
+                                            int(m), int(j_total), _lib.ptr(rec), ctypes.byref(plan), _lib.ptr(grad_out),
+                                            _lib.ptr(grid_work), B, _lib.dtype_code(x.dtype), se2_eps(x.dtype),
+                                            _lib.stream_ptr(x.device)), "thx_trajse2_vjp")
+
     # ---- implicit backward ----------------------------------------------------------------------
     def _retract_vjp(self, grp: PGGroup, poses, delta, step, grad_out, grad_delta):
         P, B = poses.shape[:2]

@@ -11,7 +11,13 @@ as thx_se2_retract, velocity records x + step * delta), the masked copies thx_co
 
 Non-differentiated path (under no_grad, or nothing tracked requires grad): ``assemble`` = thx_trajse2_eval into persistent block
 buffers + thx_block_assemble on them, ``error_metric`` = thx_trajse2_error; no cost function is evaluated by torch.
-``backward_mode="implicit"``: PackedState.implicit_step on the torch classes, retracting with se2_torch.retract / a plain add.
+``backward_mode="implicit"`` with an auxiliary tensor that requires grad (the SDF, its origin and cell size, cost_eps, the weights,
+dt, Qc_inv, the prior targets, the hinge's limits and threshold): the last step is the same fused forward, and g is returned through
+``term_table._FusedGradient``, whose backward is thx_trajse2_vjp (csrc/trajse2_vjp_kernels.hip) -- no cost function is evaluated by
+torch there either.  The gate is ``TermTable._fused_backward_route``; a kernel set without ``trajse2_vjp``, ``fused_backward =
+False``, ``fused = False`` and a state that requires grad keep the torch route: the last step evaluates the torch classes at the
+detached state with the graph, forms g by torch, H from the detached blocks on the kernels.  Both routes solve through the cached
+factor and retract with se2_torch.retract / a plain add.
 ``"unroll"`` / ``"truncated"`` with something to differentiate are refused by the optimizer (no ``unrolled_step`` here).
 ``fused = False``: the same class on the torch classes (tools/bench_trajse2.py's baseline).
 """
@@ -178,6 +184,15 @@ class PackedTrajectorySE2(TermTable, PackedState):
     def _launch_error(self, state, err):
         self.K.trajse2_error(self._table, len(self.costs), state, err)
 
+    # the implicit step's backward (thx_trajse2_vjp): where each aux slot's derivative sits in a term's record
+    _VJP_KERNEL, _VJP_REC = "trajse2_vjp", _lib.THX_TRAJSE2_REC
+    _VJP_ENTRIES = {_lib.TRAJSE2_COLLISION: (0, 8, 10, 11, 12), _lib.TRAJSE2_GP: (0, 1, 2), _lib.TRAJSE2_NONHOLONOMIC: (0,),
+                    _lib.TRAJSE2_HINGE: (0, 3, 6, 9), _lib.TRAJSE2_PRIOR_SE2: (0, 4), _lib.TRAJSE2_PRIOR_VEC: (0, 3),
+                    _lib.TRAJSE2_PRIOR_XY: (0, 2)}
+
+    def _launch_vjp(self, table, state, u, rec, plan, grad_out, grid_work):
+        self.K.trajse2_vjp(table, len(self.costs), state, u, self.m, self.j_total, rec, plan, grad_out, grid_work)
+
     def _cost_error(self, c):
         if "Difference" in _names(c) and _is_se2(c.var):   # (its error() is a kernel of its own, outside autograd)
             return c.weighted_jacobians_error()[1]
@@ -190,11 +205,16 @@ class PackedTrajectorySE2(TermTable, PackedState):
         return self._e
 
     def assemble(self, H: torch.Tensor, g: torch.Tensor, graph: bool = False):
-        """H (lower blocks) and g.  ``graph``: the blocks come from the torch classes, g is ALSO returned as a differentiable
-        function of whatever they depend on (the implicit step); H stays outside autograd."""
+        """H (lower blocks) and g.  ``graph``: g is ALSO returned as a differentiable function of the auxiliary tensors (the implicit
+        step), H stays outside autograd -- through the fused forward and thx_trajse2_vjp where ``_fused_backward_route`` holds,
+        otherwise (also with nothing to differentiate) with the blocks from the torch classes."""
         if fast_approx_local_jacobians() and _lib.TRAJSE2_PRIOR_SE2 in self.kinds:
             raise NotImplementedError("HIP backend, fused SE2 motion planning: fast_approx_local_jacobians=True is not fused into the "
                                       "kernels.")
-        if graph:   # (always the torch classes, whether or not anything requires grad)
+        if graph:
+            if self.fused and self._differentiated():
+                self.sync()
+                if self._fused_backward_route():
+                    return super().assemble(H, g, True)
             return PackedState.assemble(self, H, g, True)
         return super().assemble(H, g)
