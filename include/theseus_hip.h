@@ -724,6 +724,28 @@ int thx_kin_eval(const thx_kin_term* terms, int32_t n_terms, const thx_kin_joint
 int thx_kin_error(const thx_kin_term* terms, int32_t n_terms, const thx_kin_joint* paths, int32_t n_paths, const void* x, int64_t ldx,
                   int32_t n, int32_t dof, void* err, int32_t B, int dtype, const thx_lie_eps* eps, void* stream);
 
+/* ---- ... and the backward of its implicit step, thx_traj2_vjp's twin: with g = -sum_t J_t^T e_t what thx_kin_eval +
+ *      thx_block_assemble form at the (detached) state x and u (B, n, row stride ldu) a cotangent of g, the gradient of u^T g
+ *      w.r.t. every auxiliary tensor the plan (a thx_traj2_grad_plan, above) asks for.  Deterministic, no atomics, two stages:
+ *      A  one thread per (term, problem): the term's partial derivatives in fp64 into a record of rec_stride >= max(18, 4 dof)
+ *         doubles, entry k of term t of problem b at rec[(t * rec_stride + k) * B + b].  A link term contracts the body Jacobian
+ *         with u on the walk back from the link (six doubles, no dim x dof block); the pose target is differentiated through its
+ *         12 raw entries, the closed forms of log / Jlog on dual numbers with the Taylor switches where thx_kin_eval puts them;
+ *         the hinge's strict comparisons are made in the run's dtype exactly as thx_kin_eval makes them:
+ *           POSE      0-11 target (row major 3 x 4), 12-17 weight (wdim = 1: their sum in 12)
+ *           POSITION  0-2 target, 3-5 weight (wdim = 1: their sum in 3)
+ *           HINGE     0... down_limit, dof... up_limit, 2 dof... threshold, 3 dof... weight (wdim = 1: their sum in 3 dof); a limit
+ *                     whose comparison does not hold gets exactly 0, also where it is +-inf
+ *           PRIOR     0... target, dof... weight (wdim = 1: their sum in dof)
+ *         a (term, problem) writes the entries its kind defines (18, 6, 4 dof, 2 dof) and no others; terms that thx_kin_eval skips
+ *         write zeros to them.  The rest of a record is never read: plan pairs must stay inside these.
+ *      B  the small-tensor stage of thx_traj2_vjp on the records, by (term, entry) pairs, with the record width read at run time.
+ *         The family has no grids: a plan with n_grids != 0 is refused.
+ *      grad_out has plan->out_elems elements of the run's dtype, rec n_terms * rec_stride * B doubles. */
+int thx_kin_vjp(const thx_kin_term* terms, int32_t n_terms, const thx_kin_joint* paths, int32_t n_paths, const void* x, int64_t ldx,
+                int32_t n, int32_t dof, const void* u, int64_t ldu, int32_t m, int64_t j_total, double* rec, int32_t rec_stride,
+                const thx_traj2_grad_plan* plan, void* grad_out, int32_t B, int dtype, const thx_lie_eps* eps, void* stream);
+
 /* ---- DCEM, the differentiable cross-entropy method (theseus/optimizer/nonlinear/dcem.py:94-158; the LML projection:
  *      theseus/third_party/lml.py:53-177): what one iteration does with the S sampled states X (S, B, n) -- sample major, every
  *      X[s] a contiguous (B, n) state -- and their errors fX (S, B), and its backward.  One workgroup per problem; values in the

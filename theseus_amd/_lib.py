@@ -341,6 +341,8 @@ _SIGNATURES = {
                      c_int32, c_int32, c_int, POINTER(LieEps), c_void_p],
     "thx_kin_error": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_int,
                       POINTER(LieEps), c_void_p],
+    "thx_kin_vjp": [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int64, c_int32, c_int64,
+                    c_void_p, c_int32, POINTER(Traj2GradPlan), c_void_p, c_int32, c_int, POINTER(LieEps), c_void_p],
     "thx_dcem_update": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_int, c_double, c_int32, c_int32, c_void_p,
                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     "thx_dcem_update_vjp": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,

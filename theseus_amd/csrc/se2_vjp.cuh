@@ -1,36 +1,17 @@
 // What the stage A kernels of the SE2 families' implicit backward (push_vjp_kernels.hip: thx_push2_vjp, trajse2_vjp_kernels.hip:
-// thx_trajse2_vjp) share: where a (term, problem) stores its record, the fp64 / Dual<double> forms of an SE2 record with the forward's
-// Taylor branch forced, and the backward of a Difference on SE2.  Included after the source's own ``#pragma clang fp contract(off)``.
+// thx_trajse2_vjp) share: the fp64 / Dual<double> forms of an SE2 record with the forward's Taylor branch forced, and the backward of
+// a Difference on SE2 (records go out through RecOutT of term_family.cuh).  Included after the source's own
+// ``#pragma clang fp contract(off)``.
 #pragma once
 #include <cmath>
 
+#include "term_family.cuh"
 #include "lie_se2.cuh"
 #include "dual.cuh"
 
 namespace thx {
 
 using D64 = Dual<double>;
-
-// where one (term, problem) stores its record of REC doubles: entry k at p[k * B]
-template <int REC>
-struct RecOutT {
-  double* __restrict__ p;
-  int64_t B;
-  __device__ __forceinline__ void put(int k, double v) const { p[k * B] = v; }
-  __device__ __forceinline__ void zeros(int from, int to = REC) const {
-    for (int k = from; k < to; ++k) p[k * B] = 0.0;
-  }
-  // d phi / d row weights from the n per-row values: n entries for a DiagonalCostWeight, their sum (and zeros) for a ScaleCostWeight
-  template <int n = 3>
-  __device__ __forceinline__ void weights(int k, int wdim, const double* gw) const {
-    double sum = gw[0];
-#pragma unroll
-    for (int i = 1; i < n; ++i) sum += gw[i];
-    put(k, wdim == n ? gw[0] : sum);
-#pragma unroll
-    for (int i = 1; i < n; ++i) put(k + i, wdim == n ? gw[i] : 0.0);
-  }
-};
 
 template <typename T>
 __device__ __forceinline__ SE2<double> widen(const SE2<T>& X) {

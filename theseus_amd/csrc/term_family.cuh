@@ -1,5 +1,5 @@
 // What the fused cost families (traj_kernels.hip, push_kernels.hip + push_vjp_kernels.hip, trajse2_kernels.hip + trajse2_vjp_kernels.hip, homog_kernels.hip +
-// homog_vjp_kernels.hip, kin_kernels.hip) share: a family evaluates a whole objective from a table of 128-byte terms (thx_traj2_term,
+// homog_vjp_kernels.hip, kin_kernels.hip + kin_vjp_kernels.hip) share: a family evaluates a whole objective from a table of 128-byte terms (thx_traj2_term,
 // thx_push2_term, thx_trajse2_term of include/theseus_hip.h: the same layout, the variable field named by the family).
 // Here: the per-term aux accessor, the bilinear signed-distance lookup and the backward of a Collision2D term on it, the fixed-order reduction of a *_error kernel, stage B of a
 // *_vjp export on its per-(term, problem) records (vjp_reduce_kernel for the small tensors; vjp_scatter_kernel + vjp_grid_out_kernel
@@ -116,13 +116,35 @@ __device__ __forceinline__ void store_half_sum(double acc, T* __restrict__ err) 
   if (threadIdx.x == 0) *err = (T)(0.5 * part[0]);
 }
 
-// The small-tensor stage of a family's VJP export (thx_traj2_vjp, thx_push2_vjp, thx_homog_vjp): rec holds REC doubles per (term, problem), entry k
+// where one (term, problem) of a stage A kernel stores its record of REC doubles: entry k at p[k * B]
+template <int REC>
+struct RecOutT {
+  double* __restrict__ p;
+  int64_t B;
+  __device__ __forceinline__ void put(int k, double v) const { p[k * B] = v; }
+  __device__ __forceinline__ void zeros(int from, int to = REC) const {
+    for (int k = from; k < to; ++k) p[k * B] = 0.0;
+  }
+  // d phi / d row weights from the n per-row values: n entries for a DiagonalCostWeight, their sum (and zeros) for a ScaleCostWeight
+  template <int n = 3>
+  __device__ __forceinline__ void weights(int k, int wdim, const double* gw) const {
+    double sum = gw[0];
+#pragma unroll
+    for (int i = 1; i < n; ++i) sum += gw[i];
+    put(k, wdim == n ? gw[0] : sum);
+#pragma unroll
+    for (int i = 1; i < n; ++i) put(k + i, wdim == n ? gw[i] : 0.0);
+  }
+};
+
+// The small-tensor stage of a family's VJP export (thx_traj2_vjp, thx_push2_vjp, thx_homog_vjp, thx_kin_vjp): rec holds REC doubles per (term, problem), entry k
 // of term t of problem b at rec[(t * REC + k) * B + b].  Workgroup = (tensor, problem), or the tensor when it is shared; fixed-order
 // sums in fp64
-template <typename T, int REC>
-__global__ void __launch_bounds__(256)
-vjp_reduce_kernel(const double* __restrict__ rec, int n_terms, const thx_traj2_grad_tensor* __restrict__ tensors,
-                        const thx_traj2_grad_pair* __restrict__ pairs, int n_pairs, T* __restrict__ out, int64_t out_elems, int B) {
+template <typename T>
+__device__ __forceinline__ void vjp_reduce(const double* __restrict__ rec, const int REC, int n_terms,
+                                           const thx_traj2_grad_tensor* __restrict__ tensors,
+                                           const thx_traj2_grad_pair* __restrict__ pairs, int n_pairs, T* __restrict__ out,
+                                           int64_t out_elems, int B) {
   __shared__ double part[256];
   const int g = (int)(blockIdx.x / (unsigned)B), b = (int)(blockIdx.x % (unsigned)B);
   const thx_traj2_grad_tensor tg = tensors[g];
@@ -149,6 +171,19 @@ vjp_reduce_kernel(const double* __restrict__ rec, int n_terms, const thx_traj2_g
     if (threadIdx.x == 0) out[o0 + j] = (T)part[0];
     __syncthreads();
   }
+}
+template <typename T, int REC>
+__global__ void __launch_bounds__(256)
+vjp_reduce_kernel(const double* __restrict__ rec, int n_terms, const thx_traj2_grad_tensor* __restrict__ tensors,
+                        const thx_traj2_grad_pair* __restrict__ pairs, int n_pairs, T* __restrict__ out, int64_t out_elems, int B) {
+  vjp_reduce<T>(rec, REC, n_terms, tensors, pairs, n_pairs, out, out_elems, B);
+}
+// ... for a family whose record width is known at run time only (thx_kin_vjp: it grows with the robot's degrees of freedom)
+template <typename T>
+__global__ void __launch_bounds__(256)
+vjp_reduce_strided_kernel(const double* __restrict__ rec, int rec_stride, int n_terms, const thx_traj2_grad_tensor* __restrict__ tensors,
+                          const thx_traj2_grad_pair* __restrict__ pairs, int n_pairs, T* __restrict__ out, int64_t out_elems, int B) {
+  vjp_reduce<T>(rec, rec_stride, n_terms, tensors, pairs, n_pairs, out, out_elems, B);
 }
 
 constexpr int kSortChunk = THX_TRAJ2_SORT_CHUNK;   // (cell, value) pairs the grid scatter sorts at a time

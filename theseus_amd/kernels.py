@@ -784,6 +784,22 @@ class HipKernels:
         _lib.check(self.lib.thx_kin_error(*args, _lib.ptr(err), B, _lib.dtype_code(x.dtype), lie_eps(x.dtype),
                                           _lib.stream_ptr(x.device)), "thx_kin_error")
 
+    def kin_vjp(self, table, n_terms, paths, n_paths, x, n, dof, u, m, j_total, rec, rec_stride, plan, grad_out):
+        """The gradient of (u * g).sum(), g what ``kin_eval`` + the block assembly form at x, w.r.t. the auxiliary tensors of the
+        gradient plan: x (B, >= n), u (B, >= n); rec fp64 scratch (n_terms * rec_stride * B), rec_stride >= max(18, 4 dof); plan a
+        ``_lib.Traj2GradPlan`` without grids whose tables are device tensors; grad_out (plan.out_elems) of x's dtype."""
+        B = x.shape[0]
+        if (u.ndim != 2 or u.stride(1) != 1 or u.shape[0] != B or u.shape[1] < n or u.dtype != x.dtype or grad_out.dtype != x.dtype
+                or rec.dtype != torch.float64 or rec_stride < max(18, 4 * dof) or rec.numel() < n_terms * rec_stride * B
+                or grad_out.numel() < plan.out_elems or plan.n_grids):
+            raise ValueError("kin_vjp: state / cotangent / scratch do not fit")
+        args = self._kin_args("kin_vjp", table, n_terms, paths, n_paths, x, n, dof)
+        if not u.is_cuda:
+            raise RuntimeError(f"kin_vjp: the cotangent must live on a HIP device (got {u.device}); there is no CPU fallback")
+        _lib.check(self.lib.thx_kin_vjp(*args, ctypes.c_void_p(u.data_ptr()), u.stride(0), int(m), int(j_total), _lib.ptr(rec),
+                                        int(rec_stride), ctypes.byref(plan), _lib.ptr(grad_out), B, _lib.dtype_code(x.dtype),
+                                        lie_eps(x.dtype), _lib.stream_ptr(x.device)), "thx_kin_vjp")
+
     # ---- DCEM: weights and moments of one iteration, and their backward (csrc/dcem_kernels.hip) ------------
     @staticmethod
     def _dcem_shapes(what, fX, X, bn, bs, other=()):

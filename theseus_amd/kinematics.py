@@ -8,10 +8,15 @@ theseus.embodied.kinematics.UrdfRobotModel, examples/inverse_kinematics.py).
 ``LinkPoseCost``     6 rows, target.local(T_link(theta)) = log(target^-1 T_link), Jacobian Jlog J_body.  The reference example writes
                      pose.local(target), its negation: the same squared error and the same Gauss-Newton step.
 ``LinkPositionCost`` 3 rows, t_link(theta) - target, Jacobian R_link J_body[:3].
-``PackedKinematics`` PackedEuclidean -- the (B, n) state, retraction by thx_vec_retract, implicit / unrolled / truncated backward
-                     through the torch classes -- whose NON-differentiated evaluation is fused (theseus_amd/term_table.py):
-                     ``assemble`` = thx_kin_eval into persistent block buffers + thx_block_assemble, ``error_metric`` =
-                     thx_kin_error (csrc/kin_kernels.hip).  It accepts an objective whose optimisation variables are Vector(dof) of
+``PackedKinematics`` PackedEuclidean -- the (B, n) state, retraction by thx_vec_retract, unrolled / truncated backward through the
+                     torch classes -- whose evaluation is fused (theseus_amd/term_table.py): ``assemble`` = thx_kin_eval into
+                     persistent block buffers + thx_block_assemble, ``error_metric`` = thx_kin_error (csrc/kin_kernels.hip).  The
+                     implicit step's backward is fused as well: with an auxiliary tensor requiring grad ``assemble(graph=True)``
+                     returns g through ``_FusedGradient``, whose backward is thx_kin_vjp (csrc/kin_vjp_kernels.hip) -- the
+                     gradients of the pose / position / prior targets, every weight and the hinge's limits and threshold; a
+                     pose target that is fk of a leaf gets its gradient there and autograd goes on through the forward
+                     kinematics.  Kernel sets without ``kin_vjp``, ``fused_backward = False``, ``fused = False`` and a state
+                     that requires grad keep the torch classes.  It accepts an objective whose optimisation variables are Vector(dof) of
                      ONE robot and whose costs are link costs, Difference on such a vector (rest-pose prior) and HingeCost on one
                      (joint limits), each with a Scale / DiagonalCostWeight, at least one of them a link cost.
 
@@ -445,6 +450,9 @@ class PackedKinematics(TermTable, PackedEuclidean):
         if any(c.robot is not self.robot for c in links) or any(v.dof() != dof for v in self.vars):
             raise UnsupportedObjective(_KINDS_MESSAGE)
         self._TANGENT = dof
+        self._VJP_KERNEL, self._VJP_REC = "kin_vjp", max(18, 4 * dof)
+        self._VJP_ENTRIES = {_lib.KIN_POSE: (0, 12), _lib.KIN_POSITION: (0, 3), _lib.KIN_HINGE: (0, dof, 2 * dof, 3 * dof),
+                             _lib.KIN_PRIOR: (0, dof)}
         self._WEIGHT_WIDTHS = (tuple(sorted({1, 3, 6, dof})), "This cost needs a DiagonalCostWeight of the cost's own dimension.")
         # the path table: every distinct link once
         self.path_of, entries = {}, []
@@ -494,3 +502,7 @@ class PackedKinematics(TermTable, PackedEuclidean):
 
     def _launch_error(self, state, err):
         self.K.kin_error(self._table, len(self.costs), self._paths(), len(self._path_joints), state, self.n, self.robot.dof, err)
+
+    def _launch_vjp(self, table, state, u, rec, plan, grad_out, grid_work):
+        self.K.kin_vjp(table, len(self.costs), self._paths(), len(self._path_joints), state, self.n, self.robot.dof, u, self.m,
+                       self.j_total, rec, self._VJP_REC, plan, grad_out)
