@@ -1045,6 +1045,27 @@ int thx_chol_solve_env(const void* L, int64_t ld, int32_t n, int32_t B, const vo
  *        of the call.  Agrees with thx_chol_solve to rounding (another summation order). */
 int thx_chol_solve_multi(const void* L, int64_t ld, int32_t n, int32_t B, const void* Winv, const void* rhs, void* x, int32_t nrhs,
                          int64_t ldv, int64_t bstride, int which, int dtype, void* stream);
+/*      thx_chol_solve_multi_sparse: the same block solves on the TILE-SPARSE factor -- posterior samples and marginal covariances of
+ *        the large graphs whose dense frame cannot exist (HipSparseCholeskySolver).  L and Winv exactly as thx_chol_factor_sparse,
+ *        thx_chol_factor_hblocks (with a pattern) and thx_chol_factor_levels leave them, both 16-byte aligned: ld > 0 a dense
+ *        (B, ld, ld) frame (ld >= n, ld % 32 == 0), tile (i, k) at row THX_TILE * i, column THX_TILE * k; ld == 0 the tile-packed
+ *        factor (B, nslots, THX_TILE, THX_TILE), tile (i, k) in the slot the pattern names (row_slot), the convention of
+ *        thx_chol_solve_sparse.  Of the pattern only ntiles, nslots, row_ptr, row_tile and (ld == 0) row_slot are read.
+ *        rhs / x: (B, nrhs, n) with the ldv / bstride contract and the `which` codes of thx_chol_solve_multi, ALWAYS in the
+ *        linearization's column order.  tile_row0: DEVICE int32 (ntiles + 1), prefix sums of the rows of each tile that belong to the
+ *        matrix (a LevelPattern: tile_valid summed, last entry n): tile j holds matrix rows tile_row0[j] .. tile_row0[j + 1] in its
+ *        first rows, the rest is padding -- no padded vectors, no thx_vec_gather around the solve; only with ld == 0.  NULL: unpadded
+ *        tiles, tile j holds rows THX_TILE * j .. min(THX_TILE * j + THX_TILE, n) and ntiles == ceil(n / THX_TILE).
+ *        One workgroup per (problem, group of 32 vectors), one launch: the forward pass walks the block rows upwards and PULLS along
+ *        each row list (T = R_i - sum_k L_ik X_k, then the panel); the backward pass walks them downwards, finishes X_i through the
+ *        panel and PUSHES X_k -= L_ik^T X_i along the same row list -- no column lists, no level launches.  Products on the matrix
+ *        cores; the block of vectors stays in x: no limit on n or nrhs.  Tiles the lists do not name are never read; rows and
+ *        columns of a tile or panel beyond the tile's valid count are masked (padding may hold anything); nothing outside nrhs rows
+ *        of n elements is read or written; a vector's result does not depend on the other vectors of the call nor on what x held;
+ *        x may alias rhs.  Agrees with thx_chol_solve_sparse to rounding (another summation order). */
+int thx_chol_solve_multi_sparse(const void* L, int64_t ld, int32_t n, int32_t B, const void* Winv, const void* rhs, void* x, int32_t nrhs,
+                                int64_t ldv, int64_t bstride, int which, const thx_tile_pattern* pattern, const int32_t* tile_row0,
+                                int dtype, void* stream);
 /*      (block-compact Hessian, see thx_hblock_layout) */
 int thx_chol_factor_hblocks(const thx_hblock_layout* layout, const void* Hc, int64_t bstride, int32_t n, int32_t B,
                             const void* damping, int ellipsoidal, double damping_eps, void* L, int64_t ld, void* Winv,

@@ -291,6 +291,8 @@ _SIGNATURES = {
                                     c_void_p],
     "thx_chol_solve_multi": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int, c_int,
                              c_void_p],
+    "thx_chol_solve_multi_sparse": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int,
+                                    POINTER(TilePattern), c_void_p, c_int, c_void_p],
     "thx_lu_factor": [c_void_p, c_int64, c_int32, c_int32, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_int,
                       c_void_p],
     "thx_lu_solve_forward": [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p],

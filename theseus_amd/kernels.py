@@ -1123,6 +1123,27 @@ class HipKernels:
                                                  _lib.c_void_p(x.data_ptr()), nrhs, ldv, bstride, int(which), _lib.dtype_code(L.dtype),
                                                  _lib.stream_ptr(L.device)), "thx_chol_solve_multi")
 
+    def chol_solve_multi_sparse(self, L, n, panels, rhs, x, pattern, which=0, tile_row0=None):
+        """thx_chol_solve_multi_sparse: ``chol_solve_multi`` over the structurally non-zero tiles of L only (``pattern``: a
+        theseus_amd.sparse.TilePattern or LevelPattern).  ``L``: the dense frame (3-D) or the tile-packed factor (4-D);
+        ``tile_row0``: the (ntiles + 1) int32 device table of a LevelPattern's padded tiles.  Vectors are in the linearization's
+        column order whatever the layout; ``x`` may be ``rhs``."""
+        B, T = L.shape[0], _lib.THX_TILE
+        packed = L.dim() == 4
+        ld = 0 if packed else L.shape[-1]
+        if (tuple(L.shape[1:]) != (pattern.nslots, T, T) if packed else (L.dim() != 3 or L.shape[1] != ld)) or \
+                tuple(panels.shape) != (B, pattern.ntiles, T, T):
+            raise ValueError(f"chol_solve_multi_sparse: L {tuple(L.shape)} / panels {tuple(panels.shape)} are not a factor of order {n} "
+                             f"on this pattern ({pattern.ntiles} tiles, {pattern.nslots} slots)")
+        if tile_row0 is not None and (tile_row0.dtype != torch.int32 or tile_row0.numel() != pattern.ntiles + 1):
+            raise ValueError(f"chol_solve_multi_sparse: tile_row0 must hold {pattern.ntiles + 1} int32 values")
+        nrhs, ldv, bstride = self._rhs_block("chol_solve_multi_sparse", "L, panels", (L, panels), B, n, rhs, x)
+        _lib.check(self.lib.thx_chol_solve_multi_sparse(_lib.ptr(L, "L"), ld, n, B, _lib.ptr(panels, "panels"), _lib.c_void_p(rhs.data_ptr()),
+                                                        _lib.c_void_p(x.data_ptr()), nrhs, ldv, bstride, int(which),
+                                                        pattern.c_struct(L.device), _lib.ptr(tile_row0, "tile_row0"),
+                                                        _lib.dtype_code(L.dtype), _lib.stream_ptr(L.device)),
+                   "thx_chol_solve_multi_sparse")
+
     # ---- dense pivoted LU (include/theseus_hip.h: thx_lu_factor) --------------------------------------
     def lu_factor(self, M, n, damping, ellipsoidal, damping_eps, LU, piv, info, symmetric_lower=True):
         """P (M + damping) = L U.  ``symmetric_lower``: M is a (B, ld, ld) frame whose lower triangle is mirrored; otherwise a full

@@ -79,7 +79,8 @@ class FactorCore:
       ``factor_snapshot()`` / ``solve_with_snapshot(snapshot, rhs)``
 
     and, where its factor serves blocks of right-hand sides, ``_apply_multi`` (dense Cholesky: thx_chol_solve_multi, banded
-    Cholesky: thx_pb_solve_multi; the others leave it None and the multi-right-hand-side surface raises)."""
+    Cholesky: thx_pb_solve_multi, tile-sparse Cholesky: thx_chol_solve_multi_sparse, bound per instance when the kernel set has
+    it; the others leave it None and the multi-right-hand-side surface raises)."""
 
     def _core_init(self):
         self.K = self.linearization.K

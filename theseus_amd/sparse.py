@@ -563,6 +563,9 @@ class LevelPattern:
         src = np.full(self.npad, -1, dtype=np.int32)
         src[self.pad_of_col] = np.arange(self.n, dtype=np.int32)
         self.col_of_pad = src
+        # ... and, for the kernels that address the linearization's vectors directly (thx_chol_solve_multi_sparse): tile j holds
+        # the matrix rows tile_row0[j] .. tile_row0[j + 1] in its first rows
+        self.tile_row0_host = np.ascontiguousarray(np.concatenate([[0], np.cumsum(counts * dof)]).astype(np.int32))
         self._dev: Dict[str, Any] = {}
 
     def piece_tables(self, hblocks) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -602,7 +605,8 @@ class LevelPattern:
             lt.level_col_host = self.tree_level_col.ctypes.data
             lt.level_ent_host, lt.level_maxk_host = self.tree_level_ent.ctypes.data, self.tree_level_maxk.ctypes.data
             lt.ent_col, lt.tile_valid = t["ent_col"].data_ptr(), t["tile_valid"].data_ptr()
-            vec = dict(pad_of_col=torch.from_numpy(self.pad_of_col).to(device), col_of_pad=torch.from_numpy(self.col_of_pad).to(device))
+            vec = dict(pad_of_col=torch.from_numpy(self.pad_of_col).to(device), col_of_pad=torch.from_numpy(self.col_of_pad).to(device),
+                       tile_row0=torch.from_numpy(self.tile_row0_host).to(device))
             self._dev[key] = (c, ls, t, vec, lt)
         return self._dev[key]
 
@@ -617,6 +621,10 @@ class LevelPattern:
 
     def vec_maps(self, device):
         return self._device(device)[3]
+
+    def tile_row0(self, device) -> torch.Tensor:
+        """(ntiles + 1) int32 on ``device``: prefix sums of the matrix rows of the padded tiles (the last entry is n)."""
+        return self._device(device)[3]["tile_row0"]
 
 
 def tile_pattern(structure, dof: int) -> TilePattern:
@@ -649,6 +657,8 @@ class HipSparseCholeskyCore(DenseFrameCore):
 
     def _sparse_init(self, packed_factor: Optional[bool] = None, tile_count: Optional[Sequence[int]] = None):
         self._core_init()
+        if hasattr(self.K, "chol_solve_multi_sparse"):   # (the class keeps _apply_multi = None: no kernel set, no hook)
+            self._apply_multi = self._apply_multi_tiles
         lin = self.linearization
         compact = bool(getattr(lin, "_compact", False))
         self.levels = tile_count is not None
@@ -753,6 +763,18 @@ class HipSparseCholeskyCore(DenseFrameCore):
         if self.levels:
             return self._solve_levels(self.L, self.panels, rhs, x, backward_only)
         self.K.chol_solve_sparse(self.L, self.linearization.n, self.panels, rhs, x, self.pattern, backward_only=backward_only)
+
+    # ---- blocks of right-hand sides (thx_chol_solve_multi_sparse) ------------------------------------------------------------------
+    def _apply_multi_tiles(self, x, which, scratch=False):
+        """The ``_apply_multi`` hook of FactorCore (bound by ``_sparse_init`` when the kernel set has the kernel): in place on a
+        copy of ``x`` (on ``x`` itself: ``scratch``), one call for all three layouts.  Vectors go in and come out in the
+        linearization's order -- which is this solver's elimination order: the padded level factor restricted to its matrix rows
+        (``tile_row0``) is the Cholesky factor of AtA in that order, so no which needs a permutation."""
+        if not scratch:
+            x = x.clone(memory_format=torch.contiguous_format)
+        row0 = self.pattern.tile_row0(x.device) if self.levels else None
+        self.K.chol_solve_multi_sparse(self.L, self.linearization.n, self.panels, x, x, self.pattern, which=which, tile_row0=row0)
+        return x
 
 
 class HipSparseCholeskySolver(HipSparseCholeskyCore, LinearSolver):
