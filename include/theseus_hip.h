@@ -1325,6 +1325,25 @@ int thx_ba_schur_blocks(const thx_ba_structure* s, int32_t B, const void* Hcc, c
 /* delta_p = tvec - Hinv Hpc delta_c, written to delta[:, 6C:] (delta_c = delta[:, :6C] is read) */
 int thx_ba_backsub(const thx_ba_structure* s, int32_t B, const void* W, const void* Hinv, const void* tvec, void* delta,
                    int64_t ldv, int dtype, void* stream);
+/* thx_ba_reduce_multi / thx_ba_backsub_multi: the point elimination and the back substitution for a BLOCK of vectors per problem,
+ * around thx_chol_solve_multi / thx_chol_solve_multi_sparse on the camera columns -- blocks of right-hand sides, posterior samples
+ * and marginal covariances on the factor a bundle-adjustment solve left.  W and Hinv as thx_ba_assemble / thx_ba_schur* leave them
+ * (Hinv: the inverse of the DAMPED point blocks V).  rhs / x: (B, nrhs, n), n = 6 C + 3 Np, cameras then points, one vector per
+ * row, with the ldv / bstride contract of thx_chol_solve_multi, so that the camera columns are a strided view the solves take with
+ * n = 6 C and the same ldv / bstride.  With S = U - W V^-1 W^T = L L^T the reduced system, R the lower Cholesky factor of a point's
+ * Hinv (R R^T = V^-1) and M = [[L, W R], [0, R^-T]] (M M^T = H), `which` is the code of the solve in between:
+ *   0 (x = H^-1 rhs):  reduce  xc = rc - W V^-1 rp, xp = V^-1 rp;   solve which 0;   backsub  xp -= V^-1 W^T xc
+ *   2 (x = M^-1 rhs):  reduce  xc = rc - W V^-1 rp, xp = R^T rp;    solve which 2;   (backsub: returns without a launch)
+ *   1 (x = M^-T rhs):  (reduce: returns without a launch)           solve which 1;   backsub  xp = R xp - V^-1 W^T xc
+ * 1 after 2 is 0; with z ~ N(0, I), M^-T z has covariance H^-1 exactly.  thx_ba_reduce_multi: x may be rhs.  thx_ba_backsub_multi
+ * works in place on x.  One workgroup per (camera or point, 64 problems, group of 32 vectors): lane = problem, W and Hinv read once
+ * per group, the sums of the group in fp64 registers in the order of cam_obs / pt_obs (no atomics: the same input gives the same
+ * bits), the block staged through LDS 8 vectors at a time.  Nothing outside nrhs rows of n elements is read or written; a vector's
+ * result does not depend on the other vectors of the call. */
+int thx_ba_reduce_multi(const thx_ba_structure* s, int32_t B, const void* W, const void* Hinv, const void* rhs, void* x, int32_t nrhs,
+                        int64_t ldv, int64_t bstride, int which, int dtype, void* stream);
+int thx_ba_backsub_multi(const thx_ba_structure* s, int32_t B, const void* W, const void* Hinv, void* x, int32_t nrhs, int64_t ldv,
+                         int64_t bstride, int which, int dtype, void* stream);
 /* partials: scratch (THX_BA_ERR_CHUNKS, B) */
 #define THX_BA_ERR_CHUNKS 256
 int thx_ba_error(const thx_ba_structure* s, const thx_ba_data* d, void* partials, void* err, int dtype,

@@ -593,7 +593,9 @@ class HipSchurSolverCore(FactorCore):
     """(H + damping) delta = g of a bundle-adjustment linearization by block elimination of the points + the tiled dense
     Cholesky on the reduced camera system.  Same ``solve`` contract and failure behaviour as ``HipCholeskySolver``.  The
     elimination wraps the factorisation, so this core writes ``_solve`` and ``solve_with_factor`` whole instead of the factor
-    hooks of ``FactorCore``; the factor of the reduced system serves no blocks of right-hand sides."""
+    hooks of ``FactorCore``.  Blocks of right-hand sides (``_apply_multi``, bound per instance when the kernel set has the
+    kernels): thx_ba_reduce_multi, the multi-vector solve of the reduced system's factor on the camera columns of the block,
+    thx_ba_backsub_multi -- in all three modes (dense frame, tile pattern, level mode)."""
 
     def _schur_solver_init(self, sparse_reduced_system: bool = True, ordering: str = "auto"):
         self.K = self.linearization.K
@@ -601,6 +603,9 @@ class HipSchurSolverCore(FactorCore):
         self.pattern, self.sparse, self._want_sparse = None, False, bool(sparse_reduced_system)
         self.factor_version = 0
         self._odo_only = None
+        self._y = self._lam = None
+        if all(hasattr(self.K, k) for k in ("ba_reduce_multi", "ba_backsub_multi", "chol_solve_multi", "chol_solve_multi_sparse")):
+            self._apply_multi = self._apply_multi_schur   # (the class keeps _apply_multi = None: no kernel set, no hook)
         # LEVEL MODE (round 6): S as a block list (thx_ba_schur_blocks) in a tile-level nested-dissection order of the cameras,
         # factorised along its elimination tree (thx_chol_factor_levels).  ordering: "auto" (the time model of
         # theseus_amd.sparse ranks the candidate orders at this batch size; the band order keeps the column-by-column schedule
@@ -661,6 +666,9 @@ class HipSchurSolverCore(FactorCore):
         i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)  # noqa: E731
         self._level_t = dict(diag_blk=i32(np.arange(C)), blk_dst=i32(dst if dst.size else [0]), pad_of_col=i32(pad_of_col),
                              col_of_pad=i32(col_of_pad))
+        # blocks of vectors (_apply_multi_schur): the camera columns structure order <-> solver order, unpadded
+        self._level_t["cam_from_solver"] = torch.from_numpy(col).to(dev)
+        self._level_t["cam_to_solver"] = torch.from_numpy(np.argsort(col)).to(dev)
         from .sparse import _LevelLayout
         self._level_layout = _LevelLayout(self.pattern, self._blocklist, dev)
         self._level = True
@@ -678,7 +686,7 @@ class HipSchurSolverCore(FactorCore):
                 self.Sc = torch.zeros(B, self._blocklist.bstride, dtype=dt, device=dev)
                 self.L = torch.zeros(B, pat.nslots, T, T, dtype=dt, device=dev)       # tile-packed factor
                 self.panels = torch.empty(B, pat.ntiles, T, T, dtype=dt, device=dev)
-                self.rhs, self._dc = (torch.empty(B, nc, dtype=dt, device=dev) for _ in range(2))
+                self.rhs, self._y, self._dc = (torch.empty(B, nc, dtype=dt, device=dev) for _ in range(3))   # (_y: batch / dtype for FactorCore)
                 self._xp, self._yp = (torch.zeros(B, pat.npad, dtype=dt, device=dev) for _ in range(2))   # (padding stays zero)
                 self.Hinv = torch.empty(s.num_points, 6, B, dtype=torch.float64, device=dev)
                 self.tvec = torch.empty(s.num_points, 3, B, dtype=torch.float64, device=dev)
@@ -783,6 +791,42 @@ class HipSchurSolverCore(FactorCore):
             self.check_info()
         return self.delta
 
+    # ---- blocks of right-hand sides: FactorCore's surface on the factor of the reduced system ----------------------------------------
+    def _factorize_undamped(self):
+        """The undamped solve of the linearization as it stands (the elimination wraps the factorisation: there is no factor-only
+        call); its factor and ``Hinv`` are what ``_apply_multi`` then reads."""
+        self._solve(None, True, 1e-8, check_info=True)
+        return self
+
+    def _apply_multi_schur(self, x, which, scratch=False):
+        """The ``_apply_multi`` hook of FactorCore, in place on a copy of ``x`` (on ``x`` itself: ``scratch``).  With the factorised
+        H = [[U, W], [W^T, V]] = M M^T, M = [[L, W R], [0, R^-T]] (S = L L^T the reduced system in the solver's camera order,
+        R R^T = V^-1 per point): which = 0: H^-1 x, 2: M^-1 x, 1: M^-T x -- the solver's own order is the cameras in the reduced
+        factor's order, then the points.  reduce (not for 1) -> the multi-vector solve on the camera columns, a strided view of
+        the block -> back substitution (not for 2)."""
+        lin = self.linearization
+        p, K = lin.packed, self.K
+        nc = p.nc
+        if not scratch:
+            x = x.clone(memory_format=torch.contiguous_format)
+        if which != 1:
+            K.ba_reduce_multi(p.dstruct, lin.W, self.Hinv, x, x, which=which)
+        xc = x[:, :, :nc]
+        if self.levels:
+            # the nested-dissection camera order: the tile-packed factor restricted to its matrix rows (tile_row0) is the factor of S
+            # in that order; one index_select each way on the camera section, as HipCholeskyCore._apply_multi does for its order
+            t = self._level_t
+            xs = xc.index_select(2, t["cam_to_solver"]) if which != 1 else xc.contiguous()
+            K.chol_solve_multi_sparse(self.L, nc, self.panels, xs, xs, self.pattern, which=which,
+                                      tile_row0=self.pattern.tile_row0(x.device))
+            xc.copy_(xs.index_select(2, t["cam_from_solver"]) if which != 2 else xs)
+        elif self.sparse:
+            K.chol_solve_multi_sparse(self.L, nc, self.panels, xc, xc, self.pattern, which=which)
+        else:
+            K.chol_solve_multi(self.L, nc, self.panels, xc, xc, which=which)
+        if which != 2:
+            K.ba_backsub_multi(p.dstruct, lin.W, self.Hinv, x, which=which)
+        return x
 
     def solve_with_factor(self, rhs: torch.Tensor) -> torch.Tensor:
         """(H + damping)^-1 rhs for another right-hand side (B, n) = [r_c | r_p] with the CACHED factor of the reduced camera

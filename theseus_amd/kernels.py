@@ -568,6 +568,30 @@ class HipKernels:
                                            delta.stride(0), _lib.dtype_code(delta.dtype), _lib.stream_ptr(delta.device)),
                    "thx_ba_backsub")
 
+    def _ba_block(self, what, s, W, Hinv, B, *blocks):
+        """-> (nrhs, ldv, bstride) of the (B, nrhs, n) blocks of the multi-vector BA kernels (W / Hinv: the fp64 planar workspaces)."""
+        n = s.host.n
+        if W.dtype != torch.float64 or Hinv.dtype != torch.float64 or tuple(Hinv.shape) != (s.host.num_points, 6, B) or \
+                tuple(W.shape) != (max(s.host.num_obs, 1), 18, B) or not (W.is_contiguous() and Hinv.is_contiguous()):
+            raise ValueError(f"{what}: W {tuple(W.shape)} / Hinv {tuple(Hinv.shape)} are not the fp64 planar workspaces of batch {B}")
+        return self._rhs_block(what, "the block", (), B, n, blocks[0], blocks[-1])
+
+    def ba_reduce_multi(self, s, W, Hinv, rhs, x, which=0):
+        """thx_ba_reduce_multi: ``rhs`` / ``x`` (B, nrhs, n) blocks (the strides of ``chol_solve_multi``); ``x`` may be ``rhs``."""
+        B = Hinv.shape[2]
+        nrhs, ldv, bstride = self._ba_block("ba_reduce_multi", s, W, Hinv, B, rhs, x)
+        _lib.check(self.lib.thx_ba_reduce_multi(s.c, B, _lib.ptr(W), _lib.ptr(Hinv), _lib.c_void_p(rhs.data_ptr()),
+                                                _lib.c_void_p(x.data_ptr()), nrhs, ldv, bstride, int(which), _lib.dtype_code(x.dtype),
+                                                _lib.stream_ptr(x.device)), "thx_ba_reduce_multi")
+
+    def ba_backsub_multi(self, s, W, Hinv, x, which=0):
+        """thx_ba_backsub_multi, in place on the (B, nrhs, n) block ``x`` whose camera columns hold the reduced solve's result."""
+        B = Hinv.shape[2]
+        nrhs, ldv, bstride = self._ba_block("ba_backsub_multi", s, W, Hinv, B, x)
+        _lib.check(self.lib.thx_ba_backsub_multi(s.c, B, _lib.ptr(W), _lib.ptr(Hinv), _lib.c_void_p(x.data_ptr()), nrhs, ldv, bstride,
+                                                 int(which), _lib.dtype_code(x.dtype), _lib.stream_ptr(x.device)),
+                   "thx_ba_backsub_multi")
+
     def ba_error(self, s, t, partials, err, cams=None, points=None):
         d = t.c_struct(cams, points)
         dt = err.dtype

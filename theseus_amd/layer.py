@@ -62,6 +62,16 @@ class TheseusLayer(torch.nn.Module):
             if not return_dict:
                 return out.transpose(1, 2)
             return {v.name: out[:, :, c0:c0 + d] for v, (c0, d) in zip(packed.vars, packed.cols)}
+        if getattr(packed, "group", None) == "BA":   # cameras: the SE3 retraction on columns [0, 6C); points: the vector one
+            t, d = packed.tensors, deltas.view(B * k, n)
+            xc = t.cams.unsqueeze(2).expand(-1, B, k, 3, 4).reshape(-1, B * k, 3, 4)
+            xp = t.points.unsqueeze(2).expand(-1, B, k, 3).reshape(-1, B * k, 3)
+            oc, op = torch.empty_like(xc), torch.empty_like(xp)
+            K.se3_retract(xc, d, 1.0, None, oc)
+            K.vec_retract(xp, d, packed.nc, 1.0, None, op)
+            out = {v.name: oc[i].view(B, k, 3, 4) for i, v in enumerate(packed.cam_vars)}
+            out.update({v.name: op[i].view(B, k, 3) for i, v in enumerate(packed.pt_vars)})
+            return out
         poses = packed.tensors.poses                                                                      # (P, B, *record)
         P, rec = poses.shape[0], tuple(poses.shape[2:])
         x = poses.unsqueeze(2).expand(P, B, k, *rec).reshape(P, B * k, *rec)

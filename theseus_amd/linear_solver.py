@@ -79,8 +79,9 @@ class FactorCore:
       ``factor_snapshot()`` / ``solve_with_snapshot(snapshot, rhs)``
 
     and, where its factor serves blocks of right-hand sides, ``_apply_multi`` (dense Cholesky: thx_chol_solve_multi, banded
-    Cholesky: thx_pb_solve_multi, tile-sparse Cholesky: thx_chol_solve_multi_sparse, bound per instance when the kernel set has
-    it; the others leave it None and the multi-right-hand-side surface raises)."""
+    Cholesky: thx_pb_solve_multi, tile-sparse Cholesky: thx_chol_solve_multi_sparse, and the bundle-adjustment Schur core
+    (theseus_amd/ba.py): thx_ba_reduce_multi / thx_ba_backsub_multi around those solves, both bound per instance when the kernel
+    set has them; the others leave it None and the multi-right-hand-side surface raises)."""
 
     def _core_init(self):
         self.K = self.linearization.K
@@ -215,7 +216,7 @@ class FactorCore:
         if not cols:
             raise ValueError("marginal_covariance: no variables named")
         own = self._factorize_undamped()
-        (B, n), d = own._y.shape, len(cols)
+        B, n, d = own._y.shape[0], own.linearization.n, len(cols)   # (n: of the linearization -- a Schur core's _y is the camera part)
         idx = own._factor_cols(torch.tensor(cols, dtype=torch.long, device=own._y.device))
         E = torch.zeros(B, d, n, dtype=own._y.dtype, device=own._y.device)
         E[:, torch.arange(d, device=idx.device), idx] = 1
